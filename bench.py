@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched rollout hot path (BASELINE.json metric) on N MI355X GPUs of one node.
 
-  python bench.py --gpus N --steps K --warmup W [--config 1|2]
+  python bench.py --gpus N --steps K --warmup W [--config 1|2] [--dump-outputs DIR] [--full]
 
 N > 1 without a launcher (no WORLD_SIZE in the environment): bench.py starts its own N ranks (python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free port> bench.py <same arguments>), one process per GPU over RCCL; under the
@@ -20,10 +20,14 @@ Timing protocol. The batch starts in lock-step (every env in the same pose and g
 window right behind a short warm-up measures a cheaper workload than the steady state (round 2: 21.3 M in frames 5-25 vs 18.3 M later).
 Therefore: (1) an untimed PRE-ROLL steps the batch until the reset rate is stationary (>= 60 frames, independent of --warmup); (2) --warmup W
 untimed frames; (3) R REPEATS of a window of EXACTLY --steps K frames, each bracketed by barrier + torch.cuda.synchronize() on both sides with the
-max over ranks taken; R is chosen so that the timed GPU work totals >= 1 s. `value` / `ms_per_step` are the MEDIAN window; min / max / repeats are
-in the line. Inputs (state, terrain windows, weights) are resident in HBM when a window starts.
+max over ranks taken. A plain run times ONE window (R = 1: exactly K timed frames); with --full R is chosen so that the timed GPU work totals >= 5 s
+(--repeats R sets it either way). `value` / `ms_per_step` are the MEDIAN window; min / max / repeats are in the line. Inputs (state, terrain windows,
+weights) are resident in HBM when a window starts. --dump-outputs DIR writes the batch state the last timed frame left (float64 .npy files); the
+inputs are seeded, so two runs with the same arguments start from the same state.
 
-`value` is always the pure rollout (weak scaling of the config across N). With --config 1 the line also carries an "exchange" object: a second timed leg
+A plain run measures the headline and nothing else. --full adds the CPU baseline, the side figures (trained policy, fp32 library) and the exchange leg(s).
+
+`value` is always the pure rollout (weak scaling of the config across N). With --full and --config 1 the line also carries an "exchange" object: a second timed leg
 on the BASELINE configs[3] workload (args/opt_args_train_mace.txt: exploration on, rates 0.2 / 0.025 / 0.002) in which every outer frame's experience
 tuples are drained device-to-device into a right-sized block, gathered to rank 0 over RCCL on a side stream while the next frame's kernel runs, appended
 to a device replay ring there, and the policy is re-broadcast (one packed buffer) every --bcast-every frames -- the two exchange steps of
@@ -185,6 +189,32 @@ def cpu_baseline(cfg, frames=60):
             "logical_cpus": os.cpu_count() or 1}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(b, n, out_dir, suffix=""):
+    """--dump-outputs: the batch state the last timed frame left, read back the way a caller of RunFrames reads it, as float64 .npy files. Larger batches than
+    DUMP_MAX_BYTES allows are written for a fixed, seeded sample of envs (env_ids.npy lists them)."""
+    def read(ids):
+        q, qd = b.PoseVel(ids)
+        com, vel, ang = b.LinkStates(ids)
+        nc, nr, _, _, _ = b.CycleInfo(ids)
+        return {"pose": q, "vel": qd, "link_com": com, "link_vel": vel, "link_angle": ang, "policy_output": b.PolicyOutput(ids), "cycles": nc, "resets": nr}
+    ids = np.arange(min(n, 8))
+    row_bytes = sum(np.asarray(v, np.float64).nbytes for v in read(ids).values()) / float(len(ids))
+    if n * row_bytes > DUMP_MAX_BYTES - (1 << 20):
+        ids = np.sort(np.random.RandomState(0).choice(n, int((DUMP_MAX_BYTES - (1 << 20)) // row_bytes), replace=False))
+    else:
+        ids = np.arange(n)
+    out = read(list(ids))
+    st = b.EvalStats()
+    out["eval_stats"] = [st["avg_dist"], st["episodes"], st["cycles"], st["resets"]]
+    out["env_ids"] = ids
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.asarray(v, np.float64))
+
+
 class _Dev:
     """Where the batch lives: cuda:<local rank> (the product) or -- --backend emul-tests-only -- the host, with the package's BatchScenario bound to the lane-loop check build
     (tests/emul/libdtrl_emul.so). Keeps the measurement code below free of backend switches."""
@@ -331,7 +361,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--config", type=int, choices=sorted(CONFIGS), default=1, help="BASELINE.json configs[] index of the single-GPU workload: 1 = dog slopes_mixed 4096 envs (the metric's config), 2 = raptor narrow_gaps 8192 envs")
     ap.add_argument("--envs-per-gpu", type=int, default=0, help="override the config's batch size")
-    ap.add_argument("--repeats", type=int, default=0, help="timed windows of --steps frames (default: as many as make >= 1 s of timed GPU work, 3..25)")
+    ap.add_argument("--repeats", type=int, default=0, help="timed windows of --steps frames (default: one; with --full as many as make >= 5 s of timed GPU work, 3..60)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: >= 5 s of timed windows, the CPU baseline, the side figures (trained policy, fp32 library) and the exchange leg(s)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed frame left in the batch (pose, velocity, link states, policy output, counters) as DIR/<name>.npy")
     ap.add_argument("--terrain-gen", choices=["host", "device"], default="host",
                     help="host: the reference's terrain generator streams (bit-exact windows), regenerated by host workers at the frame boundary (default, the parity-tested mode); "
                          "device: counter-based streams, windows generated and slid by the GPU, no host sync per frame")
@@ -395,7 +429,7 @@ def main():
         torch.cuda.set_device(local_rank)
 
     # the CPU leg FIRST (round 5): 16 s of host work no longer sit between the timed GPU region and the end of the process, where the driver's SMI samples fell
-    cpu_rec = cpu_baseline(cfg, a.cpu_frames) if (rank == 0 and world == 1 and not a.no_cpu_baseline) else None
+    cpu_rec = cpu_baseline(cfg, a.cpu_frames) if (a.full and rank == 0 and world == 1 and not a.no_cpu_baseline) else None
     import deepterrainrl_amd as da
     if a.lib:
         da.LIB_PATH = os.path.abspath(a.lib)
@@ -434,7 +468,7 @@ def main():
     b.KernelTimeMs()   # drop pre-roll / warm-up launches from the kernel-time average
     stats0 = b.EvalStats()
     windows = []
-    repeats = a.repeats
+    repeats = a.repeats if (a.repeats > 0 or a.full) else 1     # a plain run times exactly --steps frames
     while True:
         fence()
         t0 = time.perf_counter()
@@ -450,6 +484,8 @@ def main():
             break
     kern_ms, launches = b.KernelTimeMs()
     stats1 = b.EvalStats()
+    if a.dump_outputs:
+        dump_outputs(b, n, a.dump_outputs, "" if world == 1 else ".rank%d" % rank)
     dt = float(np.median(windows))
     total_env_steps = float(world) * n * a.steps * STEPS_PER_FRAME
     value = total_env_steps / dt
@@ -520,21 +556,21 @@ def main():
                              "note": "rank 0's envs over all %d windows: %d falls (terrain regeneration + reset launch each) and %d policy forwards happened inside the timed region; the pre-roll ran until the reset rate was stationary" % (len(windows), resets, cycles)},
         }
     b.close()
-    if rank == 0 and world == 1 and not model_overrides and not a.no_trained_leg and not emul:
+    if a.full and rank == 0 and world == 1 and not model_overrides and not a.no_trained_leg and not emul:
         pth = os.path.join(REPO, TRAINED_POLICY[a.config])
         if os.path.exists(pth) and n == cfg["envs"]:
             try:
                 line["trained_policy"] = trained_policy_leg(da, torch, cfg, n, local_rank, a, pth)
             except Exception as exc:
                 line["trained_policy"] = {"error": repr(exc)}
-    if rank == 0 and world == 1 and not model_overrides and not a.no_fp32_leg and not emul and n == cfg["envs"]:
+    if a.full and rank == 0 and world == 1 and not model_overrides and not a.no_fp32_leg and not emul and n == cfg["envs"]:
         try:
             line["fp32_physics"] = fp32_physics_leg(da, torch, cfg, n, local_rank, a, w, scale)
         except Exception as exc:
             line["fp32_physics"] = {"error": repr(exc)}
     ex_steps = a.exchange_steps if a.exchange_steps >= 0 else max(a.steps // 2, 50)
     legs = []
-    if ex_steps > 0 and a.config == 1:
+    if a.full and ex_steps > 0 and a.config == 1:
         guard = None
         if rank == 0 and dist is not None:
             # a collective that never completes (a rank died mid-exchange) must not cost the headline measurement above: after EXCHANGE_GUARD_S

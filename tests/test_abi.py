@@ -135,7 +135,7 @@ def test_bench_eight_ranks_end_to_end_on_the_check_build_over_gloo():
                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     assert refused.returncode != 0 and b"DTRL_TESTS_ONLY_EMUL" in refused.stdout
     n, steps = 6, 3
-    out = subprocess.check_output([sys.executable, bench, "--gpus", "8", "--backend", "emul-tests-only", "--envs-per-gpu", str(n), "--steps", str(steps), "--warmup", "1", "--repeats", "2",
+    out = subprocess.check_output([sys.executable, bench, "--gpus", "8", "--full", "--backend", "emul-tests-only", "--envs-per-gpu", str(n), "--steps", str(steps), "--warmup", "1", "--repeats", "2",
                                    "--preroll-max", "20", "--exchange-steps", "45", "--bcast-every", "10", "--no-cpu-baseline"], env=env, stderr=subprocess.STDOUT, timeout=1500).decode()
     lines = [l for l in out.splitlines() if l.startswith("{") and '"metric"' in l]
     assert len(lines) == 1, out[-3000:]                   # ONE JSON line, from rank 0
@@ -150,3 +150,34 @@ def test_bench_eight_ranks_end_to_end_on_the_check_build_over_gloo():
     assert "error" not in ex and ex["steps"] == 45 and ex["dropped_tuples"] == 0 and "8 GPUs" in ex["workload"] and "gather to rank 0" in ex["collective"]
     assert ex["collective_bytes_per_frame"]["received_by_rank0"] == 8 * ex["collective_bytes_per_frame"]["sent_per_rank"] > 0
     assert ex["tuples"] > 0                                # 48 envs x 45 frames past the two warm-up cycles: tuples from every shard reached rank 0's replay ring
+
+
+def test_bench_plain_run_times_exactly_steps_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) on the lane-loop check build: ONE timed window of exactly --steps frames, none of the --full legs (CPU baseline, side figures,
+    exchange), and --dump-outputs DIR writes the batch state the last timed frame left as float64 .npy files -- the same files, bit for bit, from a second run with the
+    same arguments."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["DTRL_TESTS_ONLY_EMUL"] = "1"
+    n, steps = 6, 3
+    outs = []
+    for k in range(2):
+        d_out = tmp_path / ("run%d" % k)
+        out = subprocess.check_output([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--backend", "emul-tests-only", "--envs-per-gpu", str(n), "--steps", str(steps),
+                                       "--warmup", "1", "--preroll-max", "20", "--dump-outputs", str(d_out)], env=env, stderr=subprocess.STDOUT, timeout=900).decode()
+        lines = [l for l in out.splitlines() if l.startswith("{") and '"metric"' in l]
+        assert len(lines) == 1, out[-3000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["repeats"] == 1 and d["timed_window"]["frames"] == steps and len(d["window_s"]["each"]) == 1
+        assert abs(d["ms_per_step"] - d["window_s"]["median"] / steps * 1e3) < 1e-9 and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert all(key not in d for key in ("cpu_baseline", "trained_policy", "fp32_physics", "exchange_alt")) and d["exchange"] is None
+        files = sorted(p.name for p in d_out.iterdir())
+        assert {"pose.npy", "vel.npy", "link_com.npy", "policy_output.npy", "env_ids.npy"} <= set(files), files
+        arrs = {f: np.load(str(d_out / f)) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values()) and arrs["pose.npy"].shape[0] == n and np.isfinite(arrs["pose.npy"]).all()
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        outs.append(arrs)
+    assert outs[0].keys() == outs[1].keys() and all(np.array_equal(outs[0][f], outs[1][f]) for f in outs[0])

@@ -256,7 +256,7 @@ def test_bench_contract_line():
     """bench.py prints ONE JSON line with the driver's contract keys, the roofline object and (unless skipped) the CPU baseline."""
     import json, subprocess, sys
     from conftest import REPO
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "2", "--envs-per-gpu", "512", "--cpu-frames", "8"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "3", "--warmup", "2", "--envs-per-gpu", "512", "--cpu-frames", "8"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -282,7 +282,7 @@ def test_bench_trained_policy_leg_and_policy_files():
     (seeded xavier weights), and the headline itself is untouched by the leg."""
     import json, subprocess, sys
     from conftest import REPO
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--exchange-steps", "0", "--no-rccl-leg"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--exchange-steps", "0", "--no-rccl-leg"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     tp = d["trained_policy"]
@@ -299,7 +299,7 @@ def test_bench_under_a_launcher_with_the_rccl_path_on_one_rank():
     from conftest import REPO
     env = dict(os.environ, DTRL_FORCE_COLLECTIVES="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--envs-per-gpu", "512", "--exchange-steps", "40", "--no-cpu-baseline"]
+           os.path.join(REPO, "bench.py"), "--gpus", "1", "--full", "--steps", "3", "--warmup", "2", "--envs-per-gpu", "512", "--exchange-steps", "40", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -471,16 +471,16 @@ def test_device_resident_tuple_drain_and_policy_hand_over(da, om):
     assert np.array_equal(a.PoseVel()[0], b.PoseVel()[0])
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(TB.SHIM_DIR, "drive_shim_hip")), reason="tests/shim/drive_shim_hip not built")
+@pytest.mark.skipif(not os.path.exists(os.path.join(TB.SHIM_DIR, "drive_shim_hip")), reason="oracle/_ref/shim/drive_shim_hip not built")
 def test_shim_drives_the_hip_library(da, om, tmp_path):
-    """include/BatchScenarioExp.h (compiled inside the reference's header tree, tests/shim/Makefile) linked against libdtrl.so: 100 frames on the GPU,
+    """include/BatchScenarioExp.h (compiled inside the reference's header tree, oracle/_ref_build/shim.mk) linked against libdtrl.so: 100 frames on the GPU,
     same tuple buffers as the Python mirror."""
     lines, pol = TB._run_shim(os.path.join(TB.SHIM_DIR, "drive_shim_hip"), tmp_path, om)
     py_lines, py_total = TB._python_side(100, 12, pol, scenario=da.BatchScenario)
     TB._check_shim_output(lines, py_lines, py_total)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(TB.SHIM_DIR, "drive_shim_eval_hip")), reason="tests/shim/drive_shim_eval_hip not built")
+@pytest.mark.skipif(not os.path.exists(os.path.join(TB.SHIM_DIR, "drive_shim_eval_hip")), reason="oracle/_ref/shim/drive_shim_eval_hip not built")
 def test_poli_eval_shim_drives_the_hip_library(da, om, tmp_path):
     """include/BatchScenarioPoliEval.h (compiled inside the reference's header tree on the build box, linked against libdtrl.so) runs cOptScenarioPoliEval's
     pool protocol on the GPU -- SetRandSeed + Reset, the EvalHelper loop over GetNumEpisodes / GetNumCycles / GetAvgDist / ResetAvgDist, GetDistLog,

@@ -285,12 +285,12 @@ def test_reference_mace_trainer_running_on_the_product_nets(rl, om):
     run_reference_trainer_on_the_product_nets(rl, om, rl.NATIVE_LIB_PATH, TH.make_native(TH.EMUL_TRAINER_LIB, mem_size=256, num_init_samples=100, seed=21, freeze_target_iters=2), 3e-4)
 
 
-def test_batch_neural_net_shim_inside_the_reference_tree():
-    """include/BatchNeuralNet.h compiled against /root/reference's headers (tests/shim/Makefile) and driven through cNeuralNet's calls on the plain-loop check build"""
+def test_batch_neural_net_shim_inside_the_reference_tree(tmp_path):
+    """include/BatchNeuralNet.h compiled against the reference's headers (oracle/_ref_build/shim.mk) and driven through cNeuralNet's calls on the plain-loop check build"""
     import subprocess
     from conftest import REFDATA
-    exe = os.path.join(REPO, "tests", "shim", "drive_shim_net_emul")
+    exe = os.path.join(REPO, "oracle", "_ref", "shim", "drive_shim_net_emul")
     if not os.path.exists(exe):
-        pytest.skip("tests/shim/drive_shim_net_emul not built")
-    r = subprocess.run([exe, REFDATA, "/tmp"], capture_output=True, text=True, timeout=300)
+        pytest.skip("oracle/_ref/shim/drive_shim_net_emul not built")
+    r = subprocess.run([exe, REFDATA, str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "shim net ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

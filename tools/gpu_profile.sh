@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py --config $CFG --steps 60 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+python $R/bench.py --full --config $CFG --steps 60 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
 tail -c 1500 $OUT/bench.json
 # the kernel-trace pass runs the SAME command as the bench line above (minus the CPU leg) so the timed launches can be compared 1:1: 3 windows of 60 frames
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o stats -- python $R/bench.py --config $CFG --steps 60 --warmup 20 --repeats 3 --no-cpu-baseline --no-trained-leg --no-fp32-leg --exchange-steps 0 > $OUT/stats.log 2>&1

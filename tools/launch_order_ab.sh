@@ -7,7 +7,7 @@ for cfg in 1 2; do
   echo "== configs[$cfg]" >> $OUT
   for rep in 1 2 3; do for lib in libdtrl libdtrl_cost1 libdtrl_cost2; do
     echo -n "$lib rep $rep: " >> $OUT
-    python bench.py --config $cfg --no-cpu-baseline --no-trained-leg --no-fp32-leg --exchange-steps 0 --no-rccl-leg --lib deepterrainrl_amd/lib/$lib.so 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --config $cfg --no-cpu-baseline --no-trained-leg --no-fp32-leg --exchange-steps 0 --no-rccl-leg --lib deepterrainrl_amd/lib/$lib.so 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read())
 print('%.3f M env-steps/s (min %.3f max %.3f)  %.3f ms/frame  kernel avg %.3f ms' % (d['value']/1e6, d['value_min']/1e6, d['value_max']/1e6, d['ms_per_step'], d['roofline']['kernel_avg_ms']))" >> $OUT 2>&1
   done; done

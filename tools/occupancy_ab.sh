@@ -11,7 +11,7 @@ run() {  # label, env assignments..., then bench args
   label=$1; shift
   for rep in 1 2; do
     echo -n "$label rep $rep: " >> $OUT
-    env "$@" python bench.py --no-cpu-baseline --no-trained-leg --exchange-steps 0 --no-rccl-leg $BARGS 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.3f M env-steps/s  %.3f ms/frame  kernel avg %.3f ms  resets/frame %.1f' % (d['value']/1e6, d['ms_per_step'], d['roofline']['kernel_avg_ms'], d['timed_window']['resets_per_frame']))" >> $OUT
+    env "$@" python bench.py --full --no-cpu-baseline --no-trained-leg --exchange-steps 0 --no-rccl-leg $BARGS 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.3f M env-steps/s  %.3f ms/frame  kernel avg %.3f ms  resets/frame %.1f' % (d['value']/1e6, d['ms_per_step'], d['roofline']['kernel_avg_ms'], d['timed_window']['resets_per_frame']))" >> $OUT
   done
 }
 for cfg in 1 2; do
