@@ -95,7 +95,7 @@ __device__ __forceinline__ void env_sync()
 inline void env_sync() {}      // (the lane-loop build runs a phase to its end before the next one starts)
 #endif
 
-enum ProfSection { kProfFK, kProfMass, kProfBias, kProfFact, kProfDetect, kProfRows, kProfFsub, kProfDelassus, kProfPgs, kProfFinish, kProfCtrl, kProfAction, kProfFrameIO, kProfTotal, kProfRowsSum, kProfSubsteps, kProfP1, kProfP2, kProfP3, kProfP4, kProfR0, kProfR1_6, kProfR7_12, kProfR13_18, kProfR19_24, kProfT0, kProfT1_6, kProfT7_12, kProfT13_18, kProfT19_24, kProfNNConv, kProfNNFcTerr, kProfNNRest, kProfNNEvals, kProfC_Fsm, kProfC_Feedback, kProfC_PdSetup, kProfC_PdSolve, kProfC_Grav, kProfC_Tail, kProfMax };
+enum ProfSection { kProfFK, kProfMass, kProfBias, kProfFact, kProfDetect, kProfRows, kProfFsub, kProfDelassus, kProfPgs, kProfFinish, kProfCtrl, kProfAction, kProfFrameIO, kProfTotal, kProfRowsSum, kProfSubsteps, kProfP1, kProfP2, kProfP3, kProfP4, kProfR0, kProfR1_6, kProfR7_12, kProfR13_18, kProfR19_24, kProfT0, kProfT1_6, kProfT7_12, kProfT13_18, kProfT19_24, kProfNNConv, kProfNNFcTerr, kProfNNRest, kProfNNEvals, kProfC_Fsm, kProfC_Feedback, kProfC_PdSetup, kProfC_PdSolve, kProfC_Grav, kProfC_Tail, kProfFsubR0, kProfFsubR1_6, kProfFsubR7_12, kProfFsubR13_18, kProfFsubR19_24, kProfMax };
 
 // hot, read-mostly model fields staged in LDS (per-substep readers only; the controller's once-per-env-step gains, torque
 // limits and body angles stay in the HBM/L2-resident DevModel)

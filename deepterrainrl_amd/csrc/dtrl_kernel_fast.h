@@ -252,6 +252,54 @@ __device__ __forceinline__ void usolve_regs_n(const real (&h)[D], real (&z)[NR])
 		fnma_lanes_lt<k>(z, h[k], zk);
 	});
 }
+// the first (largest) column k > i whose elimination updates entry i of a right-hand side; 0 = none (a leaf DoF: its entry is final as given)
+template <class Topo>
+constexpr int first_update_col(int i)
+{
+	for (int k = Topo::L + 1; k > i; --k) if (dof_coupled<Topo>(i, k)) return k;
+	return 0;
+}
+// Z_r = U^-1 Z_r in place for the rows r = 0 .. R of Z (the R constraint rows and the free right-hand side), ROW PER LANE: lane r walks its own row
+// (odd row stride: no bank conflicts), right-looking from the last DoF up. U(i, k) is wave-uniform, a broadcast LDS read of the packed triangle that
+// factorize_regs() left in Apk, so the R + 1 substitutions together cost the structurally non-zero updates once (129 FMAs for the dog, 89 for the raptor)
+// where usolve_regs_n() pays two v_readlane and an FMA per DoF and right-hand side. Entry i sees fma(-U(i, k), z_k, .) for k descending from the
+// initial value, as in forward_subst_rows() of dtrl_kernel.h and usolve_regs_n(); the updates left out are those with a structurally zero U(i, k).
+// An accumulator is read from the row just before its first update and stored when it is final, so only the frontier of the tree is live.
+template <class Topo, int kAhead = 1>
+__device__ __forceinline__ void usolve_rows(WSFast& ws, int R)
+{
+	constexpr int D = Topo::L + 2;
+	const int lane = static_cast<int>(threadIdx.x);
+	if (lane > R) return;
+	real* z = ws.Z[lane];
+	const real* U = ws.Apk;
+	real acc[D], u[D * (D - 1) / 2];   // (constant indices only: registers)
+	// the LDS reads column k needs: its U entries, the accumulators it opens, z_k itself when nothing updates it
+	auto fetch = [&](auto kc) {
+		constexpr int k = decltype(kc)::value;
+		static_for<0, k>([&](auto ic) {
+			constexpr int i = decltype(ic)::value;
+			if constexpr (dof_coupled<Topo>(i, k)) u[k * (k - 1) / 2 + i] = U[k * (k - 1) / 2 + i];
+			if constexpr (first_update_col<Topo>(i) == k) acc[i] = z[i];
+		});
+		if constexpr (first_update_col<Topo>(k) == 0) acc[k] = z[k];
+	};
+	static_for_down<D - kAhead, D>(fetch);
+	static_for_down<1, D>([&](auto kc) {
+		constexpr int k = decltype(kc)::value;
+		// one column per scheduling region (nothing crosses): the ILP scheduler would otherwise hoist the reads and spread the FMAs across the columns, and the
+		// substep loop would spill (one column of reads ahead and a full barrier: no scratch access in the substep loop of either instance)
+		__builtin_amdgcn_sched_barrier(0);
+		if constexpr (k - kAhead >= 1) fetch(std::integral_constant<int, k - kAhead>{});
+		const real zk = acc[k];
+		if constexpr (first_update_col<Topo>(k) != 0) z[k] = zk;
+		static_for_down<0, k>([&](auto ic) {
+			constexpr int i = decltype(ic)::value;
+			if constexpr (dof_coupled<Topo>(i, k)) acc[i] = fmadd(-u[k * (k - 1) / 2 + i], zk, acc[i]);
+		});
+	});
+	z[0] = acc[0];
+}
 // x = U^-T u: from DoF 0 down
 template <int D>
 __device__ __forceinline__ real utsolve_regs(const real (&h)[D], real u)
@@ -804,6 +852,12 @@ __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 	env_sync();
 }
 
+// substeps with at least this many constraint rows solve their right-hand sides row per lane (usolve_rows), the others with usolve_regs_n
+#ifndef DTRL_FSUB_ROWS_MIN_R
+#define DTRL_FSUB_ROWS_MIN_R 1
+#endif
+constexpr int kFsubRowsMinR = DTRL_FSUB_ROWS_MIN_R;
+
 template <class Topo>
 struct FastPath {
 	static constexpr int D = Topo::L + 2;
@@ -857,27 +911,42 @@ struct FastPath {
 				const real jr = dx * (-(y - mypy)) + dy * (x - mypx);
 				return on > 0 ? jr : -jr;
 			};
-			int r0 = 0;
-			for (; r0 + 4 <= R + 1; r0 += 4) {
-				real z[4] = {rhs_of(r0), rhs_of(r0 + 1), rhs_of(r0 + 2), rhs_of(r0 + 3)};
-				usolve_regs_n<D, 4>(hrow, z);
+			if (R < kFsubRowsMinR) {
+				// few right-hand sides (R = 0, airborne: one): the lane = DoF broadcast chains in registers, in batches of 4 / 2 / 1, are cheaper than the row form
+				int r0 = 0;
+				if constexpr (kFsubRowsMinR >= 4) {
+					for (; r0 + 4 <= R + 1; r0 += 4) {
+						real z[4] = {rhs_of(r0), rhs_of(r0 + 1), rhs_of(r0 + 2), rhs_of(r0 + 3)};
+						usolve_regs_n<D, 4>(hrow, z);
 #pragma unroll
-				for (int j = 0; j < 4; ++j) if (lane < D) ws.Z[r0 + j][lane] = z[j];
-			}
-			if (r0 + 2 <= R + 1) {
-				real z[2] = {rhs_of(r0), rhs_of(r0 + 1)};
-				usolve_regs_n<D, 2>(hrow, z);
-				if (lane < D) { ws.Z[r0][lane] = z[0]; ws.Z[r0 + 1][lane] = z[1]; }
-				r0 += 2;
-			}
-			if (r0 <= R) {
-				real z[1] = {rhs_of(r0)};
-				usolve_regs_n<D, 1>(hrow, z);
-				if (lane < D) ws.Z[r0][lane] = z[0];
+						for (int j = 0; j < 4; ++j) if (lane < D) ws.Z[r0 + j][lane] = z[j];
+					}
+				}
+				if constexpr (kFsubRowsMinR >= 2) {
+					if (r0 + 2 <= R + 1) {
+						real z[2] = {rhs_of(r0), rhs_of(r0 + 1)};
+						usolve_regs_n<D, 2>(hrow, z);
+						if (lane < D) { ws.Z[r0][lane] = z[0]; ws.Z[r0 + 1][lane] = z[1]; }
+						r0 += 2;
+					}
+				}
+				if (r0 <= R) {
+					real z[1] = {rhs_of(r0)};
+					usolve_regs_n<D, 1>(hrow, z);
+					if (lane < D) ws.Z[r0][lane] = z[0];
+				}
+			} else {
+				// the R + 1 right-hand sides into Z unsolved (lane = DoF), then solved in place with lane = row
+				for (int r = 0; r <= R; ++r) { const real v = rhs_of(r); if (lane < D) ws.Z[r][lane] = v; }
+				env_sync();
+				usolve_rows<Topo>(ws, R);
 			}
 			if (lane < D) ws.dinv[lane] = dinv;   // the Delassus product reads 1/d per DoF from LDS
 			env_sync();
 			PROF_ADD(ws, kProfFsub);
+#if defined(DTRL_PROFILE)
+			PROF_ADD(ws, kProfFsubR0 + (R == 0 ? 0 : (R <= 6 ? 1 : (R <= 12 ? 2 : (R <= 18 ? 3 : 4)))));
+#endif
 		}
 		if (R > 0) {
 			{ PROF_T0(); build_delassus_fast<D>(ws, h, dinv); PROF_ADD(ws, kProfDelassus); }
