@@ -122,24 +122,6 @@ __device__ __forceinline__ void fnma_lanes_ge(real& acc, real a, real b)
 	asm("s_lshl_b64 %2, -1, %5\n\ts_and_saveexec_b64 %1, %2\n\t" DTRL_VFMA " %0, -%3, %4, %0\n\ts_mov_b64 exec, %1"
 	    : "+v"(acc), "=&s"(sv), "=&s"(m) : "v"(a), "s"(b), "n"(J) : "scc");
 }
-template <int J>
-__device__ __forceinline__ void fnma_lanes_ge(real (&acc)[1], real a, const real (&b)[1]) { fnma_lanes_ge<J>(acc[0], a, b[0]); }
-template <int J>
-__device__ __forceinline__ void fnma_lanes_ge(real (&acc)[2], real a, const real (&b)[2])
-{
-	unsigned long long sv, m;
-	asm("s_lshl_b64 %3, -1, %7\n\ts_and_saveexec_b64 %2, %3\n\t" DTRL_VFMA " %0, -%4, %5, %0\n\t" DTRL_VFMA " %1, -%4, %6, %1\n\ts_mov_b64 exec, %2"
-	    : "+v"(acc[0]), "+v"(acc[1]), "=&s"(sv), "=&s"(m) : "v"(a), "s"(b[0]), "s"(b[1]), "n"(J) : "scc");
-}
-template <int J>
-__device__ __forceinline__ void fnma_lanes_ge(real (&acc)[4], real a, const real (&b)[4])
-{
-	unsigned long long sv, m;
-	asm("s_lshl_b64 %5, -1, %11\n\ts_and_saveexec_b64 %4, %5\n\t" DTRL_VFMA " %0, -%6, %7, %0\n\t" DTRL_VFMA " %1, -%6, %8, %1\n\t"
-	    "" DTRL_VFMA " %2, -%6, %9, %2\n\t" DTRL_VFMA " %3, -%6, %10, %3\n\ts_mov_b64 exec, %4"
-	    : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "=&s"(sv), "=&s"(m)
-	    : "v"(a), "s"(b[0]), "s"(b[1]), "s"(b[2]), "s"(b[3]), "n"(J) : "scc");
-}
 // acc = fma(-a, b, acc) on lanes < I
 template <int I>
 __device__ __forceinline__ void fnma_lanes_lt(real& acc, real a, real b)
@@ -162,33 +144,6 @@ __device__ __forceinline__ void mov_lanes_lt(real& dst, real src)
 	unsigned long long sv, m;
 	asm("s_bfm_b64 %2, %4, 0\n\ts_and_saveexec_b64 %1, %2\n\t" DTRL_VMOV " %0, %3\n\ts_mov_b64 exec, %1"
 	    : "+v"(dst), "=&s"(sv), "=&s"(m) : "v"(src), "n"(I) : "scc");
-}
-// dst = src on lanes >= J
-template <int J>
-__device__ __forceinline__ void mov_lanes_ge(real& dst, real src)
-{
-	unsigned long long sv, m;
-	asm("s_lshl_b64 %2, -1, %4\n\ts_and_saveexec_b64 %1, %2\n\t" DTRL_VMOV " %0, %3\n\ts_mov_b64 exec, %1"
-	    : "+v"(dst), "=&s"(sv), "=&s"(m) : "v"(src), "n"(J) : "scc");
-}
-
-template <int I>
-__device__ __forceinline__ void fnma_lanes_lt(real (&acc)[1], real a, const real (&b)[1]) { fnma_lanes_lt<I>(acc[0], a, b[0]); }
-template <int I>
-__device__ __forceinline__ void fnma_lanes_lt(real (&acc)[2], real a, const real (&b)[2])
-{
-	unsigned long long sv, m;
-	asm("s_bfm_b64 %3, %7, 0\n\ts_and_saveexec_b64 %2, %3\n\t" DTRL_VFMA " %0, -%4, %5, %0\n\t" DTRL_VFMA " %1, -%4, %6, %1\n\ts_mov_b64 exec, %2"
-	    : "+v"(acc[0]), "+v"(acc[1]), "=&s"(sv), "=&s"(m) : "v"(a), "s"(b[0]), "s"(b[1]), "n"(I) : "scc");
-}
-template <int I>
-__device__ __forceinline__ void fnma_lanes_lt(real (&acc)[4], real a, const real (&b)[4])
-{
-	unsigned long long sv, m;
-	asm("s_bfm_b64 %5, %11, 0\n\ts_and_saveexec_b64 %4, %5\n\t" DTRL_VFMA " %0, -%6, %7, %0\n\t" DTRL_VFMA " %1, -%6, %8, %1\n\t"
-	    "" DTRL_VFMA " %2, -%6, %9, %2\n\t" DTRL_VFMA " %3, -%6, %10, %3\n\ts_mov_b64 exec, %4"
-	    : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "=&s"(sv), "=&s"(m)
-	    : "v"(a), "s"(b[0]), "s"(b[1]), "s"(b[2]), "s"(b[3]), "n"(I) : "scc");
 }
 
 // in-register H = U D U^T, last DoF first; returns 1/d_lane. Same elimination order and operations as factorize(), minus the
@@ -239,19 +194,6 @@ __device__ __forceinline__ real usolve_regs(const real (&h)[D], real z)
 	});
 	return z;
 }
-// NR right-hand sides at once: the substitution is a 22-step dependent chain per right-hand side, so interleaving independent
-// chains divides the exposed latency at the same instruction count (and the NR updates of a step share one EXEC window)
-template <int D, int NR>
-__device__ __forceinline__ void usolve_regs_n(const real (&h)[D], real (&z)[NR])
-{
-	static_for_down<1, D>([&](auto kc) {
-		constexpr int k = decltype(kc)::value;
-		real zk[NR];
-#pragma unroll
-		for (int j = 0; j < NR; ++j) zk[j] = bcast(z[j], k);
-		fnma_lanes_lt<k>(z, h[k], zk);
-	});
-}
 // the first (largest) column k > i whose elimination updates entry i of a right-hand side; 0 = none (a leaf DoF: its entry is final as given)
 template <class Topo>
 constexpr int first_update_col(int i)
@@ -262,8 +204,8 @@ constexpr int first_update_col(int i)
 // Z_r = U^-1 Z_r in place for the rows r = 0 .. R of Z (the R constraint rows and the free right-hand side), ROW PER LANE: lane r walks its own row
 // (odd row stride: no bank conflicts), right-looking from the last DoF up. U(i, k) is wave-uniform, a broadcast LDS read of the packed triangle that
 // factorize_regs() left in Apk, so the R + 1 substitutions together cost the structurally non-zero updates once (129 FMAs for the dog, 89 for the raptor)
-// where usolve_regs_n() pays two v_readlane and an FMA per DoF and right-hand side. Entry i sees fma(-U(i, k), z_k, .) for k descending from the
-// initial value, as in forward_subst_rows() of dtrl_kernel.h and usolve_regs_n(); the updates left out are those with a structurally zero U(i, k).
+// where the lane = DoF chain of usolve_regs() pays two v_readlane and an FMA per DoF and right-hand side. Entry i sees fma(-U(i, k), z_k, .) for k descending from the
+// initial value, as in forward_subst_rows() of dtrl_kernel.h and usolve_regs(); the updates left out are those with a structurally zero U(i, k).
 // An accumulator is read from the row just before its first update and stored when it is final, so only the frontier of the tree is live.
 template <class Topo, int kAhead = 1>
 __device__ __forceinline__ void usolve_rows(WSFast& ws, int R)
@@ -637,6 +579,36 @@ __device__ __forceinline__ real wave_shr1(real v)
 	return __hiloint2double(hi, lo);
 #endif
 }
+// ONE row update of the Gauss-Seidel chain, the only spelling of it: project lane r's candidate, broadcast its delta, apply it to every lane's residual through the
+// lane's Delassus entry a_sr = A(lane, r). The unrolled sequences and the plain loop of pgs_solve_fast() all call it, which is what keeps them -- and pgs_solve() of
+// dtrl_kernel.h -- on the same bits. The kinds differ in the projection only:
+//   kPgsRowNormal    limit and normal rows, onto [0, inf): fma, max, sub, readlane, fma
+//   kPgsRowFriction  friction rows that are not held, onto [lo, hi] = +-mu lambda_n, LANE REGISTERS set once per pass (every normal row is final for the sweep by then):
+//                    fma, max, min, sub, readlane, fma
+//   kPgsRowGeneric   the row step of rounds 1-4, bounds evaluated per step (normal rows [0, inf), tangent rows +-mu * lambda of the row before it, a DPP move, a multiply,
+//                    a compare and selects more than the two above). Only -warm_start= 0 (the round-4 contact model, an ablation) still runs it.
+//                    (A wave-uniform branch on the kind of row r instead of the selects was measured twice, round 1 and round 4 under the ILP scheduler: -6 % / -3 %.)
+enum PgsRowKind { kPgsRowNormal, kPgsRowFriction, kPgsRowGeneric };
+template <PgsRowKind kKind>
+__device__ __forceinline__ void pgs_row_step(real& w, real& lam, real rinv, real a_sr, int r, int lane, bool tang, real lo, real hi)
+{
+	real nl;
+	if constexpr (kKind == kPgsRowGeneric) {
+		const real lim = kMu * wave_shr1(lam);
+		const real glo = tang ? -lim : 0.0, ghi = tang ? lim : __builtin_huge_val();
+		nl = fmin(fmax(fmadd(-w, rinv, lam), glo), ghi);
+	} else {
+		nl = fmadd(-w, rinv, lam);
+		if constexpr (kKind == kPgsRowFriction) nl = fmin(fmax(nl, lo), hi); else nl = fmax(nl, 0.0);   // (pgs_solve(): normal and limit rows are projected onto [0, inf))
+	}
+	const real dl = bcast(nl - lam, r);
+	if (lane == r) lam = nl;
+	w = fmadd(a_sr, dl, w);
+}
+// The unrolled row sequences (substeps with up to K rows, the lane's Delassus row in registers). They are NESTED (row r + 1 sits inside `if (r < R)` of row r), so a
+// substep leaves them at its first absent row with one scalar compare + branch per row that exists: tested row by row, the absent rows cost 4 dependent SALU
+// instructions each, ten sweeps per substep -- +4 k cycles on the typical substep with 3 rows (round 4).
+// a[r] = A(lane, r) for the rows that exist
 template <int r, int K>
 __device__ __forceinline__ void pgs_rows_load(real (&a)[K], const WSFast& ws, int lane, bool mine, int R)
 {
@@ -648,78 +620,36 @@ __device__ __forceinline__ void pgs_rows_load(real (&a)[K], const WSFast& ws, in
 		}
 	}
 }
-// one sweep over rows r, r + 1, ...: rows below K read the lane's Delassus entry from registers, rows K .. kMaxRows - 1 (the tail only characters lying on the
-// ground reach) from LDS, fetched one row update ahead (a_pref) so that the load's latency sits under the previous row's dependent chain
-// The generic row step of rounds 1-4: ONE interleaved sweep over all rows, the bounds of row r evaluated per step (normal rows [0, inf), tangent rows +-mu * lambda of the
-// row before it). Only -warm_start= 0 (the round-4 contact model, an ablation) still runs it; the shipped model's sweep is the two passes below.
-template <int r, int K, int kEnd>
-__device__ __forceinline__ void pgs_rows_sweep(const real (&a)[K], const WSFast& ws, real& w, real& lam, real rinv, bool tang, bool mine, unsigned long long actR, int lane, int R, real a_pref)
+// -warm_start= 0: one interleaved sweep over the rows r, r + 1, ... of actR
+template <int r, int K>
+__device__ __forceinline__ void pgs_rows_sweep(const real (&a)[K], real& w, real& lam, real rinv, bool tang, unsigned long long actR, int lane, int R)
 {
-	if constexpr (r < kEnd) {
+	if constexpr (r < K) {
 		if (r < R) {
-			real a_sr;
-			if constexpr (r < K) a_sr = a[r]; else a_sr = a_pref;
-			real a_nx = 0.0;
-			if constexpr (r + 1 >= K && r + 1 < kEnd) {
-				constexpr int rn = r + 1;
-				const int mx = lane > rn ? lane : rn, mn = lane < rn ? lane : rn;
-				a_nx = ws.Apk[(mine && rn < R) ? mx * (mx + 1) / 2 + mn : 0];
-			}
-			if ((actR >> r) & 1ull) {
-				// (a wave-uniform branch on the kind of row r -- normal rows need neither the friction bound nor the upper clamp -- was measured twice, round 1 and
-				// round 4 under the ILP scheduler: -6 % / -3 %. The selects are cheaper than the branch.)
-				const real lim = kMu * wave_shr1(lam);
-				const real lo = tang ? -lim : 0.0, hi = tang ? lim : __builtin_huge_val();
-				const real nl = fmin(fmax(fmadd(-w, rinv, lam), lo), hi);
-				const real dl = bcast(nl - lam, r);
-				if (lane == r) lam = nl;
-				w = fmadd(a_sr, dl, w);
-			}
-			pgs_rows_sweep<r + 1, K, kEnd>(a, ws, w, lam, rinv, tang, mine, actR, lane, R, a_nx);
+			if ((actR >> r) & 1ull) pgs_row_step<kPgsRowGeneric>(w, lam, rinv, a[r], r, lane, tang, 0.0, 0.0);
+			pgs_rows_sweep<r + 1, K>(a, w, lam, rinv, tang, actR, lane, R);
 		}
 	}
 }
-// The two passes of a sweep under Bullet's contact persistence as their own row steps (round 5). kFric = false: limit and normal rows, projection onto [0, inf) -- fma, max,
-// sub, readlane, fma. kFric = true: the friction rows that are not held; their bounds +-mu lambda_n are LANE REGISTERS set once per pass (every normal row is final for
-// the sweep by then) -- fma, max, min, sub, readlane, fma. Same operations on the same operands as the generic step above, without its per-step DPP move, multiply,
-// compare and selects.
-template <bool kFric, int r, int K, int kEnd>
-__device__ __forceinline__ void pgs_rows_pass(const real (&a)[K], const WSFast& ws, real& w, real& lam, real rinv, real lo, real hi, bool mine, unsigned long long rows, int lane, int R, real a_pref)
+// one of the two passes of a sweep under Bullet's contact persistence (round 5) over the rows r, r + 1, ... of `rows`
+template <PgsRowKind kKind, int r, int K>
+__device__ __forceinline__ void pgs_rows_pass(const real (&a)[K], real& w, real& lam, real rinv, real lo, real hi, unsigned long long rows, int lane, int R)
 {
-	if constexpr (r < kEnd) {
+	if constexpr (r < K) {
 		if (r < R) {
-			real a_sr;
-			if constexpr (r < K) a_sr = a[r]; else a_sr = a_pref;
-			real a_nx = 0.0;
-			if constexpr (r + 1 >= K && r + 1 < kEnd) {
-				constexpr int rn = r + 1;
-				const int mx = lane > rn ? lane : rn, mn = lane < rn ? lane : rn;
-				a_nx = ws.Apk[(mine && rn < R) ? mx * (mx + 1) / 2 + mn : 0];
-			}
-			if ((rows >> r) & 1ull) {
-				real nl = fmadd(-w, rinv, lam);
-				if constexpr (kFric) nl = fmin(fmax(nl, lo), hi); else nl = fmax(nl, 0.0);   // (pgs_solve(): normal and limit rows are projected onto [0, inf))
-				const real dl = bcast(nl - lam, r);
-				if (lane == r) lam = nl;
-				w = fmadd(a_sr, dl, w);
-			}
-			pgs_rows_pass<kFric, r + 1, K, kEnd>(a, ws, w, lam, rinv, lo, hi, mine, rows, lane, R, a_nx);
+			if ((rows >> r) & 1ull) pgs_row_step<kKind>(w, lam, rinv, a[r], r, lane, false, lo, hi);
+			pgs_rows_pass<kKind, r + 1, K>(a, w, lam, rinv, lo, hi, rows, lane, R);
 		}
 	}
 }
 // w += A lambda_0 (the warm-started impulses), column by column in row order: the same fused operations as pgs_solve()'s first loop
-template <int r, int K, int kEnd>
-__device__ __forceinline__ void pgs_rows_warm(const real (&a)[K], const WSFast& ws, real& w, real lam, bool mine, unsigned long long nz, int lane, int R)
+template <int r, int K>
+__device__ __forceinline__ void pgs_rows_warm(const real (&a)[K], real& w, real lam, unsigned long long nz, int R)
 {
-	if constexpr (r < kEnd) {
+	if constexpr (r < K) {
 		if (r < R) {
-			if ((nz >> r) & 1ull) {   // (rows that start from zero -- limit rows, link--link rows, new contacts -- add exactly nothing)
-				real a_sr;
-				if constexpr (r < K) a_sr = a[r];
-				else { const int mx = lane > r ? lane : r, mn = lane < r ? lane : r; a_sr = ws.Apk[mine ? mx * (mx + 1) / 2 + mn : 0]; }
-				w = fmadd(a_sr, bcast(lam, r), w);
-			}
-			pgs_rows_warm<r + 1, K, kEnd>(a, ws, w, lam, mine, nz, lane, R);
+			if ((nz >> r) & 1ull) w = fmadd(a[r], bcast(lam, r), w);   // (rows that start from zero -- limit rows, link--link rows, new contacts -- add exactly nothing)
+			pgs_rows_warm<r + 1, K>(a, w, lam, nz, R);
 		}
 	}
 }
@@ -743,7 +673,7 @@ __device__ __forceinline__ void warm_match_fast(WSFast& ws)
 	if (lane == 0) ws.st.ws_R = R;
 	// (no fence behind the writes either: their next reader is the Gauss-Seidel solve, several phase boundaries further on)
 }
-template <int kPgsRegRows, bool kTailInSweep>
+template <int kPgsRegRows>
 __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 {
 	const int lane = opaque_lane();
@@ -760,52 +690,45 @@ __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 	const unsigned long long tmask = __ballot(tang);
 	const unsigned long long nz_l0 = __ballot(lam != 0.0);
 	const bool any_l0 = nz_l0 != 0ull;
-	// The lane's Delassus row: the first kPgsRegRows entries (per skeleton, dtrl_topo.h; eight until round 3, twelve in round 3) live in registers for all sweeps
-	// -- no LDS read and no packed-index arithmetic per row update -- and the entries of the tail rows come from LDS one update ahead. Same operations on the
-	// same values in the same order as pgs_solve() of dtrl_kernel.h. The rare substeps with many rows matter out of proportion: they are what the slowest envs of
-	// a launch do in EVERY substep (a character lying on the ground), and a launch lasts as long as its slowest env.
-	// The row sequences are NESTED (row r + 1 sits inside `if (r < R)` of row r), so a substep leaves them at its first absent row with one scalar compare + branch
-	// per row that exists: tested row by row, the 24 - R absent rows cost 4 dependent SALU instructions each, ten sweeps per substep -- +4 k cycles on the typical
-	// substep with 3 rows (round 4).
-	// Per skeleton (dtrl_topo.h, same-box A/B in profiles/r04_pgs_rows_ab.txt): the dog's instance keeps 20 rows in registers and runs the tail rows inside the same
-	// unrolled sweep (kTailInSweep); the raptor's pays for that longer sweep body with spills, keeps 16 and sends a substep with more rows through the plain loop below.
-	if (kTailInSweep || R <= kPgsRegRows) {
+	// Substeps with up to kPgsRegRows rows (per skeleton, dtrl_topo.h: every substep of the dog's instance) keep the lane's Delassus row in registers for all sweeps
+	// -- no LDS read and no packed-index arithmetic per row update -- and run the unrolled, nested row sequences. Same operations on the same values in the same order
+	// as pgs_solve() of dtrl_kernel.h. The rare substeps with many rows matter out of proportion: they are what the slowest envs of a launch do in EVERY substep (a
+	// character lying on the ground), and a launch lasts as long as its slowest env.
+	// (the first test is a compile-time constant: an instance whose register rows cover every row count does not contain the plain loop)
+	if (kPgsRegRows == kMaxRows || R <= kPgsRegRows) {
 		real a[kPgsRegRows];
 		pgs_rows_load<0, kPgsRegRows>(a, ws, lane, mine, R);
 		const unsigned long long actR = act & ((R < 64) ? ((1ull << R) - 1ull) : ~0ull);
-		constexpr int kEnd = kTailInSweep ? kMaxRows : kPgsRegRows;
-		if (any_l0) pgs_rows_warm<0, kPgsRegRows, kEnd>(a, ws, w, lam, mine, nz_l0, lane, R);
+		if (any_l0) pgs_rows_warm<0, kPgsRegRows>(a, w, lam, nz_l0, R);
 		const unsigned long long pass0 = warm ? (actR & ~tmask) : actR, pass1 = actR & tmask;
 		if (warm) {
 			// a pass leaves the nested row sequence behind its LAST row (not at R): the rows of the other pass that follow it are not even looked at
-			// (with tail rows in the sweep the row count also guards the LDS prefetch of the next column: that instance keeps R)
-			constexpr bool kPrefetch = kTailInSweep && kPgsRegRows < kMaxRows;
-			const int end0 = (kPrefetch || pass0 == 0ull) ? R : 64 - __builtin_clzll(pass0);
+			const int end0 = (pass0 == 0ull) ? R : 64 - __builtin_clzll(pass0);
 #pragma unroll 1
 			for (int it = 0; it < kPgsIters; ++it) {
-				if (pass0 != 0ull) pgs_rows_pass<false, 0, kPgsRegRows, kEnd>(a, ws, w, lam, rinv, 0.0, 0.0, mine, pass0, lane, end0, 0.0);
+				if (pass0 != 0ull) pgs_rows_pass<kPgsRowNormal, 0, kPgsRegRows>(a, w, lam, rinv, 0.0, 0.0, pass0, lane, end0);
 				// friction pass: every normal row is final for this sweep, so the bounds +-mu lambda_n are fixed for the pass, and which friction rows Bullet's rule HOLDS
 				// (normal row without impulse: their update is exactly zero) is known up front -- they leave the pass instead of walking through a row step each
 				const real ln = wave_shr1(lam);   // (all lanes: a DPP move under a narrowed EXEC does not see the lanes that are switched off)
 				const real lim = kMu * ln;
 				const unsigned long long rows = pass1 & __ballot(tang && ln > kHoldEps);
-				if (rows != 0ull) pgs_rows_pass<true, 0, kPgsRegRows, kEnd>(a, ws, w, lam, rinv, -lim, lim, mine, rows, lane, kPrefetch ? R : 64 - __builtin_clzll(rows), 0.0);
+				if (rows != 0ull) pgs_rows_pass<kPgsRowFriction, 0, kPgsRegRows>(a, w, lam, rinv, -lim, lim, rows, lane, 64 - __builtin_clzll(rows));
 			}
 		} else {
 #pragma unroll 1
-			for (int it = 0; it < kPgsIters; ++it) pgs_rows_sweep<0, kPgsRegRows, kEnd>(a, ws, w, lam, rinv, tang, mine, actR, lane, R, 0.0);   // (-warm_start= 0: one interleaved sweep, rounds 1-4)
+			for (int it = 0; it < kPgsIters; ++it) pgs_rows_sweep<0, kPgsRegRows>(a, w, lam, rinv, tang, actR, lane, R);
 		}
 		if (mine) ws.st.ws_lam[lane] = lam;
 		env_sync();
 		return;
 	}
+	// more rows than register rows: the plain loop, the lane's entry of the next row update's column fetched from LDS one update ahead
+	// (the fetch is written out in each of the three loops: folded into a helper or a lambda, both instances of the kernel come out with a different register allocation)
 	const int tri = lane * (lane + 1) / 2;
-	const real inf = __builtin_huge_val();
 	if (any_l0) for (int r = 0; r < R; ++r) if ((nz_l0 >> r) & 1ull) { const int mx = lane > r ? lane : r, mn = lane < r ? lane : r; w = fmadd(ws.Apk[mine ? mx * (mx + 1) / 2 + mn : 0], bcast(lam, r), w); }
-	real a_nx = mine ? ws.Apk[tri] : 0.0;   // column 0; the column of the next row update is fetched one update ahead
+	real a_nx = mine ? ws.Apk[tri] : 0.0;   // column 0
 	const unsigned long long actR = act & ((R < 64) ? ((1ull << R) - 1ull) : ~0ull);
 	if (warm) {
-		// the two passes with their own row steps, as in the unrolled form above (pgs_rows_pass)
 		const unsigned long long pass0 = actR & ~tmask, pass1 = actR & tmask;
 		for (int it = 0; it < kPgsIters; ++it) {
 			for (int r = 0; r < R; ++r) {
@@ -813,10 +736,7 @@ __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 				const int rn = (r + 1 < R) ? r + 1 : 0;
 				{ const int mx = lane > rn ? lane : rn, mn = lane < rn ? lane : rn; a_nx = ws.Apk[mine ? mx * (mx + 1) / 2 + mn : 0]; }   // branch-free packed index
 				if (!((pass0 >> r) & 1ull)) continue;
-				const real nl = fmax(fmadd(-w, rinv, lam), 0.0);
-				const real dl = bcast(nl - lam, r);
-				if (lane == r) lam = nl;
-				w = fmadd(a_sr, dl, w);
+				pgs_row_step<kPgsRowNormal>(w, lam, rinv, a_sr, r, lane, false, 0.0, 0.0);
 			}
 			const real ln = wave_shr1(lam);
 			const real lim = kMu * ln;
@@ -826,25 +746,17 @@ __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 				const int rn = (r + 1 < R) ? r + 1 : 0;
 				{ const int mx = lane > rn ? lane : rn, mn = lane < rn ? lane : rn; a_nx = ws.Apk[mine ? mx * (mx + 1) / 2 + mn : 0]; }
 				if (!((rows >> r) & 1ull)) continue;
-				const real nl = fmin(fmax(fmadd(-w, rinv, lam), -lim), lim);
-				const real dl = bcast(nl - lam, r);
-				if (lane == r) lam = nl;
-				w = fmadd(a_sr, dl, w);
+				pgs_row_step<kPgsRowFriction>(w, lam, rinv, a_sr, r, lane, false, -lim, lim);
 			}
 		}
 	} else {
 		for (int it = 0; it < kPgsIters; ++it) {
-			for (int r = 0; r < R; ++r) {   // (-warm_start= 0: one interleaved sweep, rounds 1-4)
+			for (int r = 0; r < R; ++r) {
 				const real a_sr = a_nx;
 				const int rn = (r + 1 < R) ? r + 1 : 0;
 				{ const int mx = lane > rn ? lane : rn, mn = lane < rn ? lane : rn; a_nx = ws.Apk[mine ? mx * (mx + 1) / 2 + mn : 0]; }   // branch-free packed index
 				if (!((act >> r) & 1ull)) continue;
-				const real lim = kMu * wave_shr1(lam);
-				const real lo = tang ? -lim : 0.0, hi = tang ? lim : inf;
-				const real nl = fmin(fmax(fmadd(-w, rinv, lam), lo), hi);
-				const real dl = bcast(nl - lam, r);
-				if (lane == r) lam = nl;
-				w = fmadd(a_sr, dl, w);
+				pgs_row_step<kPgsRowGeneric>(w, lam, rinv, a_sr, r, lane, tang, 0.0, 0.0);
 			}
 		}
 	}
@@ -852,12 +764,10 @@ __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 	env_sync();
 }
 
-// substeps with at least this many constraint rows solve their right-hand sides row per lane (usolve_rows), the others with usolve_regs_n
-#ifndef DTRL_FSUB_ROWS_MIN_R
-#define DTRL_FSUB_ROWS_MIN_R 1
+#if defined(DTRL_PROFILE)
+// constraint-row bucket of the per-bucket counters (kProfFsubR0, kProfR0, kProfT0): 0 rows, 1-6, 7-12, 13-18, 19+
+__device__ __forceinline__ int prof_row_bucket(int R) { return R == 0 ? 0 : (R <= 6 ? 1 : (R <= 12 ? 2 : (R <= 18 ? 3 : 4))); }
 #endif
-constexpr int kFsubRowsMinR = DTRL_FSUB_ROWS_MIN_R;
-
 template <class Topo>
 struct FastPath {
 	static constexpr int D = Topo::L + 2;
@@ -911,29 +821,12 @@ struct FastPath {
 				const real jr = dx * (-(y - mypy)) + dy * (x - mypx);
 				return on > 0 ? jr : -jr;
 			};
-			if (R < kFsubRowsMinR) {
-				// few right-hand sides (R = 0, airborne: one): the lane = DoF broadcast chains in registers, in batches of 4 / 2 / 1, are cheaper than the row form
-				int r0 = 0;
-				if constexpr (kFsubRowsMinR >= 4) {
-					for (; r0 + 4 <= R + 1; r0 += 4) {
-						real z[4] = {rhs_of(r0), rhs_of(r0 + 1), rhs_of(r0 + 2), rhs_of(r0 + 3)};
-						usolve_regs_n<D, 4>(hrow, z);
-#pragma unroll
-						for (int j = 0; j < 4; ++j) if (lane < D) ws.Z[r0 + j][lane] = z[j];
-					}
-				}
-				if constexpr (kFsubRowsMinR >= 2) {
-					if (r0 + 2 <= R + 1) {
-						real z[2] = {rhs_of(r0), rhs_of(r0 + 1)};
-						usolve_regs_n<D, 2>(hrow, z);
-						if (lane < D) { ws.Z[r0][lane] = z[0]; ws.Z[r0 + 1][lane] = z[1]; }
-						r0 += 2;
-					}
-				}
-				if (r0 <= R) {
-					real z[1] = {rhs_of(r0)};
-					usolve_regs_n<D, 1>(hrow, z);
-					if (lane < D) ws.Z[r0][lane] = z[0];
+			if (R < 1) {
+				// airborne, one right-hand side: the lane = DoF broadcast chain in registers is cheaper than the row form
+				// (spelled through rhs_of() under a second test of R: with `R == 0` and rhs0 used directly the compiler allocates the substep loop differently and spills in it)
+				if (0 <= R) {
+					const real z = usolve_regs<D>(hrow, rhs_of(0));
+					if (lane < D) ws.Z[0][lane] = z;
 				}
 			} else {
 				// the R + 1 right-hand sides into Z unsolved (lane = DoF), then solved in place with lane = row
@@ -945,12 +838,12 @@ struct FastPath {
 			env_sync();
 			PROF_ADD(ws, kProfFsub);
 #if defined(DTRL_PROFILE)
-			PROF_ADD(ws, kProfFsubR0 + (R == 0 ? 0 : (R <= 6 ? 1 : (R <= 12 ? 2 : (R <= 18 ? 3 : 4)))));
+			PROF_ADD(ws, kProfFsubR0 + prof_row_bucket(R));
 #endif
 		}
 		if (R > 0) {
 			{ PROF_T0(); build_delassus_fast<D>(ws, h, dinv); PROF_ADD(ws, kProfDelassus); }
-			{ PROF_T0(); pgs_solve_fast<Topo::kPgsRegRows, Topo::kPgsTailInSweep>(ws); PROF_ADD(ws, kProfPgs); }
+			{ PROF_T0(); pgs_solve_fast<Topo::kPgsRegRows>(ws); PROF_ADD(ws, kProfPgs); }
 		}
 		{
 			PROF_T0();
@@ -966,7 +859,7 @@ struct FastPath {
 			PROF_ADD(ws, kProfFinish);
 		}
 #if defined(DTRL_PROFILE)
-		if (threadIdx.x == 0) { ws.prof[kProfRowsSum] += R; ws.prof[kProfSubsteps] += 1; const int bk = R == 0 ? 0 : (R <= 6 ? 1 : (R <= 12 ? 2 : (R <= 18 ? 3 : 4))); ws.prof[kProfR0 + bk] += 1; ws.prof[kProfT0 + bk] += __builtin_readcyclecounter() - prof_sub_t0; }
+		if (threadIdx.x == 0) { ws.prof[kProfRowsSum] += R; ws.prof[kProfSubsteps] += 1; const int bk = prof_row_bucket(R); ws.prof[kProfR0 + bk] += 1; ws.prof[kProfT0 + bk] += __builtin_readcyclecounter() - prof_sub_t0; }
 #endif
 	}
 	static __device__ void pd_solve(WSFast& ws, real dt)
