@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "dtrl_get_ctrl", "dtrl_sample_ground", "dtrl_eval_stats", "dtrl_dims", "dtrl_kernel_time_ms", "dtrl_last_error", "dtrl_version",
     "dtrl_terrain_build", "dtrl_terrain_load_file", "dtrl_args_parse_string",
     "dtrl_drain_tuples_device", "dtrl_tuple_stats", "dtrl_set_policy_device", "dtrl_get_dist_log", "dtrl_reset_avg_dist", "dtrl_write_dist_log", "dtrl_get_ground_window", "dtrl_drain_tuples_packed", "dtrl_get_policy_output", "dtrl_set_tuple_pipelining", "dtrl_step_end_begin", "dtrl_command_action", "dtrl_side_stream", "dtrl_step_poll", "dtrl_set_policy_device_on", "dtrl_set_policy_device_async",
+    "dtrl_snapshot_save", "dtrl_snapshot_restore", "dtrl_clone_envs", "dtrl_snapshot_export", "dtrl_snapshot_import", "dtrl_snapshot_info", "dtrl_snapshot_free",
 ]
 
 
@@ -126,6 +127,13 @@ def _bind(path):
     L.dtrl_get_dist_log.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.dtrl_reset_avg_dist.argtypes = [vp]
     L.dtrl_write_dist_log.argtypes = [vp, C.c_char_p]
+    L.dtrl_snapshot_save.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+    L.dtrl_snapshot_restore.argtypes = [vp, vp, vp, C.c_int]
+    L.dtrl_clone_envs.argtypes = [vp, vp, vp, C.c_int]
+    L.dtrl_snapshot_export.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.dtrl_snapshot_import.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
+    L.dtrl_snapshot_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.dtrl_snapshot_free.argtypes = [vp]
     L.dtrl_last_error.restype = C.c_char_p
     L.dtrl_last_error.argtypes = [vp]
     L.dtrl_version.restype = C.c_char_p
@@ -134,6 +142,104 @@ def _bind(path):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# ---- env snapshots: the layout of dtrl_types.h EnvState and of dtrl_engine.h SnapHeader, for reading or editing an exported blob ----
+_MAX_D, _MAX_L, _MAX_P, _MAX_ROWS = 24, 24, 40, 24
+
+
+def env_state_dtype(real):
+    """numpy structured dtype of `struct EnvState` (csrc/dtrl_types.h) for real = np.float64 (libdtrl.so) or np.float32 (libdtrl_f32.so), C alignment rules applied."""
+    r = np.dtype(real)
+    i32, u32, i64, u64 = np.int32, np.uint32, np.int64, np.uint64
+    return np.dtype([
+        ("q", r, _MAX_D), ("qd", r, _MAX_D), ("tau", r, _MAX_D), ("tau_ctrl", r, _MAX_D), ("pd_target", r, _MAX_L), ("params", r, _MAX_P),
+        ("phase", r), ("curr_cycle_time", r), ("prev_cycle_time", r), ("prev_stumble", r), ("curr_stumble", r),
+        ("prev_com", r, 2), ("prev_dist", r, 2), ("fall_dist_counter", r), ("fall_contact_counter", r), ("sum_fall_contact", r), ("prev_check", r, 2),
+        ("sample_origin", r, 2), ("time", r), ("pos_start_x", r), ("avg_dist", r),
+        ("rng_ctr", u64), ("num_cycles", i64), ("num_resets", i64), ("num_episodes", i64),
+        ("action_id", i32), ("state", i32), ("first_cycle", i32), ("is_off_policy", i32),
+        ("exp_actor", i32), ("exp_critic", i32), ("cmd_action", i32), ("fail_fall_dist", i32),
+        ("stance", i32), ("pd_active_bits", u32), ("contact_bits", u32), ("cycle_count", i32), ("tuple_flags", i32),
+        ("need_reset", i32), ("do_reset", i32), ("do_init", i32), ("pert_link", i32), ("pert_on", i32), ("pad_", i32),
+        ("pert_f", r, 2), ("pert_lp", r, 2), ("pert_torque", r), ("pert_time", r), ("pert_dur", r),
+        ("ws_lam", r, _MAX_ROWS), ("ws_id", np.uint16, _MAX_ROWS), ("ws_R", i32), ("pad_ws_", i32),
+    ], align=True)
+
+
+SNAP_MAGIC = 0x31504E534C525444   # "DTRLSNP1"
+SNAP_HEADER_DTYPE = np.dtype([
+    ("magic", np.uint64), ("version", np.uint32), ("header_bytes", np.uint32),
+    ("sizeof_real", np.uint32), ("sizeof_env_state", np.uint32), ("sizeof_ground_rec", np.uint32), ("sizeof_ground_gen", np.uint32),
+    ("sizeof_env_status", np.uint32), ("sizeof_ground_host", np.uint32),
+    ("char_type", np.int32), ("ctrl_type", np.int32), ("L", np.int32), ("D", np.int32), ("S", np.int32), ("A", np.int32), ("nn_out", np.int32),
+    ("terrain_mode", np.int32), ("env_bytes", np.uint32), ("host_bytes", np.uint32), ("n_envs", np.int32), ("pad_", np.int32)], align=True)
+
+
+class Snapshot:
+    """Everything that decides the future of a list of envs of one batch (include/dtrl.h: dtrl_snapshot_save), held by the library with its payload in device
+    memory. Made by BatchScenario.SaveState / ImportState; goes back with RestoreState. Not held: policy, exploration settings, terrain lerp, tuple rings."""
+
+    def __init__(self, batch, handle):
+        self._b, self._h = batch, handle
+        n = C.c_int32(); pe = C.c_size_t(); se = C.c_size_t(); he = C.c_size_t()
+        batch._lib.dtrl_snapshot_info(handle, C.byref(n), C.byref(pe), C.byref(se), C.byref(he))
+        self.num_envs, self.bytes_per_env, self.sizeof_env_state, self.host_bytes_per_env = n.value, pe.value, se.value, he.value
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._b._lib.dtrl_snapshot_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def export(self):
+        """The snapshot as one flat, self-describing host blob (bytes): header, saved slot ids, device payload, host payload."""
+        n = C.c_size_t()
+        self._b._chk(self._b._lib.dtrl_snapshot_export(self._h, None, 0, C.byref(n)))
+        buf = np.empty(n.value, np.uint8)
+        self._b._chk(self._b._lib.dtrl_snapshot_export(self._h, _p(buf), buf.size, C.byref(n)))
+        return buf.tobytes()
+
+    def env_ids(self):
+        """The slots the envs were saved from, in saved order."""
+        hdr, ids, _ = snapshot_blob_views(bytearray(self.export()))
+        return ids.copy()
+
+    def env_state(self, blob=None):
+        """The EnvState section of an exported blob as a numpy structured array [num_envs] (env_state_dtype: FSM state, phase, timers, the soft-fall filter ...).
+        Without an argument: a copy read from a fresh export. With a bytearray `blob` (bytearray(snap.export())): a writable VIEW into it -- edit fields, then
+        BatchScenario.ImportState(blob) and RestoreState."""
+        own = blob is None
+        if own:
+            blob = bytearray(self.export())
+        _, _, st = snapshot_blob_views(blob)
+        if st.dtype.itemsize != self.sizeof_env_state:
+            raise DtrlError("env_state dtype is %d bytes, the library's EnvState %d" % (st.dtype.itemsize, self.sizeof_env_state))
+        return st.copy() if own else st
+
+
+def snapshot_blob_views(blob):
+    """(header record, slot ids int32[n], EnvState records [n]) of an exported snapshot blob; views into `blob` when it is a bytearray (writable)."""
+    raw = np.frombuffer(blob, np.uint8)
+    if raw.size < SNAP_HEADER_DTYPE.itemsize:
+        raise DtrlError("snapshot blob shorter than its header")
+    hdr = raw[:SNAP_HEADER_DTYPE.itemsize].view(SNAP_HEADER_DTYPE)[0]
+    if int(hdr["magic"]) != SNAP_MAGIC:
+        raise DtrlError("not a snapshot blob (magic)")
+    n = int(hdr["n_envs"]); off = int(hdr["header_bytes"])
+    ids = raw[off:off + 4 * n].view(np.int32)
+    off += (4 * n + 7) & ~7
+    dt = env_state_dtype(np.float32 if int(hdr["sizeof_real"]) == 4 else np.float64)
+    if dt.itemsize != int(hdr["sizeof_env_state"]):
+        raise DtrlError("env_state dtype is %d bytes, the blob's EnvState %d" % (dt.itemsize, int(hdr["sizeof_env_state"])))
+    eb = int(hdr["env_bytes"])
+    st = np.ndarray((n,), dt, buffer=blob, offset=off, strides=(eb,))
+    return hdr, ids, st
 
 
 class BatchScenario:
@@ -461,6 +567,34 @@ class BatchScenario:
         a = C.c_double(); e, c, r = C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self._lib.dtrl_eval_stats(self._h, C.byref(a), C.byref(e), C.byref(c), C.byref(r)))
         return {"avg_dist": a.value, "episodes": e.value, "cycles": c.value, "resets": r.value}
+
+    # ---- full env snapshots (no counterpart in the reference: it keeps one scene per object) ----
+    def SaveState(self, env_ids=None):
+        """Save everything that decides the listed envs' future (all envs by default) into a device-resident Snapshot. Not between UpdateBegin and UpdateEnd."""
+        ids, n = self._ids(env_ids)
+        h = C.c_void_p()
+        self._chk(self._lib.dtrl_snapshot_save(self._h, _p(ids), n, C.byref(h)))
+        return Snapshot(self, h)
+
+    def RestoreState(self, snap, env_ids=None):
+        """Put the saved envs back into their own slots, or -- env_ids given -- the first len(env_ids) saved envs into those slots (transplant: the env then
+        continues with the exploration stream of its new slot)."""
+        ids, n = self._ids(env_ids)
+        self._chk(self._lib.dtrl_snapshot_restore(self._h, snap._h, _p(ids), n if ids is not None else 0))
+
+    def CloneEnvs(self, src, dst):
+        """Env dst[i] becomes a copy of env src[i]; overlapping lists behave as read-all-then-write-all."""
+        s = np.ascontiguousarray(src, np.int32); d = np.ascontiguousarray(dst, np.int32)
+        if s.shape != d.shape or s.ndim != 1:
+            raise DtrlError("CloneEnvs: src and dst must be lists of the same length")
+        self._chk(self._lib.dtrl_clone_envs(self._h, _p(s), _p(d), len(s)))
+
+    def ImportState(self, blob):
+        """A blob written by Snapshot.export() (this or another process, same character / precision / terrain mode) -> a Snapshot held by this batch."""
+        raw = np.frombuffer(bytes(blob), np.uint8)
+        h = C.c_void_p()
+        self._chk(self._lib.dtrl_snapshot_import(self._h, _p(raw), raw.size, C.byref(h)))
+        return Snapshot(self, h)
 
     def KernelTimeMs(self):
         a = C.c_double(); n = C.c_int64()

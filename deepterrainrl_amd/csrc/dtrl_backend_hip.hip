@@ -89,6 +89,41 @@ __global__ void dtrl_gather_f32(float* __restrict__ dst, const float* __restrict
 	}
 }
 
+// Env snapshots (dtrl_engine.h SnapPlan; include/dtrl.h dtrl_snapshot_save / _restore, dtrl_clone_envs): one wavefront per listed env moves every record of that
+// env as consecutive 64-bit words (32-bit words for a record whose size is not a multiple of 8: the fp32 library's policy-state rows), lane k taking words
+// k, k + 64, ... -- every load and store a coalesced burst, all records of all listed envs in ONE launch.
+//   mode 0  gather   payload slice i <- env a[i]   (an env whose regenerated terrain record still waits in page-locked memory is read from there)
+//   mode 1  scatter  env a[i] <- payload slice i
+//   mode 2  copy     env b[i] <- env a[i]          (no env is both read and written: Engine::CloneEnvs stages overlapping lists)
+template <class Word>
+__device__ inline void snap_copy_words(char* __restrict__ dst, const char* __restrict__ src, uint32_t bytes, int lane)
+{
+	Word* d = reinterpret_cast<Word*>(dst); const Word* s = reinterpret_cast<const Word*>(src);
+	const uint32_t n = bytes / static_cast<uint32_t>(sizeof(Word));
+#pragma unroll 4
+	for (uint32_t w = static_cast<uint32_t>(lane); w < n; w += kGroup) d[w] = s[w];
+}
+__global__ void __launch_bounds__(kGroup) dtrl_snap_move(SnapPlan p, char* payload, const int32_t* __restrict__ a, const int32_t* __restrict__ b, int n, int mode)
+{
+	const int i = static_cast<int>(blockIdx.x);
+	if (i >= n) return;
+	const int lane = static_cast<int>(threadIdx.x);
+	const int ea = a[i], eb = mode == 2 ? b[i] : 0;   // wave-uniform
+	char* slice = payload ? payload + static_cast<size_t>(i) * p.env_bytes : nullptr;
+	for (int r = 0; r < p.n_rec; ++r) {
+		const SnapRec rec = p.rec[r];
+		const char* src; char* dst;
+		if (mode == 1) { src = slice + rec.off; dst = rec.slab + static_cast<size_t>(ea) * rec.bytes; }
+		else {
+			src = rec.slab + static_cast<size_t>(ea) * rec.bytes;
+			if (r == p.gr_rec && p.stage_slot != nullptr) { const int slot = p.stage_slot[ea] - 1; if (slot >= 0) src = reinterpret_cast<const char*>(&p.gr_stage[slot]); }
+			dst = mode == 0 ? slice + rec.off : rec.slab + static_cast<size_t>(eb) * rec.bytes;
+		}
+		if ((rec.bytes & 7u) == 0) snap_copy_words<uint64_t>(dst, src, rec.bytes, lane);
+		else snap_copy_words<uint32_t>(dst, src, rec.bytes, lane);
+	}
+}
+
 // gr[ids[b]] = staged[b]: one workgroup per record (4 176 B as 16-byte words)
 // -terrain_gen= device: one thread per env; only the few envs whose window must move (or that fell) do any work
 __global__ void dtrl_terrain_boundary(DevBuffers buf, int e0, int n, int mode, const int32_t* __restrict__ env_list)
@@ -201,6 +236,7 @@ public:
 	{
 		for (auto& ev : events_) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
 		for (auto& m : marks_) if (m.second) hipEventDestroy(m.second);
+		for (hipEvent_t ev : snap_ev_) if (ev) hipEventDestroy(ev);
 		if (policy_ready_) hipEventDestroy(policy_ready_);
 		if (!owned_.empty()) { for (int i = kNumStreams / 2; i < kNumStreams; ++i) streams_[i] = nullptr; for (hipStream_t st : owned_) hipStreamDestroy(st); }
 		for (hipStream_t st : streams_) if (st) hipStreamDestroy(st);
@@ -321,6 +357,24 @@ public:
 	void FreeHostStaging(void* p) override { if (p) hipHostFree(p); }
 	bool D2H(void* dst, const void* src, size_t n) override { return Check(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H") && Check(hipStreamSynchronize(stream_), "sync"); }
 	bool D2D(void* dst, const void* src, size_t n) override { return Check(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, stream_), "hipMemcpy D2D") && Check(hipStreamSynchronize(stream_), "sync"); }
+	// snapshot transport: one launch each. DTRL_SNAPSHOT_FALLBACK=1 takes the copy-per-record defaults instead (the A/B of profiles/r08_snapshot.txt)
+	bool SnapMove(const SnapPlan& p, char* payload, const int32_t* a, const int32_t* b, int n, int mode)
+	{
+		if (n <= 0) return true;
+		if (!snap_ev_[0] && (!Check(hipEventCreate(&snap_ev_[0]), "hipEventCreate") || !Check(hipEventCreate(&snap_ev_[1]), "hipEventCreate"))) return false;
+		hipEventRecord(snap_ev_[0], stream_);
+		hipLaunchKernelGGL(dtrl_snap_move, dim3(n), dim3(kGroup), 0, stream_, p, payload, a, b, n, mode);
+		hipEventRecord(snap_ev_[1], stream_);
+		if (!Check(hipGetLastError(), "snapshot launch") || !Check(hipStreamSynchronize(stream_), "snapshot")) return false;
+		float ms = 0;
+		if (hipEventElapsedTime(&ms, snap_ev_[0], snap_ev_[1]) == hipSuccess) snap_ms_ += ms;
+		return true;
+	}
+	double SnapLaunchMs() override { const double v = snap_ms_; snap_ms_ = 0; return v; }
+	static bool SnapFallback() { const char* e = std::getenv("DTRL_SNAPSHOT_FALLBACK"); return e && std::atoi(e) != 0; }
+	bool SnapGather(const SnapPlan& p, char* payload, const int32_t* ids, int n) override { return SnapFallback() ? Backend::SnapGather(p, payload, ids, n) : SnapMove(p, payload, ids, nullptr, n, 0); }
+	bool SnapScatter(const SnapPlan& p, const char* payload, const int32_t* ids, int n) override { return SnapFallback() ? Backend::SnapScatter(p, payload, ids, n) : SnapMove(p, const_cast<char*>(payload), ids, nullptr, n, 1); }
+	bool SnapCopy(const SnapPlan& p, const int32_t* src_ids, const int32_t* dst_ids, int n) override { return SnapFallback() ? Backend::SnapCopy(p, src_ids, dst_ids, n) : SnapMove(p, nullptr, src_ids, dst_ids, n, 2); }
 	bool GatherF32(float* dst, const float* src, const int32_t* idx, size_t n) override
 	{
 		hipLaunchKernelGGL(dtrl_gather_f32, dim3(1024), dim3(256), 0, stream_, dst, src, idx, n);
@@ -473,6 +527,7 @@ private:
 	hipStream_t stream_ = nullptr;   // the selected one
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> events_, free_events_, pending_;
 	static int Key(int group, int slot) { return group * 16 + slot; }
+	hipEvent_t snap_ev_[2] = {nullptr, nullptr}; double snap_ms_ = 0;   // the snapshot launches since the last SnapLaunchMs(), timed with events
 	hipEvent_t policy_ready_ = nullptr;   // behind the latest asynchronous policy gather (GatherF32Async)
 	std::map<int, hipEvent_t> marks_;   // (env group, tuple ring) -> event behind the group's latest frame launch that wrote that ring
 };

@@ -348,8 +348,53 @@ try {
 	return DTRL_OK;
 } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(nullptr)); }
 
+// ---- env snapshots (the handle is a dtrl::Snapshot; its payload lives with the batch that saved or imported it) ----
+static dtrl::Snapshot* snap_of(const dtrl_snapshot* s) { return reinterpret_cast<dtrl::Snapshot*>(const_cast<dtrl_snapshot*>(s)); }
+dtrl_status dtrl_snapshot_save(dtrl_batch* b, const int32_t* env_ids, int n, dtrl_snapshot** out)
+try {
+	CHECK_B(); dtrl::Snapshot* s = nullptr;
+	const int rc = b->eng.SnapshotSave(env_ids, n, out ? &s : nullptr);
+	if (out) *out = reinterpret_cast<dtrl_snapshot*>(s);
+	return static_cast<dtrl_status>(rc);
+} catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_snapshot_restore(dtrl_batch* b, const dtrl_snapshot* snap, const int32_t* env_ids, int n) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SnapshotRestore(snap_of(snap), env_ids, n)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_clone_envs(dtrl_batch* b, const int32_t* src_ids, const int32_t* dst_ids, int n) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.CloneEnvs(src_ids, dst_ids, n)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_snapshot_export(const dtrl_snapshot* snap, void* buf, size_t cap, size_t* bytes)
+try {
+	dtrl::Snapshot* s = snap_of(snap);
+	if (!s) { g_create_error = "dtrl_snapshot_export: null snapshot"; return DTRL_ERR_ARG; }
+	if (!s->owner) { g_create_error = "dtrl_snapshot_export: the batch that held this snapshot's payload has been destroyed"; return DTRL_ERR_ARG; }
+	return static_cast<dtrl_status>(s->owner->SnapshotExport(s, buf, cap, bytes));
+} catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(nullptr)); }
+dtrl_status dtrl_snapshot_import(dtrl_batch* b, const void* blob, size_t bytes, dtrl_snapshot** out)
+try {
+	CHECK_B(); dtrl::Snapshot* s = nullptr;
+	const int rc = b->eng.SnapshotImport(blob, bytes, out ? &s : nullptr);
+	if (out) *out = reinterpret_cast<dtrl_snapshot*>(s);
+	return static_cast<dtrl_status>(rc);
+} catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_snapshot_info(const dtrl_snapshot* snap, int32_t* n_envs, size_t* bytes_per_env, size_t* sizeof_env_state, size_t* host_bytes_per_env)
+{
+	const dtrl::Snapshot* s = snap_of(snap);
+	if (!s) return DTRL_ERR_ARG;
+	if (n_envs) *n_envs = s->hdr.n_envs;
+	if (bytes_per_env) *bytes_per_env = s->hdr.env_bytes;
+	if (sizeof_env_state) *sizeof_env_state = s->hdr.sizeof_env_state;
+	if (host_bytes_per_env) *host_bytes_per_env = s->hdr.host_bytes;
+	return DTRL_OK;
+}
+dtrl_status dtrl_snapshot_free(dtrl_snapshot* snap)
+try {
+	dtrl::Snapshot* s = snap_of(snap);
+	if (!s) return DTRL_OK;
+	if (s->owner) s->owner->SnapshotRelease(s); else delete s;
+	return DTRL_OK;
+} catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(nullptr)); }
+
 // not part of include/dtrl.h: developer hook used by tools/gpu_sections.py with the DTRL_PROFILE build
 int dtrlx_profile_env(dtrl_batch* b, int section, unsigned long long* out, int cap) try { return b ? b->eng.ProfileEnv(section, out, cap) : 1; } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+// device time (ms, HIP events) of the snapshot kernel launches since the last call; -1 on a backend without launches (tools/snapshot_bench.py)
+double dtrlx_snapshot_launch_ms(dtrl_batch* b) { return b ? b->eng.SnapLaunchMs() : -1.0; }
 int dtrlx_profile_sections(dtrl_batch* b, unsigned long long* out, int cap) try { return b ? b->eng.ProfileSections(out, cap) : 1; } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 
 }  // extern "C"

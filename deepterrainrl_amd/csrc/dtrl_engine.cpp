@@ -117,6 +117,8 @@ Engine::~Engine()
 {
 	if (be_) {
 		be_->Sync();
+		for (Snapshot* s : snapshots_) { be_->Free(s->payload); s->payload = nullptr; s->owner = nullptr; }   // (the handles stay valid for dtrl_snapshot_info / _free)
+		be_->FreeHostStaging(snap_ids_);
 		for (void* p : allocs_) be_->Free(p);
 		for (void* p : host_allocs_) be_->FreeHostStaging(p);
 		be_->FreeHostStaging(pin_drain_); be_->FreeHostStaging(pin_recs_); be_->FreeHostStaging(pin_order_); be_->FreeHostStaging(pin_ids_); be_->FreeHostStaging(status_); be_->FreeHostStaging(stage_slot_);
@@ -1302,6 +1304,285 @@ int Engine::ProfileEnv(int section, unsigned long long* out, int cap)
 	std::vector<unsigned long long> all(static_cast<size_t>(kProfMax) * n_);
 	if (!be_->D2H(all.data(), buf_.prof, all.size() * sizeof(unsigned long long))) return Fail(DTRL_ERR_DEVICE, be_->error());
 	for (int e = 0; e < n_; ++e) out[e] = all[static_cast<size_t>(e) * kProfMax + section];
+	return DTRL_OK;
+}
+
+// ---- env snapshots (include/dtrl.h: dtrl_snapshot_save / _restore / _export / _import, dtrl_clone_envs) ----
+// A snapshot holds, per listed env, every record that decides the env's future: EnvState (FSM state and phase, action, PD targets, timers, the soft-fall
+// filter, bookkeeping, the exploration counter, a pending command, the perturbation slot, the pending reset / init flags), its GroundRec, its GroundGen
+// (-terrain_gen= device) or its host GroundWindow (host generator), the policy state, the begin state and action of the tuple in progress, the net's last
+// output and the EnvStatus record the next frame boundary reads. Batch settings (policy, RunParams, terrain lerp) and outputs (tuple rings, totals, dist log) stay out.
+namespace {
+constexpr uint32_t pad8(uint32_t b) { return (b + 7u) & ~7u; }
+size_t SnapBlobBytes(const SnapHeader& h) { return sizeof(SnapHeader) + pad8(4u * static_cast<uint32_t>(h.n_envs)) + static_cast<size_t>(h.n_envs) * (static_cast<size_t>(h.env_bytes) + h.host_bytes); }
+}
+
+int Engine::SnapReady(const char* what)
+{
+	// refuse, do not wait: the frame in flight ends with the caller's own dtrl_step_end, and after dtrl_step_poll the env groups are a frame apart
+	if (step_pending_ || early_any_) return Fail(DTRL_ERR_ARG, std::string(what) + " between dtrl_step_begin and dtrl_step_end (or after dtrl_step_poll relaunched a group): a frame is in flight; call dtrl_step_end first");
+	be_->SelectStream(0);
+	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (!snap_ids_) {
+		snap_ids_ = static_cast<int32_t*>(be_->HostStaging(sizeof(int32_t) * 2 * static_cast<size_t>(n_)));
+		if (!snap_ids_) return Fail(DTRL_ERR_DEVICE, "host staging allocation failed: " + be_->error());
+	}
+	return DTRL_OK;
+}
+
+SnapPlan Engine::MakeSnapPlan() const
+{
+	SnapPlan p;
+	auto add = [&](void* slab, size_t bytes, bool host) { SnapRec& r = p.rec[p.n_rec++]; r.slab = static_cast<char*>(slab); r.bytes = static_cast<uint32_t>(bytes); r.off = p.env_bytes; r.host = host ? 1 : 0; p.env_bytes += pad8(r.bytes); };
+	add(buf_.st, sizeof(EnvState), false);
+	if (zero_copy_) { p.gr_rec = p.n_rec; p.gr_stage = pin_recs_; p.stage_slot = stage_slot_; }   // a regenerated record may still wait for the env's next launch (FetchGroundRec)
+	add(buf_.gr, sizeof(GroundRec), false);
+	if (cfg_.device_terrain) add(buf_.gen, sizeof(GroundGen), false);
+	add(buf_.status, sizeof(EnvStatus), zero_copy_);   // host terrain mode: the page-locked array the frame kernel writes and HostFrameWork reads
+	add(buf_.poli_state, sizeof(real) * S_, false);
+	add(buf_.tup_s0, sizeof(real) * S_, false);
+	add(buf_.tup_a, sizeof(real) * A_, false);
+	if (buf_.nn_out) add(buf_.nn_out, sizeof(real) * static_cast<size_t>(cfg_.net.out_size), false);
+	return p;
+}
+
+SnapHeader Engine::MakeSnapHeader(int n) const
+{
+	SnapHeader h{};
+	h.magic = kSnapMagic; h.version = kSnapVersion; h.header_bytes = sizeof(SnapHeader);
+	h.sizeof_real = sizeof(real); h.sizeof_env_state = sizeof(EnvState); h.sizeof_ground_rec = sizeof(GroundRec); h.sizeof_ground_gen = sizeof(GroundGen);
+	h.sizeof_env_status = sizeof(EnvStatus); h.sizeof_ground_host = sizeof(GroundWindowState);
+	const DevModel& m = cfg_.model;
+	h.char_type = m.char_type; h.ctrl_type = m.ctrl_type; h.L = m.L; h.D = m.D; h.S = S_; h.A = A_; h.nn_out = cfg_.has_policy_net ? cfg_.net.out_size : 0;
+	h.terrain_mode = cfg_.device_terrain ? 1 : 0;
+	h.env_bytes = MakeSnapPlan().env_bytes; h.host_bytes = cfg_.device_terrain ? 0 : static_cast<uint32_t>(sizeof(GroundWindowState));
+	h.n_envs = n;
+	return h;
+}
+
+// the snapshot (or blob) was made by a batch of the same shape: same precision, record layouts, character, controller, sizes and terrain mode
+int Engine::CheckSnapHeader(const SnapHeader& h, const char* what)
+{
+	const SnapHeader me = MakeSnapHeader(h.n_envs);
+	auto bad = [&](const char* field, long long got, long long want, const char* hint) {
+		return Fail(DTRL_ERR_ARG, std::string(what) + ": snapshot does not fit this batch: " + field + " is " + std::to_string(got) + ", the batch has " + std::to_string(want) + hint);
+	};
+	if (h.magic != kSnapMagic) return Fail(DTRL_ERR_ARG, std::string(what) + ": not a snapshot blob (magic)");
+	if (h.version != kSnapVersion) return bad("format version", h.version, kSnapVersion, "");
+	if (h.header_bytes != sizeof(SnapHeader)) return bad("header size", h.header_bytes, sizeof(SnapHeader), "");
+	if (h.sizeof_real != me.sizeof_real) return bad("sizeof(real)", h.sizeof_real, me.sizeof_real, " (the other precision's library: -physics_precision=)");
+	if (h.sizeof_env_state != me.sizeof_env_state) return bad("sizeof(EnvState)", h.sizeof_env_state, me.sizeof_env_state, "");
+	if (h.sizeof_ground_rec != me.sizeof_ground_rec) return bad("sizeof(GroundRec)", h.sizeof_ground_rec, me.sizeof_ground_rec, "");
+	if (h.sizeof_ground_gen != me.sizeof_ground_gen) return bad("sizeof(GroundGen)", h.sizeof_ground_gen, me.sizeof_ground_gen, "");
+	if (h.sizeof_env_status != me.sizeof_env_status) return bad("sizeof(EnvStatus)", h.sizeof_env_status, me.sizeof_env_status, "");
+	if (h.sizeof_ground_host != me.sizeof_ground_host) return bad("sizeof(GroundWindowState)", h.sizeof_ground_host, me.sizeof_ground_host, "");
+	if (h.char_type != me.char_type) return bad("character type", h.char_type, me.char_type, " (another character)");
+	if (h.ctrl_type != me.ctrl_type) return bad("controller type", h.ctrl_type, me.ctrl_type, "");
+	if (h.L != me.L) return bad("L (links)", h.L, me.L, "");
+	if (h.D != me.D) return bad("D (dofs)", h.D, me.D, "");
+	if (h.S != me.S) return bad("S (policy state size)", h.S, me.S, "");
+	if (h.A != me.A) return bad("A (policy action size)", h.A, me.A, "");
+	if (h.nn_out != me.nn_out) return bad("net output size", h.nn_out, me.nn_out, "");
+	if (h.terrain_mode != me.terrain_mode) return bad("terrain mode", h.terrain_mode, me.terrain_mode, " (0 = host generator, 1 = -terrain_gen= device)");
+	if (h.env_bytes != me.env_bytes) return bad("device bytes per env", h.env_bytes, me.env_bytes, "");
+	if (h.host_bytes != me.host_bytes) return bad("host bytes per env", h.host_bytes, me.host_bytes, "");
+	return DTRL_OK;
+}
+
+int Engine::CheckSlots(const int32_t* ids, int n, const char* what)
+{
+	std::vector<char> seen(static_cast<size_t>(n_), 0);
+	for (int i = 0; i < n; ++i) {
+		const int e = ids[i];
+		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, std::string(what) + ": env id out of range");
+		if (seen[e]) return Fail(DTRL_ERR_ARG, std::string(what) + ": env " + std::to_string(e) + " is listed twice");
+		seen[e] = 1;
+	}
+	return DTRL_OK;
+}
+
+Snapshot* Engine::NewSnapshot(int n)
+{
+	std::unique_ptr<Snapshot> s(new Snapshot());
+	s->hdr = MakeSnapHeader(n);
+	s->ids.resize(static_cast<size_t>(n));
+	s->host.resize(static_cast<size_t>(n) * s->hdr.host_bytes);
+	s->payload = static_cast<char*>(be_->Alloc(static_cast<size_t>(n) * s->hdr.env_bytes));
+	if (!s->payload) return nullptr;
+	s->owner = this;
+	snapshots_.push_back(s.get());
+	return s.release();
+}
+
+void Engine::SnapshotRelease(Snapshot* s)
+{
+	if (!s) return;
+	auto it = std::find(snapshots_.begin(), snapshots_.end(), s);
+	if (it != snapshots_.end()) snapshots_.erase(it);
+	if (s->payload) { be_->Sync(); be_->Free(s->payload); }
+	delete s;
+}
+
+int Engine::SnapshotSave(const int32_t* env_ids, int n, Snapshot** out)
+{
+	if (!out) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_save: null output");
+	*out = nullptr;
+	if (env_ids && n <= 0) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_save: empty env list");
+	int rc = SnapReady("dtrl_snapshot_save");
+	if (rc != DTRL_OK) return rc;
+	const int cnt = env_ids ? n : n_;
+	if (cnt > n_) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_save: more envs listed than the batch has");
+	for (int i = 0; i < cnt; ++i) snap_ids_[i] = EnvIndex(env_ids, i);
+	rc = CheckSlots(snap_ids_, cnt, "dtrl_snapshot_save");
+	if (rc != DTRL_OK) return rc;
+	Snapshot* s = NewSnapshot(cnt);
+	if (!s) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+	std::memcpy(s->ids.data(), snap_ids_, sizeof(int32_t) * cnt);
+	bool ok = be_->SnapGather(MakeSnapPlan(), s->payload, snap_ids_, cnt);
+	if (!ok) { Fail(DTRL_ERR_DEVICE, be_->error()); SnapshotRelease(s); return DTRL_ERR_DEVICE; }
+	if (!cfg_.device_terrain) {
+		GroundWindowState gs;
+		for (int i = 0; i < cnt && ok; ++i) { ok = grounds_[snap_ids_[i]].SaveState(gs); std::memcpy(s->host.data() + static_cast<size_t>(i) * sizeof(gs), &gs, sizeof(gs)); }
+		if (!ok) { SnapshotRelease(s); return Fail(DTRL_ERR_CAPACITY, "terrain segment exceeds kSegCap vertices"); }
+	}
+	*out = s;
+	return DTRL_OK;
+}
+
+int Engine::SnapshotRestore(const Snapshot* s, const int32_t* env_ids, int n)
+{
+	if (!s) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_restore: null snapshot");
+	int rc = SnapReady("dtrl_snapshot_restore");
+	if (rc != DTRL_OK) return rc;
+	if (s->owner != this) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_restore: the snapshot's payload lives with another batch; carry it over with dtrl_snapshot_export / dtrl_snapshot_import");
+	rc = CheckSnapHeader(s->hdr, "dtrl_snapshot_restore");
+	if (rc != DTRL_OK) return rc;
+	if (env_ids && (n <= 0 || n > s->hdr.n_envs)) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_restore: the slot list must name between 1 and the snapshot's env count slots");
+	const int cnt = env_ids ? n : s->hdr.n_envs;
+	if (cnt > n_) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_restore: env id out of range (the snapshot holds more envs than the batch)");
+	for (int i = 0; i < cnt; ++i) snap_ids_[i] = env_ids ? env_ids[i] : s->ids[i];
+	rc = CheckSlots(snap_ids_, cnt, "dtrl_snapshot_restore");
+	if (rc != DTRL_OK) return rc;
+	if (!cfg_.device_terrain) {
+		// the host generator's window first (it validates its record): segments built after the restore are the ones the saved env would have built
+		GroundWindowState gs;
+		std::vector<GroundWindow> tmp(static_cast<size_t>(cnt));
+		for (int i = 0; i < cnt; ++i) {
+			std::memcpy(&gs, s->host.data() + static_cast<size_t>(i) * sizeof(gs), sizeof(gs));
+			tmp[i] = grounds_[snap_ids_[i]];   // (keeps the batch's terrain type and current parameters)
+			if (!tmp[i].LoadState(gs)) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_restore: malformed ground window record of saved env " + std::to_string(i));
+		}
+		for (int i = 0; i < cnt; ++i) grounds_[snap_ids_[i]] = tmp[i];
+	}
+	if (zero_copy_) for (int i = 0; i < cnt; ++i) stage_slot_[snap_ids_[i]] = 0;   // a record waiting for the env's next launch is superseded (UploadGround)
+	if (!be_->SnapScatter(MakeSnapPlan(), s->payload, snap_ids_, cnt)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::CloneEnvs(const int32_t* src_ids, const int32_t* dst_ids, int n)
+{
+	if (!src_ids || !dst_ids || n <= 0) return Fail(DTRL_ERR_ARG, "dtrl_clone_envs: source and destination lists are required");
+	int rc = SnapReady("dtrl_clone_envs");
+	if (rc != DTRL_OK) return rc;
+	if (n > n_) return Fail(DTRL_ERR_ARG, "dtrl_clone_envs: more envs listed than the batch has");
+	int32_t* src = snap_ids_; int32_t* dst = snap_ids_ + n_;
+	std::vector<char> written(static_cast<size_t>(n_), 0);
+	for (int i = 0; i < n; ++i) { src[i] = src_ids[i]; dst[i] = dst_ids[i]; if (src[i] < 0 || src[i] >= n_) return Fail(DTRL_ERR_ARG, "dtrl_clone_envs: env id out of range"); }
+	rc = CheckSlots(dst, n, "dtrl_clone_envs (destination)");   // (a source may repeat: one env duplicated across the batch)
+	if (rc != DTRL_OK) return rc;
+	for (int i = 0; i < n; ++i) written[dst[i]] = 1;
+	bool overlap = false;
+	for (int i = 0; i < n; ++i) overlap = overlap || written[src[i]];
+	const SnapPlan plan = MakeSnapPlan();
+	std::vector<GroundWindow> tmp;
+	if (!cfg_.device_terrain) { tmp.resize(static_cast<size_t>(n)); for (int i = 0; i < n; ++i) tmp[i] = grounds_[src[i]]; }
+	bool ok = true;
+	if (!overlap) {
+		if (zero_copy_) for (int i = 0; i < n; ++i) stage_slot_[dst[i]] = 0;
+		ok = be_->SnapCopy(plan, src, dst, n);
+	} else {
+		// an env is both read and written: read all, then write all, through a staging payload (two launches; wavefronts of one launch run in no order)
+		if (!snap_scratch_) {
+			snap_scratch_ = static_cast<char*>(be_->Alloc(static_cast<size_t>(n_) * plan.env_bytes));
+			if (!snap_scratch_) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+			allocs_.push_back(snap_scratch_);
+		}
+		ok = be_->SnapGather(plan, snap_scratch_, src, n);
+		if (ok && zero_copy_) for (int i = 0; i < n; ++i) stage_slot_[dst[i]] = 0;
+		ok = ok && be_->SnapScatter(plan, snap_scratch_, dst, n);
+	}
+	if (!ok) return Fail(DTRL_ERR_DEVICE, be_->error());
+	for (size_t i = 0; i < tmp.size(); ++i) grounds_[dst[i]] = tmp[i];
+	return DTRL_OK;
+}
+
+int Engine::SnapshotExport(const Snapshot* s, void* buf, size_t cap, size_t* bytes)
+{
+	if (!s) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_export: null snapshot");
+	const size_t total = SnapBlobBytes(s->hdr);
+	if (bytes) *bytes = total;
+	if (cap == 0) return DTRL_OK;
+	if (!buf) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_export: null buffer");
+	if (cap < total) return Fail(DTRL_ERR_CAPACITY, "dtrl_snapshot_export: buffer smaller than the blob (" + std::to_string(total) + " bytes)");
+	int rc = SnapReady("dtrl_snapshot_export");
+	if (rc != DTRL_OK) return rc;
+	char* p = static_cast<char*>(buf);
+	const size_t nb = static_cast<size_t>(s->hdr.n_envs);
+	std::memcpy(p, &s->hdr, sizeof(SnapHeader)); p += sizeof(SnapHeader);
+	std::memset(p, 0, pad8(4u * s->hdr.n_envs)); std::memcpy(p, s->ids.data(), sizeof(int32_t) * nb); p += pad8(4u * s->hdr.n_envs);
+	if (!be_->D2H(p, s->payload, nb * s->hdr.env_bytes)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	p += nb * s->hdr.env_bytes;
+	if (!s->host.empty()) std::memcpy(p, s->host.data(), s->host.size());
+	return DTRL_OK;
+}
+
+int Engine::SnapshotImport(const void* blob, size_t bytes, Snapshot** out)
+{
+	if (!out) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_import: null output");
+	*out = nullptr;
+	if (!blob || bytes < sizeof(SnapHeader)) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_import: blob truncated (shorter than its header)");
+	SnapHeader h;
+	std::memcpy(&h, blob, sizeof(h));
+	int rc = CheckSnapHeader(h, "dtrl_snapshot_import");
+	if (rc != DTRL_OK) return rc;
+	if (h.n_envs <= 0 || h.n_envs > (1 << 24)) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_import: env count out of range");
+	if (bytes != SnapBlobBytes(h)) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_import: blob truncated or padded: " + std::to_string(bytes) + " bytes, its header describes " + std::to_string(SnapBlobBytes(h)));
+	rc = SnapReady("dtrl_snapshot_import");
+	if (rc != DTRL_OK) return rc;
+	const char* p = static_cast<const char*>(blob) + sizeof(SnapHeader);
+	const char* p_ids = p; p += pad8(4u * h.n_envs);
+	const char* p_dev = p; p += static_cast<size_t>(h.n_envs) * h.env_bytes;
+	const char* p_host = p;
+	// a blob may have been edited (Snapshot.env_state in the Python package): whatever the kernels use as an index is checked before it reaches the device
+	const SnapPlan plan = MakeSnapPlan();
+	const DevModel& m = cfg_.model;
+	for (int i = 0; i < h.n_envs; ++i) {
+		EnvState st; GroundRec gr;
+		std::memcpy(&st, p_dev + static_cast<size_t>(i) * h.env_bytes + plan.rec[0].off, sizeof(st));
+		std::memcpy(&gr, p_dev + static_cast<size_t>(i) * h.env_bytes + plan.rec[1].off, sizeof(gr));
+		const char* bad = nullptr;
+		if (st.ws_R < 0 || st.ws_R > kMaxRows) bad = "ws_R";
+		else if (st.action_id < 0 || st.action_id >= std::max(1, m.n_actions)) bad = "action_id";
+		else if (st.cmd_action < -1 || st.cmd_action >= std::max(1, m.n_actions)) bad = "cmd_action";
+		else if (st.pert_link < -1 || st.pert_link >= m.L) bad = "pert_link";
+		else if (st.state < 0 || st.state >= 4) bad = "state";
+		else if (st.stance < 0 || st.stance > 1) bad = "stance";
+		else if (gr.w[0] < 0 || gr.w[0] > kSegCap || gr.w[1] < 0 || gr.w[1] > kSegCap) bad = "ground segment width";
+		if (bad) return Fail(DTRL_ERR_ARG, std::string("dtrl_snapshot_import: ") + bad + " of saved env " + std::to_string(i) + " is out of range");
+	}
+	if (h.host_bytes) {
+		GroundWindowState gs; GroundWindow probe;
+		for (int i = 0; i < h.n_envs; ++i) {
+			std::memcpy(&gs, p_host + static_cast<size_t>(i) * sizeof(gs), sizeof(gs));
+			if (!probe.LoadState(gs)) return Fail(DTRL_ERR_ARG, "dtrl_snapshot_import: malformed ground window record of saved env " + std::to_string(i));
+		}
+	}
+	Snapshot* s = NewSnapshot(h.n_envs);
+	if (!s) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+	std::memcpy(s->ids.data(), p_ids, sizeof(int32_t) * static_cast<size_t>(h.n_envs));
+	if (!s->host.empty()) std::memcpy(s->host.data(), p_host, s->host.size());
+	if (!be_->H2D(s->payload, p_dev, static_cast<size_t>(h.n_envs) * h.env_bytes)) { Fail(DTRL_ERR_DEVICE, be_->error()); SnapshotRelease(s); return DTRL_ERR_DEVICE; }
+	*out = s;
 	return DTRL_OK;
 }
 

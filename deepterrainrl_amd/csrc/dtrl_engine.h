@@ -12,9 +12,28 @@ namespace dtrl {
 // scratch of the packed tuple drain (device memory): order [cap], hist [n_envs + 1], meta [4], carry staging rows [cap][W] / flags [cap] / env [cap]
 struct PackScratch { int32_t* order = nullptr; int32_t* hist = nullptr; int32_t* meta = nullptr; float* rows = nullptr; uint32_t* flags = nullptr; int32_t* env = nullptr; };
 
+// ---- env snapshots (include/dtrl.h: dtrl_snapshot_save ...) ----
+// One per-env record family of a snapshot: env e's record is `bytes` bytes at slab + e * bytes (records are contiguous in every slab) and sits at byte `off`
+// (a multiple of 8) of the env's slice of a snapshot payload. `bytes` is a multiple of 4 (the fp32 library's policy-state rows); everything else is 8-aligned.
+struct SnapRec { char* slab = nullptr; uint32_t bytes = 0, off = 0, host = 0, pad_ = 0; };   // host: the slab is page-locked HOST memory (the status array of host terrain mode)
+constexpr int kSnapRecs = 8;
+// what moves with an env, and how a payload slice is laid out. gr_rec >= 0 (host terrain mode): rec[gr_rec] is the GroundRec slab, and an env whose regenerated
+// record is still waiting in page-locked memory (stage_slot[e] > 0) is READ from gr_stage[stage_slot[e] - 1], the record that will be in force at its next launch
+struct SnapPlan { SnapRec rec[kSnapRecs]; int32_t n_rec = 0, gr_rec = -1; uint32_t env_bytes = 0; const GroundRec* gr_stage = nullptr; const int32_t* stage_slot = nullptr; };
+
 class Backend {
 public:
 	virtual ~Backend() {}
+	// Snapshot transport. ids / src_ids / dst_ids live in HostStaging() memory (host- and device-addressable), payload is device memory laid out [n][env_bytes].
+	// Queued on the selected stream and synchronised. The defaults are built from D2D (one copy per record and env); the HIP backend overrides them with
+	// one kernel launch each (one wavefront per listed env, every record copied as consecutive 64-bit words).
+	//   SnapGather   payload slice i  <- env ids[i]          (save)
+	//   SnapScatter  env ids[i]       <- payload slice i     (restore; ids are distinct)
+	//   SnapCopy     env dst_ids[i]   <- env src_ids[i]      (clone; dst ids are distinct and NO env is both read and written: the engine stages overlapping lists)
+	virtual bool SnapGather(const SnapPlan& p, char* payload, const int32_t* ids, int n);
+	virtual bool SnapScatter(const SnapPlan& p, const char* payload, const int32_t* ids, int n);
+	virtual bool SnapCopy(const SnapPlan& p, const int32_t* src_ids, const int32_t* dst_ids, int n);
+	virtual double SnapLaunchMs() { return -1.0; }   // device time of the snapshot launches since the last call (HIP events; -1: this backend launches nothing)
 	virtual bool Init(int device_id, std::string& err) = 0;
 	// -reserve_cus= k (before Init): keep k compute units per XCD out of the frame launches (HIP backend; see dtrl_side_stream in include/dtrl.h)
 	virtual void SetReserveCus(int) {}
@@ -76,11 +95,77 @@ public:
 protected:
 	std::string err_;
 };
+// where env e's record r is read from, and whether that is host memory (the status array of host terrain mode; a staged terrain record)
+inline const char* SnapSrc(const SnapPlan& p, int r, int e, bool* host)
+{
+	if (r == p.gr_rec && p.stage_slot && p.stage_slot[e] > 0) { *host = true; return reinterpret_cast<const char*>(&p.gr_stage[p.stage_slot[e] - 1]); }
+	*host = p.rec[r].host != 0;
+	return p.rec[r].slab + static_cast<size_t>(e) * p.rec[r].bytes;
+}
+inline bool Backend::SnapGather(const SnapPlan& p, char* payload, const int32_t* ids, int n)
+{
+	for (int i = 0; i < n; ++i) for (int r = 0; r < p.n_rec; ++r) {
+		bool host; const char* src = SnapSrc(p, r, ids[i], &host);
+		char* dst = payload + static_cast<size_t>(i) * p.env_bytes + p.rec[r].off;
+		if (!(host ? H2D(dst, src, p.rec[r].bytes) : D2D(dst, src, p.rec[r].bytes))) return false;
+	}
+	return true;
+}
+inline bool Backend::SnapScatter(const SnapPlan& p, const char* payload, const int32_t* ids, int n)
+{
+	for (int i = 0; i < n; ++i) for (int r = 0; r < p.n_rec; ++r) {
+		char* dst = p.rec[r].slab + static_cast<size_t>(ids[i]) * p.rec[r].bytes;
+		const char* src = payload + static_cast<size_t>(i) * p.env_bytes + p.rec[r].off;
+		if (!(p.rec[r].host ? D2H(dst, src, p.rec[r].bytes) : D2D(dst, src, p.rec[r].bytes))) return false;
+	}
+	return true;
+}
+inline bool Backend::SnapCopy(const SnapPlan& p, const int32_t* src_ids, const int32_t* dst_ids, int n)
+{
+	for (int i = 0; i < n; ++i) for (int r = 0; r < p.n_rec; ++r) {
+		bool host; const char* src = SnapSrc(p, r, src_ids[i], &host);
+		char* dst = p.rec[r].slab + static_cast<size_t>(dst_ids[i]) * p.rec[r].bytes;
+		if (p.rec[r].host) { for (uint32_t k = 0; k < p.rec[r].bytes; ++k) dst[k] = src[k]; continue; }   // host to host (the streams are idle)
+		if (!(host ? H2D(dst, src, p.rec[r].bytes) : D2D(dst, src, p.rec[r].bytes))) return false;
+	}
+	return true;
+}
 Backend* MakeBackend();   // resolved at link time: HIP in libdtrl.so, the lane-loop test backend under tests/emul/
+
+// Header of an exported snapshot blob (dtrl_snapshot_export): [SnapHeader][int32 slot ids, padded to 8 bytes][device payload n x env_bytes][host payload n x host_bytes].
+// dtrl_snapshot_import / dtrl_snapshot_restore compare every field up to `terrain_mode` with the batch and refuse a mismatch by name.
+constexpr uint64_t kSnapMagic = 0x31504e534c525444ULL;   // "DTRLSNP1"
+constexpr uint32_t kSnapVersion = 1;
+struct SnapHeader {
+	uint64_t magic;
+	uint32_t version, header_bytes;
+	uint32_t sizeof_real, sizeof_env_state, sizeof_ground_rec, sizeof_ground_gen, sizeof_env_status, sizeof_ground_host;
+	int32_t char_type, ctrl_type, L, D, S, A, nn_out;
+	int32_t terrain_mode;                      // 0 = host generator (GroundWindow records in the host payload), 1 = -terrain_gen= device (GroundGen in the device payload)
+	uint32_t env_bytes, host_bytes;            // per env: device payload, host payload
+	int32_t n_envs, pad_;
+};
+static_assert(sizeof(SnapHeader) % 8 == 0, "the payload behind the header is copied as 64-bit words");
+class Engine;
+struct Snapshot {
+	SnapHeader hdr{};
+	std::vector<int32_t> ids;     // the slots the envs were saved from
+	char* payload = nullptr;      // device memory [n][env_bytes], owned by `owner`'s backend
+	std::vector<char> host;       // [n][host_bytes]: the host generator's windows (host terrain mode)
+	Engine* owner = nullptr;      // the batch that holds the payload; nullptr once that batch is gone
+};
 
 class Engine {
 public:
 	Engine() {}
+	// env snapshots (include/dtrl.h)
+	int SnapshotSave(const int32_t* env_ids, int n, Snapshot** out);
+	int SnapshotRestore(const Snapshot* s, const int32_t* env_ids, int n);
+	int CloneEnvs(const int32_t* src_ids, const int32_t* dst_ids, int n);
+	int SnapshotExport(const Snapshot* s, void* buf, size_t cap, size_t* bytes);
+	int SnapshotImport(const void* blob, size_t bytes, Snapshot** out);
+	void SnapshotRelease(Snapshot* s);
+	double SnapLaunchMs() { return be_ ? be_->SnapLaunchMs() : -1.0; }
 	~Engine();
 	int Create(const char* const* argv, int argc, int num_envs, int device_id);
 	int Reset(const int32_t* env_ids, int n, const uint64_t* seeds);
@@ -197,6 +282,16 @@ private:
 	bool DrainSync();   // make the drain ring's contents final: all streams, or -- while a pipelined frame runs -- only the drain stream
 	int PendingTuples(int32_t* stored, int32_t* overflow);
 	std::vector<int32_t> work_;
+	// snapshots
+	int SnapReady(const char* what);                       // refuses while a frame is in flight, else waits for every stream
+	SnapPlan MakeSnapPlan() const;
+	SnapHeader MakeSnapHeader(int n) const;
+	int CheckSnapHeader(const SnapHeader& h, const char* what);
+	int CheckSlots(const int32_t* ids, int n, const char* what);   // in range and distinct
+	Snapshot* NewSnapshot(int n);
+	int32_t* snap_ids_ = nullptr;                          // page-locked [2 n]: the env lists the transport kernels read
+	char* snap_scratch_ = nullptr;                         // device [n][env_bytes]: staging of a clone whose lists overlap (allocated on first use)
+	std::vector<Snapshot*> snapshots_;                     // live snapshots whose payload this batch holds
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

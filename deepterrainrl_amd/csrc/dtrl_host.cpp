@@ -227,6 +227,36 @@ bool GroundWindow::Update(double bmin, double bmax)
 	flip_ = unflipped;
 	return true;
 }
+bool GroundWindow::SaveState(GroundWindowState& out) const
+{
+	std::memset(&out, 0, sizeof(out));
+	for (int s = 0; s < 2; ++s) {
+		const Seg& seg = segs_[s];
+		if (static_cast<int>(seg.data.size()) > kSegCap) return false;
+		out.min_x[s] = seg.min_x; out.origin_x[s] = seg.origin_x; out.scale_x[s] = seg.scale_x;
+		out.n[s] = static_cast<int32_t>(seg.data.size());
+		std::memcpy(out.data[s], seg.data.data(), seg.data.size() * sizeof(float));
+	}
+	out.flip = flip_ ? 1 : 0; out.builds = builds_;
+	const std::string txt = rand_.State();
+	if (txt.size() >= sizeof(out.rng)) return false;
+	std::memcpy(out.rng, txt.data(), txt.size());
+	return true;
+}
+bool GroundWindow::LoadState(const GroundWindowState& in)
+{
+	if (in.n[0] < 0 || in.n[0] > kSegCap || in.n[1] < 0 || in.n[1] > kSegCap || in.rng[sizeof(in.rng) - 1] != 0) return false;
+	TerrainRand r = rand_;
+	if (!r.SetState(in.rng)) return false;
+	rand_ = r;
+	for (int s = 0; s < 2; ++s) {
+		Seg& seg = segs_[s];
+		seg.min_x = in.min_x[s]; seg.origin_x = in.origin_x[s]; seg.scale_x = in.scale_x[s];
+		seg.data.assign(in.data[s], in.data[s] + in.n[s]);
+	}
+	flip_ = in.flip != 0; builds_ = static_cast<long>(in.builds);
+	return true;
+}
 bool GroundWindow::FillRecord(GroundRec& rec, std::string& err) const
 {
 	for (int s = 0; s < 2; ++s) {

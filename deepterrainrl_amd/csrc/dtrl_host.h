@@ -10,6 +10,7 @@
 #include <map>
 #include <memory>
 #include <random>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -56,6 +57,9 @@ public:
 	int RandInt(int mn, int mx) { if (mn == mx) return mn; int r = int_(gen_); return mn + r % (mx - mn); }
 	bool FlipCoin() { return RandDouble(0, 1) < 0.5; }
 	int RandSign() { return FlipCoin() ? -1 : 1; }
+	// the engine's state as text (the distributions keep none between draws: every draw above is one engine call)
+	std::string State() const { std::ostringstream os; os << gen_; return os.str(); }
+	bool SetState(const char* txt) { std::istringstream is(txt); std::default_random_engine g; is >> g; if (is.fail()) return false; gen_ = g; real_.reset(); int_.reset(); return true; }
 private:
 	std::default_random_engine gen_;
 	std::uniform_real_distribution<double> real_{0, 1};
@@ -72,9 +76,22 @@ extern const double kTerrainParamDefaults[kNumTerrainParams];
 // appends one terrain strip of (at least) `width` metres to `out`; returns the width added (cTerrainGen2D::tTerrainFunc)
 double BuildTerrain(int type, double width, const double* params, TerrainRand& rand, std::vector<float>& out);
 
+// Everything of a GroundWindow that decides which segments it holds and which it builds NEXT (cGroundVar2D's mSegments, mFlipSeg and its cRand, sim/GroundVar2D.cpp):
+// both segments in storage order, the flip flag, the build count and the generator's state (its textual form: operator<< of the standard engine). The terrain
+// type and parameters are batch settings and stay out. Plain data: part of an env snapshot's host payload (dtrl_engine.h Snapshot).
+struct GroundWindowState {
+	double min_x[2], origin_x[2], scale_x[2];
+	int64_t builds;
+	int32_t n[2];
+	int32_t flip, pad_;
+	char rng[64];
+	float data[2][kSegCap];
+};
 // cGroundVar2D: two sliding heightfield segments of one env, host-resident mirror of the device GroundRec
 class GroundWindow {
 public:
+	bool SaveState(GroundWindowState& out) const;   // false: a segment exceeds kSegCap vertices
+	bool LoadState(const GroundWindowState& in);    // false: malformed record (vertex counts, generator state)
 	void Configure(int type, const double* params, double world_scale, double segment_width);
 	void SetParams(const double* params);
 	void SeedRand(unsigned long seed) { rand_.Seed(seed); }

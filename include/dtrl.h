@@ -202,6 +202,54 @@ dtrl_status dtrl_set_pose_vel(dtrl_batch* b, const int32_t* env_ids, int n, cons
 dtrl_status dtrl_get_contact_cache(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* count, int32_t* ids, double* lambda);
 dtrl_status dtrl_set_contact_cache(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* count, const int32_t* ids, const double* lambda);
 
+/* ---- full env snapshots: save, restore, clone, export ----
+ * No counterpart in the reference: it keeps ONE scene per object (a cScenarioSimChar owns its world, character, controller and ground; the learner threads of
+ * scenarios/ScenarioTrain.cpp:100-115 own one each) and never copies a running scene. A batch of thousands of envs needs what a rollout engine's users expect:
+ * checkpoint the envs of a long run, rewind a batch and try something else, duplicate an interesting env, hand a full state to another process.
+ * dtrl_set_pose_vel + dtrl_set_contact_cache move the Bullet half of an env only. A SNAPSHOT is an object owned by the library that holds, for a list of envs of
+ * one batch, everything that decides their future, with its payload in DEVICE memory (saving and restoring is one kernel launch, no host round trip per env):
+ *   - the whole env state record: pose, velocity, torques, the persistent contact rows; FSM state, phase, current action id and parameters, PD targets, cycle
+ *     timers and stumble times (the members of sim/DogController.cpp:805-845 and sim/RaptorController.cpp:804-849 -- mState, mPhase, mCurrAction, mCurrCycleTime,
+ *     mPrevCycleTime, mPrevStumbleCount, mCurrStumbleCount ..., stance leg and PD active flags of the raptor); the soft-fall filter and its counters
+ *     (sim/SimCharSoftFall.cpp:74-125: mFallDistCounter, mFallContactCounter, mSumFallContact, the previous check position); distance and episode bookkeeping, the
+ *     exploration counter, a pending commanded action, the perturbation slot, and the pending reset / init flags (a snapshot taken after a fall and before
+ *     the env's next launch replays that reset);
+ *   - the ground: the two-segment window the kernels sample (cGroundVar2D's mSegments, sim/GroundVar2D.cpp) and what decides the segments built AFTER a restore --
+ *     the host generator's window with both segments, mFlipSeg, its build count and its cRand state, or with `-terrain_gen= device` the env's generator counters;
+ *     a regenerated window still waiting for the env's next launch is the one saved, and a restore supersedes a waiting one;
+ *   - the policy state recorded for the current action, the begin state and action of the tuple in progress (anim/Character.cpp:217-262 is what the reference
+ *     could write out -- a pose and a velocity; cScenarioExp's mCurrTuple has no writer at all) and the net's last output;
+ *   - the env's status record (root x, which drives the window slide; the launch-order cost; a pending reset request).
+ * A snapshot does NOT hold what belongs to the batch or is an output of it: policy weights and normalisers, the exploration settings (dtrl_set_explore), the
+ * terrain lerp, a policy hand-over still pending, the tuple rings with their drained / dropped totals, and the dist log.
+ * Exploration streams are keyed by (seed, GLOBAL env id, per-env counter): an env restored into its own slot continues bit-identically; an env transplanted or
+ * cloned into another slot carries its counter along and continues with THAT slot's stream.
+ * None of these calls waits for a frame in flight: between dtrl_step_begin and dtrl_step_end (or after dtrl_step_poll relaunched a group) save, restore,
+ * clone, export and import fail with DTRL_ERR_ARG. Env ids out of range, and a slot listed twice as a destination, are DTRL_ERR_ARG. */
+typedef struct dtrl_snapshot dtrl_snapshot;
+/* Save the listed envs (env_ids == NULL: all, n ignored) into a new snapshot; the slot list is kept in it. Free it with dtrl_snapshot_free. */
+dtrl_status dtrl_snapshot_save(dtrl_batch* b, const int32_t* env_ids, int n, dtrl_snapshot** out);
+/* env_ids == NULL: every saved env goes back into the slot it came from. Otherwise the first n saved envs, in saved order, go into the listed slots (a saved env
+ * transplanted into another slot). The snapshot must have been saved by, or imported into, this batch; it is compared with the batch like a blob (below). */
+dtrl_status dtrl_snapshot_restore(dtrl_batch* b, const dtrl_snapshot* snap, const int32_t* env_ids, int n);
+/* Env dst_ids[i] becomes a copy of env src_ids[i], inside one batch, without a snapshot object. A source may repeat; destinations are distinct. Lists that
+ * overlap behave as "read all, then write all" (src = {0, 1}, dst = {1, 2}: env 2 gets the OLD env 1). */
+dtrl_status dtrl_clone_envs(dtrl_batch* b, const int32_t* src_ids, const int32_t* dst_ids, int n);
+/* One flat, self-describing host blob: a header (magic "DTRLSNP1", format version, sizeof(real), sizeof(EnvState), sizeof(GroundRec) and the other record sizes,
+ * character and controller type, L, D, S, A, the net's output size, the terrain mode, bytes per env, env count), the saved slot ids, the device payload
+ * [n][bytes per env] (each env: EnvState first, then GroundRec, ...), the host payload. *bytes = the blob's size; cap == 0 returns the size only; a smaller
+ * buffer is DTRL_ERR_CAPACITY. Needs the batch that holds the snapshot to be alive and idle (errors are reported through that batch's dtrl_last_error). */
+dtrl_status dtrl_snapshot_export(const dtrl_snapshot* snap, void* buf, size_t cap, size_t* bytes);
+/* A blob -> a snapshot held by batch b. The header is compared with the batch, field by field: another character or controller, the other precision's library
+ * (sizeof(real)), another terrain mode, other sizes, a wrong magic or version, a truncated blob are refused with DTRL_ERR_ARG and a message naming the field.
+ * The values the kernels use as indices (action ids, row counts, segment widths ...) are range-checked, so that an edited blob cannot address out of bounds. */
+dtrl_status dtrl_snapshot_import(dtrl_batch* b, const void* blob, size_t bytes, dtrl_snapshot** out);
+/* Any output may be NULL: number of envs, device payload bytes per env, sizeof(EnvState) of the library that made it (the record at the start of every env's
+ * payload slice, dtrl_types.h), host payload bytes per env. */
+dtrl_status dtrl_snapshot_info(const dtrl_snapshot* snap, int32_t* n_envs, size_t* bytes_per_env, size_t* sizeof_env_state, size_t* host_bytes_per_env);
+/* Valid before or after dtrl_destroy of the batch (which releases the payload; the handle then only answers dtrl_snapshot_info). */
+dtrl_status dtrl_snapshot_free(dtrl_snapshot* snap);
+
 /* Replaces: cScenarioSimChar::AddPerturb -> cWorld::AddPerturb (scenarios/ScenarioSimChar.cpp:204-207, sim/World.cpp:256-259) with a
  * tPerturb of type ePerturbForce (sim/Perturb.cpp:52-79, sim/World.cpp:445-470): a world-frame force[n][2] on body part link[n] at the
  * body-local offset local_pos[n][2] (NULL = the COM) for duration[n] seconds of simulated time, advanced and applied at the start of
