@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "dtrl_terrain_build", "dtrl_terrain_load_file", "dtrl_args_parse_string",
     "dtrl_drain_tuples_device", "dtrl_tuple_stats", "dtrl_set_policy_device", "dtrl_get_dist_log", "dtrl_reset_avg_dist", "dtrl_write_dist_log", "dtrl_get_ground_window", "dtrl_drain_tuples_packed", "dtrl_get_policy_output", "dtrl_set_tuple_pipelining", "dtrl_step_end_begin", "dtrl_command_action", "dtrl_side_stream", "dtrl_step_poll", "dtrl_set_policy_device_on", "dtrl_set_policy_device_async",
     "dtrl_snapshot_save", "dtrl_snapshot_restore", "dtrl_clone_envs", "dtrl_snapshot_export", "dtrl_snapshot_import", "dtrl_snapshot_info", "dtrl_snapshot_free",
+    "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
 
 
@@ -134,6 +135,14 @@ def _bind(path):
     L.dtrl_snapshot_import.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
     L.dtrl_snapshot_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.dtrl_snapshot_free.argtypes = [vp]
+    L.dtrl_pending_actions.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.dtrl_pending_actions_device.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.dtrl_supply_actions.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.dtrl_supply_actions_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
+    L.dtrl_ext_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
+    L.dtrl_ext_env_info.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.dtrl_action_dims.argtypes = [vp] + [C.POINTER(C.c_int)] * 4
+    L.dtrl_ext_launch_ms.restype = C.c_double; L.dtrl_ext_launch_ms.argtypes = [vp, C.c_int]
     L.dtrl_last_error.restype = C.c_char_p
     L.dtrl_last_error.argtypes = [vp]
     L.dtrl_version.restype = C.c_char_p
@@ -161,9 +170,9 @@ def env_state_dtype(real):
         ("action_id", i32), ("state", i32), ("first_cycle", i32), ("is_off_policy", i32),
         ("exp_actor", i32), ("exp_critic", i32), ("cmd_action", i32), ("fail_fall_dist", i32),
         ("stance", i32), ("pd_active_bits", u32), ("contact_bits", u32), ("cycle_count", i32), ("tuple_flags", i32),
-        ("need_reset", i32), ("do_reset", i32), ("do_init", i32), ("pert_link", i32), ("pert_on", i32), ("pad_", i32),
+        ("need_reset", i32), ("do_reset", i32), ("do_init", i32), ("pert_link", i32), ("pert_on", i32), ("ext_steps_left", i32),
         ("pert_f", r, 2), ("pert_lp", r, 2), ("pert_torque", r), ("pert_time", r), ("pert_dur", r),
-        ("ws_lam", r, _MAX_ROWS), ("ws_id", np.uint16, _MAX_ROWS), ("ws_R", i32), ("pad_ws_", i32),
+        ("ws_lam", r, _MAX_ROWS), ("ws_id", np.uint16, _MAX_ROWS), ("ws_R", i32), ("ext_park", i32),
     ], align=True)
 
 
@@ -173,7 +182,7 @@ SNAP_HEADER_DTYPE = np.dtype([
     ("sizeof_real", np.uint32), ("sizeof_env_state", np.uint32), ("sizeof_ground_rec", np.uint32), ("sizeof_ground_gen", np.uint32),
     ("sizeof_env_status", np.uint32), ("sizeof_ground_host", np.uint32),
     ("char_type", np.int32), ("ctrl_type", np.int32), ("L", np.int32), ("D", np.int32), ("S", np.int32), ("A", np.int32), ("nn_out", np.int32),
-    ("terrain_mode", np.int32), ("env_bytes", np.uint32), ("host_bytes", np.uint32), ("n_envs", np.int32), ("pad_", np.int32)], align=True)
+    ("terrain_mode", np.int32), ("env_bytes", np.uint32), ("host_bytes", np.uint32), ("n_envs", np.int32), ("policy_mode", np.int32)], align=True)
 
 
 class Snapshot:
@@ -273,6 +282,10 @@ class BatchScenario:
         self._lib.dtrl_dims(self._h, *[C.byref(x) for x in d])
         self.L, self.D, self.S, self.A, self.P, self.nn_out, self.num_frags, self.frag_size = (x.value for x in d)
         self.W = 1 + 2 * self.S + self.A
+        d = [C.c_int() for _ in range(4)]
+        self._lib.dtrl_action_dims(self._h, *[C.byref(x) for x in d])
+        self.n_opt, self.n_labels, self.num_update_steps, ext = (x.value for x in d)
+        self.external = bool(ext)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -316,6 +329,57 @@ class BatchScenario:
         n = C.c_int(0)
         self._chk(self._lib.dtrl_step_poll(self._h, float(dt), C.byref(n)))
         return n.value
+
+    # ---- external policy mode (extra_args={"policy_mode": "external"}; include/dtrl.h) ----
+    def PendingActions(self, with_states=True):
+        """(ids int32[m], states float64[m][S]) of the envs parked at a decision, ascending env id (dtrl_pending_actions). After Update(), hand the states to
+        your policy and give every env its row with SupplyActions; the next Update() carries them on."""
+        ids = np.empty(self.num_envs, np.int32)
+        st = np.empty((self.num_envs, self.S), np.float64) if with_states else None
+        n = C.c_int(0)
+        self._chk(self._lib.dtrl_pending_actions(self._h, _p(ids), _p(st), self.num_envs, C.byref(n)))
+        return ids[:n.value].copy(), (st[:n.value].copy() if with_states else None)
+
+    def SupplyActions(self, ids, action_ids, params, flags=None):
+        """One action row per awaiting env (dtrl_supply_actions): action_ids int[m] (labels, 0 .. n_labels - 1; None = zeros), params float64[m][n_opt], flags uint32[m]
+        (TUPLE_EXP_CRITIC | TUPLE_EXP_ACTOR; None = zeros). All or nothing: raises DtrlError if any listed env is not awaiting."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        prm = np.ascontiguousarray(params, np.float64).reshape(len(ids), self.n_opt) if len(ids) else np.zeros((0, self.n_opt))
+        aid = None if action_ids is None else np.ascontiguousarray(action_ids, np.int32)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint32)
+        if (aid is not None and len(aid) != len(ids)) or (fl is not None and len(fl) != len(ids)):
+            raise DtrlError("SupplyActions: action_ids / flags must have one entry per env id")
+        self._chk(self._lib.dtrl_supply_actions(self._h, _p(ids), len(ids), _p(aid), _p(prm), _p(fl)))
+
+    def PendingActionsDevice(self, env_ids_ptr, states_ptr, cap):
+        """dtrl_pending_actions_device on raw device pointers (int32[cap], float32[cap][S]); returns the number of awaiting envs written."""
+        n = C.c_int(0)
+        self._chk(self._lib.dtrl_pending_actions_device(self._h, C.c_void_p(env_ids_ptr), C.c_void_p(states_ptr) if states_ptr else None, int(cap), C.byref(n)))
+        return n.value
+
+    def SupplyActionsDevice(self, env_ids_ptr, n, action_ids_ptr, params_ptr, flags_ptr=None):
+        """dtrl_supply_actions_device on raw device pointers (int32[n], int32[n] or 0, float32[n][n_opt], uint32[n] or 0); returns the number of rejected rows."""
+        rej = C.c_int(0)
+        self._chk(self._lib.dtrl_supply_actions_device(self._h, C.c_void_p(env_ids_ptr), int(n), C.c_void_p(action_ids_ptr) if action_ids_ptr else None,
+                                                       C.c_void_p(params_ptr), C.c_void_p(flags_ptr) if flags_ptr else None, C.byref(rej)))
+        return rej.value
+
+    def ExtStats(self):
+        """dict(awaiting, ready, env_steps_total, env_frames_total): envs parked without / with a delivered action, env-steps and env frames run since creation."""
+        v = [C.c_int64() for _ in range(4)]
+        self._chk(self._lib.dtrl_ext_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("awaiting", "ready", "env_steps_total", "env_frames_total"), (x.value for x in v)))
+
+    def ExtEnvInfo(self, env_ids=None):
+        """(park int32[n]: 0 running / frame complete, 1 awaiting, 2 action delivered; steps_left int32[n]: env-steps the env's current frame has yet to finish)"""
+        ids, n = self._ids(env_ids)
+        park = np.zeros(n, np.int32); left = np.zeros(n, np.int32)
+        self._chk(self._lib.dtrl_ext_env_info(self._h, _p(ids), n, _p(park), _p(left)))
+        return park, left
+
+    def ExtLaunchMs(self, which):
+        """Device time (ms) of the collection (0) / scatter (1) launches since the last call."""
+        return float(self._lib.dtrl_ext_launch_ms(self._h, int(which)))
 
     def StepUpdates(self, n):
         self._chk(self._lib.dtrl_step_updates(self._h, int(n)))

@@ -7,6 +7,7 @@
 // except the read-only model and policy weights.
 #include "dtrl_engine.h"
 #include "dtrl_kernel_fast.h"
+#include "dtrl_launch_cfg.h"
 #include "dtrl_terrain_dev.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -25,7 +26,7 @@ __global__ void __launch_bounds__(kGroup) dtrl_frame_kernel(const DevModel* __re
 	__shared__ WSRef ws;
 	if (static_cast<int>(blockIdx.x) >= n_envs) return;
 	const int env = buf.env_list ? buf.env_list[blockIdx.x] : static_cast<int>(blockIdx.x);
-	env_frame<RefPath>(ws, *gm, rp, buf, env, n_steps, dt, frame_end != 0);
+	env_frame_impl<RefPath, false>(ws, *gm, rp, buf, env, n_steps, dt, frame_end != 0);
 }
 
 // register-resident fast path (dtrl_kernel_fast.h), one instantiation per skeleton of the shipped characters (dtrl_topo.h)
@@ -33,18 +34,6 @@ __global__ void __launch_bounds__(kGroup) dtrl_frame_kernel(const DevModel* __re
 // longer derives "two waves per SIMD at most" from the 20 KB static allocation and honours -DDTRL_WAVES_PER_EU=3 (<= 168 registers per lane): the register diet a third wave
 // per SIMD would need, priced at unchanged occupancy. Run-time knob of the shipped kernel: DTRL_LDS_PAD=<bytes> of dynamic LDS on top (fewer workgroups per CU: the
 // throughput-vs-occupancy curve from the other side).
-#ifndef DTRL_WAVES_PER_EU
-#define DTRL_WAVES_PER_EU 2
-#endif
-#ifndef DTRL_WAVES_DOG
-#define DTRL_WAVES_DOG DTRL_WAVES_PER_EU
-#endif
-#ifndef DTRL_WAVES_RAPTOR
-#define DTRL_WAVES_RAPTOR DTRL_WAVES_PER_EU
-#endif
-template <class Topo> struct WavesPerEu { static constexpr int value = DTRL_WAVES_PER_EU; };
-template <> struct WavesPerEu<TopoDog> { static constexpr int value = DTRL_WAVES_DOG; };          // (the fp32 build gives each skeleton's instance its own register budget:
-template <> struct WavesPerEu<TopoRaptor> { static constexpr int value = DTRL_WAVES_RAPTOR; };    //  profiles/r06_fp32_physics.txt)
 template <class Topo>
 __global__ void __launch_bounds__(kGroup, WavesPerEu<Topo>::value) dtrl_frame_kernel_fast(const DevModel* __restrict__ gm, RunParams rp, DevBuffers buf, int n_envs, int n_steps, real dt, int frame_end)
 {
@@ -57,8 +46,72 @@ __global__ void __launch_bounds__(kGroup, WavesPerEu<Topo>::value) dtrl_frame_ke
 	if (static_cast<int>(blockIdx.x) >= n_envs) return;
 	const int env = buf.env_list ? buf.env_list[blockIdx.x] : static_cast<int>(blockIdx.x);
 #if defined(__HIP_DEVICE_COMPILE__)
-	env_frame<FastPath<Topo>>(ws, *gm, rp, buf, env, n_steps, dt, frame_end != 0);
+	env_frame_impl<FastPath<Topo>, false>(ws, *gm, rp, buf, env, n_steps, dt, frame_end != 0);
 #endif
+}
+
+// ---- external policy mode: the hand-over kernels (include/dtrl.h dtrl_pending_actions* / dtrl_supply_actions*) ----
+// dtrl_ext_collect: ids[0 .. m) = the awaiting envs in ascending env id, m = min(#awaiting, cap). One workgroup; thread t owns the contiguous env range
+// [t c, (t + 1) c): it counts its awaiting envs, the counts are scanned across the workgroup (wave shuffles + one LDS level), and it writes its ids behind the
+// ranges in front of it -- a deterministic compaction, no atomic cursor. meta (page-locked): {m, #awaiting, #ready, 0}.
+constexpr int kExtThreads = 1024;
+__global__ void __launch_bounds__(kExtThreads) dtrl_ext_collect(const EnvState* __restrict__ st, int n_envs, int cap, int32_t* __restrict__ ids, int32_t* __restrict__ meta)
+{
+	__shared__ int part_a[kExtThreads / 64], part_r[kExtThreads / 64];
+	const int t = static_cast<int>(threadIdx.x);
+	const int chunk = (n_envs + kExtThreads - 1) / kExtThreads;
+	const int c0 = t * chunk < n_envs ? t * chunk : n_envs, c1 = c0 + chunk < n_envs ? c0 + chunk : n_envs;
+	int na = 0, nr = 0;
+	for (int e = c0; e < c1; ++e) { const int p = st[e].ext_park; na += p == kExtAwaiting; nr += p == kExtReady; }
+	int incl = na, rsum = nr;
+	for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d, 64); if ((t & 63) >= d) incl += o; }
+	for (int d = 32; d > 0; d >>= 1) rsum += __shfl_xor(rsum, d, 64);
+	if ((t & 63) == 63) part_a[t >> 6] = incl;
+	if ((t & 63) == 0) part_r[t >> 6] = rsum;
+	__syncthreads();
+	int base = 0, total = 0, ready = 0;
+	for (int w = 0; w < kExtThreads / 64; ++w) { const int c = part_a[w]; if (w < (t >> 6)) base += c; total += c; ready += part_r[w]; }
+	int k = base + incl - na;
+	for (int e = c0; e < c1 && k < cap; ++e) if (st[e].ext_park == kExtAwaiting) ids[k++] = e;
+	if (t == 0) { meta[0] = total < cap ? total : cap; meta[1] = total; meta[2] = ready; meta[3] = 0; }
+}
+// dtrl_ext_states: one wavefront per collected env copies its S policy-state values into row i of the dense block [m][S] (reads and writes are consecutive
+// per lane: coalesced rows), converting to the caller's type (float: device call, double: host call)
+template <class T>
+__global__ void __launch_bounds__(kGroup) dtrl_ext_states(const real* __restrict__ poli_state, int S, const int32_t* __restrict__ ids, const int32_t* __restrict__ meta, int n_envs, T* __restrict__ out)
+{
+	const int i = static_cast<int>(blockIdx.x);
+	if (i >= meta[0]) return;
+	const int e = ids[i];
+	if (e < 0 || e >= n_envs) return;
+	const real* src = poli_state + static_cast<size_t>(e) * S;
+	T* dst = out + static_cast<size_t>(i) * S;
+	for (int k = static_cast<int>(threadIdx.x); k < S; k += kGroup) dst[k] = static_cast<T>(src[k]);
+}
+// dtrl_ext_supply: one wavefront per delivered row. Lane 0 claims the env (env id and label in range, then awaiting -> ready by compare-and-swap: of two rows for one env the
+// second is rejected), the wavefront writes the row into the env's slab record. apply == 0: validate only (count the rows that would be rejected, write nothing)
+template <class T>
+__global__ void __launch_bounds__(kGroup) dtrl_ext_supply(EnvState* __restrict__ st, ExtAction* __restrict__ slab, int n_envs, int n_opt, int n_labels, const int32_t* __restrict__ ids, int n,
+	const int32_t* __restrict__ action_ids, const T* __restrict__ params, const uint32_t* __restrict__ flags, int apply, int32_t* __restrict__ rejected)
+{
+	const int i = static_cast<int>(blockIdx.x);
+	if (i >= n) return;
+	const int lane = static_cast<int>(threadIdx.x);
+	const int e = ids[i];   // wave-uniform
+	int ok = 0;
+	if (lane == 0) {
+		const int label = action_ids ? action_ids[i] : 0;
+		if (e >= 0 && e < n_envs && label >= 0 && label < n_labels) {
+			if (apply) ok = atomicCAS(&st[e].ext_park, static_cast<int>(kExtAwaiting), static_cast<int>(kExtReady)) == kExtAwaiting;
+			else ok = st[e].ext_park == kExtAwaiting;
+		}
+		if (!ok) atomicAdd(rejected, 1);
+	}
+	ok = __shfl(ok, 0, 64);
+	if (!ok || !apply) return;
+	ExtAction& a = slab[e];
+	if (lane == 0) { a.action_id = action_ids ? action_ids[i] : 0; a.flags = flags ? flags[i] : 0u; }
+	if (lane < n_opt && lane < kMaxP) a.params[lane] = static_cast<real>(params[static_cast<size_t>(i) * n_opt + lane]);
 }
 
 // dst[i] = idx[i] >= 0 ? src[idx[i]] : 0: re-lays a policy blob handed over in device memory into the kernel's weight layout
@@ -238,6 +291,7 @@ public:
 		for (auto& m : marks_) if (m.second) hipEventDestroy(m.second);
 		for (hipEvent_t ev : snap_ev_) if (ev) hipEventDestroy(ev);
 		if (policy_ready_) hipEventDestroy(policy_ready_);
+		if (ext_rej_) hipFree(ext_rej_);
 		if (!owned_.empty()) { for (int i = kNumStreams / 2; i < kNumStreams; ++i) streams_[i] = nullptr; for (hipStream_t st : owned_) hipStreamDestroy(st); }
 		for (hipStream_t st : streams_) if (st) hipStreamDestroy(st);
 	}
@@ -371,6 +425,40 @@ public:
 		return true;
 	}
 	double SnapLaunchMs() override { const double v = snap_ms_; snap_ms_ = 0; return v; }
+	// external policy mode: collection (a compaction launch + a row-copy launch) and scatter, timed with the snapshot transport's event pair
+	bool ExtTimed(int which, bool begin)
+	{
+		if (!snap_ev_[0] && (!Check(hipEventCreate(&snap_ev_[0]), "hipEventCreate") || !Check(hipEventCreate(&snap_ev_[1]), "hipEventCreate"))) return false;
+		if (begin) return Check(hipEventRecord(snap_ev_[0], stream_), "hipEventRecord");
+		hipEventRecord(snap_ev_[1], stream_);
+		if (!Check(hipGetLastError(), "external-policy launch") || !Check(hipStreamSynchronize(stream_), "external-policy hand-over")) return false;
+		float ms = 0;
+		if (hipEventElapsedTime(&ms, snap_ev_[0], snap_ev_[1]) == hipSuccess) ext_ms_[which] += ms;
+		return true;
+	}
+	bool ExtCollect(const DevBuffers& buf, int n_envs, int cap, int32_t* ids, void* states, bool f32, int32_t* meta) override
+	{
+		if (!ExtTimed(0, true)) return false;
+		hipLaunchKernelGGL(dtrl_ext_collect, dim3(1), dim3(kExtThreads), 0, stream_, buf.st, n_envs, cap, ids, meta);
+		const int rows = std::min(cap, n_envs);
+		if (states && rows > 0) {
+			if (f32) hipLaunchKernelGGL(dtrl_ext_states<float>, dim3(rows), dim3(kGroup), 0, stream_, buf.poli_state, buf.S, ids, meta, n_envs, static_cast<float*>(states));
+			else hipLaunchKernelGGL(dtrl_ext_states<double>, dim3(rows), dim3(kGroup), 0, stream_, buf.poli_state, buf.S, ids, meta, n_envs, static_cast<double*>(states));
+		}
+		return ExtTimed(0, false);
+	}
+	bool ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labels, const int32_t* ids, int n, const int32_t* action_ids, const void* params, bool f32, const uint32_t* flags, bool apply, int32_t* rejected) override
+	{
+		*rejected = 0;
+		if (n <= 0) return true;
+		if (!ext_rej_ && !Check(hipMalloc(&ext_rej_, sizeof(int32_t)), "hipMalloc")) return false;
+		if (!Check(hipMemsetAsync(ext_rej_, 0, sizeof(int32_t), stream_), "hipMemset") || !ExtTimed(1, true)) return false;
+		if (f32) hipLaunchKernelGGL(dtrl_ext_supply<float>, dim3(n), dim3(kGroup), 0, stream_, buf.st, ext_actions(buf), n_envs, n_opt, n_labels, ids, n, action_ids, static_cast<const float*>(params), flags, apply ? 1 : 0, ext_rej_);
+		else hipLaunchKernelGGL(dtrl_ext_supply<double>, dim3(n), dim3(kGroup), 0, stream_, buf.st, ext_actions(buf), n_envs, n_opt, n_labels, ids, n, action_ids, static_cast<const double*>(params), flags, apply ? 1 : 0, ext_rej_);
+		if (!ExtTimed(1, false)) return false;
+		return Check(hipMemcpyAsync(rejected, ext_rej_, sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H") && Check(hipStreamSynchronize(stream_), "sync");
+	}
+	double ExtLaunchMs(int which) override { const int k = which ? 1 : 0; const double v = ext_ms_[k]; ext_ms_[k] = 0; return v; }
 	static bool SnapFallback() { const char* e = std::getenv("DTRL_SNAPSHOT_FALLBACK"); return e && std::atoi(e) != 0; }
 	bool SnapGather(const SnapPlan& p, char* payload, const int32_t* ids, int n) override { return SnapFallback() ? Backend::SnapGather(p, payload, ids, n) : SnapMove(p, payload, ids, nullptr, n, 0); }
 	bool SnapScatter(const SnapPlan& p, const char* payload, const int32_t* ids, int n) override { return SnapFallback() ? Backend::SnapScatter(p, payload, ids, n) : SnapMove(p, const_cast<char*>(payload), ids, nullptr, n, 1); }
@@ -473,7 +561,8 @@ public:
 		// DTRL_KERNEL=ref selects the LDS-phase reference kernel (A/B and bitwise cross-check); default is the fast path
 		const char* sel = std::getenv("DTRL_KERNEL");
 		const bool use_ref = sel && std::strcmp(sel, "ref") == 0;
-		if (!use_ref && buf.model_topo == TopoDog::kId)
+		if (buf.ext_envs != 0) LaunchExtFrame(stream_, use_ref, FastDynLds(), gm, rp, buf, n_envs, n_steps, dt, frame_end);   // external policy mode: dtrl_backend_hip_ext.hip
+		else if (!use_ref && buf.model_topo == TopoDog::kId)
 			hipLaunchKernelGGL(dtrl_frame_kernel_fast<TopoDog>, dim3(n_envs), dim3(kGroup), FastDynLds(), stream_, gm, rp, buf, n_envs, n_steps, dt, frame_end ? 1 : 0);
 		else if (!use_ref && buf.model_topo == TopoRaptor::kId)
 			hipLaunchKernelGGL(dtrl_frame_kernel_fast<TopoRaptor>, dim3(n_envs), dim3(kGroup), FastDynLds(), stream_, gm, rp, buf, n_envs, n_steps, dt, frame_end ? 1 : 0);
@@ -527,6 +616,7 @@ private:
 	hipStream_t stream_ = nullptr;   // the selected one
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> events_, free_events_, pending_;
 	static int Key(int group, int slot) { return group * 16 + slot; }
+	int32_t* ext_rej_ = nullptr; double ext_ms_[2] = {0, 0};   // external policy mode: rejected-row counter (device), device time of the collection / scatter launches
 	hipEvent_t snap_ev_[2] = {nullptr, nullptr}; double snap_ms_ = 0;   // the snapshot launches since the last SnapLaunchMs(), timed with events
 	hipEvent_t policy_ready_ = nullptr;   // behind the latest asynchronous policy gather (GatherF32Async)
 	std::map<int, hipEvent_t> marks_;   // (env group, tuple ring) -> event behind the group's latest frame launch that wrote that ring

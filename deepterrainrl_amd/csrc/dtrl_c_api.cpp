@@ -255,6 +255,24 @@ try {
 	if (frag_size) *frag_size = c.model.n_opt;
 	return DTRL_OK;
 } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+// ---- external policy mode ----
+dtrl_status dtrl_pending_actions(dtrl_batch* b, int32_t* env_ids, double* states, int cap, int* out_n) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.PendingActions(env_ids, states, cap, out_n, false)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_pending_actions_device(dtrl_batch* b, int32_t* env_ids_dev, float* states_dev, int cap, int* out_n) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.PendingActions(env_ids_dev, states_dev, cap, out_n, true)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_supply_actions(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* action_ids, const double* params, const uint32_t* flags) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SupplyActions(env_ids, n, action_ids, params, flags, false, nullptr)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_supply_actions_device(dtrl_batch* b, const int32_t* env_ids_dev, int n, const int32_t* action_ids_dev, const float* params_dev, const uint32_t* flags_dev, int* rejected) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SupplyActions(env_ids_dev, n, action_ids_dev, params_dev, flags_dev, true, rejected)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_ext_stats(dtrl_batch* b, int64_t* awaiting, int64_t* ready, int64_t* env_steps_total, int64_t* env_frames_total) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.ExtStats(awaiting, ready, env_steps_total, env_frames_total)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_ext_env_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* park, int32_t* steps_left) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.ExtEnvInfo(env_ids, n, park, steps_left)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_action_dims(const dtrl_batch* b, int* n_opt, int* n_labels, int* num_update_steps, int* external)
+try {
+	CHECK_B();
+	const dtrl::ScenarioConfig& c = b->eng.cfg();
+	if (n_opt) *n_opt = c.model.n_opt;
+	if (n_labels) *n_labels = c.model.n_actions > 1 ? c.model.n_actions : 1;
+	if (num_update_steps) *num_update_steps = c.model.num_update_steps;
+	if (external) *external = c.external_policy ? 1 : 0;
+	return DTRL_OK;
+} catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+double dtrl_ext_launch_ms(dtrl_batch* b, int which) try { return b ? b->eng.ExtLaunchMs(which) : -1.0; } catch (...) { return -1.0; }
 dtrl_status dtrl_kernel_time_ms(dtrl_batch* b, double* avg_ms, int64_t* launches) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.KernelTime(avg_ms, launches)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 
 dtrl_status dtrl_drain_tuples_device(dtrl_batch* b, float* rows_dev, uint32_t* flags_dev, int32_t* env_ids_dev, int cap, int* out_n)

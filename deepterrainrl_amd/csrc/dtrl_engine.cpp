@@ -119,6 +119,7 @@ Engine::~Engine()
 		be_->Sync();
 		for (Snapshot* s : snapshots_) { be_->Free(s->payload); s->payload = nullptr; s->owner = nullptr; }   // (the handles stay valid for dtrl_snapshot_info / _free)
 		be_->FreeHostStaging(snap_ids_);
+		if (ext_meta_) be_->FreeHostStaging(ext_meta_);
 		for (void* p : allocs_) be_->Free(p);
 		for (void* p : host_allocs_) be_->FreeHostStaging(p);
 		be_->FreeHostStaging(pin_drain_); be_->FreeHostStaging(pin_recs_); be_->FreeHostStaging(pin_order_); be_->FreeHostStaging(pin_ids_); be_->FreeHostStaging(status_); be_->FreeHostStaging(stage_slot_);
@@ -149,9 +150,16 @@ int Engine::Create(const char* const* argv, int argc, int num_envs, int device_i
 		std::string path = (arg_file.empty() || arg_file[0] == '/' || root.empty()) ? arg_file : root + "/" + arg_file;
 		if (!args.AppendArgs(path)) return Fail(DTRL_ERR_IO, "Failed to load args from: " + path);
 	}
+	{   // (a misspelt mode is an argument error, not a file error)
+		std::string pm;
+		if (args.ParseString("policy_mode", pm) && pm != "internal" && pm != "external") return Fail(DTRL_ERR_ARG, "-policy_mode= must be internal (the policy net runs inside the frame kernel) or external (envs park at their decisions, the caller supplies the actions), not '" + pm + "'");
+	}
 	if (!LoadScenario(args, cfg_, err_)) return DTRL_ERR_IO;
 	n_ = num_envs;
 	const DevModel& m = cfg_.model;
+	// external policy mode takes the place of cBaseControllerMACE::DecideAction (sim/BaseControllerMACE.cpp:267-296); the Q and CACLA controllers decide differently
+	if (cfg_.external_policy && m.ctrl_type != 1)
+		return Fail(DTRL_ERR_ARG, "-policy_mode= external needs a MACE controller (dog_mace, goat_mace, raptor_mace): char_ctrl '" + cfg_.char_ctrl + "' is a " + (m.ctrl_type == 0 ? "Q" : "CACLA") + " controller");
 	S_ = kNumGroundSamples + (2 * m.L - 1) + 2 * m.L;   // sim/TerrainRLCharController.cpp:308-342
 	// sim/BaseControllerMACE.cpp:28-31; sim/BaseControllerCacla.cpp:13-16 (the parameters alone); sim/BaseControllerQ.cpp:12-23 (one-hot over the base actions)
 	A_ = (m.ctrl_type == 2) ? m.n_opt : (m.ctrl_type == 0 ? m.n_actions : 1 + m.n_opt);
@@ -163,7 +171,18 @@ int Engine::Create(const char* const* argv, int argc, int num_envs, int device_i
 
 	auto alloc = [&](size_t bytes) -> void* { void* p = be_->Alloc(bytes); if (p) allocs_.push_back(p); return p; };
 	d_model_ = static_cast<DevModel*>(alloc(sizeof(DevModel)));
-	buf_.st = static_cast<EnvState*>(alloc(sizeof(EnvState) * n_));
+	// (external policy mode: the delivered action rows and the per-env counts follow the state records in the same allocation -- DevBuffers::ext_envs)
+	buf_.st = static_cast<EnvState*>(alloc((sizeof(EnvState) + (cfg_.external_policy ? sizeof(ExtAction) + sizeof(ExtCount) : 0)) * n_));
+	if (cfg_.external_policy) {
+		buf_.ext_envs = n_;
+		ext_meta_ = static_cast<int32_t*>(be_->HostStaging(sizeof(int32_t) * 4));
+		d_ext_ids_ = static_cast<int32_t*>(alloc(sizeof(int32_t) * n_));
+		d_ext_action_ids_ = static_cast<int32_t*>(alloc(sizeof(int32_t) * n_));
+		d_ext_flags_ = static_cast<uint32_t*>(alloc(sizeof(uint32_t) * n_));
+		d_ext_states_ = static_cast<double*>(alloc(sizeof(double) * S_ * n_));
+		d_ext_params_ = static_cast<double*>(alloc(sizeof(double) * std::max(1, m.n_opt) * n_));
+		if (!ext_meta_ || !d_ext_ids_ || !d_ext_action_ids_ || !d_ext_flags_ || !d_ext_states_ || !d_ext_params_) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+	}
 	buf_.gr = static_cast<GroundRec*>(alloc(sizeof(GroundRec) * n_));
 	buf_.status = static_cast<EnvStatus*>(alloc(sizeof(EnvStatus) * n_));
 	buf_.poli_state = static_cast<real*>(alloc(sizeof(real) * S_ * n_));
@@ -453,7 +472,8 @@ int Engine::StepBegin(double dt)
 {
 	if (step_pending_) return Fail(DTRL_ERR_ARG, early_any_ ? "dtrl_step_begin after dtrl_step_poll relaunched a group: call dtrl_step_end_begin" : "dtrl_step_begin called twice without dtrl_step_end");
 	if (dt <= 0) return DTRL_OK;   // cScenarioSimChar::Update returns early (scenarios/ScenarioSimChar.cpp:148-151)
-	if (cfg_.model.has_net && !policy_set_) return Fail(DTRL_ERR_ARG, "policy_net was given but dtrl_set_policy has not been called");
+	if (cfg_.model.has_net && !policy_set_ && !cfg_.external_policy) return Fail(DTRL_ERR_ARG, "policy_net was given but dtrl_set_policy has not been called");
+	// (external policy mode: the launch is a TICK -- every env starts or continues its own frame of `steps` env-steps: dtrl_kernel.h env_frame_impl)
 	const int steps = cfg_.model.num_update_steps;
 	ApplyPendingPolicy();
 	if (tuple_pipelining_) { wr_ring_ ^= 1; UseRing(buf_, wr_ring_); }   // this frame's tuples go to the ring that is not being drained
@@ -476,6 +496,7 @@ int Engine::StepEnd()
 // With tuple pipelining on, the new launches write the other tuple ring and the frame that has just ended can be drained when this returns.
 int Engine::StepEndBegin(double dt)
 {
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_step_end_begin: not available with -policy_mode= external (envs wait for the caller's actions between ticks: use dtrl_step or dtrl_step_begin / dtrl_step_end)");
 	if (!step_pending_) return StepBegin(dt);
 	if (dt <= 0) return StepEnd();
 	const int G = static_cast<int>(groups_.size());
@@ -505,6 +526,7 @@ int Engine::StepEndBegin(double dt)
 int Engine::StepPoll(double dt, int* relaunched)
 {
 	if (relaunched) *relaunched = 0;
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_step_poll: not available with -policy_mode= external (it relaunches frames, and tuple pipelining is off in this mode)");
 	if (!step_pending_ || !tuple_pipelining_ || dt <= 0 || cfg_.device_terrain) return DTRL_OK;
 	const int G = static_cast<int>(groups_.size());
 	if (static_cast<int>(early_.size()) != G) early_.assign(static_cast<size_t>(G), 0);
@@ -541,6 +563,7 @@ int Engine::Step(double dt)
 
 int Engine::StepUpdates(int n)
 {
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_step_updates: not available with -policy_mode= external (every env keeps its own frame of num_update_steps env-steps: use dtrl_step)");
 	if (n <= 0) return DTRL_OK;
 	if (early_any_ || step_pending_) return Fail(DTRL_ERR_ARG, "dtrl_step_updates while a frame is in flight (dtrl_step_begin / dtrl_step_poll): call dtrl_step_end_begin / dtrl_step_end first");
 	if (cfg_.model.has_net && !policy_set_) return Fail(DTRL_ERR_ARG, "policy_net was given but dtrl_set_policy has not been called");
@@ -556,6 +579,7 @@ int Engine::StepUpdates(int n)
 // covered by the other groups' next launches. Same results as `frames` calls of Step(dt).
 int Engine::RunFrames(int frames, double dt)
 {
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_run_frames: not available with -policy_mode= external (envs wait for the caller's actions between ticks: use dtrl_step)");
 	if (frames <= 0 || dt <= 0) return DTRL_OK;
 	if (early_any_ || step_pending_) return Fail(DTRL_ERR_ARG, "dtrl_run_frames while a frame is in flight (dtrl_step_begin / dtrl_step_poll): call dtrl_step_end_begin / dtrl_step_end first");
 	if (cfg_.model.has_net && !policy_set_) return Fail(DTRL_ERR_ARG, "policy_net was given but dtrl_set_policy has not been called");
@@ -680,6 +704,7 @@ void Engine::BuildRelayoutMap(std::vector<int32_t>& map) const
 
 int Engine::SetPolicy(const float* w, size_t n, const double* io, const double* is, const double* oo, const double* os)
 {
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_set_policy: not available with -policy_mode= external (the caller's policy decides: dtrl_pending_actions / dtrl_supply_actions; no policy net runs inside the frame kernel)");
 	if (!cfg_.has_policy_net) return Fail(DTRL_ERR_ARG, "no -policy_net= in the arguments: this batch has no network");
 	const NetDesc& d = cfg_.net;
 	if (!w || n != static_cast<size_t>(cfg_.user_num_params)) return Fail(DTRL_ERR_ARG, "weight count does not match the deploy prototxt");
@@ -718,6 +743,7 @@ void Engine::ApplyPendingPolicy()
 // to the buffer. Valid at any time (frame in flight or not); w_dev must stay unchanged until the caller's stream has passed this point.
 int Engine::SetPolicyDeviceAsync(const float* w_dev, size_t n, void* stream)
 {
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_set_policy_device_async: not available with -policy_mode= external (the caller's policy decides: dtrl_pending_actions / dtrl_supply_actions; no policy net runs inside the frame kernel)");
 	if (!cfg_.has_policy_net) return Fail(DTRL_ERR_ARG, "no -policy_net= in the arguments: this batch has no network");
 	if (!w_dev || n != static_cast<size_t>(cfg_.user_num_params)) return Fail(DTRL_ERR_ARG, "weight count does not match the deploy prototxt");
 	if (!policy_set_ || !weights_alt_) return Fail(DTRL_ERR_ARG, "dtrl_set_policy_device_async needs a policy (normalisers) installed by dtrl_set_policy / dtrl_set_policy_device first");
@@ -732,6 +758,7 @@ int Engine::SetPolicyDeviceAsync(const float* w_dev, size_t n, void* stream)
 }
 int Engine::SetPolicyDevice(const float* w_dev, size_t n, const double* io_dev, const double* is_dev, const double* oo_dev, const double* os_dev, void* stream)
 {
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_set_policy_device: not available with -policy_mode= external (the caller's policy decides: dtrl_pending_actions / dtrl_supply_actions; no policy net runs inside the frame kernel)");
 	if (!cfg_.has_policy_net) return Fail(DTRL_ERR_ARG, "no -policy_net= in the arguments: this batch has no network");
 	const NetDesc& d = cfg_.net;
 	if (!w_dev || n != static_cast<size_t>(cfg_.user_num_params)) return Fail(DTRL_ERR_ARG, "weight count does not match the deploy prototxt");
@@ -784,6 +811,7 @@ int Engine::UploadNormalizers()
 // cNeuralNet::LoadScale, learning/NeuralNet.cpp:137-215
 int Engine::LoadScaleFile(const char* path)
 {
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_load_scale_file: not available with -policy_mode= external (the caller's policy decides: dtrl_pending_actions / dtrl_supply_actions; no policy net runs inside the frame kernel)");
 	if (!cfg_.has_policy_net) return Fail(DTRL_ERR_ARG, "no -policy_net= in the arguments: this batch has no network");
 	if (!path) return Fail(DTRL_ERR_ARG, "null path");
 	const NetDesc& d = cfg_.net;
@@ -861,6 +889,7 @@ bool Engine::RingRead(void* dst, const void* src, size_t n) { if (cfg_.tuple_rin
 bool Engine::RingWrite(void* dst, const void* src, size_t n) { if (cfg_.tuple_ring_host) { std::memcpy(dst, src, n); return true; } return be_->H2D(dst, src, n); }
 int Engine::SetTuplePipelining(bool on)
 {
+	if (on && cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_set_tuple_pipelining(1): not available with -policy_mode= external (a tick is not a frame: envs complete their frames in different ticks, so no ring is ever idle)");
 	if (step_pending_) return Fail(DTRL_ERR_ARG, "dtrl_set_tuple_pipelining between dtrl_step_begin and dtrl_step_end");
 	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	if (on && !ring_[1].rows) {
@@ -1343,6 +1372,7 @@ SnapPlan Engine::MakeSnapPlan() const
 	add(buf_.tup_s0, sizeof(real) * S_, false);
 	add(buf_.tup_a, sizeof(real) * A_, false);
 	if (buf_.nn_out) add(buf_.nn_out, sizeof(real) * static_cast<size_t>(cfg_.net.out_size), false);
+	if (cfg_.external_policy) add(ext_actions(buf_), sizeof(ExtAction), false);   // a delivered, not yet consumed action row (EnvState carries the park state itself)
 	return p;
 }
 
@@ -1357,6 +1387,7 @@ SnapHeader Engine::MakeSnapHeader(int n) const
 	h.terrain_mode = cfg_.device_terrain ? 1 : 0;
 	h.env_bytes = MakeSnapPlan().env_bytes; h.host_bytes = cfg_.device_terrain ? 0 : static_cast<uint32_t>(sizeof(GroundWindowState));
 	h.n_envs = n;
+	h.policy_mode = cfg_.external_policy ? 1 : 0;
 	return h;
 }
 
@@ -1383,6 +1414,7 @@ int Engine::CheckSnapHeader(const SnapHeader& h, const char* what)
 	if (h.S != me.S) return bad("S (policy state size)", h.S, me.S, "");
 	if (h.A != me.A) return bad("A (policy action size)", h.A, me.A, "");
 	if (h.nn_out != me.nn_out) return bad("net output size", h.nn_out, me.nn_out, "");
+	if (h.policy_mode != me.policy_mode) return bad("policy_mode", h.policy_mode, me.policy_mode, " (0 = internal, 1 = -policy_mode= external)");
 	if (h.terrain_mode != me.terrain_mode) return bad("terrain mode", h.terrain_mode, me.terrain_mode, " (0 = host generator, 1 = -terrain_gen= device)");
 	if (h.env_bytes != me.env_bytes) return bad("device bytes per env", h.env_bytes, me.env_bytes, "");
 	if (h.host_bytes != me.host_bytes) return bad("host bytes per env", h.host_bytes, me.host_bytes, "");
@@ -1567,6 +1599,8 @@ int Engine::SnapshotImport(const void* blob, size_t bytes, Snapshot** out)
 		else if (st.pert_link < -1 || st.pert_link >= m.L) bad = "pert_link";
 		else if (st.state < 0 || st.state >= 4) bad = "state";
 		else if (st.stance < 0 || st.stance > 1) bad = "stance";
+		else if (st.ext_park < 0 || st.ext_park > (cfg_.external_policy ? kExtReady : 0)) bad = "ext_park";
+		else if (st.ext_steps_left < (st.ext_park != 0 ? 1 : 0) || st.ext_steps_left > (cfg_.external_policy ? m.num_update_steps : 0)) bad = "ext_steps_left";   // (an env parks INSIDE an env-step: at least that one is left)
 		else if (gr.w[0] < 0 || gr.w[0] > kSegCap || gr.w[1] < 0 || gr.w[1] > kSegCap) bad = "ground segment width";
 		if (bad) return Fail(DTRL_ERR_ARG, std::string("dtrl_snapshot_import: ") + bad + " of saved env " + std::to_string(i) + " is out of range");
 	}
@@ -1583,6 +1617,109 @@ int Engine::SnapshotImport(const void* blob, size_t bytes, Snapshot** out)
 	if (!s->host.empty()) std::memcpy(s->host.data(), p_host, s->host.size());
 	if (!be_->H2D(s->payload, p_dev, static_cast<size_t>(h.n_envs) * h.env_bytes)) { Fail(DTRL_ERR_DEVICE, be_->error()); SnapshotRelease(s); return DTRL_ERR_DEVICE; }
 	*out = s;
+	return DTRL_OK;
+}
+
+// ---- external policy mode (include/dtrl.h: dtrl_pending_actions ... dtrl_ext_stats) ----
+int Engine::ExtRefuse(const char* what)
+{
+	if (!cfg_.external_policy) return Fail(DTRL_ERR_ARG, std::string(what) + ": the batch runs in internal policy mode (create it with -policy_mode= external)");
+	// refuse, do not wait: the tick in flight ends with the caller's own dtrl_step_end
+	if (step_pending_ || early_any_) return Fail(DTRL_ERR_ARG, std::string(what) + " between dtrl_step_begin and dtrl_step_end: a tick is in flight; call dtrl_step_end first");
+	be_->SelectStream(0);
+	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::PendingActions(int32_t* env_ids, void* states, int cap, int* out_n, bool device)
+{
+	const char* what = device ? "dtrl_pending_actions_device" : "dtrl_pending_actions";
+	if (out_n) *out_n = 0;
+	int rc = ExtRefuse(what);
+	if (rc != DTRL_OK) return rc;
+	if (cap < 0 || !out_n || (cap > 0 && !env_ids)) return Fail(DTRL_ERR_ARG, std::string(what) + ": env_ids and out_n are required, cap must not be negative");
+	cap = std::min(cap, n_);
+	if (device) {
+		if (!be_->ExtCollect(buf_, n_, cap, cap > 0 ? env_ids : d_ext_ids_, cap > 0 ? states : nullptr, true, ext_meta_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+		*out_n = ext_meta_[0];
+		return DTRL_OK;
+	}
+	if (!be_->ExtCollect(buf_, n_, cap, d_ext_ids_, (states && cap > 0) ? d_ext_states_ : nullptr, false, ext_meta_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	const int m = ext_meta_[0];
+	if (m > 0 && !be_->D2H(env_ids, d_ext_ids_, sizeof(int32_t) * m)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (m > 0 && states && !be_->D2H(states, d_ext_states_, sizeof(double) * static_cast<size_t>(m) * S_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	*out_n = m;
+	return DTRL_OK;
+}
+
+int Engine::SupplyActions(const int32_t* env_ids, int n, const int32_t* action_ids, const void* params, const uint32_t* flags, bool device, int* rejected)
+{
+	const char* what = device ? "dtrl_supply_actions_device" : "dtrl_supply_actions";
+	if (rejected) *rejected = 0;
+	int rc = ExtRefuse(what);
+	if (rc != DTRL_OK) return rc;
+	if (n < 0 || n > n_) return Fail(DTRL_ERR_ARG, std::string(what) + ": row count out of range (0 .. num_envs)");
+	if (n == 0) return DTRL_OK;
+	if (!env_ids || !params) return Fail(DTRL_ERR_ARG, std::string(what) + ": env_ids and params are required");
+	const int n_opt = cfg_.model.n_opt, n_labels = std::max(1, cfg_.model.n_actions);
+	int32_t rej = 0;
+	if (device) {
+		// rows straight from the caller's device arrays; a row that does not apply (id or label out of range, env not awaiting, env named twice) is skipped and counted
+		if (!be_->ExtSupply(buf_, n_, n_opt, n_labels, env_ids, n, action_ids, params, true, flags, true, &rej)) return Fail(DTRL_ERR_DEVICE, be_->error());
+		if (rejected) *rejected = rej;
+		return DTRL_OK;
+	}
+	// host rows: all or nothing. Ids in range and distinct (host), every env awaiting (a counting pass of the scatter), labels in range -- then the scatter
+	std::vector<char> seen(static_cast<size_t>(n_), 0);
+	for (int i = 0; i < n; ++i) {
+		const int e = env_ids[i];
+		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, std::string(what) + ": env id " + std::to_string(e) + " out of range; nothing applied");
+		if (seen[e]) return Fail(DTRL_ERR_ARG, std::string(what) + ": env " + std::to_string(e) + " is listed twice; nothing applied");
+		seen[e] = 1;
+		if (action_ids && (action_ids[i] < 0 || action_ids[i] >= n_labels)) return Fail(DTRL_ERR_ARG, std::string(what) + ": action_id of row " + std::to_string(i) + " out of range (0 .. " + std::to_string(n_labels - 1) + ", the range a snapshot accepts); nothing applied");
+	}
+	if (!be_->H2D(d_ext_ids_, env_ids, sizeof(int32_t) * n) || !be_->H2D(d_ext_params_, params, sizeof(double) * static_cast<size_t>(n) * n_opt)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (action_ids && !be_->H2D(d_ext_action_ids_, action_ids, sizeof(int32_t) * n)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (flags && !be_->H2D(d_ext_flags_, flags, sizeof(uint32_t) * n)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (!be_->ExtSupply(buf_, n_, n_opt, n_labels, d_ext_ids_, n, action_ids ? d_ext_action_ids_ : nullptr, d_ext_params_, false, flags ? d_ext_flags_ : nullptr, false, &rej)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (rej > 0) {
+		std::vector<EnvState> st;
+		std::string which;
+		if (GetStates(env_ids, n, st) == DTRL_OK) for (int i = 0; i < n && which.empty(); ++i) if (st[i].ext_park != kExtAwaiting) which = " (first: env " + std::to_string(env_ids[i]) + (st[i].ext_park == kExtReady ? ", which already has its action)" : ", which is running)");
+		return Fail(DTRL_ERR_ARG, std::string(what) + ": " + std::to_string(rej) + " of " + std::to_string(n) + " rows name an env that is not awaiting an action" + which + "; nothing applied");
+	}
+	if (!be_->ExtSupply(buf_, n_, n_opt, n_labels, d_ext_ids_, n, action_ids ? d_ext_action_ids_ : nullptr, d_ext_params_, false, flags ? d_ext_flags_ : nullptr, true, &rej)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (rejected) *rejected = rej;
+	return DTRL_OK;
+}
+
+int Engine::ExtStats(int64_t* awaiting, int64_t* ready, int64_t* env_steps_total, int64_t* env_frames_total)
+{
+	int rc = ExtRefuse("dtrl_ext_stats");
+	if (rc != DTRL_OK) return rc;
+	if (!be_->ExtCollect(buf_, n_, 0, d_ext_ids_, nullptr, false, ext_meta_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (awaiting) *awaiting = ext_meta_[1];
+	if (ready) *ready = ext_meta_[2];
+	if (env_steps_total || env_frames_total) {
+		std::vector<ExtCount> c(static_cast<size_t>(n_));
+		if (!be_->D2H(c.data(), ext_counts(buf_), sizeof(ExtCount) * c.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+		int64_t s = 0, f = 0;
+		for (const ExtCount& x : c) { s += x.env_steps; f += x.env_frames; }
+		if (env_steps_total) *env_steps_total = s;
+		if (env_frames_total) *env_frames_total = f;
+	}
+	return DTRL_OK;
+}
+
+int Engine::ExtEnvInfo(const int32_t* env_ids, int n, int32_t* park, int32_t* steps_left)
+{
+	int rc = ExtRefuse("dtrl_ext_env_info");
+	if (rc != DTRL_OK) return rc;
+	const int cnt = env_ids ? n : n_;
+	std::vector<EnvState> st;
+	rc = GetStates(env_ids, cnt, st);
+	if (rc != DTRL_OK) return rc;
+	for (int i = 0; i < cnt; ++i) { if (park) park[i] = st[i].ext_park; if (steps_left) steps_left[i] = st[i].ext_steps_left; }
 	return DTRL_OK;
 }
 

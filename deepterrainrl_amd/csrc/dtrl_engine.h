@@ -16,7 +16,7 @@ struct PackScratch { int32_t* order = nullptr; int32_t* hist = nullptr; int32_t*
 // One per-env record family of a snapshot: env e's record is `bytes` bytes at slab + e * bytes (records are contiguous in every slab) and sits at byte `off`
 // (a multiple of 8) of the env's slice of a snapshot payload. `bytes` is a multiple of 4 (the fp32 library's policy-state rows); everything else is 8-aligned.
 struct SnapRec { char* slab = nullptr; uint32_t bytes = 0, off = 0, host = 0, pad_ = 0; };   // host: the slab is page-locked HOST memory (the status array of host terrain mode)
-constexpr int kSnapRecs = 8;
+constexpr int kSnapRecs = 12;   // (most in use: 9 -- external policy mode with -terrain_gen= device)
 // what moves with an env, and how a payload slice is laid out. gr_rec >= 0 (host terrain mode): rec[gr_rec] is the GroundRec slab, and an env whose regenerated
 // record is still waiting in page-locked memory (stage_slot[e] > 0) is READ from gr_stage[stage_slot[e] - 1], the record that will be in force at its next launch
 struct SnapPlan { SnapRec rec[kSnapRecs]; int32_t n_rec = 0, gr_rec = -1; uint32_t env_bytes = 0; const GroundRec* gr_stage = nullptr; const int32_t* stage_slot = nullptr; };
@@ -33,6 +33,16 @@ public:
 	virtual bool SnapGather(const SnapPlan& p, char* payload, const int32_t* ids, int n);
 	virtual bool SnapScatter(const SnapPlan& p, const char* payload, const int32_t* ids, int n);
 	virtual bool SnapCopy(const SnapPlan& p, const int32_t* src_ids, const int32_t* dst_ids, int n);
+	// External policy mode (include/dtrl.h dtrl_pending_actions* / dtrl_supply_actions*). Queued on the selected stream and synchronised. ids / states / the row
+	// arrays are device memory, meta is HostStaging() memory. The defaults are host loops over D2H / H2D (what the lane-loop check build runs); the HIP backend
+	// overrides them with its kernels (a scan-based compaction + one wavefront per env / per row).
+	//   ExtCollect  ids[0 .. m) = the awaiting envs in ascending env id (m = min(#awaiting, cap)), states row i = env ids[i]'s S policy-state values as float
+	//               (f32) or double; meta = {m, #awaiting, #ready, 0}. states may be null (counts and ids only)
+	//   ExtSupply   row i -> env ids[i]'s slab record, awaiting -> ready; a row whose id or label (0 .. n_labels - 1) is out of range or whose env is not awaiting is skipped and counted in *rejected
+	//               (host memory). apply = false: count only, write nothing
+	virtual bool ExtCollect(const DevBuffers& buf, int n_envs, int cap, int32_t* ids, void* states, bool f32, int32_t* meta);
+	virtual bool ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labels, const int32_t* ids, int n, const int32_t* action_ids, const void* params, bool f32, const uint32_t* flags, bool apply, int32_t* rejected);
+	virtual double ExtLaunchMs(int which) { (void)which; return -1.0; }   // device time of the collection (0) / scatter (1) launches since the last call (HIP events)
 	virtual double SnapLaunchMs() { return -1.0; }   // device time of the snapshot launches since the last call (HIP events; -1: this backend launches nothing)
 	virtual bool Init(int device_id, std::string& err) = 0;
 	// -reserve_cus= k (before Init): keep k compute units per XCD out of the frame launches (HIP backend; see dtrl_side_stream in include/dtrl.h)
@@ -130,6 +140,50 @@ inline bool Backend::SnapCopy(const SnapPlan& p, const int32_t* src_ids, const i
 	}
 	return true;
 }
+inline bool Backend::ExtCollect(const DevBuffers& buf, int n_envs, int cap, int32_t* ids, void* states, bool f32, int32_t* meta)
+{
+	int m = 0, na = 0, nr = 0;
+	std::vector<real> row(static_cast<size_t>(buf.S));
+	std::vector<float> rf(f32 ? row.size() : 0); std::vector<double> rd(f32 ? 0 : row.size());
+	for (int e = 0; e < n_envs; ++e) {
+		int32_t park = 0;
+		if (!D2H(&park, &buf.st[e].ext_park, sizeof(park))) return false;
+		if (park == kExtReady) ++nr;
+		if (park != kExtAwaiting) continue;
+		++na;
+		if (m >= cap) continue;
+		const int32_t id = e;
+		if (!H2D(ids + m, &id, sizeof(id))) return false;
+		if (states) {
+			if (!D2H(row.data(), buf.poli_state + static_cast<size_t>(e) * buf.S, sizeof(real) * row.size())) return false;
+			if (f32) { for (size_t k = 0; k < row.size(); ++k) rf[k] = static_cast<float>(row[k]); if (!H2D(static_cast<float*>(states) + static_cast<size_t>(m) * buf.S, rf.data(), sizeof(float) * rf.size())) return false; }
+			else { for (size_t k = 0; k < row.size(); ++k) rd[k] = static_cast<double>(row[k]); if (!H2D(static_cast<double*>(states) + static_cast<size_t>(m) * buf.S, rd.data(), sizeof(double) * rd.size())) return false; }
+		}
+		++m;
+	}
+	meta[0] = m; meta[1] = na; meta[2] = nr; meta[3] = 0;
+	return true;
+}
+inline bool Backend::ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labels, const int32_t* ids, int n, const int32_t* action_ids, const void* params, bool f32, const uint32_t* flags, bool apply, int32_t* rejected)
+{
+	*rejected = 0;
+	std::vector<float> pf(f32 ? n_opt : 0); std::vector<double> pd(f32 ? 0 : n_opt);
+	for (int i = 0; i < n; ++i) {
+		int32_t e = -1, park = 0;
+		if (!D2H(&e, ids + i, sizeof(e))) return false;
+		if (e >= 0 && e < n_envs && !D2H(&park, &buf.st[e].ext_park, sizeof(park))) return false;
+		ExtAction a{};
+		if (action_ids && !D2H(&a.action_id, action_ids + i, sizeof(int32_t))) return false;
+		if (e < 0 || e >= n_envs || park != kExtAwaiting || a.action_id < 0 || a.action_id >= n_labels) { ++*rejected; continue; }
+		if (!apply) continue;
+		if (flags && !D2H(&a.flags, flags + i, sizeof(uint32_t))) return false;
+		if (f32) { if (!D2H(pf.data(), static_cast<const float*>(params) + static_cast<size_t>(i) * n_opt, sizeof(float) * n_opt)) return false; for (int k = 0; k < n_opt; ++k) a.params[k] = static_cast<real>(pf[k]); }
+		else { if (!D2H(pd.data(), static_cast<const double*>(params) + static_cast<size_t>(i) * n_opt, sizeof(double) * n_opt)) return false; for (int k = 0; k < n_opt; ++k) a.params[k] = static_cast<real>(pd[k]); }
+		park = kExtReady;
+		if (!H2D(&ext_actions(buf)[e], &a, sizeof(a)) || !H2D(&buf.st[e].ext_park, &park, sizeof(park))) return false;
+	}
+	return true;
+}
 Backend* MakeBackend();   // resolved at link time: HIP in libdtrl.so, the lane-loop test backend under tests/emul/
 
 // Header of an exported snapshot blob (dtrl_snapshot_export): [SnapHeader][int32 slot ids, padded to 8 bytes][device payload n x env_bytes][host payload n x host_bytes].
@@ -143,7 +197,8 @@ struct SnapHeader {
 	int32_t char_type, ctrl_type, L, D, S, A, nn_out;
 	int32_t terrain_mode;                      // 0 = host generator (GroundWindow records in the host payload), 1 = -terrain_gen= device (GroundGen in the device payload)
 	uint32_t env_bytes, host_bytes;            // per env: device payload, host payload
-	int32_t n_envs, pad_;
+	int32_t n_envs;
+	int32_t policy_mode;                       // 0 = internal, 1 = -policy_mode= external (the device payload then ends with the env's ExtAction record); was padding: older blobs read as internal
 };
 static_assert(sizeof(SnapHeader) % 8 == 0, "the payload behind the header is copied as 64-bit words");
 class Engine;
@@ -159,6 +214,13 @@ class Engine {
 public:
 	Engine() {}
 	// env snapshots (include/dtrl.h)
+	// external policy mode (include/dtrl.h)
+	bool external() const { return cfg_.external_policy; }
+	int PendingActions(int32_t* env_ids, void* states, int cap, int* out_n, bool device);
+	int SupplyActions(const int32_t* env_ids, int n, const int32_t* action_ids, const void* params, const uint32_t* flags, bool device, int* rejected);
+	int ExtStats(int64_t* awaiting, int64_t* ready, int64_t* env_steps_total, int64_t* env_frames_total);
+	int ExtEnvInfo(const int32_t* env_ids, int n, int32_t* park, int32_t* steps_left);
+	double ExtLaunchMs(int which) { return be_ ? be_->ExtLaunchMs(which) : -1.0; }
 	int SnapshotSave(const int32_t* env_ids, int n, Snapshot** out);
 	int SnapshotRestore(const Snapshot* s, const int32_t* env_ids, int n);
 	int CloneEnvs(const int32_t* src_ids, const int32_t* dst_ids, int n);
@@ -292,6 +354,12 @@ private:
 	int32_t* snap_ids_ = nullptr;                          // page-locked [2 n]: the env lists the transport kernels read
 	char* snap_scratch_ = nullptr;                         // device [n][env_bytes]: staging of a clone whose lists overlap (allocated on first use)
 	std::vector<Snapshot*> snapshots_;                     // live snapshots whose payload this batch holds
+	// external policy mode: scratch of the hand-over calls
+	int ExtRefuse(const char* what);                       // DTRL_ERR_ARG unless the batch is in external mode and no step is pending
+	int32_t* ext_meta_ = nullptr;                          // page-locked {m, awaiting, ready, 0}
+	int32_t* d_ext_ids_ = nullptr;                         // device [n]
+	double* d_ext_states_ = nullptr;                       // device [n][S] (host call)
+	int32_t* d_ext_action_ids_ = nullptr; uint32_t* d_ext_flags_ = nullptr; double* d_ext_params_ = nullptr;   // device [n], [n], [n][n_opt]: the rows of a host call
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

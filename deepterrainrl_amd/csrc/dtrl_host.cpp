@@ -648,6 +648,11 @@ bool LoadScenario(const ArgParser& args, ScenarioConfig& cfg, std::string& err)
 		std::string gen = "host"; args.ParseString("terrain_gen", gen);
 		if (gen != "host" && gen != "device") { err = "-terrain_gen= must be host (the reference's generator streams, bit-exact) or device (counter-based streams, generated on the GPU)"; return false; }
 		cfg.device_terrain = gen == "device";
+		// -policy_mode= internal | external: who decides at the end of a gait cycle -- the MACE forward inside the frame kernel, or the caller (the env parks)
+		std::string pm = "internal"; args.ParseString("policy_mode", pm);
+		if (pm != "internal" && pm != "external") { err = "-policy_mode= must be internal (the policy net runs inside the frame kernel) or external (envs park at decisions, the caller supplies the actions)"; return false; }
+		cfg.external_policy = pm == "external";
+		cfg.char_ctrl = char_ctrl;
 	}
 
 	// exploration (scenarios/ScenarioExp.cpp:16-45)

@@ -128,6 +128,8 @@ struct ScenarioConfig {
 	std::vector<std::vector<double>> terrain_param_sets;
 	double terrain_blend = 0;
 	uint64_t terrain_seed = 0;
+	bool external_policy = false;  // -policy_mode= external: envs park at their decisions and the caller supplies the actions (dtrl_pending_actions / dtrl_supply_actions)
+	std::string char_ctrl;         // the controller's name as given (messages)
 	bool device_terrain = false;   // -terrain_gen= device: windows are generated and slid by the GPU at the frame boundary (dtrl_terrain_dev.h)
 	int tuple_buffer_size = 16;
 	bool tuple_ring_host = false;  // -tuple_ring= host: the tuple rings live in page-locked host memory the kernels write directly (drains without a device copy)

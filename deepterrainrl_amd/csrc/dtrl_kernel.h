@@ -137,6 +137,11 @@ struct DevBuffers {
 	const int32_t* env_list;   // optional indirection: workgroup b handles env_list[b] (launch order, compact reset launches)
 	int32_t reset_listed;      // 1: every env of this launch performs the device half of a reset (compact reset launches);
 	                           // 2: (-terrain_gen= device) a 0-step launch over a whole group in which the envs that fell (st.need_reset) do, the others return
+	// External policy mode (-policy_mode= external): N, the number of envs, else 0. The allocation behind `st` then continues past its N EnvState records with N
+	// ExtAction records (the delivered action rows) and N ExtCount records (ext_actions() / ext_counts() below). The one new field sits in what was alignment
+	// padding, and the new slabs are reached through `st`, because this struct is a by-value kernel argument: a larger struct moves the launch arguments behind
+	// it, i.e. changes kernarg offsets inside the internal-mode kernels, which must stay the instructions they were
+	int32_t ext_envs;
 	// on-device terrain generation (dtrl_terrain_dev.h); null / 0 in the default (host generator) mode
 	GroundGen* gen;
 	const TerrainCfg* tcfg;
@@ -148,6 +153,9 @@ struct DevBuffers {
 	const real* in_off; const real* in_scale; const real* out_off; const real* out_scale;
 	NetDesc net;
 };
+// external policy mode: the env's delivered action row and its step / frame counts (records of their own, behind the EnvState records: DevBuffers::ext_envs)
+DTRL_HD_INLINE ExtAction* ext_actions(const DevBuffers& b) { return reinterpret_cast<ExtAction*>(b.st + b.ext_envs); }
+DTRL_HD_INLINE ExtCount* ext_counts(const DevBuffers& b) { return reinterpret_cast<ExtCount*>(ext_actions(b) + b.ext_envs); }
 
 // per-env LDS workspace. WSRef (reference / lane-loop path) keeps the joint-space inertia matrix, the square Delassus matrix
 // and the contact sample points in LDS; the register-resident gfx950 path (WSFast) never materialises H or the sample
@@ -1463,7 +1471,9 @@ DTRL_HD inline void nn_eval(W& ws, const DevBuffers& buf, int env)
 }
 
 // cDogController(MACE)::UpdateAction: ParseGround + BuildPoliState + action decision + ApplyAction
-template <class W>
+// Ext (external policy mode, MACE controllers): the policy state is built and a pending command is served as in internal mode; otherwise the env PARKS
+// (st.ext_park = kExtAwaiting) in place of the forward -- the caller's action row is applied by ext_apply_action() when the env resumes
+template <bool Ext, class W>
 DTRL_HD inline void update_action(W& ws, const DevModel& gm, const RunParams& rp, const DevBuffers& buf, const GroundRec& g, int env)
 {
 	real* ps = buf.poli_state + static_cast<int64_t>(env) * buf.S;
@@ -1499,8 +1509,15 @@ DTRL_HD inline void update_action(W& ws, const DevModel& gm, const RunParams& rp
 	if (lane == 0) {
 		if (gm.ctrl_type == 1) { ws.st.exp_actor = 0; ws.st.exp_critic = 0; }
 		ws.st.is_off_policy = 1;
-		int mode = 0;  // 0: keep / default action, 1: command, 2: net, 3: random base action (MACE / CACLA exploration), 4: random base action (Q exploration)
+		int mode = 0;  // 0: keep / default action, 1: command, 2: net, 3: random base action (MACE / CACLA exploration), 4: random base action (Q exploration), 5: park (external mode)
 		if (ws.st.cmd_action >= 0) mode = 1;
+		else if (Ext) {
+			// the caller decides and explores (dtrl_set_explore is ignored here). The one draw the internal MACE branch makes in front of its forward is made
+			// here as well, so that the env's counter stream -- the random first action of its next Exp episode -- does not depend on the mode
+			if (gm.has_net) { Rng rng = make_rng(rp, env, &ws.st.rng_ctr); ws.st.is_off_policy = 0; (void)rng.uniform(); }
+			mode = 5;
+			ws.st.ext_park = kExtAwaiting;
+		}
 		else if (gm.has_net && gm.ctrl_type == 2) {
 			// cBaseControllerCacla::DecideAction / ShouldExplore / ExploreAction (sim/BaseControllerCacla.cpp:124-151, 219-234): explore with
 			// probability exp_rate; an exploring step is a random base action with probability exp_base_rate, the actor's output plus noise otherwise
@@ -1527,6 +1544,7 @@ DTRL_HD inline void update_action(W& ws, const DevModel& gm, const RunParams& rp
 		ws.flag_misc = mode;
 	}
 	LANES_END
+	if (Ext) { if (ws.flag_misc == 5) return; }   // parked (wave-uniform: LDS flag)
 	if (ws.flag_misc == 2) nn_eval(ws, buf, env);
 	LANES_BEGIN
 	if (lane == 0) {
@@ -1589,6 +1607,27 @@ DTRL_HD inline void update_action(W& ws, const DevModel& gm, const RunParams& rp
 			if (!cyclic) build_base_action(gm, num_frags, gm.default_action, rng, &id, prm);
 		}
 		apply_action(ws, id, prm, P);
+	}
+	LANES_END
+}
+
+// external policy mode, resume: the delivered row takes the place of the MACE branch above (sim/BaseControllerMACE.cpp:267-296 -- fragment parameters over
+// the current ones at opt_index, PostProcessParams, ApplyAction); the flag word sets what scenario_new_cycle records for the tuple that starts here
+template <class W>
+DTRL_HD inline void ext_apply_action(W& ws, const DevModel& gm, const DevBuffers& buf, int env)
+{
+	LANES_BEGIN
+	if (lane == 0) {
+		const ExtAction& a = ext_actions(buf)[env];
+		real prm[kMaxP];
+		for (int i = 0; i < gm.P; ++i) prm[i] = ws.st.params[i];
+		for (int k = 0; k < gm.n_opt; ++k) prm[gm.opt_index[k]] = a.params[k];
+		post_process_params(prm, gm.char_type);
+		ws.st.exp_critic = (a.flags >> 1) & 1u; ws.st.exp_actor = (a.flags >> 2) & 1u;
+		ws.st.is_off_policy = (ws.st.exp_actor || ws.st.exp_critic) ? 1 : 0;
+		apply_action(ws, a.action_id, prm, gm.P);
+		ws.st.ext_park = kExtRunning;
+		ws.st.first_cycle = 0;
 	}
 	LANES_END
 }
@@ -1680,12 +1719,16 @@ DTRL_HD inline void solve_ls4(const real (*basis)[4], const real* tau_g, const r
 }
 
 // cDogController::Update (sim/DogController.cpp:229-268) / cRaptorController::Update (sim/RaptorController.cpp:195-233)
-template <class Path, class W>
-DTRL_HD inline void controller_update(W& ws, const DevModel& gm, const RunParams& rp, const DevBuffers& buf, const GroundRec& g, int env, real dt)
+// Ext (external policy mode): returns with st.ext_park == kExtAwaiting when the env parked at its decision; `resume` re-enters behind the FSM head with the
+// delivered action (no time is added twice)
+template <class Path, bool Ext = false, class W>
+DTRL_HD inline void controller_update(W& ws, const DevModel& gm, const RunParams& rp, const DevBuffers& buf, const GroundRec& g, int env, real dt, bool resume = false)
 {
 	const int D = ws.M.D, L = ws.M.L;
 	const bool raptor = gm.char_type == 1;
 	unsigned long long pc_t = PROF_NOW();
+	if (Ext && resume) ext_apply_action(ws, gm, buf, env);
+	else {
 	// UpdateRBDModel: kinematics, composite inertias and the textbook bias at the post-step configuration were produced by
 	// kin_dyn_terms() in env_step (quirk_bias() turns it into the reference's C); H itself is assembled inside the PD solve
 	LANES_BEGIN
@@ -1723,11 +1766,13 @@ DTRL_HD inline void controller_update(W& ws, const DevModel& gm, const RunParams
 	PROF_ADD_SINCE(ws, kProfC_Fsm, pc_t); pc_t = PROF_NOW();
 	if (__builtin_expect(ws.flag_update_action != 0, 0)) {   // once per gait cycle: cold, keep its register pressure out of the step loop
 		PROF_T0();
-		update_action(ws, gm, rp, buf, g, env);
+		update_action<Ext>(ws, gm, rp, buf, g, env);
 		PROF_ADD(ws, kProfAction);
+		if (Ext) { if (ws.st.ext_park == kExtAwaiting) return; }   // wave-uniform (LDS)
 		LANES_BEGIN
 		if (lane == 0) ws.st.first_cycle = 0;
 		LANES_END
+	}
 	}
 	LANES_BEGIN
 	if (lane == 0) {
@@ -1970,18 +2015,23 @@ DTRL_HD inline void scenario_new_cycle(W& ws, const DevModel& gm, const DevBuffe
 }
 
 // one iteration of scenarios/ScenarioSimChar.cpp:162-173
-template <class Path, class W>
-DTRL_HD inline void env_step(W& ws, const DevModel& gm, const RunParams& rp, const DevBuffers& buf, const GroundRec& g, int env, real dt)
+// Ext (external policy mode): the env-step ends early, behind its physics, when the env parks at a decision (st.ext_park == kExtAwaiting); `resume` runs the
+// rest of that env-step in a later launch: the physics is done, the post-step kinematics and contacts are recomputed from the stored (q, qd)
+template <class Path, bool Ext = false, class W>
+DTRL_HD inline void env_step(W& ws, const DevModel& gm, const RunParams& rp, const DevBuffers& buf, const GroundRec& g, int env, real dt, bool resume = false)
 {
 	const real h = dt / gm.num_sim_substeps;
+	if (!(Ext && resume)) {
 	if (__builtin_expect(ws.st.pert_link >= 0, 0)) perturb_begin_step(ws, dt);   // wave-uniform (LDS)
 	// UpdateWorld. The kinematics / composites / bias of the configuration at entry are already in the workspace (frame start, reset,
 	// or the post-step evaluation of the previous env-step), so the first substep does not recompute them
 	for (int s = 0; s < gm.num_sim_substeps; ++s) Path::substep(ws, gm, g, h, s == 0);
+	}
 	kin_dyn_terms(ws);                                                      // post-step kinematics: controller's RBD terms AND the next substep's
 	Path::contacts(ws, gm, g, h);                                               // cContactManager::Update
 	// UpdateGround is host-side at frame boundaries (the 1 m look-ahead margin makes that equivalent; DESIGN.md "Ground")
-	{ PROF_T0(); controller_update<Path>(ws, gm, rp, buf, g, env, dt); PROF_ADD(ws, kProfCtrl); }   // UpdateCharacter
+	{ PROF_T0(); controller_update<Path, Ext>(ws, gm, rp, buf, g, env, dt, resume); PROF_ADD(ws, kProfCtrl); }   // UpdateCharacter
+	if (Ext) { if (ws.st.ext_park == kExtAwaiting) return; }   // parked: wave-uniform (LDS)
 	LANES_BEGIN
 	if (lane == 0) {
 		// cSimCharSoftFall::UpdateFallDistCheck / UpdateFallContactCheck
@@ -2103,8 +2153,14 @@ DTRL_HD inline void load_hot_model(W& ws, const DevModel& gm)
 #ifndef DTRL_COST_MODE
 #define DTRL_COST_MODE 1   // (round 6: the last substep's rows; +1.0 % dog, +0.3 % raptor in 6 of 6 same-box pairs, results unchanged bit for bit -- profiles/r06_launch_order_ab.txt)
 #endif
-template <class Path, class W>
-DTRL_HD inline void env_frame(W& ws, const DevModel& gm, const RunParams& rp, const DevBuffers& buf, int env, int n_steps, real dt, bool do_frame_end)
+// Ext = false: the frame as above (internal policy mode). Ext = true (external policy mode, -policy_mode= external): a launch with n_steps > 0 is a TICK of the
+// env's OWN frame -- an env whose frame is complete starts a new one of n_steps env-steps, an env that parked at a decision and has its action (kExtReady)
+// finishes the env-step it parked in, and either runs until the frame is complete (frame_end) or it parks; an env that is still waiting for its action
+// returns at once with state and status untouched. The status record is written only by an env that completed its frame in this launch (and by 0-step
+// reset launches), so the frame-boundary work behind the launch finds nothing to do for the others. The kernels instantiate one case each; env_frame()
+// below picks by buf.ext_envs for callers that take either (the lane-loop check build).
+template <class Path, bool Ext, class W>
+DTRL_HD inline void env_frame_impl(W& ws, const DevModel& gm, const RunParams& rp, const DevBuffers& buf, int env, int n_steps, real dt, bool do_frame_end)
 {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(DTRL_PROFILE)
 	const unsigned long long prof_frame_t0 = __builtin_readcyclecounter();
@@ -2136,11 +2192,49 @@ DTRL_HD inline void env_frame(W& ws, const DevModel& gm, const RunParams& rp, co
 	}
 	const GroundRec& g = buf.gr[env];
 	if (buf.reset_listed == 2 && ws.st.need_reset == 0 && ws.st.do_init == 0) return;   // wave-uniform: this env did not fall, nothing to do (state, status untouched)
+	if (Ext) { if (n_steps > 0 && ws.st.ext_park == kExtAwaiting) return; }               // wave-uniform: parked and nobody has answered yet
+	bool ext_resume = false;
+	const bool ext_was_reset = Ext && (ws.st.do_init != 0 || ws.st.do_reset != 0 || buf.reset_listed != 0);
 	if (__builtin_expect(ws.st.do_init != 0, 0)) reset_env(ws, gm, rp, buf, g, env, true);
 	else if (__builtin_expect(ws.st.do_reset != 0 || buf.reset_listed != 0, 0)) reset_env(ws, gm, rp, buf, g, env, false);
-	else forward_kinematics(ws);
+	else { forward_kinematics(ws); if (Ext) ext_resume = n_steps > 0 && ws.st.ext_park == kExtReady; }
+	if (Ext) {
+		if (ext_was_reset) {   // a reset env is at the start of a frame, whatever it was waiting for
+			LANES_BEGIN
+			if (lane == 0) { ws.st.ext_park = kExtRunning; ws.st.ext_steps_left = 0; }
+			LANES_END
+		}
+	}
+	if (!Ext) {
 	for (int s = 0; s < n_steps; ++s) env_step<Path>(ws, gm, rp, buf, g, env, dt);
 	if (do_frame_end) frame_end(ws, gm, buf, env);
+	} else if (n_steps > 0) {
+		// the remaining-steps counter lives in LDS with the rest of the state (lane 0 writes, every lane reads behind the phase's end: wave-uniform)
+		LANES_BEGIN
+		if (lane == 0) { if (!ext_resume && ws.st.ext_steps_left <= 0) ws.st.ext_steps_left = n_steps; }
+		LANES_END
+		int done = 0;
+		bool parked = false;
+		// (one instance of the env-step: the first iteration of a resumed env enters it behind the physics; a parked env always has a step left)
+		for (bool resume = ext_resume; ws.st.ext_steps_left > 0; resume = false) {
+			env_step<Path, true>(ws, gm, rp, buf, g, env, dt, resume);
+			if (ws.st.ext_park == kExtAwaiting) { parked = true; break; }
+			LANES_BEGIN
+			if (lane == 0) ws.st.ext_steps_left -= 1;
+			LANES_END
+			++done;
+		}
+		if (!parked && do_frame_end) frame_end(ws, gm, buf, env);
+		{
+			uint64_t* dst = reinterpret_cast<uint64_t*>(&buf.st[env]);
+			const uint64_t* src = reinterpret_cast<const uint64_t*>(&ws.st);
+			LANES_BEGIN
+			if (parked) for (int i = lane; i < static_cast<int>(sizeof(EnvState) / 8); i += kGroup) dst[i] = src[i];
+			if (lane == 0) { ExtCount& c = ext_counts(buf)[env]; c.env_steps += done; if (!parked) c.env_frames += 1; }
+			LANES_END
+		}
+		if (parked) return;   // mid-frame: the status record keeps what the env's last completed frame (or its reset) wrote
+	}
 	{
 		uint64_t* dst = reinterpret_cast<uint64_t*>(&buf.st[env]);
 		const uint64_t* src = reinterpret_cast<const uint64_t*>(&ws.st);
@@ -2172,6 +2266,12 @@ DTRL_HD inline void env_frame(W& ws, const DevModel& gm, const RunParams& rp, co
 		if (threadIdx.x < kProfMax) buf.prof[static_cast<int64_t>(env) * kProfMax + threadIdx.x] += ws.prof[threadIdx.x];
 	}
 #endif
+}
+template <class Path, class W>
+DTRL_HD inline void env_frame(W& ws, const DevModel& gm, const RunParams& rp, const DevBuffers& buf, int env, int n_steps, real dt, bool do_frame_end)
+{
+	if (buf.ext_envs) env_frame_impl<Path, true>(ws, gm, rp, buf, env, n_steps, dt, do_frame_end);
+	else env_frame_impl<Path, false>(ws, gm, rp, buf, env, n_steps, dt, do_frame_end);
 }
 
 }  // namespace dtrl

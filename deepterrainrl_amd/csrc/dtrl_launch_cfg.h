@@ -1,0 +1,25 @@
+// dtrl_launch_cfg.h -- register budget of the fast frame kernels, shared by the translation units that instantiate them (dtrl_backend_hip.hip: internal policy
+// mode; dtrl_backend_hip_ext.hip: external policy mode)
+#pragma once
+#include "dtrl_kernel.h"
+#include "dtrl_topo.h"
+
+namespace dtrl {
+
+#ifndef DTRL_WAVES_PER_EU
+#define DTRL_WAVES_PER_EU 2
+#endif
+#ifndef DTRL_WAVES_DOG
+#define DTRL_WAVES_DOG DTRL_WAVES_PER_EU
+#endif
+#ifndef DTRL_WAVES_RAPTOR
+#define DTRL_WAVES_RAPTOR DTRL_WAVES_PER_EU
+#endif
+template <class Topo> struct WavesPerEu { static constexpr int value = DTRL_WAVES_PER_EU; };
+template <> struct WavesPerEu<TopoDog> { static constexpr int value = DTRL_WAVES_DOG; };          // (the fp32 build gives each skeleton's instance its own register budget:
+template <> struct WavesPerEu<TopoRaptor> { static constexpr int value = DTRL_WAVES_RAPTOR; };    //  profiles/r06_fp32_physics.txt)
+
+// launches the external-mode instantiation of the frame kernel (dtrl_backend_hip_ext.hip) on `stream` (a hipStream_t); use_ref: the LDS-phase reference form
+bool LaunchExtFrame(void* stream, bool use_ref, unsigned dyn_lds, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end);
+
+}  // namespace dtrl

@@ -154,16 +154,30 @@ struct EnvState {
 	// on link pert_link at its COM plus the constant torque of its application offset, while pert_time < pert_dur
 	int32_t pert_link;       // -1 = none
 	int32_t pert_on;         // applied during the current env-step (set at the env-step's start)
-	int32_t pad_;
+	int32_t ext_steps_left;  // external policy mode (-policy_mode= external): env-steps of the env's current frame that are not finished yet, 0 = the frame is complete (always 0 in internal mode)
 	real pert_f[2], pert_lp[2], pert_torque, pert_time, pert_dur;   // pert_lp: application point relative to the COM, in the link's joint frame
 	// Bullet's persistent contact points (DevModel::warm_start): the rows of the last solved substep by identity, with the impulses they ended with. Row ids
 	// (16 bit, shared with oracle/or_sim.h): ground contact 2 x sample point + (0 normal, 1 tangent); link--link contact 512 + 2 x (pair x 12 + candidate) + (0, 1);
 	// limit rows 0xffff (never matched). Carried across env-steps and frames; emptied by a reset
 	real ws_lam[kMaxRows];
 	uint16_t ws_id[kMaxRows];
-	int32_t ws_R, pad_ws_;
+	int32_t ws_R;
+	int32_t ext_park;        // external policy mode: kExtRunning, kExtAwaiting (parked at a decision, no action yet) or kExtReady (parked, its action row is in the slab); always 0 in internal mode
 };
 static_assert(sizeof(EnvState) % 8 == 0, "EnvState is copied as 64-bit words");
+
+// ---- external policy mode (-policy_mode= external; include/dtrl.h dtrl_pending_actions / dtrl_supply_actions) ----
+enum ExtPark { kExtRunning = 0, kExtAwaiting = 1, kExtReady = 2 };
+// the action row the caller delivered for a parked env (one record per env in a device slab of its own: DevBuffers::ext_envs): what cBaseControllerMACE::DecideAction
+// would have produced -- a label, the optimisable parameters in opt_index order, and the tuple-flag word (bit 1 exp_critic, bit 2 exp_actor: scenario_new_cycle's layout)
+struct ExtAction {
+	int32_t action_id;
+	uint32_t flags;
+	real params[kMaxP];
+};
+static_assert(sizeof(ExtAction) % 8 == 0, "ExtAction is copied as 64-bit words");
+// what one env did in external mode, written by its own wavefront (no atomics): env-steps finished and frames completed since the batch was created
+struct ExtCount { int64_t env_steps, env_frames; };
 
 struct GroundRec {
 	// logical order: slot 0 = min segment, slot 1 = max segment (the host resolves the reference's mFlipSeg)

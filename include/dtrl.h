@@ -236,7 +236,7 @@ dtrl_status dtrl_snapshot_restore(dtrl_batch* b, const dtrl_snapshot* snap, cons
  * overlap behave as "read all, then write all" (src = {0, 1}, dst = {1, 2}: env 2 gets the OLD env 1). */
 dtrl_status dtrl_clone_envs(dtrl_batch* b, const int32_t* src_ids, const int32_t* dst_ids, int n);
 /* One flat, self-describing host blob: a header (magic "DTRLSNP1", format version, sizeof(real), sizeof(EnvState), sizeof(GroundRec) and the other record sizes,
- * character and controller type, L, D, S, A, the net's output size, the terrain mode, bytes per env, env count), the saved slot ids, the device payload
+ * character and controller type, L, D, S, A, the net's output size, the terrain mode, bytes per env, env count, the policy mode), the saved slot ids, the device payload
  * [n][bytes per env] (each env: EnvState first, then GroundRec, ...), the host payload. *bytes = the blob's size; cap == 0 returns the size only; a smaller
  * buffer is DTRL_ERR_CAPACITY. Needs the batch that holds the snapshot to be alive and idle (errors are reported through that batch's dtrl_last_error). */
 dtrl_status dtrl_snapshot_export(const dtrl_snapshot* snap, void* buf, size_t cap, size_t* bytes);
@@ -249,6 +249,49 @@ dtrl_status dtrl_snapshot_import(dtrl_batch* b, const void* blob, size_t bytes, 
 dtrl_status dtrl_snapshot_info(const dtrl_snapshot* snap, int32_t* n_envs, size_t* bytes_per_env, size_t* sizeof_env_state, size_t* host_bytes_per_env);
 /* Valid before or after dtrl_destroy of the batch (which releases the payload; the handle then only answers dtrl_snapshot_info). */
 dtrl_status dtrl_snapshot_free(dtrl_snapshot* snap);
+
+/* ---- External policy mode: the caller's policy in place of the net inside the frame kernel (`-policy_mode= external`; default `internal`) ----
+ * Replaces: the decision inside cBaseControllerMACE::UpdateAction -- DecideAction / DecideActionBoltzmann and the forward behind it
+ * (sim/BaseControllerMACE.cpp:267-296) -- through the seam the reference itself has: a controller takes a commanded action from outside
+ * (cCharController::CommandAction, sim/CharController.h:23) and cScenarioExp hands every decision's state and action to a learner it does not own
+ * (scenarios/ScenarioExp.cpp:63-73). MACE controllers only (dog_mace, goat_mace, raptor_mace): with a Q or CACLA controller dtrl_create fails with DTRL_ERR_ARG.
+ *
+ * Every env keeps its own frame of num_update_steps env-steps. dtrl_step (or dtrl_step_begin / dtrl_step_end) is a TICK: an env whose frame is complete
+ * starts a new one; every env runs until its frame is complete (falls, resets and episode bookkeeping happen there, as in internal mode) or until its gait
+ * cycle ends and it needs an action, whichever comes first. An env that needs an action PARKS behind the physics of that env-step, with its policy state
+ * built (ParseGround / BuildPoliState); a pending commanded action -- dtrl_command_action, the random first action of an Exp episode -- is served without
+ * asking. A parked env that has been given its action finishes that env-step and the rest of its frame in the next tick; one that has not stays exactly as
+ * it is. The env-steps, decisions and fall checks of one env are the sequence internal mode runs; only their grouping into launches differs. Terrain windows,
+ * resets and the dist log are handled in the tick in which an env completes its frame.
+ *
+ * An action row is what the MACE branch would have produced: action_id (a label, 0 .. number of base actions - 1: stored as the current action id and in the
+ * tuple), params[frag_size of dtrl_action_dims] (written over the current parameters at the optimisable indices, then PostProcessParams and ApplyAction), and
+ * an optional flag word in the tuple-flag layout (DTRL_TUPLE_EXP_CRITIC, DTRL_TUPLE_EXP_ACTOR: what the tuple that starts here is recorded with).
+ * dtrl_set_explore is ignored at these decisions: the caller explores.
+ *
+ * Refused in this mode (DTRL_ERR_ARG): dtrl_step_updates, dtrl_run_frames, dtrl_step_poll, dtrl_step_end_begin, dtrl_set_tuple_pipelining(1), dtrl_set_policy*,
+ * dtrl_load_scale_file. The calls below fail with DTRL_ERR_ARG on an internal-mode batch, and -- they never wait -- between dtrl_step_begin and dtrl_step_end.
+ * Snapshots carry the park state and a delivered action; a blob of one mode is refused by a batch of the other. */
+/* The awaiting envs in ascending env id: env_ids[0 .. *out_n) and their policy states states[*out_n][S of dtrl_dims] (may be NULL); at most cap of them. */
+dtrl_status dtrl_pending_actions(dtrl_batch* b, int32_t* env_ids, double* states, int cap, int* out_n);
+/* The same into DEVICE memory, states as float (a torch policy on the same GPU reads them in place). The arrays are complete when the call returns. */
+dtrl_status dtrl_pending_actions_device(dtrl_batch* b, int32_t* env_ids_dev, float* states_dev, int cap, int* out_n);
+/* n rows (host memory) for n distinct awaiting envs; action_ids and flags may be NULL (zeros). All or nothing: an id that is out of range, named twice or not
+ * awaiting, or a label out of range, is DTRL_ERR_ARG and nothing is applied. */
+dtrl_status dtrl_supply_actions(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* action_ids, const double* params, const uint32_t* flags);
+/* n rows in DEVICE memory (params as float; the caller's stream must have finished writing them). A row that does not apply -- id or label out of range, env
+ * not awaiting, env named by an earlier row -- is skipped, changes nothing and is counted in *rejected (may be NULL); the call still returns DTRL_OK. */
+dtrl_status dtrl_supply_actions_device(dtrl_batch* b, const int32_t* env_ids_dev, int n, const int32_t* action_ids_dev, const float* params_dev, const uint32_t* flags_dev, int* rejected);
+/* Envs parked without / with a delivered action now; env-steps run and env frames completed by all envs since creation (counted on the device per env,
+ * what a throughput figure in this mode has to be taken from: a tick advances an env by anything between 0 and num_update_steps env-steps). Any may be NULL. */
+dtrl_status dtrl_ext_stats(dtrl_batch* b, int64_t* awaiting, int64_t* ready, int64_t* env_steps_total, int64_t* env_frames_total);
+/* Per env: park state (0 running / frame complete, 1 awaiting, 2 action delivered) and the env-steps its current frame still has to finish (0: complete). */
+dtrl_status dtrl_ext_env_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* park, int32_t* steps_left);
+/* What an action row is made of: n_opt = params per row (cTerrainRLCharController::GetNumOptParams), n_labels = valid action_id values 0 .. n_labels - 1,
+ * num_update_steps = env-steps per env frame, external = 1 for a -policy_mode= external batch. Works in either mode; any output may be NULL. */
+dtrl_status dtrl_action_dims(const dtrl_batch* b, int* n_opt, int* n_labels, int* num_update_steps, int* external);
+/* Device time (ms, HIP events) of the collection (which = 0) / scatter (which = 1) launches since the previous call; -1 where nothing is launched. */
+double dtrl_ext_launch_ms(dtrl_batch* b, int which);
 
 /* Replaces: cScenarioSimChar::AddPerturb -> cWorld::AddPerturb (scenarios/ScenarioSimChar.cpp:204-207, sim/World.cpp:256-259) with a
  * tPerturb of type ePerturbForce (sim/Perturb.cpp:52-79, sim/World.cpp:445-470): a world-frame force[n][2] on body part link[n] at the
