@@ -26,6 +26,14 @@
 namespace dtrl {
 
 __device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x); }
+// lane id the optimiser cannot see through: address / index arithmetic derived from it is recomputed where it is used instead of being
+// hoisted out of the 4000-instruction physics loop as a loop invariant and spilled to scratch across it
+__device__ __forceinline__ int opaque_lane()
+{
+	int lane = static_cast<int>(threadIdx.x);
+	asm volatile("" : "+v"(lane));
+	return lane;
+}
 // the EXEC-window helpers below are spelled per arithmetic type (dtrl_types.h: fp64 shipped, fp32 opt-in build)
 #if defined(DTRL_REAL_F32)
 #define DTRL_VFMA "v_fma_f32"
@@ -145,6 +153,22 @@ __device__ __forceinline__ void mov_lanes_lt(real& dst, real src)
 	asm("s_bfm_b64 %2, %4, 0\n\ts_and_saveexec_b64 %1, %2\n\t" DTRL_VMOV " %0, %3\n\ts_mov_b64 exec, %1"
 	    : "+v"(dst), "=&s"(sv), "=&s"(m) : "v"(src), "n"(I) : "scc");
 }
+// dst = src on lanes B <= lane < E
+template <int B, int E>
+__device__ __forceinline__ void mov_lanes_in(real& dst, real src)
+{
+	static_assert(0 <= B && B < E && E <= 64 && E - B < 64, "lane window (s_bfm_b64 takes the width modulo 64)");
+	unsigned long long sv, m;
+	asm("s_bfm_b64 %2, %4, %5\n\ts_and_saveexec_b64 %1, %2\n\t" DTRL_VMOV " %0, %3\n\ts_mov_b64 exec, %1"
+	    : "+v"(dst), "=&s"(sv), "=&s"(m) : "v"(src), "n"(E - B), "n"(B) : "scc");
+}
+// dst = v as exactly ONE ds_write, in source order among the stores spelled this way: the empty asm is a barrier for memory operations, so the compiler neither merges
+// two of them into one two-address write nor reorders them (it sees stores of one lane to different addresses, which it may otherwise do freely). No instruction.
+__device__ __forceinline__ void lds_store_ordered(real& dst, real v)
+{
+	dst = v;
+	asm volatile("" : : : "memory");
+}
 
 // in-register H = U D U^T, last DoF first; returns 1/d_lane. Same elimination order and operations as factorize(), minus the
 // updates that are structurally zero for the skeleton Topo (exact no-ops in the dense form). The transposed copy of U (needed by
@@ -173,13 +197,33 @@ __device__ __forceinline__ real factorize_regs(WSFast& ws, real (&h)[Topo::L + 2
 		mov_lanes_lt<k>(h[k], lik);                     // if (lane < k) h[k] = lik
 	});
 	{ const real r0 = fast_recip(h[0]); if (lane == 0) dinv = r0; }
+	// The transposed copy: column k of U (lanes < k) goes to S[k (k - 1) / 2 + lane], lane i then reads its row back from S[i (i - 1) / 2 + k], k < i.
+	// Neither side carries a per-column lane predicate in the source (`if (lane < k)` / `if (lane > k)` compile to 2 x 22 loop-invariant 64-bit lane masks that
+	// live in SGPR spill lanes: a save / reload / and / restore of EXEC around every single LDS access).
+	// Stores: ALL 64 lanes store column k, ascending in k. Lanes >= k land on the slots of columns k + 1 ..., which are stored later, and a wave's LDS operations
+	// complete in issue order (warm_match_fast() relies on the same), so every slot of the triangle ends up with its own column's value. The overflow of the last
+	// column stays inside Apk (asserted below); slots outside the triangle are read by nobody (usolve_rows() reads U[k (k - 1) / 2 + i], i < k, only; the
+	// Delassus build and link_cap_drop_mask() / row_cap_drop_mask() / append_pair_rows_fast() write the storage before they read it).
+	// The stores go through lds_store_ordered(): each stays one ds_write in source order (two of them merged into one two-address write would leave the order
+	// of their overlapping slots open).
+	// Loads: unpredicated into a temporary (lanes >= D read row 0: in bounds, unused), then one move under an EXEC window from inline constants
+	// (mov_lanes_in: 3 SALU + 1 VALU, no SGPR kept). The alternative, a select per column (`h[k] = (lane > k && lane < D) ? t : h[k]`), needs the lane mask per
+	// column again, which is hoisted and spilled as before. Substep loop, instructions / SGPR spill reloads (tools/isa_spills.py), windows against selects:
+	// fp64 dog 6713 / 114 against 6749 / 166, fp64 raptor 6208 / 77 against 6206 / 118, fp32 dog 8614 / 161 against 8656 / 218, fp32 raptor 7404 / 70 against
+	// 7498 / 136. A window around the ds_read itself would save the move but hides the LDS access from the compiler's s_waitcnt insertion.
+	static_assert((D - 1) * (D - 2) / 2 + kGroup - 1 < static_cast<int>(sizeof(ws.Apk) / sizeof(real)), "the unpredicated store of U's last column leaves the packed-matrix storage");
 	real* S = ws.Apk;
-#pragma unroll
-	for (int k = 1; k < D; ++k) if (lane < k) S[k * (k - 1) / 2 + lane] = h[k];
+	static_for<1, D>([&](auto kc) {
+		constexpr int k = decltype(kc)::value;
+		lds_store_ordered(S[k * (k - 1) / 2 + lane], h[k]);
+	});
 	env_sync();
-	const int base = lane * (lane - 1) / 2;
-#pragma unroll
-	for (int k = 0; k < D - 1; ++k) if (lane > k && lane < D) h[k] = S[base + k];
+	const int base = lane < D ? lane * (lane - 1) / 2 : 0;
+	static_for<0, D - 1>([&](auto kc) {
+		constexpr int k = decltype(kc)::value;
+		const real t = S[base + k];
+		mov_lanes_in<k + 1, D>(h[k], t);                // if (lane > k && lane < D) h[k] = t
+	});
 	env_sync();
 	return dinv;
 }
@@ -259,14 +303,6 @@ __device__ __forceinline__ real utsolve_regs(const real (&h)[D], real u)
 // (three named values, not an array: the struct must stay in VGPRs, never in scratch)
 static_assert((kMaxPts + kGroup - 1) / kGroup == 3, "written for 3 sample points per lane");
 struct ContactPts { PtVal p0, p1, p2; unsigned long long m0, m1, m2; /* constraint-carrying points */ unsigned long long f0, f1, f2; /* points near the surface: contact flags */ };
-// lane id the optimiser cannot see through: address / index arithmetic derived from it is recomputed where it is used instead of being
-// hoisted out of the 4000-instruction physics loop as a loop invariant and spilled to scratch across it
-__device__ __forceinline__ int opaque_lane()
-{
-	int lane = static_cast<int>(threadIdx.x);
-	asm volatile("" : "+v"(lane));
-	return lane;
-}
 // the kPtsPerLink ballot bits of link `link`'s sample points (points link * 6 .. link * 6 + 5 of the three 64-point ballots)
 __device__ __forceinline__ unsigned link_field(unsigned long long m0, unsigned long long m1, unsigned long long m2, int link)
 {
@@ -440,7 +476,7 @@ __device__ __forceinline__ void emit_contact_rows(WSFast& ws, const PtVal& p, in
 __device__ __forceinline__ void build_rows_fast(WSFast& ws, const DevModel& gm, const ContactPts& c_in, real h)
 {
 	ContactPts c = c_in;
-	const int lane = static_cast<int>(threadIdx.x);
+	const int lane = opaque_lane();
 	const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 	const real inv_h = 1.0 / h;
 	// joint limits, ordered by joint id
@@ -706,7 +742,15 @@ __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 			const int end0 = (pass0 == 0ull) ? R : 64 - __builtin_clzll(pass0);
 #pragma unroll 1
 			for (int it = 0; it < kPgsIters; ++it) {
-				if (pass0 != 0ull) pgs_rows_pass<kPgsRowNormal, 0, kPgsRegRows>(a, w, lam, rinv, 0.0, 0.0, pass0, lane, end0);
+				// pass0 / end0 do not change over the sweeps. Left visible as loop invariants, the nested per-row tests below are hoisted out of the loop as two
+				// 64-bit booleans per row, which have no SGPRs to live in: a block in front of every solve writes them to VGPR lanes and every row of every
+				// sweep reads them back. Through an opaque per-sweep copy they are tested where they are used, as the friction pass's per-sweep `rows` is:
+				// s_cmp / s_bitcmp + branch per row, nothing kept.
+				// (the mask travels as two 32-bit halves: with a 64-bit operand next to the 32-bit one the fp32 build does not compile)
+				unsigned rows0_lo = static_cast<unsigned>(pass0), rows0_hi = static_cast<unsigned>(pass0 >> 32); int last0 = end0;
+				asm volatile("" : "+s"(rows0_lo), "+s"(rows0_hi), "+s"(last0));
+				const unsigned long long rows0 = (static_cast<unsigned long long>(rows0_hi) << 32) | rows0_lo;
+				if (rows0 != 0ull) pgs_rows_pass<kPgsRowNormal, 0, kPgsRegRows>(a, w, lam, rinv, 0.0, 0.0, rows0, lane, last0);
 				// friction pass: every normal row is final for this sweep, so the bounds +-mu lambda_n are fixed for the pass, and which friction rows Bullet's rule HOLDS
 				// (normal row without impulse: their update is exactly zero) is known up front -- they leave the pass instead of walking through a row step each
 				const real ln = wave_shr1(lam);   // (all lanes: a DPP move under a narrowed EXEC does not see the lanes that are switched off)
@@ -716,7 +760,17 @@ __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 			}
 		} else {
 #pragma unroll 1
-			for (int it = 0; it < kPgsIters; ++it) pgs_rows_sweep<0, kPgsRegRows>(a, w, lam, rinv, tang, actR, lane, R);
+			for (int it = 0; it < kPgsIters; ++it) {
+				// (actR / R through an opaque per-sweep copy, as pass0 / end0 above. The fp32 build keeps R visible: with it opaque as well, the 168-VGPR raptor
+				// instance of the external-policy kernel gets six scratch reloads in its substep loop)
+				unsigned rows_lo = static_cast<unsigned>(actR), rows_hi = static_cast<unsigned>(actR >> 32); int last = R;
+#if defined(DTRL_REAL_F32)
+				asm volatile("" : "+s"(rows_lo), "+s"(rows_hi));
+#else
+				asm volatile("" : "+s"(rows_lo), "+s"(rows_hi), "+s"(last));
+#endif
+				pgs_rows_sweep<0, kPgsRegRows>(a, w, lam, rinv, tang, (static_cast<unsigned long long>(rows_hi) << 32) | rows_lo, lane, last);
+			}
 		}
 		if (mine) ws.st.ws_lam[lane] = lam;
 		env_sync();
