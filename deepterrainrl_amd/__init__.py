@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "dtrl_terrain_build", "dtrl_terrain_load_file", "dtrl_args_parse_string",
     "dtrl_drain_tuples_device", "dtrl_tuple_stats", "dtrl_set_policy_device", "dtrl_get_dist_log", "dtrl_reset_avg_dist", "dtrl_write_dist_log", "dtrl_get_ground_window", "dtrl_drain_tuples_packed", "dtrl_get_policy_output", "dtrl_set_tuple_pipelining", "dtrl_step_end_begin", "dtrl_command_action", "dtrl_side_stream", "dtrl_step_poll", "dtrl_set_policy_device_on", "dtrl_set_policy_device_async",
     "dtrl_snapshot_save", "dtrl_snapshot_restore", "dtrl_clone_envs", "dtrl_snapshot_export", "dtrl_snapshot_import", "dtrl_snapshot_info", "dtrl_snapshot_free",
+    "dtrl_slots_create", "dtrl_slot_set_policy", "dtrl_slot_set_policy_device", "dtrl_slot_alias", "dtrl_slot_set_explore", "dtrl_assign_slots", "dtrl_get_slots", "dtrl_slot_stats",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
 
@@ -143,6 +144,14 @@ def _bind(path):
     L.dtrl_ext_env_info.argtypes = [vp, vp, C.c_int, vp, vp]
     L.dtrl_action_dims.argtypes = [vp] + [C.POINTER(C.c_int)] * 4
     L.dtrl_ext_launch_ms.restype = C.c_double; L.dtrl_ext_launch_ms.argtypes = [vp, C.c_int]
+    L.dtrl_slots_create.argtypes = [vp, C.c_int]
+    L.dtrl_slot_set_policy.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, vp, vp, vp]
+    L.dtrl_slot_set_policy_device.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, vp, vp, vp]
+    L.dtrl_slot_alias.argtypes = [vp, C.c_int, C.c_int]
+    L.dtrl_slot_set_explore.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
+    L.dtrl_assign_slots.argtypes = [vp, vp, C.c_int, vp]
+    L.dtrl_get_slots.argtypes = [vp, vp, C.c_int, vp]
+    L.dtrl_slot_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dtrl_last_error.restype = C.c_char_p
     L.dtrl_last_error.argtypes = [vp]
     L.dtrl_version.restype = C.c_char_p
@@ -631,6 +640,74 @@ class BatchScenario:
         a = C.c_double(); e, c, r = C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self._lib.dtrl_eval_stats(self._h, C.byref(a), C.byref(e), C.byref(c), C.byref(r)))
         return {"avg_dist": a.value, "episodes": e.value, "cycles": c.value, "resets": r.value}
+
+    # ---- policy slots: several policies in one batch, one per env (no counterpart in the reference: it keeps one net per scene object) ----
+    def CreateSlots(self, n_slots):
+        """dtrl_slots_create: 1 .. 32 slots, once per batch. Slot 0 is the batch's own policy (SetPolicy*, LoadScale, SetExplore keep acting on it); every env starts in it."""
+        self._chk(self._lib.dtrl_slots_create(self._h, int(n_slots)))
+        self.num_slots = int(n_slots)
+
+    def SlotSetPolicy(self, slot, weights, in_off=None, in_scale=None, out_off=None, out_scale=None):
+        """SetPolicy into a slot. `weights` is a host array (float32, Caffe blob order; normalisers float64 arrays, None = identity) or a torch tensor on the
+        batch's GPU (float32; normalisers float64 device tensors, None = keep the slot's vector -- dtrl_slot_set_policy_device). Between frames only."""
+        if hasattr(weights, "data_ptr") and getattr(weights, "is_cuda", False):
+            ts = [weights] + [t for t in (in_off, in_scale, out_off, out_scale)]
+            for t in ts:
+                if t is not None and not (hasattr(t, "data_ptr") and t.is_cuda and t.is_contiguous()):
+                    raise DtrlError("SlotSetPolicy: with device weights every normaliser must be a contiguous device tensor (or None)")
+            if str(weights.dtype) != "torch.float32" or not weights.is_contiguous():
+                raise DtrlError("SlotSetPolicy: device weights must be a contiguous float32 tensor")
+            q = [None if t is None else C.c_void_p(t.data_ptr()) for t in ts[1:]]
+            import torch
+            torch.cuda.current_stream(weights.device).synchronize()      # the tensors are complete before the engine's stream reads them
+            self._chk(self._lib.dtrl_slot_set_policy_device(self._h, int(slot), C.c_void_p(weights.data_ptr()), int(weights.numel()), *q))
+            return
+        w = np.ascontiguousarray(weights, np.float32)
+        arrs = [None if a is None else np.ascontiguousarray(a, np.float64) for a in (in_off, in_scale, out_off, out_scale)]
+        self._chk(self._lib.dtrl_slot_set_policy(self._h, int(slot), _p(w), w.size, *[_p(a) for a in arrs]))
+
+    def SlotLoadModel(self, slot, model_file):
+        """LoadModel into a slot: Caffe HDF5 weights by layer name plus the normalisers of '<model>_scale.txt' next to it when that file exists."""
+        from . import caffe_hdf5
+        w = caffe_hdf5.load_mace_weights(model_file, self.num_frags)
+        if w.size != self.PolicyNumParams():
+            raise DtrlError("%s holds %d parameters, the deploy net needs %d" % (model_file, w.size, self.PolicyNumParams()))
+        scale = os.path.splitext(model_file)[0] + "_scale.txt"
+        norm = (None,) * 4
+        if os.path.exists(scale):
+            import json
+            with open(scale) as f:
+                j = json.load(f)
+            norm = tuple(None if j.get(k) is None else np.asarray(j[k], np.float64) for k in ("InputOffset", "InputScale", "OutputOffset", "OutputScale"))
+        self.SlotSetPolicy(slot, w, *norm)
+        return w
+
+    def SlotAlias(self, slot, src_slot):
+        """dtrl_slot_alias: `slot` reads src_slot's weights and normalisers from now on (hand-overs into slot 0 included) and keeps its own exploration settings."""
+        self._chk(self._lib.dtrl_slot_alias(self._h, int(slot), int(src_slot)))
+
+    def SlotSetExplore(self, slot, enable, rate, temp, base_rate):
+        self._chk(self._lib.dtrl_slot_set_explore(self._h, int(slot), int(enable), float(rate), float(temp), float(base_rate)))
+
+    def AssignSlots(self, env_ids, slots):
+        """env_ids[i] -> slots[i] (env_ids None: the first len(slots) envs); takes effect with the env's next launch. Between frames only."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32)
+        if ids is not None and ids.shape != sl.shape:
+            raise DtrlError("AssignSlots: env_ids and slots must have the same length")
+        self._chk(self._lib.dtrl_assign_slots(self._h, _p(ids), len(sl), _p(sl)))
+
+    def GetSlots(self, env_ids=None):
+        ids, n = self._ids(env_ids)
+        out = np.zeros(n, np.int32)
+        self._chk(self._lib.dtrl_get_slots(self._h, _p(ids), n, _p(out)))
+        return out
+
+    def SlotStats(self, slot):
+        """EvalStats restricted to the envs currently in `slot` (plus their number), reduced on the device in a fixed order."""
+        a = C.c_double(); n, e, c, r = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._lib.dtrl_slot_stats(self._h, int(slot), C.byref(n), C.byref(a), C.byref(e), C.byref(c), C.byref(r)))
+        return {"n_envs": n.value, "avg_dist": a.value, "episodes": e.value, "cycles": c.value, "resets": r.value}
 
     # ---- full env snapshots (no counterpart in the reference: it keeps one scene per object) ----
     def SaveState(self, env_ids=None):

@@ -292,6 +292,7 @@ public:
 		for (hipEvent_t ev : snap_ev_) if (ev) hipEventDestroy(ev);
 		if (policy_ready_) hipEventDestroy(policy_ready_);
 		if (ext_rej_) hipFree(ext_rej_);
+		if (slot_scratch_) hipFree(slot_scratch_);
 		if (!owned_.empty()) { for (int i = kNumStreams / 2; i < kNumStreams; ++i) streams_[i] = nullptr; for (hipStream_t st : owned_) hipStreamDestroy(st); }
 		for (hipStream_t st : streams_) if (st) hipStreamDestroy(st);
 	}
@@ -548,7 +549,28 @@ public:
 		}();
 		return bytes;
 	}
-	bool Launch(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end) override
+	bool Launch(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end) override { return LaunchFrame(gm, rp, buf, n_envs, n_steps, dt, frame_end, nullptr, nullptr); }
+	// policy slots: ONE launch of the slot kernels (dtrl_backend_hip_slots.hip) over the list as it stands -- the group's costliest-first order is kept across slots.
+	// DTRL_SLOTS_FALLBACK=1 takes the per-slot default instead (A/B and cross-check)
+	bool LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end) override
+	{
+		const char* fb = std::getenv("DTRL_SLOTS_FALLBACK");   // (read per launch, like DTRL_KERNEL: a test switches it inside one process)
+		if (fb && std::atoi(fb) != 0) return Backend::LaunchSlots(gm, rp, buf, slots, env_slot, n_envs, n_steps, dt, frame_end);
+		return LaunchFrame(gm, rp, buf, n_envs, n_steps, dt, frame_end, slots.dev, env_slot);
+	}
+	bool SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums) override
+	{
+		const size_t recs = static_cast<size_t>(SlotReduceRows(n_envs) + 1) * kMaxSlots;
+		if (slot_scratch_recs_ < recs) {
+			if (slot_scratch_) hipFree(slot_scratch_);
+			slot_scratch_ = nullptr; slot_scratch_recs_ = 0;
+			if (!Check(hipMalloc(&slot_scratch_, sizeof(SlotSums) * recs), "hipMalloc")) return false;
+			slot_scratch_recs_ = recs;
+		}
+		if (!LaunchSlotReduce(stream_, st, env_slot, n_envs, n_slots, slot_scratch_)) return Check(hipGetLastError(), "slot reduction launch") && false;
+		return Check(hipMemcpyAsync(sums, slot_scratch_ + (recs - kMaxSlots), sizeof(SlotSums) * n_slots, hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H") && Check(hipStreamSynchronize(stream_), "slot reduction");
+	}
+	bool LaunchFrame(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const SlotRec* slots, const int32_t* env_slot)
 	{
 		// only stepping launches are timed (the compact 0-step reset launches would skew the per-frame average)
 		const bool timed = n_steps > 0;
@@ -561,7 +583,8 @@ public:
 		// DTRL_KERNEL=ref selects the LDS-phase reference kernel (A/B and bitwise cross-check); default is the fast path
 		const char* sel = std::getenv("DTRL_KERNEL");
 		const bool use_ref = sel && std::strcmp(sel, "ref") == 0;
-		if (buf.ext_envs != 0) LaunchExtFrame(stream_, use_ref, FastDynLds(), gm, rp, buf, n_envs, n_steps, dt, frame_end);   // external policy mode: dtrl_backend_hip_ext.hip
+		if (slots) LaunchSlotFrame(stream_, use_ref, FastDynLds(), gm, rp, buf, n_envs, n_steps, dt, frame_end, slots, env_slot);   // policy slots: dtrl_backend_hip_slots.hip
+		else if (buf.ext_envs != 0) LaunchExtFrame(stream_, use_ref, FastDynLds(), gm, rp, buf, n_envs, n_steps, dt, frame_end);   // external policy mode: dtrl_backend_hip_ext.hip
 		else if (!use_ref && buf.model_topo == TopoDog::kId)
 			hipLaunchKernelGGL(dtrl_frame_kernel_fast<TopoDog>, dim3(n_envs), dim3(kGroup), FastDynLds(), stream_, gm, rp, buf, n_envs, n_steps, dt, frame_end ? 1 : 0);
 		else if (!use_ref && buf.model_topo == TopoRaptor::kId)
@@ -618,6 +641,7 @@ private:
 	static int Key(int group, int slot) { return group * 16 + slot; }
 	int32_t* ext_rej_ = nullptr; double ext_ms_[2] = {0, 0};   // external policy mode: rejected-row counter (device), device time of the collection / scatter launches
 	hipEvent_t snap_ev_[2] = {nullptr, nullptr}; double snap_ms_ = 0;   // the snapshot launches since the last SnapLaunchMs(), timed with events
+	SlotSums* slot_scratch_ = nullptr; size_t slot_scratch_recs_ = 0;   // dtrl_slot_stats: partial rows + totals (device)
 	hipEvent_t policy_ready_ = nullptr;   // behind the latest asynchronous policy gather (GatherF32Async)
 	std::map<int, hipEvent_t> marks_;   // (env group, tuple ring) -> event behind the group's latest frame launch that wrote that ring
 };

@@ -262,6 +262,15 @@ dtrl_status dtrl_supply_actions(dtrl_batch* b, const int32_t* env_ids, int n, co
 dtrl_status dtrl_supply_actions_device(dtrl_batch* b, const int32_t* env_ids_dev, int n, const int32_t* action_ids_dev, const float* params_dev, const uint32_t* flags_dev, int* rejected) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SupplyActions(env_ids_dev, n, action_ids_dev, params_dev, flags_dev, true, rejected)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_ext_stats(dtrl_batch* b, int64_t* awaiting, int64_t* ready, int64_t* env_steps_total, int64_t* env_frames_total) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.ExtStats(awaiting, ready, env_steps_total, env_frames_total)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_ext_env_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* park, int32_t* steps_left) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.ExtEnvInfo(env_ids, n, park, steps_left)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+// policy slots
+dtrl_status dtrl_slots_create(dtrl_batch* b, int n_slots) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SlotsCreate(n_slots)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_slot_set_policy(dtrl_batch* b, int slot, const float* weights, size_t n, const double* in_off, const double* in_scale, const double* out_off, const double* out_scale) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SlotSetPolicy(slot, weights, n, in_off, in_scale, out_off, out_scale, false)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_slot_set_policy_device(dtrl_batch* b, int slot, const float* weights_dev, size_t n, const double* in_off_dev, const double* in_scale_dev, const double* out_off_dev, const double* out_scale_dev) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SlotSetPolicy(slot, weights_dev, n, in_off_dev, in_scale_dev, out_off_dev, out_scale_dev, true)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_slot_alias(dtrl_batch* b, int slot, int src_slot) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SlotAlias(slot, src_slot)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_slot_set_explore(dtrl_batch* b, int slot, int enable, double rate, double temp, double base_rate) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SlotSetExplore(slot, enable, rate, temp, base_rate)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_assign_slots(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* slots) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.AssignSlots(env_ids, n, slots)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_get_slots(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* slots_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.GetSlots(env_ids, n, slots_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_slot_stats(dtrl_batch* b, int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SlotStats(slot, n_envs, avg_dist, episodes, cycles, resets)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_action_dims(const dtrl_batch* b, int* n_opt, int* n_labels, int* num_update_steps, int* external)
 try {
 	CHECK_B();

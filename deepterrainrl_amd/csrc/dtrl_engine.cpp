@@ -119,6 +119,7 @@ Engine::~Engine()
 		be_->Sync();
 		for (Snapshot* s : snapshots_) { be_->Free(s->payload); s->payload = nullptr; s->owner = nullptr; }   // (the handles stay valid for dtrl_snapshot_info / _free)
 		be_->FreeHostStaging(snap_ids_);
+		be_->FreeHostStaging(slot_part_);
 		if (ext_meta_) be_->FreeHostStaging(ext_meta_);
 		for (void* p : allocs_) be_->Free(p);
 		for (void* p : host_allocs_) be_->FreeHostStaging(p);
@@ -325,7 +326,7 @@ int Engine::ApplyResets(const std::vector<int32_t>& ids, int group)
 	DevBuffers b = buf_;
 	b.env_list = (zero_copy_ ? pin_ids_ : d_env_list_) + off;
 	b.reset_listed = 1;
-	if (!be_->Launch(d_model_, cfg_.run, b, static_cast<int>(ids.size()), 0, 0.0, false)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (!LaunchEnvs(b, static_cast<int>(ids.size()), 0, 0.0, false, pin_ids_ + off, group >= 0 ? off : n_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
 }
 
@@ -349,7 +350,7 @@ int Engine::LaunchGroup(int group, int n_steps, double dt_step, bool frame_end)
 	const double lt0 = g_ht.on ? now_s() : 0;
 	bool ok = true;
 	if (group < static_cast<int>(policy_wait_.size()) && policy_wait_[group]) { ok = be_->WaitPolicyReady(group); policy_wait_[group] = 0; }   // dtrl_set_policy_device_async
-	ok = ok && be_->Launch(d_model_, cfg_.run, b, g.n, n_steps, dt_step, frame_end);
+	ok = ok && LaunchEnvs(b, g.n, n_steps, dt_step, frame_end, zero_copy_ ? pin_order_ + g.e0 : nullptr, g.e0);
 	// tuple pipelining: the drain of this frame's ring runs on a stream of its own one frame later and must follow THIS launch on the device -- the host
 	// has not necessarily waited for it by then (-terrain_gen= device queues the boundary work and the next frame without a sync)
 	if (ok && tuple_pipelining_ && n_steps > 0) ok = be_->MarkFrame(group, wr_ring_);
@@ -358,6 +359,16 @@ int Engine::LaunchGroup(int group, int n_steps, double dt_step, bool frame_end)
 	if (g_ht.on) g_ht.t_launch += now_s() - lt0;
 	be_->SelectStream(0);
 	return ok ? DTRL_OK : Fail(DTRL_ERR_DEVICE, be_->error());
+}
+
+// every launch of the frame kernels after the batch's creation comes through here: a batch without slots launches exactly as it always did
+bool Engine::LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, bool frame_end, const int32_t* list_host, int part_off)
+{
+	if (slots_.empty()) return be_->Launch(d_model_, cfg_.run, b, n_envs, n_steps, dt, frame_end);
+	SlotView v;
+	v.dev = d_slot_table_; v.host = slot_table_.data(); v.n_slots = static_cast<int32_t>(slots_.size());
+	v.env_slot_host = env_slot_.data(); v.env_list_host = list_host; v.part = slot_part_ + part_off;
+	return be_->LaunchSlots(d_model_, cfg_.run, b, v, d_env_slot_, n_envs, n_steps, dt, frame_end);
 }
 
 int Engine::UploadTerrainCfg(const double* params)
@@ -387,7 +398,7 @@ int Engine::DeviceFrameWork(int group)
 	b.env_list = nullptr; b.reset_listed = 2;
 	if (!be_->TerrainBoundary(buf_, grp.e0, grp.n, 0, nullptr) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	b.env_list = d_order_ + grp.e0;
-	if (!be_->Launch(d_model_, cfg_.run, b, grp.n, 0, 0.0, false)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (!LaunchEnvs(b, grp.n, 0, 0.0, false, nullptr, grp.e0)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
 }
 // device distance ring -> dist_log_ (completion order inside the ring is whatever the atomics produced; GetDistLog groups by env, and one env
@@ -1720,6 +1731,175 @@ int Engine::ExtEnvInfo(const int32_t* env_ids, int n, int32_t* park, int32_t* st
 	rc = GetStates(env_ids, cnt, st);
 	if (rc != DTRL_OK) return rc;
 	for (int i = 0; i < cnt; ++i) { if (park) park[i] = st[i].ext_park; if (steps_left) steps_left[i] = st[i].ext_steps_left; }
+	return DTRL_OK;
+}
+
+// ---- policy slots (include/dtrl.h: dtrl_slots_create ... dtrl_slot_stats) ----
+// Two things keep a launch in flight from ever reading a half-written record. (1) The table and the per-env array change only in calls that refuse a frame in
+// flight and then wait for every stream (SlotsIdle) -- with dtrl_step_poll or -terrain_gen= device the host has not otherwise waited for the launches it queued.
+// (2) What DOES change while launches run -- slot 0's weight buffer (the double-buffered hand-over) and dtrl_set_explore -- is not in the table at all: slot 0
+// and its aliases carry kSlotLaunchPolicy / kSlotLaunchExplore and take those values from the launch's own by-value arguments, exactly where the single-policy
+// kernels take them. So MarkWeightReader / WaitWeightReaders / WaitPolicyReady and the flip order a hand-over for slot 0 and for every alias of it at once.
+int Engine::SlotsIdle(const char* what, int slot)
+{
+	if (slots_.empty()) return Fail(DTRL_ERR_ARG, std::string(what) + ": the batch has no policy slots (call dtrl_slots_create first)");
+	if (slot < 0 || slot >= static_cast<int>(slots_.size())) return Fail(DTRL_ERR_ARG, std::string(what) + ": slot " + std::to_string(slot) + " out of range (0 .. " + std::to_string(slots_.size() - 1) + ")");
+	if (step_pending_ || early_any_) return Fail(DTRL_ERR_ARG, std::string(what) + " between dtrl_step_begin and dtrl_step_end (or after dtrl_step_poll relaunched a group): a frame is in flight; call dtrl_step_end first");
+	be_->SelectStream(0);
+	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::UploadSlotTable()
+{
+	for (size_t s = 0; s < slots_.size(); ++s) {
+		const SlotHost& h = slots_[s]; const SlotHost& root = slots_[SlotRoot(static_cast<int>(s))];
+		SlotRec r{};
+		if (&root == &slots_[0]) r.flags |= kSlotLaunchPolicy;
+		else { r.weights = root.weights; r.in_off = root.norm[0]; r.in_scale = root.norm[1]; r.out_off = root.norm[2]; r.out_scale = root.norm[3]; }
+		if (s == 0) r.flags |= kSlotLaunchExplore;
+		else { r.enable_exp = h.enable_exp; r.exp_rate = static_cast<real>(h.rate); r.exp_temp = static_cast<real>(h.temp); r.exp_base_rate = static_cast<real>(h.base_rate); }
+		slot_table_[s] = r;
+	}
+	if (!be_->H2D(d_slot_table_, slot_table_.data(), sizeof(SlotRec) * slot_table_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::SlotsCreate(int n_slots)
+{
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_slots_create: not available with -policy_mode= external (the caller's policy decides; no policy net runs inside the frame kernel)");
+	if (!cfg_.has_policy_net) return Fail(DTRL_ERR_ARG, "dtrl_slots_create: no -policy_net= in the arguments: this batch has no network");
+	if (n_slots < 1 || n_slots > kMaxSlots) return Fail(DTRL_ERR_ARG, "dtrl_slots_create: n_slots must be 1 .. " + std::to_string(kMaxSlots) + ", not " + std::to_string(n_slots));
+	if (!slots_.empty()) {
+		if (n_slots == static_cast<int>(slots_.size())) return DTRL_OK;
+		return Fail(DTRL_ERR_ARG, "dtrl_slots_create: the batch already has " + std::to_string(slots_.size()) + " slots; a second call with another count (" + std::to_string(n_slots) + ") is refused");
+	}
+	if (step_pending_ || early_any_) return Fail(DTRL_ERR_ARG, "dtrl_slots_create between dtrl_step_begin and dtrl_step_end (or after dtrl_step_poll relaunched a group): a frame is in flight; call dtrl_step_end first");
+	be_->SelectStream(0);
+	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	d_slot_table_ = static_cast<SlotRec*>(be_->Alloc(sizeof(SlotRec) * n_slots)); if (d_slot_table_) allocs_.push_back(d_slot_table_);
+	d_env_slot_ = static_cast<int32_t*>(be_->Alloc(sizeof(int32_t) * n_)); if (d_env_slot_) allocs_.push_back(d_env_slot_);   // (zero-filled: every env starts in slot 0)
+	slot_part_ = static_cast<int32_t*>(be_->HostStaging(sizeof(int32_t) * 2 * static_cast<size_t>(n_)));
+	if (!d_slot_table_ || !d_env_slot_ || !slot_part_ || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+	slots_.assign(static_cast<size_t>(n_slots), SlotHost());
+	slots_[0].set = true;
+	for (SlotHost& h : slots_) { h.enable_exp = cfg_.run.enable_exp; h.rate = cfg_.run.exp_rate; h.temp = cfg_.run.exp_temp; h.base_rate = cfg_.run.exp_base_rate; }   // every slot starts with the batch's exploration settings
+	slot_table_.assign(static_cast<size_t>(n_slots), SlotRec{});
+	env_slot_.assign(static_cast<size_t>(n_), 0);
+	int rc = UploadSlotTable();
+	if (rc != DTRL_OK) { slots_.clear(); return rc; }
+	return DTRL_OK;
+}
+
+int Engine::SlotSetPolicy(int slot, const float* w, size_t n, const double* io, const double* is, const double* oo, const double* os, bool device)
+{
+	const char* what = device ? "dtrl_slot_set_policy_device" : "dtrl_slot_set_policy";
+	int rc = SlotsIdle(what, slot);
+	if (rc != DTRL_OK) return rc;
+	if (slot == 0) return device ? SetPolicyDevice(w, n, io, is, oo, os) : SetPolicy(w, n, io, is, oo, os);
+	const NetDesc& d = cfg_.net;
+	if (!w || n != static_cast<size_t>(cfg_.user_num_params)) return Fail(DTRL_ERR_ARG, std::string(what) + ": weight count does not match the deploy prototxt");
+	if (device && sizeof(real) != sizeof(double) && (io || is || oo || os)) return Fail(DTRL_ERR_ARG, "the fp32 build takes device-resident WEIGHTS only; hand the normalisers over through dtrl_slot_set_policy (host doubles)");
+	SlotHost& h = slots_[slot];
+	const bool fresh = !h.weights;
+	if (fresh) {
+		float* wd = static_cast<float*>(be_->Alloc(sizeof(float) * relayout_.size())); if (wd) allocs_.push_back(wd);
+		real* nm[4];
+		for (int k = 0; k < 4; ++k) { nm[k] = static_cast<real*>(be_->Alloc(sizeof(real) * (k < 2 ? d.in_size : d.out_size))); if (nm[k]) allocs_.push_back(nm[k]); }
+		if (!wd || !nm[0] || !nm[1] || !nm[2] || !nm[3] || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+		h.weights = wd; for (int k = 0; k < 4; ++k) h.norm[k] = nm[k];
+	}
+	const int pad = d.out_size - cfg_.user_out_size;   // CACLA actor: the neutral critic slot in front of the output normalisers (Engine::SetPolicy)
+	bool ok = true;
+	if (!device || fresh) {   // identity for every vector passed as NULL (a device hand-over into a slot that has a policy keeps the vectors it has)
+		std::vector<real> v[4];
+		v[0].assign(d.in_size, 0.0); v[1].assign(d.in_size, 1.0); v[2].assign(d.out_size, 0.0); v[3].assign(d.out_size, 1.0);
+		if (!device) {
+			if (io) for (int k = 0; k < d.in_size; ++k) v[0][k] = static_cast<real>(io[k]);
+			if (is) for (int k = 0; k < d.in_size; ++k) v[1][k] = static_cast<real>(is[k]);
+			if (oo) for (int k = 0; k < cfg_.user_out_size; ++k) v[2][pad + k] = static_cast<real>(oo[k]);
+			if (os) for (int k = 0; k < cfg_.user_out_size; ++k) v[3][pad + k] = static_cast<real>(os[k]);
+		}
+		for (int k = 0; k < 4; ++k) ok = ok && be_->H2D(h.norm[k], v[k].data(), sizeof(real) * v[k].size());
+	}
+	if (device) {
+		ok = ok && be_->GatherF32(h.weights, w, d_relayout_, relayout_.size());
+		if (io) ok = ok && be_->D2D(h.norm[0], io, sizeof(real) * d.in_size);
+		if (is) ok = ok && be_->D2D(h.norm[1], is, sizeof(real) * d.in_size);
+		if (oo) ok = ok && be_->D2D(h.norm[2] + pad, oo, sizeof(real) * cfg_.user_out_size);
+		if (os) ok = ok && be_->D2D(h.norm[3] + pad, os, sizeof(real) * cfg_.user_out_size);
+	} else {
+		std::vector<float> dev_w(relayout_.size());
+		for (size_t i = 0; i < relayout_.size(); ++i) dev_w[i] = relayout_[i] >= 0 ? w[relayout_[i]] : 0.0f;
+		ok = ok && be_->H2D(h.weights, dev_w.data(), sizeof(float) * dev_w.size());
+	}
+	if (!ok) return Fail(DTRL_ERR_DEVICE, be_->error());
+	h.set = true; h.alias = -1;
+	return UploadSlotTable();
+}
+
+int Engine::SlotAlias(int slot, int src_slot)
+{
+	int rc = SlotsIdle("dtrl_slot_alias", slot);
+	if (rc != DTRL_OK) return rc;
+	if (slot == 0) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: slot 0 is the batch's own policy and cannot be an alias");
+	if (src_slot < 0 || src_slot >= static_cast<int>(slots_.size())) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: source slot " + std::to_string(src_slot) + " out of range (0 .. " + std::to_string(slots_.size() - 1) + ")");
+	if (src_slot == slot) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: slot " + std::to_string(slot) + " cannot be an alias of itself");
+	if (!slots_[src_slot].set && slots_[src_slot].alias < 0) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: source slot " + std::to_string(src_slot) + " is empty (it has neither a policy nor an alias)");
+	for (int s = src_slot; s >= 0; s = slots_[s].alias) if (s == slot) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: slot " + std::to_string(src_slot) + " reads slot " + std::to_string(slot) + " itself: the alias would be an alias of itself");
+	slots_[slot].alias = src_slot; slots_[slot].set = false;
+	return UploadSlotTable();
+}
+
+int Engine::SlotSetExplore(int slot, int enable, double rate, double temp, double base_rate)
+{
+	if (slot == 0 && !slots_.empty()) return SetExplore(enable, rate, temp, base_rate);   // (valid at any time, as dtrl_set_explore is: it travels by value with every launch)
+	int rc = SlotsIdle("dtrl_slot_set_explore", slot);
+	if (rc != DTRL_OK) return rc;
+	SlotHost& h = slots_[slot];
+	h.enable_exp = enable ? 1 : 0; h.rate = rate; h.temp = temp; h.base_rate = base_rate;
+	return UploadSlotTable();
+}
+
+int Engine::AssignSlots(const int32_t* env_ids, int n, const int32_t* slots)
+{
+	int rc = SlotsIdle("dtrl_assign_slots", 0);
+	if (rc != DTRL_OK) return rc;
+	if (n < 0 || n > n_ || (n > 0 && !slots)) return Fail(DTRL_ERR_ARG, "dtrl_assign_slots: slots is required and the env count must be 0 .. num_envs");
+	for (int i = 0; i < n; ++i) {   // all or nothing
+		const int e = EnvIndex(env_ids, i), s = slots[i];
+		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "dtrl_assign_slots: env id " + std::to_string(e) + " out of range; nothing assigned");
+		if (s < 0 || s >= static_cast<int>(slots_.size())) return Fail(DTRL_ERR_ARG, "dtrl_assign_slots: slot " + std::to_string(s) + " out of range (0 .. " + std::to_string(slots_.size() - 1) + "); nothing assigned");
+		if (!slots_[s].set && slots_[s].alias < 0) return Fail(DTRL_ERR_ARG, "dtrl_assign_slots: slot " + std::to_string(s) + " is empty (it has neither a policy nor an alias); nothing assigned");
+	}
+	for (int i = 0; i < n; ++i) env_slot_[EnvIndex(env_ids, i)] = slots[i];
+	if (!be_->H2D(d_env_slot_, env_slot_.data(), sizeof(int32_t) * env_slot_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::GetSlots(const int32_t* env_ids, int n, int32_t* slots_out)
+{
+	if (slots_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_get_slots: the batch has no policy slots (call dtrl_slots_create first)");
+	if (n < 0 || n > n_ || (n > 0 && !slots_out)) return Fail(DTRL_ERR_ARG, "dtrl_get_slots: slots_out is required and the env count must be 0 .. num_envs");
+	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "dtrl_get_slots: env id " + std::to_string(e) + " out of range"); }
+	for (int i = 0; i < n; ++i) slots_out[i] = env_slot_[EnvIndex(env_ids, i)];
+	return DTRL_OK;
+}
+
+int Engine::SlotStats(int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets)
+{
+	if (slots_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_slot_stats: the batch has no policy slots (call dtrl_slots_create first)");
+	if (slot < 0 || slot >= static_cast<int>(slots_.size())) return Fail(DTRL_ERR_ARG, "dtrl_slot_stats: slot " + std::to_string(slot) + " out of range (0 .. " + std::to_string(slots_.size() - 1) + ")");
+	be_->SelectStream(0);
+	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	SlotSums sums[kMaxSlots];
+	if (!be_->SlotReduce(buf_.st, d_env_slot_, n_, static_cast<int>(slots_.size()), sums)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	const SlotSums& a = sums[slot];
+	if (n_envs) *n_envs = a.n_envs;
+	if (avg_dist) *avg_dist = a.episodes > 0 ? a.dist_sum / static_cast<double>(a.episodes) : 0.0;
+	if (episodes) *episodes = a.episodes;
+	if (cycles) *cycles = a.cycles;
+	if (resets) *resets = a.resets;
 	return DTRL_OK;
 }
 

@@ -21,9 +21,47 @@ constexpr int kSnapRecs = 12;   // (most in use: 9 -- external policy mode with 
 // record is still waiting in page-locked memory (stage_slot[e] > 0) is READ from gr_stage[stage_slot[e] - 1], the record that will be in force at its next launch
 struct SnapPlan { SnapRec rec[kSnapRecs]; int32_t n_rec = 0, gr_rec = -1; uint32_t env_bytes = 0; const GroundRec* gr_stage = nullptr; const int32_t* stage_slot = nullptr; };
 
+// ---- policy slots (include/dtrl.h: dtrl_slots_create ...) ----
+// One record per slot of the device-visible slot table: where the slot's net lives and how it explores. kSlotLaunchPolicy: the five policy pointers are NOT
+// taken from the record but from the launch's own DevBuffers (slot 0 and every alias of it: slot 0's weights change buffers with a hand-over while launches are
+// in flight, and a launch argument cannot change under a running kernel); kSlotLaunchExplore: the same for the exploration settings and RunParams (slot 0:
+// dtrl_set_explore acts at any time). Everything else in the table is only ever rewritten while every stream is idle.
+enum SlotFlags { kSlotLaunchPolicy = 1, kSlotLaunchExplore = 2 };
+constexpr int kMaxSlots = 32;
+struct SlotRec {
+	const float* weights;
+	const real* in_off; const real* in_scale; const real* out_off; const real* out_scale;
+	real exp_rate, exp_temp, exp_base_rate;
+	int32_t enable_exp, flags;
+};
+static_assert(sizeof(SlotRec) % 8 == 0, "slot records are read as 64-bit words");
+DTRL_HD_INLINE void slot_patch(const SlotRec& r, RunParams& rp, DevBuffers& buf)
+{
+	if (!(r.flags & kSlotLaunchPolicy)) { buf.weights = r.weights; buf.in_off = r.in_off; buf.in_scale = r.in_scale; buf.out_off = r.out_off; buf.out_scale = r.out_scale; }
+	if (!(r.flags & kSlotLaunchExplore)) { rp.enable_exp = r.enable_exp; rp.exp_rate = r.exp_rate; rp.exp_temp = r.exp_temp; rp.exp_base_rate = r.exp_base_rate; }
+}
+// what a slotted launch is given: the table as the kernels read it (device memory) and as the host loops read it, the same for the per-env slot array (indexed
+// by local env id), and what the per-slot default needs to split a launch list: the list in host-readable form (nullptr: it exists on the device only and is
+// read back; ignored when the launch has no list) and `part`, HostStaging() memory for the launch's n_envs entries regrouped by slot.
+struct SlotView {
+	const SlotRec* dev = nullptr; const SlotRec* host = nullptr; int32_t n_slots = 0;
+	const int32_t* env_slot_host = nullptr;
+	const int32_t* env_list_host = nullptr;
+	int32_t* part = nullptr;
+};
+// per-slot totals of dtrl_slot_stats (Backend::SlotReduce): envs in the slot, and over them the sums dtrl_eval_stats takes over the batch
+struct SlotSums { int64_t n_envs, episodes, cycles, resets; double dist_sum; };   // dist_sum = sum of avg_dist * num_episodes
+
 class Backend {
 public:
 	virtual ~Backend() {}
+	// A launch over envs of several policy slots (env e runs slot env_slot[e]'s record patched over rp / buf: slot_patch). The default is one Launch per
+	// non-empty slot over that slot's part of the launch list, list order kept inside a slot (what the lane-loop check build runs, and DTRL_SLOTS_FALLBACK=1 on
+	// HIP; it waits for the selected stream before it reuses slots.part). The HIP backend overrides it with ONE launch of the slot kernels (dtrl_backend_hip_slots.hip).
+	virtual bool LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end);
+	// sums[s] for s < n_slots over the envs e < n_envs with env_slot[e] == s; st / env_slot are device memory, sums host memory. Synchronised. The default is a
+	// host loop over a D2H of the records; the HIP backend reduces on the device (two launches, fixed summation order: the same bytes from call to call)
+	virtual bool SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums);
 	// Snapshot transport. ids / src_ids / dst_ids live in HostStaging() memory (host- and device-addressable), payload is device memory laid out [n][env_bytes].
 	// Queued on the selected stream and synchronised. The defaults are built from D2D (one copy per record and env); the HIP backend overrides them with
 	// one kernel launch each (one wavefront per listed env, every record copied as consecutive 64-bit words).
@@ -184,6 +222,40 @@ inline bool Backend::ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int
 	}
 	return true;
 }
+inline bool Backend::LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end)
+{
+	(void)env_slot;
+	if (n_envs <= 0) return true;
+	std::vector<int32_t> list(static_cast<size_t>(n_envs));
+	if (!buf.env_list) { for (int i = 0; i < n_envs; ++i) list[i] = i; }
+	else if (slots.env_list_host) { for (int i = 0; i < n_envs; ++i) list[i] = slots.env_list_host[i]; }
+	else if (!D2H(list.data(), buf.env_list, sizeof(int32_t) * list.size())) return false;   // (an order computed on the device: behind everything queued, this launch's list included)
+	if (!SyncSelected()) return false;   // an earlier launch of this stream may still be reading slots.part
+	int n_of[kMaxSlots] = {0}, at[kMaxSlots];
+	for (int32_t e : list) ++n_of[slots.env_slot_host[e]];
+	for (int s = 0, k = 0; s < slots.n_slots; ++s) { at[s] = k; k += n_of[s]; }
+	for (int32_t e : list) slots.part[at[slots.env_slot_host[e]]++] = e;
+	for (int s = 0, k = 0; s < slots.n_slots; k += n_of[s], ++s) {
+		if (n_of[s] == 0) continue;
+		RunParams r = rp; DevBuffers b = buf;
+		slot_patch(slots.host[s], r, b);
+		b.env_list = slots.part + k;
+		if (!Launch(gm, r, b, n_of[s], n_steps, dt, frame_end)) return false;
+	}
+	return true;
+}
+inline bool Backend::SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums)
+{
+	std::vector<EnvState> host(static_cast<size_t>(n_envs)); std::vector<int32_t> slot(static_cast<size_t>(n_envs));
+	if (!D2H(host.data(), st, sizeof(EnvState) * host.size()) || !D2H(slot.data(), env_slot, sizeof(int32_t) * slot.size())) return false;
+	for (int s = 0; s < n_slots; ++s) sums[s] = SlotSums{0, 0, 0, 0, 0.0};
+	for (int e = 0; e < n_envs; ++e) {
+		SlotSums& a = sums[slot[e]];
+		++a.n_envs; a.episodes += host[e].num_episodes; a.cycles += host[e].num_cycles; a.resets += host[e].num_resets;
+		a.dist_sum += static_cast<double>(host[e].avg_dist) * static_cast<double>(host[e].num_episodes);
+	}
+	return true;
+}
 Backend* MakeBackend();   // resolved at link time: HIP in libdtrl.so, the lane-loop test backend under tests/emul/
 
 // Header of an exported snapshot blob (dtrl_snapshot_export): [SnapHeader][int32 slot ids, padded to 8 bytes][device payload n x env_bytes][host payload n x host_bytes].
@@ -228,6 +300,14 @@ public:
 	int SnapshotImport(const void* blob, size_t bytes, Snapshot** out);
 	void SnapshotRelease(Snapshot* s);
 	double SnapLaunchMs() { return be_ ? be_->SnapLaunchMs() : -1.0; }
+	// policy slots (include/dtrl.h)
+	int SlotsCreate(int n_slots);
+	int SlotSetPolicy(int slot, const float* w, size_t n, const double* io, const double* is, const double* oo, const double* os, bool device);
+	int SlotAlias(int slot, int src_slot);
+	int SlotSetExplore(int slot, int enable, double rate, double temp, double base_rate);
+	int AssignSlots(const int32_t* env_ids, int n, const int32_t* slots);
+	int GetSlots(const int32_t* env_ids, int n, int32_t* slots_out);
+	int SlotStats(int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
 	~Engine();
 	int Create(const char* const* argv, int argc, int num_envs, int device_id);
 	int Reset(const int32_t* env_ids, int n, const uint64_t* seeds);
@@ -360,6 +440,19 @@ private:
 	int32_t* d_ext_ids_ = nullptr;                         // device [n]
 	double* d_ext_states_ = nullptr;                       // device [n][S] (host call)
 	int32_t* d_ext_action_ids_ = nullptr; uint32_t* d_ext_flags_ = nullptr; double* d_ext_params_ = nullptr;   // device [n], [n], [n][n_opt]: the rows of a host call
+	// policy slots. Slot 0 is the batch's policy (buf_'s five pointers, cfg_.run's exploration); a slot >= 1 owns storage (own_[s]) or is an alias (alias_[s] >= 0).
+	// The table and the per-env array are rewritten only by calls that have refused a frame in flight and waited for every stream (SlotsIdle)
+	struct SlotHost { float* weights = nullptr; real* norm[4] = {nullptr, nullptr, nullptr, nullptr}; int alias = -1; bool set = false; int enable_exp = 0; double rate = 0, temp = 1, base_rate = 0; };
+	std::vector<SlotHost> slots_;            // empty: no slots, every launch is Backend::Launch as it always was
+	std::vector<SlotRec> slot_table_;        // host form of the table
+	std::vector<int32_t> env_slot_;          // host form of the per-env array
+	SlotRec* d_slot_table_ = nullptr; int32_t* d_env_slot_ = nullptr; int32_t* slot_part_ = nullptr;   // device table [n_slots], device array [n], page-locked [2 n]
+	int SlotsIdle(const char* what, int slot);   // DTRL_ERR_ARG without slots / slot out of range / frame in flight, else every stream idle
+	int SlotRoot(int slot) const { while (slots_[slot].alias >= 0) slot = slots_[slot].alias; return slot; }
+	int UploadSlotTable();
+	// every frame-kernel launch of the batch: Backend::Launch, or -- once slots exist -- Backend::LaunchSlots. list_host: b.env_list in host-readable form or
+	// nullptr; part_off: offset of the launch's scratch inside slot_part_
+	bool LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, bool frame_end, const int32_t* list_host, int part_off);
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

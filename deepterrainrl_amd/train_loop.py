@@ -84,7 +84,7 @@ def feed_chunks(t, rows, flags, chunk, ph=None, poll=None):
 
 def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, device_id=-1, extra_args=None, seed=0, log_every=0, out_scale_file=None,
           trainer_device=None, overlap=False, frames_per_drain=1, scenario_cls=BatchScenario, trainer="torch", trainer_lib=None, poll=False,
-          eval_every=None, eval_fn=None, out_model_file=None):
+          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0):
     """extra_args override / extend the arg file (both for the engine and for the -trainer_* keys read here).
     overlap=True trains on frame f's tuples while the GPU already rolls out frame f+1 (dtrl_step_begin / dtrl_step_end): the policy
     each frame runs with is one frame staler, as with the reference's concurrent env threads; overlap=False is the strictly
@@ -94,13 +94,24 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     (dog 9.95-11.2 M with, 11.2-11.4 M without: the trainer's kernels and the frame waves share the same wavefront slots either way), so it is off by default.
     eval_every / eval_fn: eval_fn(iteration, trainer, batch) is called before the first iteration and then whenever the iteration counter has passed another
     eval_every (cScenarioTrain's intermediate output every trainer_int_iter, scenarios/ScenarioTrain.cpp:376-410, with an evaluation in its place: tools/learn_curve.py).
-    out_model_file: the trainer's net as a Caffe HDF5 model at the end (cNeuralNetTrainer::OutputModel), next to out_scale_file."""
+    out_model_file: the trainer's net as a Caffe HDF5 model at the end (cNeuralNetTrainer::OutputModel), next to out_scale_file.
+    greedy_envs=k > 0 keeps the last k envs greedy beside the exploring ones (policy slots: an alias of slot 0 with exploration off, so every hand-over reaches
+    them too): their tuples are left out of what the trainer is fed, and their falls per 1000 env-steps (SlotStats) are logged with log_every and returned as
+    stats["greedy"]. k = 0 (default) creates no slots and runs exactly as before."""
     if overlap:
         extra_args = dict({"tuple_ring": "host"}, **(extra_args or {}))    # drains beside a running frame must not queue copies behind it (include/dtrl.h: dtrl_drain_tuples)
     args = parse_arg_file(os.path.join(data_root, arg_file))
     args.update({k: str(v) for k, v in (extra_args or {}).items()})
     geti = lambda k, d: int(args.get(k, d)); getf = lambda k, d: float(args.get(k, d))
     b = scenario_cls(arg_file, num_envs, data_root=data_root, device_id=device_id, extra_args=extra_args)
+    if greedy_envs < 0 or greedy_envs >= num_envs:
+        raise ValueError("greedy_envs must be 0 .. num_envs - 1")
+    n_train = num_envs - greedy_envs
+    if greedy_envs:
+        b.CreateSlots(2)
+        b.SlotAlias(1, 0)
+        b.SlotSetExplore(1, 0, 0.0, 1.0, 0.0)
+        b.AssignSlots(np.arange(n_train, num_envs, dtype=np.int32), np.ones(greedy_envs, np.int32))
     solver = os.path.join(data_root, args["policy_solver"])
     train_net = os.path.join(data_root, re.search(r'net:\s*"([^"]+)"', open(solver).read()).group(1)) if re.search(r'net:\s*"', open(solver).read()) \
         else os.path.join(data_root, args["policy_net"].replace("_deploy", "_train"))
@@ -155,8 +166,15 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     clk = time.perf_counter
 
     def feed(rows, flags, ids, poll=None):
+        if greedy_envs:
+            keep = ids < n_train                 # the greedy envs' tuples are not training data
+            rows, flags, ids = rows[keep], flags[keep], ids[keep]
         o = np.argsort(ids, kind="stable")   # the device ring is filled in completion order; env-id order makes the run reproducible and shard-invariant
         return feed_chunks(t, rows[o], flags[o], chunk, ph, poll)
+
+    def greedy_falls():
+        g = b.SlotStats(1)
+        return 1000.0 * g["resets"] / max(1.0, greedy_envs * frames * 20.0)
 
     def log():
         if next_eval[0] is not None and t.GetIter() >= next_eval[0]:
@@ -165,6 +183,8 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
         if log_every and frames % log_every == 0:
             stats["log"].append((frames, t.GetIter(), t.GetNumTuples(), t.last_loss, b.EvalStats()))
             print("frame %d iter %d tuples %d critic-loss %s actor-iters %d" % (frames, t.GetIter(), t.GetNumTuples(), t.last_loss, t.actor_iter), flush=True)
+            if greedy_envs:
+                print("frame %d greedy envs: %.3f falls / 1000 env-steps" % (frames, greedy_falls()), flush=True)
 
     if not overlap:
         while t.GetIter() < max_iters and (max_frames is None or frames < max_frames):
@@ -219,6 +239,8 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
         t.OutputModel(out_model_file)
     stats.update(frames=frames, iters=t.GetIter(), tuples=tuples, seconds=dt, env_steps_per_s=frames * 20.0 * num_envs / dt,
                  trainer_iters_per_s=t.GetIter() / dt, weights=t.GetWeights(), offset_scale=t.GetOffsetScale(), phases=ph, side_stream_delay_us=side[1])
+    if greedy_envs:
+        stats["greedy"] = dict(b.SlotStats(1), falls_k=greedy_falls())
     return stats
 
 

@@ -293,6 +293,44 @@ dtrl_status dtrl_action_dims(const dtrl_batch* b, int* n_opt, int* n_labels, int
 /* Device time (ms, HIP events) of the collection (which = 0) / scatter (which = 1) launches since the previous call; -1 where nothing is launched. */
 double dtrl_ext_launch_ms(dtrl_batch* b, int which);
 
+/* ---- Policy slots: several policies in one batch, one per env ----
+ * No counterpart in the reference: it keeps one net per scene object (the controller's cNeuralNet, sim/NNController.cpp:49-78), so comparing or mixing
+ * policies there means one scenario per policy. A slot is a set of weights, the four normalisers and the exploration settings; a batch holds up to 32 and every
+ * env is assigned to one. Frames still run as one launch per env group. Slot 0 IS the batch's policy: dtrl_set_policy*, dtrl_load_scale_file and dtrl_set_explore
+ * keep acting on it (double-buffered and asynchronous hand-overs included), and every env starts in it. Every other slot starts without a policy and with the
+ * exploration settings the batch has at dtrl_slots_create. A batch that never calls dtrl_slots_create runs exactly
+ * the kernels and launches it ran before. `exp_noise` stays the batch's. The assignment is batch state like the policy: snapshots, restores, clones and blobs do
+ * not carry it and a reset does not change it. Slots use local env ids (a sharded run has slots per shard). Not available in external policy mode.
+ * Except where noted the calls below are refused with DTRL_ERR_ARG between dtrl_step_begin and dtrl_step_end (they never wait for a frame), and then wait for
+ * everything the batch has queued on the device before they change anything: no launch ever sees a half-written slot. */
+/* No counterpart in the reference: it keeps one net per scene object (sim/NNController.cpp:49-78). 1 <= n_slots <= 32, once per batch (the same count again is
+ * accepted). Refused with DTRL_ERR_ARG: external policy mode, a batch without -policy_net=, a frame in flight, a second call with another count. */
+dtrl_status dtrl_slots_create(dtrl_batch* b, int n_slots);
+/* No counterpart in the reference: it keeps one net per scene object (sim/NNController.cpp:49-78). dtrl_set_policy into a slot: the same blob order and
+ * relayout, NULL normalisers mean identity. Slot >= 1 gets weight and normaliser storage of its own on first use and stops being an alias; slot 0 is
+ * dtrl_set_policy itself. Synchronous. */
+dtrl_status dtrl_slot_set_policy(dtrl_batch* b, int slot, const float* weights, size_t n, const double* in_off, const double* in_scale, const double* out_off, const double* out_scale);
+/* No counterpart in the reference: it keeps one net per scene object (sim/NNController.cpp:49-78). The same from DEVICE memory (dtrl_set_policy_device's
+ * conventions: a NULL normaliser keeps the slot's current vector, identity in a slot that had no policy yet; the fp32 library takes weights only). Synchronous. */
+dtrl_status dtrl_slot_set_policy_device(dtrl_batch* b, int slot, const float* weights_dev, size_t n, const double* in_off_dev, const double* in_scale_dev, const double* out_off_dev, const double* out_scale_dev);
+/* No counterpart in the reference: it keeps one net per scene object (sim/NNController.cpp:49-78). Slot (>= 1) reads src_slot's weights and normalisers from now
+ * on, whatever they become -- every hand-over into slot 0 included -- and keeps exploration settings of its own: "the same net, greedy" at no memory cost.
+ * Refused: an alias of itself (directly or through other aliases), an empty source slot. */
+dtrl_status dtrl_slot_alias(dtrl_batch* b, int slot, int src_slot);
+/* No counterpart in the reference: it keeps one net per scene object (sim/NNController.cpp:49-78). dtrl_set_explore for one slot; slot 0 is dtrl_set_explore
+ * itself (and, like it, valid at any time). */
+dtrl_status dtrl_slot_set_explore(dtrl_batch* b, int slot, int enable, double rate, double temp, double base_rate);
+/* No counterpart in the reference: it keeps one net per scene object (sim/NNController.cpp:49-78). env_ids[i] -> slots[i]; env_ids == NULL means the first n
+ * envs. All or nothing: an env id or slot out of range, or a slot that has neither a policy nor an alias, is DTRL_ERR_ARG. Takes effect with the env's next
+ * launch: a mid-cycle env makes its next decision with the new slot, nothing else in its state changes. */
+dtrl_status dtrl_assign_slots(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* slots);
+/* No counterpart in the reference: it keeps one net per scene object (sim/NNController.cpp:49-78). The slots of the listed envs (valid at any time). With the
+ * env id column of dtrl_drain_tuples this tells which slot produced a tuple. */
+dtrl_status dtrl_get_slots(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* slots_out);
+/* No counterpart in the reference: it keeps one net per scene object (sim/NNController.cpp:49-78). dtrl_eval_stats restricted to the envs currently in the slot
+ * (n_envs of them), reduced on the device in a fixed order: two calls without a step between them return the same bits. Any output may be NULL. */
+dtrl_status dtrl_slot_stats(dtrl_batch* b, int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+
 /* Replaces: cScenarioSimChar::AddPerturb -> cWorld::AddPerturb (scenarios/ScenarioSimChar.cpp:204-207, sim/World.cpp:256-259) with a
  * tPerturb of type ePerturbForce (sim/Perturb.cpp:52-79, sim/World.cpp:445-470): a world-frame force[n][2] on body part link[n] at the
  * body-local offset local_pos[n][2] (NULL = the COM) for duration[n] seconds of simulated time, advanced and applied at the start of

@@ -11,7 +11,9 @@ Every --eval-every iterations (trainer_int_iter = 2000: where cScenarioTrain wri
 (poli_eval: no exploration) on a separate batch of --eval-envs envs with FIXED terrain seeds for --eval-frames outer frames (optimizer/scenarios/OptScenarioPoliEval.cpp:170-211):
   speed        metres per second of simulated time, all envs (finished episodes + the running ones)        falls_k   falls per 1000 env-steps
   avg_dist     cScenarioPoliEval's mean distance per finished episode (nan: nobody fell)                   alive     fraction of envs that never fell during the evaluation
-The first line (iteration 0) is the xavier-initialised net: the baseline every earlier number of this repository was measured on."""
+The first line (iteration 0) is the xavier-initialised net: the baseline every earlier number of this repository was measured on.
+--eval-batched keeps the intermediate weights instead and evaluates them at the end in one slotted batch per 32 of them (policy slots: evaluate_many, one slot per
+set of weights, every slot on the same terrains) -- the same figures without a fresh batch per evaluation; the lines are then printed when the run is over."""
 import argparse, os, sys, time
 import numpy as np
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
@@ -45,6 +47,41 @@ def evaluate(arg_file, root, weights, norm, n, frames, seed=777001):
                 episodes=int(st["episodes"]), cycles=int(st["cycles"]))
 
 
+MAX_SLOTS = 32
+
+
+def evaluate_many(arg_file, root, policies, n, frames, seed=777001, scenario=None):
+    """policies: [(weights, (in_off, in_scale, out_off, out_scale)), ...], at most 32. Returns one dict per policy with learn_curve.evaluate's keys."""
+    K = len(policies)
+    if not 1 <= K <= MAX_SLOTS:
+        raise ValueError("1 .. %d policies per batch" % MAX_SLOTS)
+    b = (scenario or SCENARIO)(arg_file, K * n, data_root=root, extra_args={"terrain_seed": seed})
+    b.CreateSlots(K)
+    b.SetPolicy(policies[0][0], *policies[0][1])
+    for k in range(1, K):
+        b.SlotSetPolicy(k, policies[k][0], *policies[k][1])
+    slot = np.arange(K * n, dtype=np.int32) % K
+    b.AssignSlots(None, slot)
+    b.Reset(None, [seed + e // K for e in range(K * n)])       # model k's j-th env runs on the terrain of env j of a single-policy evaluation batch
+    x0 = b.PoseVel()[0][:, 0].copy()
+    for _ in range(frames):
+        b.Update(1.0 / 30.0)
+    d, ids = b.GetDistLog()
+    ids = np.asarray(ids, np.int64)
+    x1 = b.PoseVel()[0][:, 0]
+    T = frames / 30.0
+    out = []
+    for k in range(K):
+        st = b.SlotStats(k)
+        dk = d[ids % K == k]
+        total = float(dk.sum()) + float((x1[slot == k] - x0[slot == k]).sum())
+        fell = np.zeros(K * n, bool); fell[ids] = True
+        resets = st["resets"] - st["n_envs"]                   # (the reseeding reset above is counted by the engine; it is not a fall)
+        out.append(dict(speed=total / (n * T), falls_k=1000.0 * resets / (n * frames * 20.0), avg_dist=float(dk.mean()) if len(dk) else float("nan"),
+                        alive=float(1.0 - fell[slot == k].mean()), episodes=int(st["episodes"]), cycles=int(st["cycles"])))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--char", choices=sorted(CHARS), default="dog")
@@ -59,6 +96,7 @@ def main():
     ap.add_argument("--trainer", choices=["hip", "torch"], default="hip")
     ap.add_argument("--init-samples", type=int, default=None, help="(smoke runs only) override -trainer_num_init_samples=")
     ap.add_argument("--lib", default="", help="(CPU smoke runs only) bind the scenario to this build of the engine, e.g. tests/emul/libdtrl_emul.so")
+    ap.add_argument("--eval-batched", action="store_true", help="collect the intermediate weights and evaluate them in one slotted batch at the end instead of one fresh batch per evaluation")
     ap.add_argument("--sequential", action="store_true", help="no overlap: train on frame f's tuples before frame f+1 is launched")
     a = ap.parse_args()
     c = CHARS[a.char]; envs = a.envs or c["envs"]
@@ -74,13 +112,21 @@ def main():
     t0 = time.time()
     curve = []
 
+    pending = []   # --eval-batched: (weights, normalisers, bookkeeping) of the evaluations still to run
+
+    def record(r, meta):
+        r.update(meta)
+        curve.append(r)
+        line = "  %8d %9d %9.1f %8.3f %8.3f %9.3f %7.3f %9d %9.4g" % (r["iter"], r["tuples"], r["wall"], r["speed"], r["falls_k"], r["avg_dist"], r["alive"], r["episodes"], r["loss"])
+        lines.append(line); print(line, flush=True)
+
     def eval_fn(it, t, b):
         norm = t.GetOffsetScale()
-        r = evaluate(c["evalf"], a.data_root, t.GetWeights(), norm, a.eval_envs, a.eval_frames)
-        r.update(iter=it, tuples=t.GetNumTuples(), wall=time.time() - t0, loss=float(t.last_loss) if t.last_loss is not None else float("nan"))
-        curve.append(r)
-        line = "  %8d %9d %9.1f %8.3f %8.3f %9.3f %7.3f %9d %9.4g" % (it, r["tuples"], r["wall"], r["speed"], r["falls_k"], r["avg_dist"], r["alive"], r["episodes"], r["loss"])
-        lines.append(line); print(line, flush=True)
+        meta = dict(iter=it, tuples=t.GetNumTuples(), wall=time.time() - t0, loss=float(t.last_loss) if t.last_loss is not None else float("nan"))
+        if a.eval_batched:
+            pending.append((np.array(t.GetWeights(), np.float32, copy=True), tuple(None if v is None else np.array(v, np.float64, copy=True) for v in norm), meta))
+            return
+        record(evaluate(c["evalf"], a.data_root, t.GetWeights(), norm, a.eval_envs, a.eval_frames), meta)
 
     stem = None
     if a.save:
@@ -89,6 +135,10 @@ def main():
     st = train_loop.train(c["train"], a.data_root, envs, max_iters=a.iters, overlap=not a.sequential, trainer=a.trainer, scenario_cls=SCENARIO,
                           extra_args=dict({"terrain_file": c["terrain"]}, **({"trainer_num_init_samples": a.init_samples} if a.init_samples is not None else {})),
                           eval_every=a.eval_every, eval_fn=eval_fn, out_model_file=(stem + ".h5") if stem else None, out_scale_file=(stem + "_scale.txt") if stem else None)
+    for k in range(0, len(pending), MAX_SLOTS):
+        part = pending[k:k + MAX_SLOTS]
+        for r, (_, _, meta) in zip(evaluate_many(c["evalf"], a.data_root, [(w, norm) for w, norm, _ in part], a.eval_envs, a.eval_frames), part):
+            record(r, meta)
     # the final net once more, through the files just written when there are any (policy-file row f2: caffe_hdf5 writer -> reader -> dtrl_set_policy)
     if stem:
         b = SCENARIO(c["evalf"], 8, data_root=a.data_root)

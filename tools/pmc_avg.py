@@ -2,7 +2,7 @@
 """Per-dispatch averages of the counters of a rocprofv3 --pmc pass (rocpd sqlite) for the frame kernel's full-size launches.
 Usage: pmc_avg.py <dir containing *_results.db> [label]"""
 import glob, os, sqlite3, sys
-KERNEL = "dtrl_frame_kernel"
+KERNEL = "frame_kernel"   # dtrl_frame_kernel*, dtrl_ext_frame_kernel*, dtrl_slot_frame_kernel*
 for db in sorted(glob.glob(os.path.join(sys.argv[1], "**", "*_results.db"), recursive=True)):
     cur = sqlite3.connect(db).cursor()
     q = ("select counter_name, count(*), avg(value) from counters_collection where kernel_name like '%" + KERNEL + "%' "
