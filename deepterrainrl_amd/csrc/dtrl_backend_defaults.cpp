@@ -1,0 +1,124 @@
+// dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, slotted launches
+// and the per-slot sums, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
+// of them with kernels and keeps these as its cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1).
+// Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
+// lane-loop check build of any tests/ tree, the sanitizer scripts -- has the defaults, and no source list can lack them.
+#include "dtrl_engine.h"
+
+namespace dtrl {
+
+// where env e's record r is read from, and whether that is host memory (the status array of host terrain mode; a staged terrain record)
+static const char* SnapSrc(const SnapPlan& p, int r, int e, bool* host)
+{
+	if (r == p.gr_rec && p.stage_slot && p.stage_slot[e] > 0) { *host = true; return reinterpret_cast<const char*>(&p.gr_stage[p.stage_slot[e] - 1]); }
+	*host = p.rec[r].host != 0;
+	return p.rec[r].slab + static_cast<size_t>(e) * p.rec[r].bytes;
+}
+bool Backend::SnapGather(const SnapPlan& p, char* payload, const int32_t* ids, int n)
+{
+	for (int i = 0; i < n; ++i) for (int r = 0; r < p.n_rec; ++r) {
+		bool host; const char* src = SnapSrc(p, r, ids[i], &host);
+		char* dst = payload + static_cast<size_t>(i) * p.env_bytes + p.rec[r].off;
+		if (!(host ? H2D(dst, src, p.rec[r].bytes) : D2D(dst, src, p.rec[r].bytes))) return false;
+	}
+	return true;
+}
+bool Backend::SnapScatter(const SnapPlan& p, const char* payload, const int32_t* ids, int n)
+{
+	for (int i = 0; i < n; ++i) for (int r = 0; r < p.n_rec; ++r) {
+		char* dst = p.rec[r].slab + static_cast<size_t>(ids[i]) * p.rec[r].bytes;
+		const char* src = payload + static_cast<size_t>(i) * p.env_bytes + p.rec[r].off;
+		if (!(p.rec[r].host ? D2H(dst, src, p.rec[r].bytes) : D2D(dst, src, p.rec[r].bytes))) return false;
+	}
+	return true;
+}
+bool Backend::SnapCopy(const SnapPlan& p, const int32_t* src_ids, const int32_t* dst_ids, int n)
+{
+	for (int i = 0; i < n; ++i) for (int r = 0; r < p.n_rec; ++r) {
+		bool host; const char* src = SnapSrc(p, r, src_ids[i], &host);
+		char* dst = p.rec[r].slab + static_cast<size_t>(dst_ids[i]) * p.rec[r].bytes;
+		if (p.rec[r].host) { for (uint32_t k = 0; k < p.rec[r].bytes; ++k) dst[k] = src[k]; continue; }   // host to host (the streams are idle)
+		if (!(host ? H2D(dst, src, p.rec[r].bytes) : D2D(dst, src, p.rec[r].bytes))) return false;
+	}
+	return true;
+}
+bool Backend::ExtCollect(const DevBuffers& buf, int n_envs, int cap, int32_t* ids, void* states, bool f32, int32_t* meta)
+{
+	int m = 0, na = 0, nr = 0;
+	std::vector<real> row(static_cast<size_t>(buf.S));
+	std::vector<float> rf(f32 ? row.size() : 0); std::vector<double> rd(f32 ? 0 : row.size());
+	for (int e = 0; e < n_envs; ++e) {
+		int32_t park = 0;
+		if (!D2H(&park, &buf.st[e].ext_park, sizeof(park))) return false;
+		if (park == kExtReady) ++nr;
+		if (park != kExtAwaiting) continue;
+		++na;
+		if (m >= cap) continue;
+		const int32_t id = e;
+		if (!H2D(ids + m, &id, sizeof(id))) return false;
+		if (states) {
+			if (!D2H(row.data(), buf.poli_state + static_cast<size_t>(e) * buf.S, sizeof(real) * row.size())) return false;
+			if (f32) { for (size_t k = 0; k < row.size(); ++k) rf[k] = static_cast<float>(row[k]); if (!H2D(static_cast<float*>(states) + static_cast<size_t>(m) * buf.S, rf.data(), sizeof(float) * rf.size())) return false; }
+			else { for (size_t k = 0; k < row.size(); ++k) rd[k] = static_cast<double>(row[k]); if (!H2D(static_cast<double*>(states) + static_cast<size_t>(m) * buf.S, rd.data(), sizeof(double) * rd.size())) return false; }
+		}
+		++m;
+	}
+	meta[0] = m; meta[1] = na; meta[2] = nr; meta[3] = 0;
+	return true;
+}
+bool Backend::ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labels, const int32_t* ids, int n, const int32_t* action_ids, const void* params, bool f32, const uint32_t* flags, bool apply, int32_t* rejected)
+{
+	*rejected = 0;
+	std::vector<float> pf(f32 ? n_opt : 0); std::vector<double> pd(f32 ? 0 : n_opt);
+	for (int i = 0; i < n; ++i) {
+		int32_t e = -1, park = 0;
+		if (!D2H(&e, ids + i, sizeof(e))) return false;
+		if (e >= 0 && e < n_envs && !D2H(&park, &buf.st[e].ext_park, sizeof(park))) return false;
+		ExtAction a{};
+		if (action_ids && !D2H(&a.action_id, action_ids + i, sizeof(int32_t))) return false;
+		if (e < 0 || e >= n_envs || park != kExtAwaiting || a.action_id < 0 || a.action_id >= n_labels) { ++*rejected; continue; }
+		if (!apply) continue;
+		if (flags && !D2H(&a.flags, flags + i, sizeof(uint32_t))) return false;
+		if (f32) { if (!D2H(pf.data(), static_cast<const float*>(params) + static_cast<size_t>(i) * n_opt, sizeof(float) * n_opt)) return false; for (int k = 0; k < n_opt; ++k) a.params[k] = static_cast<real>(pf[k]); }
+		else { if (!D2H(pd.data(), static_cast<const double*>(params) + static_cast<size_t>(i) * n_opt, sizeof(double) * n_opt)) return false; for (int k = 0; k < n_opt; ++k) a.params[k] = static_cast<real>(pd[k]); }
+		park = kExtReady;
+		if (!H2D(&ext_actions(buf)[e], &a, sizeof(a)) || !H2D(&buf.st[e].ext_park, &park, sizeof(park))) return false;
+	}
+	return true;
+}
+bool Backend::LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end)
+{
+	(void)env_slot;
+	if (n_envs <= 0) return true;
+	std::vector<int32_t> list(static_cast<size_t>(n_envs));
+	if (!buf.env_list) { for (int i = 0; i < n_envs; ++i) list[i] = i; }
+	else if (slots.env_list_host) { for (int i = 0; i < n_envs; ++i) list[i] = slots.env_list_host[i]; }
+	else if (!D2H(list.data(), buf.env_list, sizeof(int32_t) * list.size())) return false;   // (an order computed on the device: behind everything queued, this launch's list included)
+	if (!SyncSelected()) return false;   // an earlier launch of this stream may still be reading slots.part
+	int n_of[kMaxSlots] = {0}, at[kMaxSlots];
+	for (int32_t e : list) ++n_of[slots.env_slot_host[e]];
+	for (int s = 0, k = 0; s < slots.n_slots; ++s) { at[s] = k; k += n_of[s]; }
+	for (int32_t e : list) slots.part[at[slots.env_slot_host[e]]++] = e;
+	for (int s = 0, k = 0; s < slots.n_slots; k += n_of[s], ++s) {
+		if (n_of[s] == 0) continue;
+		RunParams r = rp; DevBuffers b = buf;
+		slot_patch(slots.host[s], r, b);
+		b.env_list = slots.part + k;
+		if (!Launch(gm, r, b, n_of[s], n_steps, dt, frame_end)) return false;
+	}
+	return true;
+}
+bool Backend::SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums)
+{
+	std::vector<EnvState> host(static_cast<size_t>(n_envs)); std::vector<int32_t> slot(static_cast<size_t>(n_envs));
+	if (!D2H(host.data(), st, sizeof(EnvState) * host.size()) || !D2H(slot.data(), env_slot, sizeof(int32_t) * slot.size())) return false;
+	for (int s = 0; s < n_slots; ++s) sums[s] = SlotSums{0, 0, 0, 0, 0.0};
+	for (int e = 0; e < n_envs; ++e) {
+		SlotSums& a = sums[slot[e]];
+		++a.n_envs; a.episodes += host[e].num_episodes; a.cycles += host[e].num_cycles; a.resets += host[e].num_resets;
+		a.dist_sum += static_cast<double>(host[e].avg_dist) * static_cast<double>(host[e].num_episodes);
+	}
+	return true;
+}
+
+}  // namespace dtrl

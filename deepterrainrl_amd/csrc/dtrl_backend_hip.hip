@@ -1,13 +1,8 @@
-// dtrl_backend_hip.hip -- the product backend: HIP runtime + the gfx950 frame kernel.
-//
-// Launch geometry: one 64-lane wavefront (one workgroup) per environment, so every __syncthreads() in the lane-phase
-// code is a single-wave barrier; a 4096-env batch is 4096 workgroups (16 per CU), enough to fill all 256 CUs / 8 XCDs.
-// Workgroup b lands on XCD b % 8 (observed dispatch order), i.e. consecutive envs spread across XCDs and each XCD's L2
-// holds only its own envs' state/terrain records -- the per-env records are private, nothing is shared between XCDs
-// except the read-only model and policy weights.
+// dtrl_backend_hip.hip -- the product backend: the HIP runtime behind the Backend interface (streams, events, copies) and every auxiliary kernel. The frame
+// kernels are launched from here and compiled elsewhere, one translation unit per family (dtrl_frame_entry.h: dtrl_backend_hip_frame.hip, _ext.hip, _slots.hip),
+// so that what changes here cannot change their instructions.
 #include "dtrl_engine.h"
-#include "dtrl_kernel_fast.h"
-#include "dtrl_launch_cfg.h"
+#include "dtrl_frame_entry.h"
 #include "dtrl_terrain_dev.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -20,35 +15,6 @@
 #include <vector>
 
 namespace dtrl {
-
-__global__ void __launch_bounds__(kGroup) dtrl_frame_kernel(const DevModel* __restrict__ gm, RunParams rp, DevBuffers buf, int n_envs, int n_steps, real dt, int frame_end)
-{
-	__shared__ WSRef ws;
-	if (static_cast<int>(blockIdx.x) >= n_envs) return;
-	const int env = buf.env_list ? buf.env_list[blockIdx.x] : static_cast<int>(blockIdx.x);
-	env_frame_impl<RefPath, false>(ws, *gm, rp, buf, env, n_steps, dt, frame_end != 0);
-}
-
-// register-resident fast path (dtrl_kernel_fast.h), one instantiation per skeleton of the shipped characters (dtrl_topo.h)
-// Experiment builds (docs/EXPERIMENTS.md 13, tools/occupancy_ab.sh; never the shipped library): -DDTRL_DYN_LDS puts the workspace into DYNAMIC LDS, so that the compiler no
-// longer derives "two waves per SIMD at most" from the 20 KB static allocation and honours -DDTRL_WAVES_PER_EU=3 (<= 168 registers per lane): the register diet a third wave
-// per SIMD would need, priced at unchanged occupancy. Run-time knob of the shipped kernel: DTRL_LDS_PAD=<bytes> of dynamic LDS on top (fewer workgroups per CU: the
-// throughput-vs-occupancy curve from the other side).
-template <class Topo>
-__global__ void __launch_bounds__(kGroup, WavesPerEu<Topo>::value) dtrl_frame_kernel_fast(const DevModel* __restrict__ gm, RunParams rp, DevBuffers buf, int n_envs, int n_steps, real dt, int frame_end)
-{
-#if defined(DTRL_DYN_LDS)
-	extern __shared__ __align__(16) unsigned char dtrl_dyn_lds[];
-	WSFast& ws = *reinterpret_cast<WSFast*>(dtrl_dyn_lds);
-#else
-	__shared__ WSFast ws;
-#endif
-	if (static_cast<int>(blockIdx.x) >= n_envs) return;
-	const int env = buf.env_list ? buf.env_list[blockIdx.x] : static_cast<int>(blockIdx.x);
-#if defined(__HIP_DEVICE_COMPILE__)
-	env_frame_impl<FastPath<Topo>, false>(ws, *gm, rp, buf, env, n_steps, dt, frame_end != 0);
-#endif
-}
 
 // ---- external policy mode: the hand-over kernels (include/dtrl.h dtrl_pending_actions* / dtrl_supply_actions*) ----
 // dtrl_ext_collect: ids[0 .. m) = the awaiting envs in ascending env id, m = min(#awaiting, cap). One workgroup; thread t owns the contiguous env range
@@ -283,13 +249,75 @@ __global__ void dtrl_tuple_finish(DevBuffers buf, const int32_t* __restrict__ me
 		if (t == 0) { buf.tuple_count[1] += take; buf.tuple_count[2] += lost; buf.tuple_count[0] = carry; }
 	}
 }
+// ---- dtrl_slot_stats: per-slot sums over the EnvState records, on the device ----
+// dtrl_slot_partials: the workgroups' wavefronts stride over the envs; per pass a wavefront folds, slot by slot, its 64 lanes' contributions with a butterfly of
+// shuffles and lane 0 adds the result to the wavefront's row in LDS; the workgroup then adds its wavefronts' rows in wavefront order and writes ONE row of
+// partials. dtrl_slot_final (one workgroup) adds the rows in workgroup order. No atomics anywhere: every sum has one fixed order, the bytes repeat from call to call.
+constexpr int kReduceThreads = 256, kReduceWaves = kReduceThreads / 64;
+
+__device__ __forceinline__ long long wave_sum(long long v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64); return v; }
+__device__ __forceinline__ double wave_sum(double v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64); return v; }
+
+__global__ void __launch_bounds__(kReduceThreads) dtrl_slot_partials(const EnvState* __restrict__ st, const int32_t* __restrict__ env_slot, int n_envs, int n_slots, SlotSums* __restrict__ rows)
+{
+	__shared__ SlotSums part[kReduceWaves][kMaxSlots];
+	const int t = static_cast<int>(threadIdx.x), wave = t >> 6, lane = t & 63;
+	for (int k = t; k < kReduceWaves * kMaxSlots; k += kReduceThreads) part[k / kMaxSlots][k % kMaxSlots] = SlotSums{0, 0, 0, 0, 0.0};
+	__syncthreads();
+	const int stride = static_cast<int>(gridDim.x) * kReduceThreads;
+	const int passes = (n_envs + stride - 1) / stride;   // the same for every thread: the shuffles below need whole wavefronts
+	for (int p = 0; p < passes; ++p) {
+		const int e = p * stride + static_cast<int>(blockIdx.x) * kReduceThreads + t;
+		int s = -1; long long ep = 0, cy = 0, rs = 0; double ds = 0.0;
+		if (e < n_envs) {
+			s = env_slot[e];
+			ep = st[e].num_episodes; cy = st[e].num_cycles; rs = st[e].num_resets;
+			ds = static_cast<double>(st[e].avg_dist) * static_cast<double>(ep);
+		}
+		for (int q = 0; q < n_slots; ++q) {
+			const bool mine = s == q;
+			if (__ballot(mine) == 0) continue;   // (wave-uniform)
+			const long long c = wave_sum(static_cast<long long>(mine ? 1 : 0)), a = wave_sum(mine ? ep : 0LL), b = wave_sum(mine ? cy : 0LL), r = wave_sum(mine ? rs : 0LL);
+			const double d = wave_sum(mine ? ds : 0.0);
+			if (lane == 0) { SlotSums& o = part[wave][q]; o.n_envs += c; o.episodes += a; o.cycles += b; o.resets += r; o.dist_sum += d; }
+		}
+	}
+	__syncthreads();
+	if (t < n_slots) {
+		SlotSums o = part[0][t];
+		for (int w = 1; w < kReduceWaves; ++w) { const SlotSums& x = part[w][t]; o.n_envs += x.n_envs; o.episodes += x.episodes; o.cycles += x.cycles; o.resets += x.resets; o.dist_sum += x.dist_sum; }
+		rows[static_cast<size_t>(blockIdx.x) * kMaxSlots + t] = o;
+	}
+}
+
+__global__ void __launch_bounds__(64) dtrl_slot_final(const SlotSums* __restrict__ rows, int n_rows, int n_slots, SlotSums* __restrict__ out)
+{
+	const int t = static_cast<int>(threadIdx.x);
+	if (t >= n_slots) return;
+	SlotSums o = rows[t];
+	for (int b = 1; b < n_rows; ++b) { const SlotSums& x = rows[static_cast<size_t>(b) * kMaxSlots + t]; o.n_envs += x.n_envs; o.episodes += x.episodes; o.cycles += x.cycles; o.resets += x.resets; o.dist_sum += x.dist_sum; }
+	out[t] = o;
+}
+
+constexpr int kSlotReduceMaxRows = 64;
+static int SlotReduceRows(int n_envs) { const int g = (n_envs + kReduceThreads - 1) / kReduceThreads; return g < 1 ? 1 : (g > kSlotReduceMaxRows ? kSlotReduceMaxRows : g); }
+
+// scratch: device memory for (SlotReduceRows(n_envs) + 1) * kMaxSlots records; the totals land in its last kMaxSlots records
+static hipError_t LaunchSlotReduce(hipStream_t s, const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* scratch)
+{
+	const int rows = SlotReduceRows(n_envs);
+	hipLaunchKernelGGL(dtrl_slot_partials, dim3(rows), dim3(kReduceThreads), 0, s, st, env_slot, n_envs, n_slots, scratch);
+	hipLaunchKernelGGL(dtrl_slot_final, dim3(1), dim3(64), 0, s, scratch, rows, n_slots, scratch + static_cast<size_t>(rows) * kMaxSlots);
+	return hipGetLastError();
+}
+
 class HipBackend : public Backend {
 public:
 	~HipBackend() override
 	{
 		for (auto& ev : events_) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
 		for (auto& m : marks_) if (m.second) hipEventDestroy(m.second);
-		for (hipEvent_t ev : snap_ev_) if (ev) hipEventDestroy(ev);
+		for (hipEvent_t ev : timed_ev_) if (ev) hipEventDestroy(ev);
 		if (policy_ready_) hipEventDestroy(policy_ready_);
 		if (ext_rej_) hipFree(ext_rej_);
 		if (slot_scratch_) hipFree(slot_scratch_);
@@ -416,47 +444,47 @@ public:
 	bool SnapMove(const SnapPlan& p, char* payload, const int32_t* a, const int32_t* b, int n, int mode)
 	{
 		if (n <= 0) return true;
-		if (!snap_ev_[0] && (!Check(hipEventCreate(&snap_ev_[0]), "hipEventCreate") || !Check(hipEventCreate(&snap_ev_[1]), "hipEventCreate"))) return false;
-		hipEventRecord(snap_ev_[0], stream_);
+		if (!TimedBegin()) return false;
 		hipLaunchKernelGGL(dtrl_snap_move, dim3(n), dim3(kGroup), 0, stream_, p, payload, a, b, n, mode);
-		hipEventRecord(snap_ev_[1], stream_);
-		if (!Check(hipGetLastError(), "snapshot launch") || !Check(hipStreamSynchronize(stream_), "snapshot")) return false;
-		float ms = 0;
-		if (hipEventElapsedTime(&ms, snap_ev_[0], snap_ev_[1]) == hipSuccess) snap_ms_ += ms;
-		return true;
+		return TimedEnd(snap_ms_, "snapshot launch", "snapshot");
 	}
 	double SnapLaunchMs() override { const double v = snap_ms_; snap_ms_ = 0; return v; }
-	// external policy mode: collection (a compaction launch + a row-copy launch) and scatter, timed with the snapshot transport's event pair
-	bool ExtTimed(int which, bool begin)
+	// A timed section of the selected stream: TimedBegin, the caller's launches, TimedEnd -- which waits for the stream and adds the launches' device time to
+	// `sum_ms`. One event pair serves every section: each ends synchronised. (Snapshot transport; external policy mode's collection and scatter.)
+	bool TimedBegin()
 	{
-		if (!snap_ev_[0] && (!Check(hipEventCreate(&snap_ev_[0]), "hipEventCreate") || !Check(hipEventCreate(&snap_ev_[1]), "hipEventCreate"))) return false;
-		if (begin) return Check(hipEventRecord(snap_ev_[0], stream_), "hipEventRecord");
-		hipEventRecord(snap_ev_[1], stream_);
-		if (!Check(hipGetLastError(), "external-policy launch") || !Check(hipStreamSynchronize(stream_), "external-policy hand-over")) return false;
+		if (!timed_ev_[0] && (!Check(hipEventCreate(&timed_ev_[0]), "hipEventCreate") || !Check(hipEventCreate(&timed_ev_[1]), "hipEventCreate"))) return false;
+		return Check(hipEventRecord(timed_ev_[0], stream_), "hipEventRecord");
+	}
+	bool TimedEnd(double& sum_ms, const char* launch_what, const char* sync_what)
+	{
+		hipEventRecord(timed_ev_[1], stream_);
+		if (!Check(hipGetLastError(), launch_what) || !Check(hipStreamSynchronize(stream_), sync_what)) return false;
 		float ms = 0;
-		if (hipEventElapsedTime(&ms, snap_ev_[0], snap_ev_[1]) == hipSuccess) ext_ms_[which] += ms;
+		if (hipEventElapsedTime(&ms, timed_ev_[0], timed_ev_[1]) == hipSuccess) sum_ms += ms;
 		return true;
 	}
+	bool ExtEnd(int which) { return TimedEnd(ext_ms_[which], "external-policy launch", "external-policy hand-over"); }
 	bool ExtCollect(const DevBuffers& buf, int n_envs, int cap, int32_t* ids, void* states, bool f32, int32_t* meta) override
 	{
-		if (!ExtTimed(0, true)) return false;
+		if (!TimedBegin()) return false;
 		hipLaunchKernelGGL(dtrl_ext_collect, dim3(1), dim3(kExtThreads), 0, stream_, buf.st, n_envs, cap, ids, meta);
 		const int rows = std::min(cap, n_envs);
 		if (states && rows > 0) {
 			if (f32) hipLaunchKernelGGL(dtrl_ext_states<float>, dim3(rows), dim3(kGroup), 0, stream_, buf.poli_state, buf.S, ids, meta, n_envs, static_cast<float*>(states));
 			else hipLaunchKernelGGL(dtrl_ext_states<double>, dim3(rows), dim3(kGroup), 0, stream_, buf.poli_state, buf.S, ids, meta, n_envs, static_cast<double*>(states));
 		}
-		return ExtTimed(0, false);
+		return ExtEnd(0);
 	}
 	bool ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labels, const int32_t* ids, int n, const int32_t* action_ids, const void* params, bool f32, const uint32_t* flags, bool apply, int32_t* rejected) override
 	{
 		*rejected = 0;
 		if (n <= 0) return true;
 		if (!ext_rej_ && !Check(hipMalloc(&ext_rej_, sizeof(int32_t)), "hipMalloc")) return false;
-		if (!Check(hipMemsetAsync(ext_rej_, 0, sizeof(int32_t), stream_), "hipMemset") || !ExtTimed(1, true)) return false;
+		if (!Check(hipMemsetAsync(ext_rej_, 0, sizeof(int32_t), stream_), "hipMemset") || !TimedBegin()) return false;
 		if (f32) hipLaunchKernelGGL(dtrl_ext_supply<float>, dim3(n), dim3(kGroup), 0, stream_, buf.st, ext_actions(buf), n_envs, n_opt, n_labels, ids, n, action_ids, static_cast<const float*>(params), flags, apply ? 1 : 0, ext_rej_);
 		else hipLaunchKernelGGL(dtrl_ext_supply<double>, dim3(n), dim3(kGroup), 0, stream_, buf.st, ext_actions(buf), n_envs, n_opt, n_labels, ids, n, action_ids, static_cast<const double*>(params), flags, apply ? 1 : 0, ext_rej_);
-		if (!ExtTimed(1, false)) return false;
+		if (!ExtEnd(1)) return false;
 		return Check(hipMemcpyAsync(rejected, ext_rej_, sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H") && Check(hipStreamSynchronize(stream_), "sync");
 	}
 	double ExtLaunchMs(int which) override { const int k = which ? 1 : 0; const double v = ext_ms_[k]; ext_ms_[k] = 0; return v; }
@@ -464,16 +492,17 @@ public:
 	bool SnapGather(const SnapPlan& p, char* payload, const int32_t* ids, int n) override { return SnapFallback() ? Backend::SnapGather(p, payload, ids, n) : SnapMove(p, payload, ids, nullptr, n, 0); }
 	bool SnapScatter(const SnapPlan& p, const char* payload, const int32_t* ids, int n) override { return SnapFallback() ? Backend::SnapScatter(p, payload, ids, n) : SnapMove(p, const_cast<char*>(payload), ids, nullptr, n, 1); }
 	bool SnapCopy(const SnapPlan& p, const int32_t* src_ids, const int32_t* dst_ids, int n) override { return SnapFallback() ? Backend::SnapCopy(p, src_ids, dst_ids, n) : SnapMove(p, nullptr, src_ids, dst_ids, n, 2); }
-	bool GatherF32(float* dst, const float* src, const int32_t* idx, size_t n) override
+	// the one gather launch; the three entry points differ in the stream and in what follows the launch
+	bool GatherLaunch(hipStream_t st, float* dst, const float* src, const int32_t* idx, size_t n)
 	{
-		hipLaunchKernelGGL(dtrl_gather_f32, dim3(1024), dim3(256), 0, stream_, dst, src, idx, n);
-		return Check(hipGetLastError(), "gather launch") && Check(hipStreamSynchronize(stream_), "sync");
+		hipLaunchKernelGGL(dtrl_gather_f32, dim3(1024), dim3(256), 0, st, dst, src, idx, n);
+		return Check(hipGetLastError(), "gather launch");
 	}
+	bool GatherF32(float* dst, const float* src, const int32_t* idx, size_t n) override { return GatherF32On(nullptr, dst, src, idx, n); }
 	bool GatherF32On(void* stream, float* dst, const float* src, const int32_t* idx, size_t n) override
 	{
 		hipStream_t st = stream ? static_cast<hipStream_t>(stream) : stream_;
-		hipLaunchKernelGGL(dtrl_gather_f32, dim3(1024), dim3(256), 0, st, dst, src, idx, n);
-		return Check(hipGetLastError(), "gather launch") && Check(hipStreamSynchronize(st), "sync");
+		return GatherLaunch(st, dst, src, idx, n) && Check(hipStreamSynchronize(st), "sync");
 	}
 	bool PackTuples(const DevBuffers& buf, float* block, int block_rows, int64_t env_id_base, int n_envs, const PackScratch& sc) override
 	{
@@ -483,47 +512,36 @@ public:
 		hipLaunchKernelGGL(dtrl_tuple_finish, dim3(grid), dim3(256), 0, stream_, buf, sc.meta, block, sc.rows, sc.flags, sc.env);
 		return Check(hipGetLastError(), "tuple pack launch") && Check(hipStreamSynchronize(stream_), "tuple pack");
 	}
-	// frame marks: MarkFrame records an event behind the frame launch of a group; WaitFrames makes the selected stream wait for the marks of a slot
-	bool MarkFrame(int group, int slot) override
+	// Marks: an event per (env group, key) behind the group's latest launch of that kind. Keys 0, 1: the frame that wrote tuple ring `slot` (MarkFrame /
+	// WaitFrames); kWeightReader + wbuf: the latest reader of weight buffer `wbuf` (the double-buffered policy hand-over, Engine::SetPolicyDevice)
+	enum MarkKey { kWeightReader = 8, kMarkKeys = 16 };
+	bool Mark(int group, int key)
 	{
-		hipEvent_t& ev = marks_[Key(group, slot)];
+		hipEvent_t& ev = marks_[group * kMarkKeys + key];
 		if (!ev && !Check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate")) return false;
 		return Check(hipEventRecord(ev, streams_[group]), "hipEventRecord");
 	}
-	bool WaitFrames(int slot, int n_groups) override
+	bool WaitMarks(hipStream_t st, int key, int n_groups)   // `st` waits, on the device, for every group's mark under `key`
 	{
 		for (int g = 0; g < n_groups; ++g) {
-			auto it = marks_.find(Key(g, slot));
-			if (it != marks_.end() && it->second && !Check(hipStreamWaitEvent(stream_, it->second, 0), "hipStreamWaitEvent")) return false;
+			auto it = marks_.find(g * kMarkKeys + key);
+			if (it != marks_.end() && it->second && !Check(hipStreamWaitEvent(st, it->second, 0), "hipStreamWaitEvent")) return false;
 		}
 		return true;
 	}
+	bool MarkFrame(int group, int slot) override { return Mark(group, slot); }
+	bool WaitFrames(int slot, int n_groups) override { return WaitMarks(stream_, slot, n_groups); }
 	bool GatherF32Async(void* stream, float* dst, const float* src, const int32_t* idx, size_t n) override
 	{
 		hipStream_t st = static_cast<hipStream_t>(stream);
-		hipLaunchKernelGGL(dtrl_gather_f32, dim3(1024), dim3(256), 0, st, dst, src, idx, n);
-		if (!Check(hipGetLastError(), "gather launch")) return false;
+		if (!GatherLaunch(st, dst, src, idx, n)) return false;
 		if (!policy_ready_ && !Check(hipEventCreateWithFlags(&policy_ready_, hipEventDisableTiming), "hipEventCreate")) return false;
 		return Check(hipEventRecord(policy_ready_, st), "hipEventRecord");
 	}
 	bool WaitPolicyReady(int group) override { return !policy_ready_ || Check(hipStreamWaitEvent(streams_[group], policy_ready_, 0), "hipStreamWaitEvent"); }
 	bool SyncPolicyReady() override { return !policy_ready_ || Check(hipEventSynchronize(policy_ready_), "hipEventSynchronize"); }
-	// latest reader of weight buffer `wbuf` per env group (the double-buffered policy hand-over, Engine::SetPolicyDevice)
-	bool MarkWeightReader(int group, int wbuf) override
-	{
-		hipEvent_t& ev = marks_[Key(group, 8 + wbuf)];
-		if (!ev && !Check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate")) return false;
-		return Check(hipEventRecord(ev, streams_[group]), "hipEventRecord");
-	}
-	bool WaitWeightReaders(void* stream, int wbuf, int n_groups) override
-	{
-		hipStream_t st = stream ? static_cast<hipStream_t>(stream) : stream_;
-		for (int g = 0; g < n_groups; ++g) {
-			auto it = marks_.find(Key(g, 8 + wbuf));
-			if (it != marks_.end() && it->second && !Check(hipStreamWaitEvent(st, it->second, 0), "hipStreamWaitEvent")) return false;
-		}
-		return true;
-	}
+	bool MarkWeightReader(int group, int wbuf) override { return Mark(group, kWeightReader + wbuf); }
+	bool WaitWeightReaders(void* stream, int wbuf, int n_groups) override { return WaitMarks(stream ? static_cast<hipStream_t>(stream) : stream_, kWeightReader + wbuf, n_groups); }
 	bool TerrainBoundary(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list) override
 	{
 		if (n <= 0) return true;
@@ -535,19 +553,6 @@ public:
 		if (n <= 0) return true;
 		hipLaunchKernelGGL(dtrl_order_by_cost, dim3(1), dim3(kOrderBuckets), 0, stream_, status, e0, n, order);
 		return Check(hipGetLastError(), "order launch");
-	}
-	// dynamic LDS of a fast-path launch: 0 in the shipped library; the workspace itself in a -DDTRL_DYN_LDS experiment build; plus DTRL_LDS_PAD bytes (occupancy experiments)
-	static unsigned FastDynLds()
-	{
-		static const unsigned bytes = []() {
-			unsigned b = 0;
-#if defined(DTRL_DYN_LDS)
-			b = static_cast<unsigned>(sizeof(WSFast));
-#endif
-			if (const char* e = std::getenv("DTRL_LDS_PAD")) b += static_cast<unsigned>(std::atoi(e));
-			return b;
-		}();
-		return bytes;
 	}
 	bool Launch(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end) override { return LaunchFrame(gm, rp, buf, n_envs, n_steps, dt, frame_end, nullptr, nullptr); }
 	// policy slots: ONE launch of the slot kernels (dtrl_backend_hip_slots.hip) over the list as it stands -- the group's costliest-first order is kept across slots.
@@ -567,8 +572,8 @@ public:
 			if (!Check(hipMalloc(&slot_scratch_, sizeof(SlotSums) * recs), "hipMalloc")) return false;
 			slot_scratch_recs_ = recs;
 		}
-		if (!LaunchSlotReduce(stream_, st, env_slot, n_envs, n_slots, slot_scratch_)) return Check(hipGetLastError(), "slot reduction launch") && false;
-		return Check(hipMemcpyAsync(sums, slot_scratch_ + (recs - kMaxSlots), sizeof(SlotSums) * n_slots, hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H") && Check(hipStreamSynchronize(stream_), "slot reduction");
+		return Check(LaunchSlotReduce(stream_, st, env_slot, n_envs, n_slots, slot_scratch_), "slot reduction launch")
+			&& Check(hipMemcpyAsync(sums, slot_scratch_ + (recs - kMaxSlots), sizeof(SlotSums) * n_slots, hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H") && Check(hipStreamSynchronize(stream_), "slot reduction");
 	}
 	bool LaunchFrame(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const SlotRec* slots, const int32_t* env_slot)
 	{
@@ -580,23 +585,15 @@ public:
 			else { ev = free_events_.back(); free_events_.pop_back(); }
 			hipEventRecord(ev.first, stream_);
 		}
-		// DTRL_KERNEL=ref selects the LDS-phase reference kernel (A/B and bitwise cross-check); default is the fast path
-		const char* sel = std::getenv("DTRL_KERNEL");
-		const bool use_ref = sel && std::strcmp(sel, "ref") == 0;
-		if (slots) LaunchSlotFrame(stream_, use_ref, FastDynLds(), gm, rp, buf, n_envs, n_steps, dt, frame_end, slots, env_slot);   // policy slots: dtrl_backend_hip_slots.hip
-		else if (buf.ext_envs != 0) LaunchExtFrame(stream_, use_ref, FastDynLds(), gm, rp, buf, n_envs, n_steps, dt, frame_end);   // external policy mode: dtrl_backend_hip_ext.hip
-		else if (!use_ref && buf.model_topo == TopoDog::kId)
-			hipLaunchKernelGGL(dtrl_frame_kernel_fast<TopoDog>, dim3(n_envs), dim3(kGroup), FastDynLds(), stream_, gm, rp, buf, n_envs, n_steps, dt, frame_end ? 1 : 0);
-		else if (!use_ref && buf.model_topo == TopoRaptor::kId)
-			hipLaunchKernelGGL(dtrl_frame_kernel_fast<TopoRaptor>, dim3(n_envs), dim3(kGroup), FastDynLds(), stream_, gm, rp, buf, n_envs, n_steps, dt, frame_end ? 1 : 0);
-		else
-			hipLaunchKernelGGL(dtrl_frame_kernel, dim3(n_envs), dim3(kGroup), 0, stream_, gm, rp, buf, n_envs, n_steps, dt, frame_end ? 1 : 0);
+		// the three families of frame kernels, a translation unit each (dtrl_frame_entry.h): policy slots, external policy mode, the shipped single-policy kernels
+		const FrameLauncher launch = slots ? LaunchSlotFrame : buf.ext_envs != 0 ? LaunchExtFrame : LaunchPlainFrame;
+		const hipError_t launched = launch(stream_, gm, rp, buf, n_envs, n_steps, dt, frame_end, slots, env_slot);
 		if (timed) {
 			hipEventRecord(ev.second, stream_); pending_.push_back(ev);
 			// a long run never asks for the timing: fold finished pairs into the running sum so the event pool stays bounded
 			if (pending_.size() > kMaxPendingEvents) FoldFinished(false);
 		}
-		return Check(hipGetLastError(), "kernel launch");
+		return Check(launched, "kernel launch");
 	}
 	bool Sync() override { bool ok = true; for (hipStream_t st : streams_) ok = Check(hipStreamSynchronize(st), "hipStreamSynchronize") && ok; return ok; }
 	int NumStreams() const override { return kNumStreams; }
@@ -638,12 +635,12 @@ private:
 	std::vector<hipStream_t> streams_;
 	hipStream_t stream_ = nullptr;   // the selected one
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> events_, free_events_, pending_;
-	static int Key(int group, int slot) { return group * 16 + slot; }
 	int32_t* ext_rej_ = nullptr; double ext_ms_[2] = {0, 0};   // external policy mode: rejected-row counter (device), device time of the collection / scatter launches
-	hipEvent_t snap_ev_[2] = {nullptr, nullptr}; double snap_ms_ = 0;   // the snapshot launches since the last SnapLaunchMs(), timed with events
+	hipEvent_t timed_ev_[2] = {nullptr, nullptr};   // TimedBegin / TimedEnd
+	double snap_ms_ = 0;   // device time of the snapshot launches since the last SnapLaunchMs()
 	SlotSums* slot_scratch_ = nullptr; size_t slot_scratch_recs_ = 0;   // dtrl_slot_stats: partial rows + totals (device)
 	hipEvent_t policy_ready_ = nullptr;   // behind the latest asynchronous policy gather (GatherF32Async)
-	std::map<int, hipEvent_t> marks_;   // (env group, tuple ring) -> event behind the group's latest frame launch that wrote that ring
+	std::map<int, hipEvent_t> marks_;   // group * kMarkKeys + key -> event (Mark / WaitMarks)
 };
 
 Backend* MakeBackend() { return new HipBackend(); }

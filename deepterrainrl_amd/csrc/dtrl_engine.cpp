@@ -572,11 +572,24 @@ int Engine::Step(double dt)
 	return rc != DTRL_OK ? rc : StepEnd();
 }
 
+// The one idle guard: refuse with `refusal` while a frame is in flight -- refuse, do not wait: that frame ends with the caller's own dtrl_step_end, and after
+// dtrl_step_poll the env groups are a frame apart -- and, with `drain`, wait for every stream (with dtrl_step_poll or -terrain_gen= device the host has not
+// otherwise waited for the launches it queued). Leaves stream 0 selected.
+int Engine::RequireIdle(const std::string& refusal, bool drain)
+{
+	if (step_pending_ || early_any_) return Fail(DTRL_ERR_ARG, refusal);
+	if (!drain) return DTRL_OK;
+	be_->SelectStream(0);
+	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+static const char* const kFrameInFlight = " between dtrl_step_begin and dtrl_step_end (or after dtrl_step_poll relaunched a group): a frame is in flight; call dtrl_step_end first";
+
 int Engine::StepUpdates(int n)
 {
 	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_step_updates: not available with -policy_mode= external (every env keeps its own frame of num_update_steps env-steps: use dtrl_step)");
 	if (n <= 0) return DTRL_OK;
-	if (early_any_ || step_pending_) return Fail(DTRL_ERR_ARG, "dtrl_step_updates while a frame is in flight (dtrl_step_begin / dtrl_step_poll): call dtrl_step_end_begin / dtrl_step_end first");
+	if (int rc = RequireIdle("dtrl_step_updates while a frame is in flight (dtrl_step_begin / dtrl_step_poll): call dtrl_step_end_begin / dtrl_step_end first", false); rc != DTRL_OK) return rc;
 	if (cfg_.model.has_net && !policy_set_) return Fail(DTRL_ERR_ARG, "policy_net was given but dtrl_set_policy has not been called");
 	const double dt = (1.0 / 30.0) / cfg_.model.num_update_steps;
 	ApplyPendingPolicy();
@@ -592,7 +605,7 @@ int Engine::RunFrames(int frames, double dt)
 {
 	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_run_frames: not available with -policy_mode= external (envs wait for the caller's actions between ticks: use dtrl_step)");
 	if (frames <= 0 || dt <= 0) return DTRL_OK;
-	if (early_any_ || step_pending_) return Fail(DTRL_ERR_ARG, "dtrl_run_frames while a frame is in flight (dtrl_step_begin / dtrl_step_poll): call dtrl_step_end_begin / dtrl_step_end first");
+	if (int rc = RequireIdle("dtrl_run_frames while a frame is in flight (dtrl_step_begin / dtrl_step_poll): call dtrl_step_end_begin / dtrl_step_end first", false); rc != DTRL_OK) return rc;
 	if (cfg_.model.has_net && !policy_set_) return Fail(DTRL_ERR_ARG, "policy_net was given but dtrl_set_policy has not been called");
 	const int G = static_cast<int>(groups_.size());
 	const int steps = cfg_.model.num_update_steps;
@@ -1359,10 +1372,7 @@ size_t SnapBlobBytes(const SnapHeader& h) { return sizeof(SnapHeader) + pad8(4u 
 
 int Engine::SnapReady(const char* what)
 {
-	// refuse, do not wait: the frame in flight ends with the caller's own dtrl_step_end, and after dtrl_step_poll the env groups are a frame apart
-	if (step_pending_ || early_any_) return Fail(DTRL_ERR_ARG, std::string(what) + " between dtrl_step_begin and dtrl_step_end (or after dtrl_step_poll relaunched a group): a frame is in flight; call dtrl_step_end first");
-	be_->SelectStream(0);
-	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (int rc = RequireIdle(std::string(what) + kFrameInFlight); rc != DTRL_OK) return rc;
 	if (!snap_ids_) {
 		snap_ids_ = static_cast<int32_t*>(be_->HostStaging(sizeof(int32_t) * 2 * static_cast<size_t>(n_)));
 		if (!snap_ids_) return Fail(DTRL_ERR_DEVICE, "host staging allocation failed: " + be_->error());
@@ -1635,11 +1645,7 @@ int Engine::SnapshotImport(const void* blob, size_t bytes, Snapshot** out)
 int Engine::ExtRefuse(const char* what)
 {
 	if (!cfg_.external_policy) return Fail(DTRL_ERR_ARG, std::string(what) + ": the batch runs in internal policy mode (create it with -policy_mode= external)");
-	// refuse, do not wait: the tick in flight ends with the caller's own dtrl_step_end
-	if (step_pending_ || early_any_) return Fail(DTRL_ERR_ARG, std::string(what) + " between dtrl_step_begin and dtrl_step_end: a tick is in flight; call dtrl_step_end first");
-	be_->SelectStream(0);
-	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
+	return RequireIdle(std::string(what) + " between dtrl_step_begin and dtrl_step_end: a tick is in flight; call dtrl_step_end first");
 }
 
 int Engine::PendingActions(int32_t* env_ids, void* states, int cap, int* out_n, bool device)
@@ -1744,10 +1750,7 @@ int Engine::SlotsIdle(const char* what, int slot)
 {
 	if (slots_.empty()) return Fail(DTRL_ERR_ARG, std::string(what) + ": the batch has no policy slots (call dtrl_slots_create first)");
 	if (slot < 0 || slot >= static_cast<int>(slots_.size())) return Fail(DTRL_ERR_ARG, std::string(what) + ": slot " + std::to_string(slot) + " out of range (0 .. " + std::to_string(slots_.size() - 1) + ")");
-	if (step_pending_ || early_any_) return Fail(DTRL_ERR_ARG, std::string(what) + " between dtrl_step_begin and dtrl_step_end (or after dtrl_step_poll relaunched a group): a frame is in flight; call dtrl_step_end first");
-	be_->SelectStream(0);
-	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
+	return RequireIdle(std::string(what) + kFrameInFlight);
 }
 
 int Engine::UploadSlotTable()
@@ -1774,9 +1777,7 @@ int Engine::SlotsCreate(int n_slots)
 		if (n_slots == static_cast<int>(slots_.size())) return DTRL_OK;
 		return Fail(DTRL_ERR_ARG, "dtrl_slots_create: the batch already has " + std::to_string(slots_.size()) + " slots; a second call with another count (" + std::to_string(n_slots) + ") is refused");
 	}
-	if (step_pending_ || early_any_) return Fail(DTRL_ERR_ARG, "dtrl_slots_create between dtrl_step_begin and dtrl_step_end (or after dtrl_step_poll relaunched a group): a frame is in flight; call dtrl_step_end first");
-	be_->SelectStream(0);
-	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (int rc = RequireIdle(std::string("dtrl_slots_create") + kFrameInFlight); rc != DTRL_OK) return rc;
 	d_slot_table_ = static_cast<SlotRec*>(be_->Alloc(sizeof(SlotRec) * n_slots)); if (d_slot_table_) allocs_.push_back(d_slot_table_);
 	d_env_slot_ = static_cast<int32_t*>(be_->Alloc(sizeof(int32_t) * n_)); if (d_env_slot_) allocs_.push_back(d_env_slot_);   // (zero-filled: every env starts in slot 0)
 	slot_part_ = static_cast<int32_t*>(be_->HostStaging(sizeof(int32_t) * 2 * static_cast<size_t>(n_)));
@@ -1904,3 +1905,5 @@ int Engine::SlotStats(int slot, int64_t* n_envs, double* avg_dist, int64_t* epis
 }
 
 }  // namespace dtrl
+
+#include "dtrl_backend_defaults.cpp"   // Backend's default implementations: part of this unit (see there)
