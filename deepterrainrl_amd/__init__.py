@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "dtrl_drain_tuples_device", "dtrl_tuple_stats", "dtrl_set_policy_device", "dtrl_get_dist_log", "dtrl_reset_avg_dist", "dtrl_write_dist_log", "dtrl_get_ground_window", "dtrl_drain_tuples_packed", "dtrl_get_policy_output", "dtrl_set_tuple_pipelining", "dtrl_step_end_begin", "dtrl_command_action", "dtrl_side_stream", "dtrl_step_poll", "dtrl_set_policy_device_on", "dtrl_set_policy_device_async",
     "dtrl_snapshot_save", "dtrl_snapshot_restore", "dtrl_clone_envs", "dtrl_snapshot_export", "dtrl_snapshot_import", "dtrl_snapshot_info", "dtrl_snapshot_free",
     "dtrl_slots_create", "dtrl_slot_set_policy", "dtrl_slot_set_policy_device", "dtrl_slot_alias", "dtrl_slot_set_explore", "dtrl_assign_slots", "dtrl_get_slots", "dtrl_slot_stats",
+    "dtrl_variants_create", "dtrl_variant_load_file", "dtrl_variant_load_json", "dtrl_assign_variants", "dtrl_get_variants", "dtrl_variant_stats",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
 
@@ -152,6 +153,12 @@ def _bind(path):
     L.dtrl_assign_slots.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_get_slots.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_slot_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.dtrl_variants_create.argtypes = [vp, C.c_int]
+    L.dtrl_variant_load_file.argtypes = [vp, C.c_int, C.c_char_p]
+    L.dtrl_variant_load_json.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t]
+    L.dtrl_assign_variants.argtypes = [vp, vp, C.c_int, vp]
+    L.dtrl_get_variants.argtypes = [vp, vp, C.c_int, vp]
+    L.dtrl_variant_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dtrl_last_error.restype = C.c_char_p
     L.dtrl_last_error.argtypes = [vp]
     L.dtrl_version.restype = C.c_char_p
@@ -280,6 +287,7 @@ class BatchScenario:
             argv += ["-data_root=", str(data_root)]
         if arg_file is not None:
             argv += ["-arg_file=", str(arg_file)]
+        self._argv = list(argv)
         arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
         h = C.c_void_p()
         rc = self._lib.dtrl_create(arr, len(argv), int(num_envs), int(device_id), C.byref(h))
@@ -707,6 +715,89 @@ class BatchScenario:
         """EvalStats restricted to the envs currently in `slot` (plus their number), reduced on the device in a fixed order."""
         a = C.c_double(); n, e, c, r = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self._lib.dtrl_slot_stats(self._h, int(slot), C.byref(n), C.byref(a), C.byref(e), C.byref(c), C.byref(r)))
+        return {"n_envs": n.value, "avg_dist": a.value, "episodes": e.value, "cycles": c.value, "resets": r.value}
+
+    # ---- model variants: several character models in one batch, one per env (no counterpart in the reference, which keeps one character per scene object) ----
+    num_variants = 0
+
+    def CreateVariants(self, n_variants):
+        """dtrl_variants_create: a table of 1 .. num_envs complete character models, once per batch. Variant 0 is the batch's own model and every env starts in it;
+        variants >= 1 are empty until LoadVariant / LoadVariantJson / ScaledVariant fills them. Not together with policy slots or external policy mode."""
+        self._chk(self._lib.dtrl_variants_create(self._h, int(n_variants)))
+        self.num_variants = int(n_variants)
+
+    def LoadVariant(self, v, path):
+        """dtrl_variant_load_file: variant v >= 1 from a character file (resolved like -character_file=), through the loader the batch was created with. Masses, box
+        sizes, attach points, joint limits and PD settings may differ from the batch's model; skeleton, scene and controller part may not. Between frames only."""
+        self._chk(self._lib.dtrl_variant_load_file(self._h, int(v), os.fsencode(str(path))))
+
+    def LoadVariantJson(self, v, text):
+        """dtrl_variant_load_json: the same from the character description itself (str or bytes)."""
+        raw = text.encode() if isinstance(text, str) else bytes(text)
+        self._chk(self._lib.dtrl_variant_load_json(self._h, int(v), raw, len(raw)))
+
+    def CharacterFile(self):
+        """The batch's character file as the library resolves it: -character_file= of the creation arguments, relative to -data_root= unless absolute."""
+        vals = []
+        for key in ("character_file", "data_root"):
+            arr = (C.c_char_p * len(self._argv))(*[a.encode() for a in self._argv])
+            buf = C.create_string_buffer(4096); found = C.c_int(); nt = C.c_int()
+            rc = self._lib.dtrl_args_parse_string(arr, len(self._argv), key.encode(), buf, 4096, C.byref(found), C.byref(nt))
+            if rc != DTRL_OK:
+                raise DtrlError("dtrl_args_parse_string failed (%d): %s" % (rc, self._lib.dtrl_last_error(None).decode()))
+            vals.append(buf.value.decode() if found.value else "")
+        path, root = vals
+        return path if (not path or path.startswith("/") or not root) else os.path.join(root, path)
+
+    def ScaledVariant(self, v, mass=None, size=None, kp=1.0, kd=1.0, torque_lim=1.0):
+        """Variant v = the batch's character with scaled bodies and motors, loaded through LoadVariantJson (no file is written). `mass` / `size`: one factor for
+        every body, or {body name: factor} (BodyDefs[].Name; size scales the box's Param0 and Param1); kp / kd / torque_lim: one factor for every PD controller,
+        or {joint name: factor} (PDControllers[].Name). Returns the JSON text that was loaded."""
+        import json
+        with open(self.CharacterFile()) as f:
+            doc = json.load(f)
+
+        def factor(spec, name):
+            if spec is None:
+                return 1.0
+            if isinstance(spec, dict):
+                return float(spec.get(name, 1.0))
+            return float(spec)
+        for spec, what in ((mass, "mass"), (size, "size")):
+            if isinstance(spec, dict):
+                unknown = set(spec) - {b.get("Name") for b in doc["BodyDefs"]}
+                if unknown:
+                    raise DtrlError("ScaledVariant: %s names no body of the character: %s" % (what, ", ".join(sorted(map(str, unknown)))))
+        for b in doc["BodyDefs"]:
+            b["Mass"] = b["Mass"] * factor(mass, b.get("Name"))
+            for key in ("Param0", "Param1"):
+                b[key] = b[key] * factor(size, b.get("Name"))
+        for pd in doc["PDControllers"]:
+            for key, spec in (("Kp", kp), ("Kd", kd), ("TorqueLim", torque_lim)):
+                pd[key] = pd[key] * factor(spec, pd.get("Name"))
+        text = json.dumps(doc)
+        self.LoadVariantJson(v, text)
+        return text
+
+    def AssignVariants(self, env_ids, variants):
+        """env_ids[i] -> variants[i] (env_ids None: the first len(variants) envs); takes effect with the env's next launch and leaves the env's state alone -- call
+        Reset on those envs if their episodes are to START under the new model. Between frames only."""
+        va = np.ascontiguousarray(variants, np.int32)
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32)
+        if ids is not None and ids.shape != va.shape:
+            raise DtrlError("AssignVariants: env_ids and variants must have the same length")
+        self._chk(self._lib.dtrl_assign_variants(self._h, _p(ids), len(va), _p(va)))
+
+    def GetVariants(self, env_ids=None):
+        ids, n = self._ids(env_ids)
+        out = np.zeros(n, np.int32)
+        self._chk(self._lib.dtrl_get_variants(self._h, _p(ids), n, _p(out)))
+        return out
+
+    def VariantStats(self, v):
+        """EvalStats restricted to the envs currently in variant v (plus their number), reduced on the device in a fixed order."""
+        a = C.c_double(); n, e, c, r = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._lib.dtrl_variant_stats(self._h, int(v), C.byref(n), C.byref(a), C.byref(e), C.byref(c), C.byref(r)))
         return {"n_envs": n.value, "avg_dist": a.value, "episodes": e.value, "cycles": c.value, "resets": r.value}
 
     # ---- full env snapshots (no counterpart in the reference: it keeps one scene per object) ----

@@ -1,6 +1,6 @@
-// dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, slotted launches
-// and the per-slot sums, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
-// of them with kernels and keeps these as its cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1).
+// dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, slotted and
+// per-variant launches and the per-slot sums, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
+// of them with kernels and keeps these as its cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1).
 // Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
 // lane-loop check build of any tests/ tree, the sanitizer scripts -- has the defaults, and no source list can lack them.
 #include "dtrl_engine.h"
@@ -86,19 +86,28 @@ bool Backend::ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labe
 	}
 	return true;
 }
+// The launch list of `buf` (n_envs entries; no list: envs 0 .. n_envs - 1) regrouped by key_of_env[] into `part`, list order kept inside a key; n_of[k] = entries
+// of key k, in key order. list_host: the list in host-readable form, nullptr = read it back. Waits for the selected stream before it writes `part`.
+bool Backend::SplitLaunchList(const DevBuffers& buf, int n_envs, const int32_t* list_host, const int32_t* key_of_env, int n_keys, int32_t* part, std::vector<int32_t>& n_of)
+{
+	std::vector<int32_t> list(static_cast<size_t>(n_envs));
+	if (!buf.env_list) { for (int i = 0; i < n_envs; ++i) list[i] = i; }
+	else if (list_host) { for (int i = 0; i < n_envs; ++i) list[i] = list_host[i]; }
+	else if (!D2H(list.data(), buf.env_list, sizeof(int32_t) * list.size())) return false;   // (an order computed on the device: behind everything queued, this launch's list included)
+	if (!SyncSelected()) return false;   // an earlier launch of this stream may still be reading `part`
+	n_of.assign(static_cast<size_t>(n_keys), 0);
+	std::vector<int32_t> at(static_cast<size_t>(n_keys));
+	for (int32_t e : list) ++n_of[key_of_env[e]];
+	for (int s = 0, k = 0; s < n_keys; ++s) { at[s] = k; k += n_of[s]; }
+	for (int32_t e : list) part[at[key_of_env[e]]++] = e;
+	return true;
+}
 bool Backend::LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end)
 {
 	(void)env_slot;
 	if (n_envs <= 0) return true;
-	std::vector<int32_t> list(static_cast<size_t>(n_envs));
-	if (!buf.env_list) { for (int i = 0; i < n_envs; ++i) list[i] = i; }
-	else if (slots.env_list_host) { for (int i = 0; i < n_envs; ++i) list[i] = slots.env_list_host[i]; }
-	else if (!D2H(list.data(), buf.env_list, sizeof(int32_t) * list.size())) return false;   // (an order computed on the device: behind everything queued, this launch's list included)
-	if (!SyncSelected()) return false;   // an earlier launch of this stream may still be reading slots.part
-	int n_of[kMaxSlots] = {0}, at[kMaxSlots];
-	for (int32_t e : list) ++n_of[slots.env_slot_host[e]];
-	for (int s = 0, k = 0; s < slots.n_slots; ++s) { at[s] = k; k += n_of[s]; }
-	for (int32_t e : list) slots.part[at[slots.env_slot_host[e]]++] = e;
+	std::vector<int32_t> n_of;
+	if (!SplitLaunchList(buf, n_envs, slots.env_list_host, slots.env_slot_host, slots.n_slots, slots.part, n_of)) return false;
 	for (int s = 0, k = 0; s < slots.n_slots; k += n_of[s], ++s) {
 		if (n_of[s] == 0) continue;
 		RunParams r = rp; DevBuffers b = buf;
@@ -108,13 +117,29 @@ bool Backend::LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuff
 	}
 	return true;
 }
-bool Backend::SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums)
+bool Backend::LaunchVariants(const RunParams& rp, const DevBuffers& buf, const VariantView& models, const int32_t* env_variant, int n_envs, int n_steps, real dt, bool frame_end)
+{
+	(void)env_variant;
+	if (n_envs <= 0) return true;
+	std::vector<int32_t> n_of;
+	if (!SplitLaunchList(buf, n_envs, models.env_list_host, models.env_variant_host, models.n_variants, models.part, n_of)) return false;
+	for (int v = 0, k = 0; v < models.n_variants; k += n_of[v], ++v) {
+		if (n_of[v] == 0) continue;
+		DevBuffers b = buf;
+		b.env_list = models.part + k;
+		if (!Launch(models.dev + v, rp, b, n_of[v], n_steps, dt, frame_end)) return false;
+	}
+	return true;
+}
+bool Backend::SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums, int slot_base)
 {
 	std::vector<EnvState> host(static_cast<size_t>(n_envs)); std::vector<int32_t> slot(static_cast<size_t>(n_envs));
 	if (!D2H(host.data(), st, sizeof(EnvState) * host.size()) || !D2H(slot.data(), env_slot, sizeof(int32_t) * slot.size())) return false;
 	for (int s = 0; s < n_slots; ++s) sums[s] = SlotSums{0, 0, 0, 0, 0.0};
 	for (int e = 0; e < n_envs; ++e) {
-		SlotSums& a = sums[slot[e]];
+		const int s = slot[e] - slot_base;
+		if (s < 0 || s >= n_slots) continue;
+		SlotSums& a = sums[s];
 		++a.n_envs; a.episodes += host[e].num_episodes; a.cycles += host[e].num_cycles; a.resets += host[e].num_resets;
 		a.dist_sum += static_cast<double>(host[e].avg_dist) * static_cast<double>(host[e].num_episodes);
 	}

@@ -1,5 +1,5 @@
 // dtrl_backend_hip.hip -- the product backend: the HIP runtime behind the Backend interface (streams, events, copies) and every auxiliary kernel. The frame
-// kernels are launched from here and compiled elsewhere, one translation unit per family (dtrl_frame_entry.h: dtrl_backend_hip_frame.hip, _ext.hip, _slots.hip),
+// kernels are launched from here and compiled elsewhere, one translation unit per family (dtrl_frame_entry.h: dtrl_backend_hip_frame.hip, _ext.hip, _slots.hip, _variants.hip),
 // so that what changes here cannot change their instructions.
 #include "dtrl_engine.h"
 #include "dtrl_frame_entry.h"
@@ -258,7 +258,7 @@ constexpr int kReduceThreads = 256, kReduceWaves = kReduceThreads / 64;
 __device__ __forceinline__ long long wave_sum(long long v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64); return v; }
 __device__ __forceinline__ double wave_sum(double v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64); return v; }
 
-__global__ void __launch_bounds__(kReduceThreads) dtrl_slot_partials(const EnvState* __restrict__ st, const int32_t* __restrict__ env_slot, int n_envs, int n_slots, SlotSums* __restrict__ rows)
+__global__ void __launch_bounds__(kReduceThreads) dtrl_slot_partials(const EnvState* __restrict__ st, const int32_t* __restrict__ env_slot, int n_envs, int n_slots, int slot_base, SlotSums* __restrict__ rows)
 {
 	__shared__ SlotSums part[kReduceWaves][kMaxSlots];
 	const int t = static_cast<int>(threadIdx.x), wave = t >> 6, lane = t & 63;
@@ -270,7 +270,7 @@ __global__ void __launch_bounds__(kReduceThreads) dtrl_slot_partials(const EnvSt
 		const int e = p * stride + static_cast<int>(blockIdx.x) * kReduceThreads + t;
 		int s = -1; long long ep = 0, cy = 0, rs = 0; double ds = 0.0;
 		if (e < n_envs) {
-			s = env_slot[e];
+			s = env_slot[e] - slot_base;   // (outside 0 .. n_slots - 1: counted nowhere)
 			ep = st[e].num_episodes; cy = st[e].num_cycles; rs = st[e].num_resets;
 			ds = static_cast<double>(st[e].avg_dist) * static_cast<double>(ep);
 		}
@@ -303,10 +303,10 @@ constexpr int kSlotReduceMaxRows = 64;
 static int SlotReduceRows(int n_envs) { const int g = (n_envs + kReduceThreads - 1) / kReduceThreads; return g < 1 ? 1 : (g > kSlotReduceMaxRows ? kSlotReduceMaxRows : g); }
 
 // scratch: device memory for (SlotReduceRows(n_envs) + 1) * kMaxSlots records; the totals land in its last kMaxSlots records
-static hipError_t LaunchSlotReduce(hipStream_t s, const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* scratch)
+static hipError_t LaunchSlotReduce(hipStream_t s, const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, int slot_base, SlotSums* scratch)
 {
 	const int rows = SlotReduceRows(n_envs);
-	hipLaunchKernelGGL(dtrl_slot_partials, dim3(rows), dim3(kReduceThreads), 0, s, st, env_slot, n_envs, n_slots, scratch);
+	hipLaunchKernelGGL(dtrl_slot_partials, dim3(rows), dim3(kReduceThreads), 0, s, st, env_slot, n_envs, n_slots, slot_base, scratch);
 	hipLaunchKernelGGL(dtrl_slot_final, dim3(1), dim3(64), 0, s, scratch, rows, n_slots, scratch + static_cast<size_t>(rows) * kMaxSlots);
 	return hipGetLastError();
 }
@@ -554,16 +554,26 @@ public:
 		hipLaunchKernelGGL(dtrl_order_by_cost, dim3(1), dim3(kOrderBuckets), 0, stream_, status, e0, n, order);
 		return Check(hipGetLastError(), "order launch");
 	}
-	bool Launch(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end) override { return LaunchFrame(gm, rp, buf, n_envs, n_steps, dt, frame_end, nullptr, nullptr); }
+	bool Launch(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end) override { return LaunchFrame(gm, rp, buf, n_envs, n_steps, dt, frame_end, FrameExtra{}); }
 	// policy slots: ONE launch of the slot kernels (dtrl_backend_hip_slots.hip) over the list as it stands -- the group's costliest-first order is kept across slots.
 	// DTRL_SLOTS_FALLBACK=1 takes the per-slot default instead (A/B and cross-check)
 	bool LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end) override
 	{
 		const char* fb = std::getenv("DTRL_SLOTS_FALLBACK");   // (read per launch, like DTRL_KERNEL: a test switches it inside one process)
 		if (fb && std::atoi(fb) != 0) return Backend::LaunchSlots(gm, rp, buf, slots, env_slot, n_envs, n_steps, dt, frame_end);
-		return LaunchFrame(gm, rp, buf, n_envs, n_steps, dt, frame_end, slots.dev, env_slot);
+		FrameExtra x; x.slots = slots.dev; x.env_slot = env_slot;
+		return LaunchFrame(gm, rp, buf, n_envs, n_steps, dt, frame_end, x);
 	}
-	bool SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums) override
+	// model variants: ONE launch of the variant kernels (dtrl_backend_hip_variants.hip) over the list as it stands -- the group's costliest-first order is kept
+	// across variants. DTRL_VARIANTS_FALLBACK=1 takes the per-variant default instead (A/B and cross-check)
+	bool LaunchVariants(const RunParams& rp, const DevBuffers& buf, const VariantView& models, const int32_t* env_variant, int n_envs, int n_steps, real dt, bool frame_end) override
+	{
+		const char* fb = std::getenv("DTRL_VARIANTS_FALLBACK");   // (read per launch, like DTRL_KERNEL: a test switches it inside one process)
+		if (fb && std::atoi(fb) != 0) return Backend::LaunchVariants(rp, buf, models, env_variant, n_envs, n_steps, dt, frame_end);
+		FrameExtra x; x.models = models.dev; x.env_model = env_variant;
+		return LaunchFrame(models.dev, rp, buf, n_envs, n_steps, dt, frame_end, x);
+	}
+	bool SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums, int slot_base) override
 	{
 		const size_t recs = static_cast<size_t>(SlotReduceRows(n_envs) + 1) * kMaxSlots;
 		if (slot_scratch_recs_ < recs) {
@@ -572,10 +582,10 @@ public:
 			if (!Check(hipMalloc(&slot_scratch_, sizeof(SlotSums) * recs), "hipMalloc")) return false;
 			slot_scratch_recs_ = recs;
 		}
-		return Check(LaunchSlotReduce(stream_, st, env_slot, n_envs, n_slots, slot_scratch_), "slot reduction launch")
+		return Check(LaunchSlotReduce(stream_, st, env_slot, n_envs, n_slots, slot_base, slot_scratch_), "slot reduction launch")
 			&& Check(hipMemcpyAsync(sums, slot_scratch_ + (recs - kMaxSlots), sizeof(SlotSums) * n_slots, hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H") && Check(hipStreamSynchronize(stream_), "slot reduction");
 	}
-	bool LaunchFrame(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const SlotRec* slots, const int32_t* env_slot)
+	bool LaunchFrame(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const FrameExtra& extra)
 	{
 		// only stepping launches are timed (the compact 0-step reset launches would skew the per-frame average)
 		const bool timed = n_steps > 0;
@@ -585,9 +595,9 @@ public:
 			else { ev = free_events_.back(); free_events_.pop_back(); }
 			hipEventRecord(ev.first, stream_);
 		}
-		// the three families of frame kernels, a translation unit each (dtrl_frame_entry.h): policy slots, external policy mode, the shipped single-policy kernels
-		const FrameLauncher launch = slots ? LaunchSlotFrame : buf.ext_envs != 0 ? LaunchExtFrame : LaunchPlainFrame;
-		const hipError_t launched = launch(stream_, gm, rp, buf, n_envs, n_steps, dt, frame_end, slots, env_slot);
+		// the four families of frame kernels, a translation unit each (dtrl_frame_entry.h): model variants, policy slots, external policy mode, the shipped kernels
+		const FrameLauncher launch = extra.models ? LaunchVariantFrame : extra.slots ? LaunchSlotFrame : buf.ext_envs != 0 ? LaunchExtFrame : LaunchPlainFrame;
+		const hipError_t launched = launch(stream_, gm, rp, buf, n_envs, n_steps, dt, frame_end, extra);
 		if (timed) {
 			hipEventRecord(ev.second, stream_); pending_.push_back(ev);
 			// a long run never asks for the timing: fold finished pairs into the running sum so the event pool stays bounded

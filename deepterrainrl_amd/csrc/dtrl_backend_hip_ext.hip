@@ -8,7 +8,7 @@ namespace dtrl {
 
 DTRL_FRAME_KERNELS(dtrl_ext_frame_kernel, true, )
 
-hipError_t LaunchExtFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const SlotRec*, const int32_t*)
+hipError_t LaunchExtFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const FrameExtra&)
 {
 	return LaunchFrameKernel<>(dtrl_ext_frame_kernel, dtrl_ext_frame_kernel_fast<TopoDog>, dtrl_ext_frame_kernel_fast<TopoRaptor>, sizeof(WSFast), stream, gm, rp, buf, n_envs, n_steps, dt, frame_end);
 }

@@ -20,10 +20,10 @@ __device__ __forceinline__ void slot_select(const SlotRec* __restrict__ slots, c
 
 DTRL_FRAME_KERNELS(dtrl_slot_frame_kernel, false, slot_select(slots, env_slot, env, rp, buf), const SlotRec* __restrict__ slots, const int32_t* __restrict__ env_slot)
 
-hipError_t LaunchSlotFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const SlotRec* slots, const int32_t* env_slot)
+hipError_t LaunchSlotFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const FrameExtra& extra)
 {
 	return LaunchFrameKernel(dtrl_slot_frame_kernel, dtrl_slot_frame_kernel_fast<TopoDog>, dtrl_slot_frame_kernel_fast<TopoRaptor>, sizeof(WSFast), stream, gm, rp, buf, n_envs, n_steps, dt, frame_end,
-		slots, env_slot);
+		extra.slots, extra.env_slot);
 }
 
 }  // namespace dtrl

@@ -141,10 +141,10 @@ try {
 	CHECK_B();
 	std::vector<EnvState> st; int rc = b->eng.GetStates(env_ids, n, st);
 	if (rc != DTRL_OK) return static_cast<dtrl_status>(rc);
-	const dtrl::DevModel& m = b->eng.cfg().model;
-	const int L = m.L;
+	const int L = b->eng.cfg().model.L;
 	for (int e = 0; e < n; ++e) {
 		const EnvState& s = st[e];
+		const dtrl::DevModel& m = b->eng.ModelOf(env_ids ? env_ids[e] : e);   // attach points and body angles are the env's variant's (GetStates has checked the ids)
 		double phi[dtrl::kMaxL], w[dtrl::kMaxL], px[dtrl::kMaxL], py[dtrl::kMaxL], vx[dtrl::kMaxL], vy[dtrl::kMaxL];
 		for (int j = 0; j < L; ++j) {   // parents precede children (cKinTree joint order)
 			const int pa = m.parent[j];
@@ -271,6 +271,18 @@ dtrl_status dtrl_slot_set_explore(dtrl_batch* b, int slot, int enable, double ra
 dtrl_status dtrl_assign_slots(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* slots) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.AssignSlots(env_ids, n, slots)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_get_slots(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* slots_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.GetSlots(env_ids, n, slots_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_slot_stats(dtrl_batch* b, int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.SlotStats(slot, n_envs, avg_dist, episodes, cycles, resets)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+// model variants
+dtrl_status dtrl_variants_create(dtrl_batch* b, int n_variants) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantsCreate(n_variants)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_variant_load_file(dtrl_batch* b, int v, const char* character_file) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantLoad(v, character_file, nullptr, 0)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_variant_load_json(dtrl_batch* b, int v, const char* text, size_t bytes)
+try {
+	CHECK_B();
+	if (!text) { b->eng.set_error("dtrl_variant_load_json: text is required"); return DTRL_ERR_ARG; }
+	return static_cast<dtrl_status>(b->eng.VariantLoad(v, nullptr, text, bytes));
+} catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_assign_variants(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* variants) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.AssignVariants(env_ids, n, variants)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_get_variants(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* variants_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.GetVariants(env_ids, n, variants_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_variant_stats(dtrl_batch* b, int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantStats(v, n_envs, avg_dist, episodes, cycles, resets)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_action_dims(const dtrl_batch* b, int* n_opt, int* n_labels, int* num_update_steps, int* external)
 try {
 	CHECK_B();

@@ -120,6 +120,7 @@ Engine::~Engine()
 		for (Snapshot* s : snapshots_) { be_->Free(s->payload); s->payload = nullptr; s->owner = nullptr; }   // (the handles stay valid for dtrl_snapshot_info / _free)
 		be_->FreeHostStaging(snap_ids_);
 		be_->FreeHostStaging(slot_part_);
+		be_->FreeHostStaging(var_part_);
 		if (ext_meta_) be_->FreeHostStaging(ext_meta_);
 		for (void* p : allocs_) be_->Free(p);
 		for (void* p : host_allocs_) be_->FreeHostStaging(p);
@@ -144,7 +145,8 @@ int Engine::Create(const char* const* argv, int argc, int num_envs, int device_i
 {
 	if (num_envs <= 0) return Fail(DTRL_ERR_ARG, "num_envs must be positive");
 	// optimizer/Main.cpp:19-32: command line first, then the arg file appended (first match wins -> command line overrides)
-	ArgParser args(argv, argc);
+	ArgParser& args = args_;   // kept: dtrl_variant_load_* runs the loader again with these arguments
+	args = ArgParser(argv, argc);
 	std::string arg_file;
 	if (args.ParseString("arg_file", arg_file)) {
 		std::string root; args.ParseString("data_root", root);
@@ -361,9 +363,15 @@ int Engine::LaunchGroup(int group, int n_steps, double dt_step, bool frame_end)
 	return ok ? DTRL_OK : Fail(DTRL_ERR_DEVICE, be_->error());
 }
 
-// every launch of the frame kernels after the batch's creation comes through here: a batch without slots launches exactly as it always did
+// every launch of the frame kernels after the batch's creation comes through here: a batch without slots and without variants launches exactly as it always did
 bool Engine::LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, bool frame_end, const int32_t* list_host, int part_off)
 {
+	if (!var_models_.empty()) {   // (variants and slots exclude each other: dtrl_variants_create / dtrl_slots_create)
+		VariantView m;
+		m.dev = d_var_models_; m.n_variants = static_cast<int32_t>(var_models_.size());
+		m.env_variant_host = env_var_.data(); m.env_list_host = list_host; m.part = var_part_ + part_off;
+		return be_->LaunchVariants(cfg_.run, b, m, d_env_var_, n_envs, n_steps, dt, frame_end);
+	}
 	if (slots_.empty()) return be_->Launch(d_model_, cfg_.run, b, n_envs, n_steps, dt, frame_end);
 	SlotView v;
 	v.dev = d_slot_table_; v.host = slot_table_.data(); v.n_slots = static_cast<int32_t>(slots_.size());
@@ -1205,12 +1213,12 @@ int Engine::AddPerturb(const int32_t* env_ids, int n, const int32_t* link, const
 {
 	if (env_ids && n < 0) return Fail(DTRL_ERR_ARG, "negative env count");
 	be_->Sync();
-	const DevModel& m = cfg_.model;
 	EnvState st;
 	const int cnt = env_ids ? n : n_;
 	for (int i = 0; i < cnt; ++i) {
 		const int e = EnvIndex(env_ids, i);
 		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "env id out of range");
+		const DevModel& m = ModelOf(e);   // (body_theta is the env's variant's)
 		const int l = link[i];
 		if (l < 0 || l >= m.L) return Fail(DTRL_ERR_ARG, "perturbation link out of range");
 		if (!(duration[i] >= 0)) return Fail(DTRL_ERR_ARG, "perturbation duration must be non-negative");
@@ -1772,6 +1780,7 @@ int Engine::SlotsCreate(int n_slots)
 {
 	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_slots_create: not available with -policy_mode= external (the caller's policy decides; no policy net runs inside the frame kernel)");
 	if (!cfg_.has_policy_net) return Fail(DTRL_ERR_ARG, "dtrl_slots_create: no -policy_net= in the arguments: this batch has no network");
+	if (!var_models_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_slots_create: not available on a batch with model variants (dtrl_variants_create): policy slots together with model variants are not supported");
 	if (n_slots < 1 || n_slots > kMaxSlots) return Fail(DTRL_ERR_ARG, "dtrl_slots_create: n_slots must be 1 .. " + std::to_string(kMaxSlots) + ", not " + std::to_string(n_slots));
 	if (!slots_.empty()) {
 		if (n_slots == static_cast<int>(slots_.size())) return DTRL_OK;
@@ -1894,8 +1903,132 @@ int Engine::SlotStats(int slot, int64_t* n_envs, double* avg_dist, int64_t* epis
 	be_->SelectStream(0);
 	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	SlotSums sums[kMaxSlots];
-	if (!be_->SlotReduce(buf_.st, d_env_slot_, n_, static_cast<int>(slots_.size()), sums)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (!be_->SlotReduce(buf_.st, d_env_slot_, n_, static_cast<int>(slots_.size()), sums, 0)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	const SlotSums& a = sums[slot];
+	if (n_envs) *n_envs = a.n_envs;
+	if (avg_dist) *avg_dist = a.episodes > 0 ? a.dist_sum / static_cast<double>(a.episodes) : 0.0;
+	if (episodes) *episodes = a.episodes;
+	if (cycles) *cycles = a.cycles;
+	if (resets) *resets = a.resets;
+	return DTRL_OK;
+}
+
+// ---- model variants (include/dtrl.h: dtrl_variants_create ... dtrl_variant_stats) ----
+// The timing rules are those of the slot calls: the table and the per-env array are read by launches in flight, so every call that rewrites them refuses a frame
+// in flight and then waits for every stream (VariantsIdle). Nothing of a variant changes while launches run: unlike slot 0's weights, the batch's own model is
+// fixed at creation, so the table holds a plain copy of it as record 0 and no launch argument has to stand in for a table entry.
+int Engine::VariantsIdle(const char* what, int v)
+{
+	if (var_models_.empty()) return Fail(DTRL_ERR_ARG, std::string(what) + ": the batch has no model variants (call dtrl_variants_create first)");
+	if (v < 0 || v >= static_cast<int>(var_models_.size())) return Fail(DTRL_ERR_ARG, std::string(what) + ": variant " + std::to_string(v) + " out of range (0 .. " + std::to_string(var_models_.size() - 1) + ")");
+	return RequireIdle(std::string(what) + kFrameInFlight);
+}
+
+int Engine::VariantsCreate(int n_variants)
+{
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_variants_create: not available with -policy_mode= external (model variants together with external policy mode are not supported)");
+	if (!slots_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_variants_create: not available on a batch with policy slots (dtrl_slots_create): model variants together with policy slots are not supported");
+	if (!var_models_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_variants_create: the batch already has " + std::to_string(var_models_.size()) + " variants; it is called once per batch");
+	if (n_variants < 1 || n_variants > n_) return Fail(DTRL_ERR_ARG, "dtrl_variants_create: n_variants must be 1 .. num_envs (" + std::to_string(n_) + "), not " + std::to_string(n_variants));
+	if (int rc = RequireIdle(std::string("dtrl_variants_create") + kFrameInFlight); rc != DTRL_OK) return rc;
+	d_var_models_ = static_cast<DevModel*>(be_->Alloc(sizeof(DevModel) * static_cast<size_t>(n_variants))); if (d_var_models_) allocs_.push_back(d_var_models_);
+	d_env_var_ = static_cast<int32_t*>(be_->Alloc(sizeof(int32_t) * n_)); if (d_env_var_) allocs_.push_back(d_env_var_);   // (zero-filled: every env starts in variant 0)
+	var_part_ = static_cast<int32_t*>(be_->HostStaging(sizeof(int32_t) * 2 * static_cast<size_t>(n_)));
+	if (!d_var_models_ || !d_env_var_ || !var_part_ || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+	if (!be_->H2D(d_var_models_, &cfg_.model, sizeof(DevModel))) return Fail(DTRL_ERR_DEVICE, be_->error());
+	var_models_.assign(static_cast<size_t>(n_variants), cfg_.model);   // (an empty variant holds the batch's model until it is loaded; it cannot be assigned)
+	var_set_.assign(static_cast<size_t>(n_variants), 0); var_set_[0] = 1;
+	env_var_.assign(static_cast<size_t>(n_), 0);
+	return DTRL_OK;
+}
+
+// what of a variant must equal the batch's model: the skeleton the fast kernels are compiled for, the scene, and the whole controller part -- the batch has one
+// policy, one action table and one set of output normalisers, and they must mean the same thing for every env. Returns the first field that differs, or nullptr.
+static const char* VariantMisfit(const DevModel& a, const DevModel& b)
+{
+#define DTRL_SAME(f) if (std::memcmp(&a.f, &b.f, sizeof(a.f)) != 0) return #f
+	DTRL_SAME(L); DTRL_SAME(D); DTRL_SAME(parent);
+	DTRL_SAME(char_type); DTRL_SAME(ctrl_type); DTRL_SAME(scenario); DTRL_SAME(num_update_steps); DTRL_SAME(num_sim_substeps); DTRL_SAME(world_scale); DTRL_SAME(valid_init_pos_x);
+	DTRL_SAME(P); DTRL_SAME(n_opt); DTRL_SAME(opt_index); DTRL_SAME(n_sets); DTRL_SAME(ctrl_params); DTRL_SAME(n_actions);
+	DTRL_SAME(act_idx0); DTRL_SAME(act_idx1); DTRL_SAME(act_blend); DTRL_SAME(act_cyclic); DTRL_SAME(default_action); DTRL_SAME(enable_grav_comp); DTRL_SAME(enable_vf);
+#undef DTRL_SAME
+	return nullptr;
+}
+
+int Engine::VariantLoad(int v, const char* character_file, const char* text, size_t bytes)
+{
+	const char* what = text ? "dtrl_variant_load_json" : "dtrl_variant_load_file";
+	int rc = VariantsIdle(what, v);
+	if (rc != DTRL_OK) return rc;
+	if (v == 0) return Fail(DTRL_ERR_ARG, std::string(what) + ": variant 0 is the batch's own model and cannot be replaced");
+	std::string doc; CharSource src;
+	if (text) { doc.assign(text, bytes); src.name = "variant " + std::to_string(v) + " (JSON text)"; }
+	else {
+		if (!character_file || !*character_file) return Fail(DTRL_ERR_ARG, std::string(what) + ": character_file is required");
+		src.name = character_file;
+		const std::string path = ResolveDataPath(cfg_.data_root, character_file);
+		FILE* fp = std::fopen(path.c_str(), "rb");
+		if (!fp) return Fail(DTRL_ERR_IO, std::string(what) + ": cannot open " + path);
+		char chunk[4096]; size_t k;
+		while ((k = std::fread(chunk, 1, sizeof(chunk), fp)) > 0) doc.append(chunk, k);
+		std::fclose(fp);
+	}
+	src.text = &doc;
+	{   // the joint count first: the loader itself refuses a skeleton its controller does not expect, and that is a misfit, not a broken file
+		Json root; std::string jerr;
+		if (!Json::parse(doc, root, jerr)) return Fail(DTRL_ERR_IO, std::string(what) + ": " + src.name + ": " + jerr);
+		const Json* skel = root.find("Skeleton"); const Json* joints = skel ? skel->find("Joints") : nullptr;
+		if (joints && static_cast<int>(joints->arr.size()) != cfg_.model.L)
+			return Fail(DTRL_ERR_ARG, std::string(what) + ": variant " + std::to_string(v) + " does not fit the batch: L differs (" + std::to_string(joints->arr.size()) + " joints, the batch's model has " + std::to_string(cfg_.model.L) + ")");
+	}
+	ScenarioConfig vc; std::string lerr;
+	if (!LoadScenario(args_, vc, lerr, &src)) return Fail(DTRL_ERR_IO, std::string(what) + ": " + lerr);
+	vc.model.has_net = cfg_.model.has_net;   // (the creation-time fix-up)
+	if (const char* f = VariantMisfit(vc.model, cfg_.model))
+		return Fail(DTRL_ERR_ARG, std::string(what) + ": variant " + std::to_string(v) + " does not fit the batch: " + f + " differs from the batch's model (the skeleton, the scene and the controller part -- parameters, actions, default action -- are one per batch)");
+	if (!be_->H2D(d_var_models_ + v, &vc.model, sizeof(DevModel))) return Fail(DTRL_ERR_DEVICE, be_->error());
+	var_models_[v] = vc.model; var_set_[v] = 1;
+	return DTRL_OK;
+}
+
+int Engine::AssignVariants(const int32_t* env_ids, int n, const int32_t* variants)
+{
+	int rc = VariantsIdle("dtrl_assign_variants", 0);
+	if (rc != DTRL_OK) return rc;
+	if (n < 0 || n > n_ || (n > 0 && !variants)) return Fail(DTRL_ERR_ARG, "dtrl_assign_variants: variants is required and the env count must be 0 .. num_envs");
+	const int cnt = n;
+	for (int i = 0; i < cnt; ++i) {
+		const int e = EnvIndex(env_ids, i), v = variants[i];
+		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "dtrl_assign_variants: env id " + std::to_string(e) + " out of range; nothing assigned");
+		if (v < 0 || v >= static_cast<int>(var_models_.size())) return Fail(DTRL_ERR_ARG, "dtrl_assign_variants: variant " + std::to_string(v) + " out of range (0 .. " + std::to_string(var_models_.size() - 1) + "); nothing assigned");
+		if (!var_set_[v]) return Fail(DTRL_ERR_ARG, "dtrl_assign_variants: variant " + std::to_string(v) + " is empty (no dtrl_variant_load_* has filled it); nothing assigned");
+	}
+	for (int i = 0; i < cnt; ++i) env_var_[EnvIndex(env_ids, i)] = variants[i];
+	if (!be_->H2D(d_env_var_, env_var_.data(), sizeof(int32_t) * env_var_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::GetVariants(const int32_t* env_ids, int n, int32_t* variants_out)
+{
+	if (var_models_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_get_variants: the batch has no model variants (call dtrl_variants_create first)");
+	const int cnt = n;
+	if (cnt < 0 || cnt > n_ || (cnt > 0 && !variants_out)) return Fail(DTRL_ERR_ARG, "dtrl_get_variants: variants_out is required and the env count must be 0 .. num_envs");
+	for (int i = 0; i < cnt; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "dtrl_get_variants: env id " + std::to_string(e) + " out of range"); }
+	for (int i = 0; i < cnt; ++i) variants_out[i] = env_var_[EnvIndex(env_ids, i)];
+	return DTRL_OK;
+}
+
+// Backend::SlotReduce with the variant array in place of the slot array; its kernels are sized by kMaxSlots, so the window of kMaxSlots variants that holds `v`
+int Engine::VariantStats(int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets)
+{
+	const int nv = static_cast<int>(var_models_.size());
+	if (nv == 0) return Fail(DTRL_ERR_ARG, "dtrl_variant_stats: the batch has no model variants (call dtrl_variants_create first)");
+	if (v < 0 || v >= nv) return Fail(DTRL_ERR_ARG, "dtrl_variant_stats: variant " + std::to_string(v) + " out of range (0 .. " + std::to_string(nv - 1) + ")");
+	if (int rc = RequireIdle(std::string("dtrl_variant_stats") + kFrameInFlight); rc != DTRL_OK) return rc;
+	const int base = v / kMaxSlots * kMaxSlots, cnt = std::min(kMaxSlots, nv - base);
+	SlotSums sums[kMaxSlots];
+	if (!be_->SlotReduce(buf_.st, d_env_var_, n_, cnt, sums, base)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	const SlotSums& a = sums[v - base];
 	if (n_envs) *n_envs = a.n_envs;
 	if (avg_dist) *avg_dist = a.episodes > 0 ? a.dist_sum / static_cast<double>(a.episodes) : 0.0;
 	if (episodes) *episodes = a.episodes;

@@ -52,16 +52,33 @@ struct SlotView {
 // per-slot totals of dtrl_slot_stats (Backend::SlotReduce): envs in the slot, and over them the sums dtrl_eval_stats takes over the batch
 struct SlotSums { int64_t n_envs, episodes, cycles, resets; double dist_sum; };   // dist_sum = sum of avg_dist * num_episodes
 
+// ---- model variants (include/dtrl.h: dtrl_variants_create ...) ----
+// what a launch over envs of several character models is given: the table of complete DevModel records (device memory; record 0 is a copy of the batch's own
+// model) and the per-env variant array (indexed by local env id) in host-readable form, and what the per-variant default needs to split a launch list:
+// env_list_host / part as in SlotView.
+struct VariantView {
+	const DevModel* dev = nullptr; int32_t n_variants = 0;
+	const int32_t* env_variant_host = nullptr;
+	const int32_t* env_list_host = nullptr;
+	int32_t* part = nullptr;
+};
+
 class Backend {
 public:
 	virtual ~Backend() {}
+	// A launch over envs of several model variants (env e runs under models.dev[env_variant[e]]; env_variant is device memory). The default is one Launch per
+	// non-empty variant over that variant's part of the launch list with that variant's record as `gm`, list order kept inside a variant (what the lane-loop check
+	// build runs, and DTRL_VARIANTS_FALLBACK=1 on HIP; it waits for the selected stream before it reuses models.part). The HIP backend overrides it with ONE
+	// launch of the variant kernels (dtrl_backend_hip_variants.hip).
+	virtual bool LaunchVariants(const RunParams& rp, const DevBuffers& buf, const VariantView& models, const int32_t* env_variant, int n_envs, int n_steps, real dt, bool frame_end);
 	// A launch over envs of several policy slots (env e runs slot env_slot[e]'s record patched over rp / buf: slot_patch). The default is one Launch per
 	// non-empty slot over that slot's part of the launch list, list order kept inside a slot (what the lane-loop check build runs, and DTRL_SLOTS_FALLBACK=1 on
 	// HIP; it waits for the selected stream before it reuses slots.part). The HIP backend overrides it with ONE launch of the slot kernels (dtrl_backend_hip_slots.hip).
 	virtual bool LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end);
-	// sums[s] for s < n_slots over the envs e < n_envs with env_slot[e] == s; st / env_slot are device memory, sums host memory. Synchronised. The default is a
+	// sums[s] for s < n_slots (<= kMaxSlots) over the envs e < n_envs with env_slot[e] == slot_base + s (an env outside the window counts nowhere: the per-variant
+	// statistics take a table of any size in windows of kMaxSlots); st / env_slot are device memory, sums host memory. Synchronised. The default is a
 	// host loop over a D2H of the records; the HIP backend reduces on the device (two launches, fixed summation order: the same bytes from call to call)
-	virtual bool SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums);
+	virtual bool SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums, int slot_base);
 	// Snapshot transport. ids / src_ids / dst_ids live in HostStaging() memory (host- and device-addressable), payload is device memory laid out [n][env_bytes].
 	// Queued on the selected stream and synchronised. The defaults are built from D2D (one copy per record and env); the HIP backend overrides them with
 	// one kernel launch each (one wavefront per listed env, every record copied as consecutive 64-bit words).
@@ -82,6 +99,8 @@ public:
 	virtual bool ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labels, const int32_t* ids, int n, const int32_t* action_ids, const void* params, bool f32, const uint32_t* flags, bool apply, int32_t* rejected);
 	virtual double ExtLaunchMs(int which) { (void)which; return -1.0; }   // device time of the collection (0) / scatter (1) launches since the last call (HIP events)
 	virtual double SnapLaunchMs() { return -1.0; }   // device time of the snapshot launches since the last call (HIP events; -1: this backend launches nothing)
+	// the list splitting LaunchSlots' and LaunchVariants' defaults share (dtrl_backend_defaults.cpp)
+	bool SplitLaunchList(const DevBuffers& buf, int n_envs, const int32_t* list_host, const int32_t* key_of_env, int n_keys, int32_t* part, std::vector<int32_t>& n_of);
 	virtual bool Init(int device_id, std::string& err) = 0;
 	// -reserve_cus= k (before Init): keep k compute units per XCD out of the frame launches (HIP backend; see dtrl_side_stream in include/dtrl.h)
 	virtual void SetReserveCus(int) {}
@@ -195,6 +214,15 @@ public:
 	int AssignSlots(const int32_t* env_ids, int n, const int32_t* slots);
 	int GetSlots(const int32_t* env_ids, int n, int32_t* slots_out);
 	int SlotStats(int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+	// model variants (include/dtrl.h)
+	int VariantsCreate(int n_variants);
+	int VariantLoad(int v, const char* character_file, const char* text, size_t bytes);   // text == nullptr: the file, resolved like -character_file=
+	int AssignVariants(const int32_t* env_ids, int n, const int32_t* variants);
+	int GetVariants(const int32_t* env_ids, int n, int32_t* variants_out);
+	int VariantStats(int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+	int num_variants() const { return static_cast<int>(var_models_.size()); }
+	// the model env e (local id, in range) runs under: what host-side readers of per-env geometry use (dtrl_get_link_states, AddPerturb)
+	const DevModel& ModelOf(int e) const { return var_models_.empty() ? cfg_.model : var_models_[env_var_[e]]; }
 	~Engine();
 	int Create(const char* const* argv, int argc, int num_envs, int device_id);
 	int Reset(const int32_t* env_ids, int n, const uint64_t* seeds);
@@ -341,6 +369,14 @@ private:
 	// every frame-kernel launch of the batch: Backend::Launch, or -- once slots exist -- Backend::LaunchSlots. list_host: b.env_list in host-readable form or
 	// nullptr; part_off: offset of the launch's scratch inside slot_part_
 	bool LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, bool frame_end, const int32_t* list_host, int part_off);
+	// model variants. Variant 0 is the batch's own model; a variant >= 1 is empty until dtrl_variant_load_* fills it. Table and per-env array are rewritten only
+	// by calls that have refused a frame in flight and waited for every stream (VariantsIdle)
+	ArgParser args_;                         // the creation arguments (command line + arg file): a variant is loaded through them with another character description
+	std::vector<DevModel> var_models_;       // empty: no variants, every launch is Backend::Launch (or LaunchSlots) as it always was
+	std::vector<char> var_set_;
+	std::vector<int32_t> env_var_;           // host form of the per-env array
+	DevModel* d_var_models_ = nullptr; int32_t* d_env_var_ = nullptr; int32_t* var_part_ = nullptr;   // device table [n_variants], device array [n], page-locked [2 n]
+	int VariantsIdle(const char* what, int v);   // DTRL_ERR_ARG without variants / variant out of range / frame in flight, else every stream idle
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

@@ -1,5 +1,5 @@
-// dtrl_frame_entry.h -- what the three translation units that instantiate the frame kernels share (dtrl_backend_hip_frame.hip: internal policy mode, the shipped
-// kernels; dtrl_backend_hip_ext.hip: external policy mode; dtrl_backend_hip_slots.hip: policy slots): the register budget of the fast kernels, the kernels' entry
+// dtrl_frame_entry.h -- what the four translation units that instantiate the frame kernels share (dtrl_backend_hip_frame.hip: internal policy mode, the shipped
+// kernels; dtrl_backend_hip_ext.hip: external policy mode; dtrl_backend_hip_slots.hip: policy slots; dtrl_backend_hip_variants.hip: model variants): the register budget of the fast kernels, the kernels' entry
 // body, and the host-side choice among a unit's three kernels. The entry body is shared as TEXT (a macro), not through a call: moved into a __forceinline__
 // function template it compiles to other instructions in the fast kernels (docs/EXPERIMENTS.md 19), and tools/asm_same.py holds them fixed.
 #pragma once
@@ -40,7 +40,7 @@ template <> struct WavesPerEu<TopoRaptor> { static constexpr int value = DTRL_WA
 #define DTRL_DEVICE_ONLY(...)
 #endif
 
-// one 64-lane workgroup = one env of the launch list; PRE runs in front of the frame (it may rewrite the kernel's own copies of rp / buf)
+// one 64-lane workgroup = one env of the launch list; PRE runs in front of the frame (it may rewrite the kernel's own copies of rp / buf and re-point gm)
 #define DTRL_FRAME_BODY(WS, PATH, EXT, PRE) \
 	WS; \
 	if (static_cast<int>(blockIdx.x) >= n_envs) return; \
@@ -91,13 +91,15 @@ hipError_t LaunchFrameKernel(FrameKernel<Extra...> ref, FrameKernel<Extra...> do
 	return hipGetLastError();
 }
 
-// the units' launchers, one signature (HipBackend::LaunchFrame chooses): slots / env_slot are device memory, read by the slot unit's kernels only (env e runs
-// under the record slots[env_slot[e]])
+// the units' launchers, one signature (HipBackend::LaunchFrame chooses). FrameExtra: what the kernels of a family take behind the common parameters, all device
+// memory -- slots / env_slot: read by the slot unit's kernels only (env e runs under the record slots[env_slot[e]]); models / env_model: read by the variant
+// unit's kernels only (env e runs under the model models[env_model[e]])
 struct SlotRec;
-using FrameLauncher = hipError_t (*)(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end,
-	const SlotRec* slots, const int32_t* env_slot);
-hipError_t LaunchPlainFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const SlotRec*, const int32_t*);
-hipError_t LaunchExtFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const SlotRec*, const int32_t*);
-hipError_t LaunchSlotFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const SlotRec* slots, const int32_t* env_slot);
+struct FrameExtra { const SlotRec* slots = nullptr; const int32_t* env_slot = nullptr; const DevModel* models = nullptr; const int32_t* env_model = nullptr; };
+using FrameLauncher = hipError_t (*)(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const FrameExtra& extra);
+hipError_t LaunchPlainFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const FrameExtra&);
+hipError_t LaunchExtFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const FrameExtra&);
+hipError_t LaunchSlotFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const FrameExtra& extra);
+hipError_t LaunchVariantFrame(hipStream_t stream, const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end, const FrameExtra& extra);
 
 }  // namespace dtrl

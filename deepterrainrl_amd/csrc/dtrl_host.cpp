@@ -398,12 +398,15 @@ void BuildOutputOffsetScale(const DevModel& m, const NetDesc& d, std::vector<dou
 	}
 }
 
-bool LoadScenario(const ArgParser& args, ScenarioConfig& cfg, std::string& err)
+std::string ResolveDataPath(const std::string& root, const std::string& rel) { return JoinPath(root, rel); }
+
+bool LoadScenario(const ArgParser& args, ScenarioConfig& cfg, std::string& err, const CharSource* src)
 {
 	DevModel& m = cfg.model;
 	std::string root; args.ParseString("data_root", root); cfg.data_root = root;
 	std::string char_file, state_file, char_type, char_ctrl, terrain_file, scenario;
-	if (!args.ParseString("character_file", char_file)) { err = "No character file specified."; return false; }
+	if (src) char_file = src->name;
+	else if (!args.ParseString("character_file", char_file)) { err = "No character file specified."; return false; }
 	args.ParseString("state_file", state_file);
 	args.ParseString("char_type", char_type); args.ParseString("char_ctrl", char_ctrl);
 	args.ParseString("terrain_file", terrain_file); args.ParseString("scenario", scenario);
@@ -430,7 +433,8 @@ bool LoadScenario(const ArgParser& args, ScenarioConfig& cfg, std::string& err)
 	else m.scenario = kScnSimChar;
 
 	Json chr;
-	if (!Json::parse_file(JoinPath(root, char_file), chr, err)) return false;
+	if (src && src->text) { if (!Json::parse(*src->text, chr, err)) { err = char_file + ": " + err; return false; } }
+	else if (!Json::parse_file(JoinPath(root, char_file), chr, err)) return false;
 	const Json* skel = chr.find("Skeleton"); const Json* joints = skel ? skel->find("Joints") : nullptr;
 	const Json* bodies = chr.find("BodyDefs"); const Json* pds = chr.find("PDControllers"); const Json* ctrls = chr.find("Controllers");
 	if (!joints || !bodies || !pds || !ctrls) { err = char_file + ": missing Skeleton/BodyDefs/PDControllers/Controllers"; return false; }
@@ -672,6 +676,7 @@ bool LoadScenario(const ArgParser& args, ScenarioConfig& cfg, std::string& err)
 
 	// policy net topology (weights arrive through dtrl_set_policy: the shipped *.h5 blobs are not in the reference checkout)
 	cfg.has_policy_net = false; m.has_net = 0;
+	if (src) return true;   // a variant is a character model: the batch's net, parsed at creation, stays what it is (Engine::VariantLoad copies has_net)
 	if (args.ParseString("policy_net", cfg.policy_net_file)) {
 		if (!ParseDeployPrototxt(JoinPath(root, cfg.policy_net_file), cfg.net, err, &cfg.actor_only)) return false;
 		if (cfg.actor_only != (m.ctrl_type != 1)) { err = "policy_net topology does not match char_ctrl (MACE nets for *_mace, the single-head actor / Q net for dog_cacla, raptor_cacla, dog, raptor)"; return false; }

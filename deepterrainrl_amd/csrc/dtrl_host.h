@@ -140,7 +140,13 @@ struct ScenarioConfig {
 	std::string policy_net_file, policy_model_file;
 };
 
-bool LoadScenario(const ArgParser& args, ScenarioConfig& cfg, std::string& err);
+// chr (model variants, dtrl_variant_load_*): the character description comes from `text` (JSON) instead of the file -character_file= names; `name` stands for
+// the file in messages. Everything else -- arguments, controller files, state file, terrain, net -- is read as at creation, so every derived field of the
+// variant's DevModel comes out of this one code path.
+struct CharSource { std::string name; const std::string* text = nullptr; };
+bool LoadScenario(const ArgParser& args, ScenarioConfig& cfg, std::string& err, const CharSource* chr = nullptr);
+// -character_file= as LoadScenario resolves it: relative to -data_root=, absolute paths as they are
+std::string ResolveDataPath(const std::string& root, const std::string& rel);
 bool ParseDeployPrototxt(const std::string& path, NetDesc& d, std::string& err, bool* actor_only = nullptr);
 // cBaseControllerMACE::BuildNNOutputOffsetScale + cDogControllerMACE::BuildActorBias
 void BuildOutputOffsetScale(const DevModel& m, const NetDesc& d, std::vector<double>& off, std::vector<double>& scale);

@@ -331,6 +331,39 @@ dtrl_status dtrl_get_slots(dtrl_batch* b, const int32_t* env_ids, int n, int32_t
  * (n_envs of them), reduced on the device in a fixed order: two calls without a step between them return the same bits. Any output may be NULL. */
 dtrl_status dtrl_slot_stats(dtrl_batch* b, int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
 
+/* ---- Model variants: several character models in one batch, one per env ----
+ * No counterpart in the reference, which keeps one character per scene object (cScenarioSimChar::BuildCharacter, scenarios/ScenarioSimChar.cpp): training or
+ * measuring a policy across masses, sizes or motor strengths there means one scenario per model. A variant is a complete character model (masses, inertias,
+ * box sizes, attach points, joint limits, PD gains, torque limits and every table derived from them); a batch holds a table of n_variants of them, up to one per
+ * env, and a per-env index says which one an env runs. The table costs sizeof(DevModel) per variant in device memory: 14 352 bytes in the fp64 library, 8 276 in
+ * the fp32 library. Frames still run as one launch per env group. Variant 0 IS the batch's own model; every env starts in it; variants >= 1 start empty. A batch
+ * that never calls dtrl_variants_create runs exactly the kernels and launches it ran before. The assignment is batch state like the slot assignment: snapshots,
+ * restores, clones and blobs do not carry it and a reset does not change it. An env that changes variant keeps every byte of its state and simply runs its next
+ * launch under the other model; a caller who wants episodes to START under the new model resets those envs (dtrl_reset) after assigning. Variants use local
+ * env ids. Not available together with policy slots or with -policy_mode= external, in either order (each combination would be one more kernel family).
+ * The calls below are refused with DTRL_ERR_ARG between dtrl_step_begin and dtrl_step_end (they never wait for a frame) and then -- dtrl_get_variants
+ * excepted, which is valid at any time -- wait for everything the batch has queued on the device before they change or read anything. */
+/* No counterpart in the reference, which keeps one character per scene object. 1 <= n_variants <= num_envs, once per batch, between frames. Refused with
+ * DTRL_ERR_ARG: a second call, a batch with policy slots, external policy mode, a frame in flight. */
+dtrl_status dtrl_variants_create(dtrl_batch* b, int n_variants);
+/* No counterpart in the reference, which keeps one character per scene object. Fill variant v >= 1 from a character file: the loader the batch was created
+ * with runs again on the creation arguments with only the character description replaced, so every derived table comes out of the one code path. The path is
+ * resolved like -character_file= (relative to -data_root=, absolute paths as they are). DTRL_ERR_ARG, naming the field, when the variant does not fit the
+ * batch: the skeleton (L, D, parent), the scene (char_type, ctrl_type, scenario, num_update_steps, num_sim_substeps, world_scale, valid_init_pos_x) and the whole
+ * controller part (P, n_opt, opt_index, n_sets, ctrl_params, n_actions, the action tables, default_action, enable_grav_comp, enable_vf) must equal variant 0:
+ * the batch has one policy, one action table and one set of output normalisers. Everything else may differ. DTRL_ERR_IO: the file cannot be read or parsed. */
+dtrl_status dtrl_variant_load_file(dtrl_batch* b, int v, const char* character_file);
+/* No counterpart in the reference, which keeps one character per scene object. The same from `bytes` bytes of JSON text in memory (a character file's content). */
+dtrl_status dtrl_variant_load_json(dtrl_batch* b, int v, const char* text, size_t bytes);
+/* No counterpart in the reference, which keeps one character per scene object. env_ids[i] -> variants[i]; env_ids == NULL means the first n envs (n = num_envs:
+ * all). All or nothing: an env id or variant out of range, or an empty variant, is DTRL_ERR_ARG. Takes effect with the env's next launch. */
+dtrl_status dtrl_assign_variants(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* variants);
+/* No counterpart in the reference, which keeps one character per scene object. The variants of the listed envs (valid at any time). */
+dtrl_status dtrl_get_variants(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* variants_out);
+/* No counterpart in the reference, which keeps one character per scene object. dtrl_eval_stats restricted to the envs currently in variant v (n_envs of them),
+ * reduced on the device in a fixed order: two calls without a step between them return the same bits. Any output may be NULL. */
+dtrl_status dtrl_variant_stats(dtrl_batch* b, int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+
 /* Replaces: cScenarioSimChar::AddPerturb -> cWorld::AddPerturb (scenarios/ScenarioSimChar.cpp:204-207, sim/World.cpp:256-259) with a
  * tPerturb of type ePerturbForce (sim/Perturb.cpp:52-79, sim/World.cpp:445-470): a world-frame force[n][2] on body part link[n] at the
  * body-local offset local_pos[n][2] (NULL = the COM) for duration[n] seconds of simulated time, advanced and applied at the start of
