@@ -325,6 +325,24 @@ class BatchScenario:
         a = np.ascontiguousarray(env_ids, np.int32)
         return a, len(a)
 
+    def _assign_keys(self, fn, who, noun, env_ids, keys):   # the ctypes marshalling policy slots and model variants share; fn: the family's entry point
+        ka = np.ascontiguousarray(keys, np.int32)
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32)
+        if ids is not None and ids.shape != ka.shape:
+            raise DtrlError("%s: env_ids and %s must have the same length" % (who, noun))
+        self._chk(fn(self._h, _p(ids), len(ka), _p(ka)))
+
+    def _get_keys(self, fn, env_ids):
+        ids, n = self._ids(env_ids)
+        out = np.zeros(n, np.int32)
+        self._chk(fn(self._h, _p(ids), n, _p(out)))
+        return out
+
+    def _key_stats(self, fn, key):
+        a = C.c_double(); n, e, c, r = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(fn(self._h, int(key), C.byref(n), C.byref(a), C.byref(e), C.byref(c), C.byref(r)))
+        return {"n_envs": n.value, "avg_dist": a.value, "episodes": e.value, "cycles": c.value, "resets": r.value}
+
     # ---- cScenario interface ----
     def Update(self, dt=1.0 / 30.0):
         self._chk(self._lib.dtrl_step(self._h, float(dt)))
@@ -699,23 +717,14 @@ class BatchScenario:
 
     def AssignSlots(self, env_ids, slots):
         """env_ids[i] -> slots[i] (env_ids None: the first len(slots) envs); takes effect with the env's next launch. Between frames only."""
-        sl = np.ascontiguousarray(slots, np.int32)
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32)
-        if ids is not None and ids.shape != sl.shape:
-            raise DtrlError("AssignSlots: env_ids and slots must have the same length")
-        self._chk(self._lib.dtrl_assign_slots(self._h, _p(ids), len(sl), _p(sl)))
+        self._assign_keys(self._lib.dtrl_assign_slots, "AssignSlots", "slots", env_ids, slots)
 
     def GetSlots(self, env_ids=None):
-        ids, n = self._ids(env_ids)
-        out = np.zeros(n, np.int32)
-        self._chk(self._lib.dtrl_get_slots(self._h, _p(ids), n, _p(out)))
-        return out
+        return self._get_keys(self._lib.dtrl_get_slots, env_ids)
 
     def SlotStats(self, slot):
         """EvalStats restricted to the envs currently in `slot` (plus their number), reduced on the device in a fixed order."""
-        a = C.c_double(); n, e, c, r = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-        self._chk(self._lib.dtrl_slot_stats(self._h, int(slot), C.byref(n), C.byref(a), C.byref(e), C.byref(c), C.byref(r)))
-        return {"n_envs": n.value, "avg_dist": a.value, "episodes": e.value, "cycles": c.value, "resets": r.value}
+        return self._key_stats(self._lib.dtrl_slot_stats, slot)
 
     # ---- model variants: several character models in one batch, one per env (no counterpart in the reference, which keeps one character per scene object) ----
     num_variants = 0
@@ -782,23 +791,14 @@ class BatchScenario:
     def AssignVariants(self, env_ids, variants):
         """env_ids[i] -> variants[i] (env_ids None: the first len(variants) envs); takes effect with the env's next launch and leaves the env's state alone -- call
         Reset on those envs if their episodes are to START under the new model. Between frames only."""
-        va = np.ascontiguousarray(variants, np.int32)
-        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32)
-        if ids is not None and ids.shape != va.shape:
-            raise DtrlError("AssignVariants: env_ids and variants must have the same length")
-        self._chk(self._lib.dtrl_assign_variants(self._h, _p(ids), len(va), _p(va)))
+        self._assign_keys(self._lib.dtrl_assign_variants, "AssignVariants", "variants", env_ids, variants)
 
     def GetVariants(self, env_ids=None):
-        ids, n = self._ids(env_ids)
-        out = np.zeros(n, np.int32)
-        self._chk(self._lib.dtrl_get_variants(self._h, _p(ids), n, _p(out)))
-        return out
+        return self._get_keys(self._lib.dtrl_get_variants, env_ids)
 
     def VariantStats(self, v):
         """EvalStats restricted to the envs currently in variant v (plus their number), reduced on the device in a fixed order."""
-        a = C.c_double(); n, e, c, r = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-        self._chk(self._lib.dtrl_variant_stats(self._h, int(v), C.byref(n), C.byref(a), C.byref(e), C.byref(c), C.byref(r)))
-        return {"n_envs": n.value, "avg_dist": a.value, "episodes": e.value, "cycles": c.value, "resets": r.value}
+        return self._key_stats(self._lib.dtrl_variant_stats, v)
 
     # ---- full env snapshots (no counterpart in the reference: it keeps one scene per object) ----
     def SaveState(self, env_ids=None):

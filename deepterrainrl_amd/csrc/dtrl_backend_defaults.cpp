@@ -1,5 +1,5 @@
-// dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, slotted and
-// per-variant launches and the per-slot sums, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
+// dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, launches over
+// envs of several slots or variants and the per-slot sums, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
 // of them with kernels and keeps these as its cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1).
 // Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
 // lane-loop check build of any tests/ tree, the sanitizer scripts -- has the defaults, and no source list can lack them.
@@ -88,13 +88,13 @@ bool Backend::ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labe
 }
 // The launch list of `buf` (n_envs entries; no list: envs 0 .. n_envs - 1) regrouped by key_of_env[] into `part`, list order kept inside a key; n_of[k] = entries
 // of key k, in key order. list_host: the list in host-readable form, nullptr = read it back. Waits for the selected stream before it writes `part`.
-bool Backend::SplitLaunchList(const DevBuffers& buf, int n_envs, const int32_t* list_host, const int32_t* key_of_env, int n_keys, int32_t* part, std::vector<int32_t>& n_of)
+static bool SplitLaunchList(Backend& be, const DevBuffers& buf, int n_envs, const int32_t* list_host, const int32_t* key_of_env, int n_keys, int32_t* part, std::vector<int32_t>& n_of)
 {
 	std::vector<int32_t> list(static_cast<size_t>(n_envs));
 	if (!buf.env_list) { for (int i = 0; i < n_envs; ++i) list[i] = i; }
 	else if (list_host) { for (int i = 0; i < n_envs; ++i) list[i] = list_host[i]; }
-	else if (!D2H(list.data(), buf.env_list, sizeof(int32_t) * list.size())) return false;   // (an order computed on the device: behind everything queued, this launch's list included)
-	if (!SyncSelected()) return false;   // an earlier launch of this stream may still be reading `part`
+	else if (!be.D2H(list.data(), buf.env_list, sizeof(int32_t) * list.size())) return false;   // (an order computed on the device: behind everything queued, this launch's list included)
+	if (!be.SyncSelected()) return false;   // an earlier launch of this stream may still be reading `part`
 	n_of.assign(static_cast<size_t>(n_keys), 0);
 	std::vector<int32_t> at(static_cast<size_t>(n_keys));
 	for (int32_t e : list) ++n_of[key_of_env[e]];
@@ -102,32 +102,17 @@ bool Backend::SplitLaunchList(const DevBuffers& buf, int n_envs, const int32_t* 
 	for (int32_t e : list) part[at[key_of_env[e]]++] = e;
 	return true;
 }
-bool Backend::LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end)
+bool Backend::LaunchKeyed(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const EnvKeyView& keys, int n_envs, int n_steps, real dt, bool frame_end)
 {
-	(void)env_slot;
 	if (n_envs <= 0) return true;
 	std::vector<int32_t> n_of;
-	if (!SplitLaunchList(buf, n_envs, slots.env_list_host, slots.env_slot_host, slots.n_slots, slots.part, n_of)) return false;
-	for (int s = 0, k = 0; s < slots.n_slots; k += n_of[s], ++s) {
-		if (n_of[s] == 0) continue;
+	if (!SplitLaunchList(*this, buf, n_envs, keys.env_list_host, keys.env_key_host, keys.n_keys, keys.part, n_of)) return false;
+	for (int k = 0, at = 0; k < keys.n_keys; at += n_of[k], ++k) {
+		if (n_of[k] == 0) continue;
 		RunParams r = rp; DevBuffers b = buf;
-		slot_patch(slots.host[s], r, b);
-		b.env_list = slots.part + k;
-		if (!Launch(gm, r, b, n_of[s], n_steps, dt, frame_end)) return false;
-	}
-	return true;
-}
-bool Backend::LaunchVariants(const RunParams& rp, const DevBuffers& buf, const VariantView& models, const int32_t* env_variant, int n_envs, int n_steps, real dt, bool frame_end)
-{
-	(void)env_variant;
-	if (n_envs <= 0) return true;
-	std::vector<int32_t> n_of;
-	if (!SplitLaunchList(buf, n_envs, models.env_list_host, models.env_variant_host, models.n_variants, models.part, n_of)) return false;
-	for (int v = 0, k = 0; v < models.n_variants; k += n_of[v], ++v) {
-		if (n_of[v] == 0) continue;
-		DevBuffers b = buf;
-		b.env_list = models.part + k;
-		if (!Launch(models.dev + v, rp, b, n_of[v], n_steps, dt, frame_end)) return false;
+		if (keys.slots_host) slot_patch(keys.slots_host[k], r, b);
+		b.env_list = keys.part + at;
+		if (!Launch(keys.models_dev ? keys.models_dev + k : gm, r, b, n_of[k], n_steps, dt, frame_end)) return false;
 	}
 	return true;
 }

@@ -488,10 +488,11 @@ public:
 		return Check(hipMemcpyAsync(rejected, ext_rej_, sizeof(int32_t), hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H") && Check(hipStreamSynchronize(stream_), "sync");
 	}
 	double ExtLaunchMs(int which) override { const int k = which ? 1 : 0; const double v = ext_ms_[k]; ext_ms_[k] = 0; return v; }
-	static bool SnapFallback() { const char* e = std::getenv("DTRL_SNAPSHOT_FALLBACK"); return e && std::atoi(e) != 0; }
-	bool SnapGather(const SnapPlan& p, char* payload, const int32_t* ids, int n) override { return SnapFallback() ? Backend::SnapGather(p, payload, ids, n) : SnapMove(p, payload, ids, nullptr, n, 0); }
-	bool SnapScatter(const SnapPlan& p, const char* payload, const int32_t* ids, int n) override { return SnapFallback() ? Backend::SnapScatter(p, payload, ids, n) : SnapMove(p, const_cast<char*>(payload), ids, nullptr, n, 1); }
-	bool SnapCopy(const SnapPlan& p, const int32_t* src_ids, const int32_t* dst_ids, int n) override { return SnapFallback() ? Backend::SnapCopy(p, src_ids, dst_ids, n) : SnapMove(p, nullptr, src_ids, dst_ids, n, 2); }
+	// an A/B and cross-check switch of the environment is set and non-zero (read per call, like DTRL_KERNEL: a test switches it inside one process)
+	static bool EnvFlag(const char* name) { const char* e = std::getenv(name); return e && std::atoi(e) != 0; }
+	bool SnapGather(const SnapPlan& p, char* payload, const int32_t* ids, int n) override { return EnvFlag("DTRL_SNAPSHOT_FALLBACK") ? Backend::SnapGather(p, payload, ids, n) : SnapMove(p, payload, ids, nullptr, n, 0); }
+	bool SnapScatter(const SnapPlan& p, const char* payload, const int32_t* ids, int n) override { return EnvFlag("DTRL_SNAPSHOT_FALLBACK") ? Backend::SnapScatter(p, payload, ids, n) : SnapMove(p, const_cast<char*>(payload), ids, nullptr, n, 1); }
+	bool SnapCopy(const SnapPlan& p, const int32_t* src_ids, const int32_t* dst_ids, int n) override { return EnvFlag("DTRL_SNAPSHOT_FALLBACK") ? Backend::SnapCopy(p, src_ids, dst_ids, n) : SnapMove(p, nullptr, src_ids, dst_ids, n, 2); }
 	// the one gather launch; the three entry points differ in the stream and in what follows the launch
 	bool GatherLaunch(hipStream_t st, float* dst, const float* src, const int32_t* idx, size_t n)
 	{
@@ -555,23 +556,15 @@ public:
 		return Check(hipGetLastError(), "order launch");
 	}
 	bool Launch(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, int n_envs, int n_steps, real dt, bool frame_end) override { return LaunchFrame(gm, rp, buf, n_envs, n_steps, dt, frame_end, FrameExtra{}); }
-	// policy slots: ONE launch of the slot kernels (dtrl_backend_hip_slots.hip) over the list as it stands -- the group's costliest-first order is kept across slots.
-	// DTRL_SLOTS_FALLBACK=1 takes the per-slot default instead (A/B and cross-check)
-	bool LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end) override
+	// policy slots / model variants: ONE launch of the family's kernels (dtrl_backend_hip_slots.hip, dtrl_backend_hip_variants.hip) over the list as it stands -- the
+	// group's costliest-first order is kept across keys. DTRL_SLOTS_FALLBACK=1 / DTRL_VARIANTS_FALLBACK=1 takes the per-key default instead (A/B and cross-check)
+	bool LaunchKeyed(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const EnvKeyView& keys, int n_envs, int n_steps, real dt, bool frame_end) override
 	{
-		const char* fb = std::getenv("DTRL_SLOTS_FALLBACK");   // (read per launch, like DTRL_KERNEL: a test switches it inside one process)
-		if (fb && std::atoi(fb) != 0) return Backend::LaunchSlots(gm, rp, buf, slots, env_slot, n_envs, n_steps, dt, frame_end);
-		FrameExtra x; x.slots = slots.dev; x.env_slot = env_slot;
+		if (EnvFlag(keys.models_dev ? "DTRL_VARIANTS_FALLBACK" : "DTRL_SLOTS_FALLBACK")) return Backend::LaunchKeyed(gm, rp, buf, keys, n_envs, n_steps, dt, frame_end);
+		FrameExtra x;
+		if (keys.models_dev) { x.models = keys.models_dev; x.env_model = keys.env_key_dev; }
+		else { x.slots = keys.slots_dev; x.env_slot = keys.env_key_dev; }
 		return LaunchFrame(gm, rp, buf, n_envs, n_steps, dt, frame_end, x);
-	}
-	// model variants: ONE launch of the variant kernels (dtrl_backend_hip_variants.hip) over the list as it stands -- the group's costliest-first order is kept
-	// across variants. DTRL_VARIANTS_FALLBACK=1 takes the per-variant default instead (A/B and cross-check)
-	bool LaunchVariants(const RunParams& rp, const DevBuffers& buf, const VariantView& models, const int32_t* env_variant, int n_envs, int n_steps, real dt, bool frame_end) override
-	{
-		const char* fb = std::getenv("DTRL_VARIANTS_FALLBACK");   // (read per launch, like DTRL_KERNEL: a test switches it inside one process)
-		if (fb && std::atoi(fb) != 0) return Backend::LaunchVariants(rp, buf, models, env_variant, n_envs, n_steps, dt, frame_end);
-		FrameExtra x; x.models = models.dev; x.env_model = env_variant;
-		return LaunchFrame(models.dev, rp, buf, n_envs, n_steps, dt, frame_end, x);
 	}
 	bool SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs, int n_slots, SlotSums* sums, int slot_base) override
 	{

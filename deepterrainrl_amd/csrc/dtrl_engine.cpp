@@ -119,8 +119,7 @@ Engine::~Engine()
 		be_->Sync();
 		for (Snapshot* s : snapshots_) { be_->Free(s->payload); s->payload = nullptr; s->owner = nullptr; }   // (the handles stay valid for dtrl_snapshot_info / _free)
 		be_->FreeHostStaging(snap_ids_);
-		be_->FreeHostStaging(slot_part_);
-		be_->FreeHostStaging(var_part_);
+		be_->FreeHostStaging(slot_keys_.part); be_->FreeHostStaging(variant_keys_.part);
 		if (ext_meta_) be_->FreeHostStaging(ext_meta_);
 		for (void* p : allocs_) be_->Free(p);
 		for (void* p : host_allocs_) be_->FreeHostStaging(p);
@@ -366,17 +365,12 @@ int Engine::LaunchGroup(int group, int n_steps, double dt_step, bool frame_end)
 // every launch of the frame kernels after the batch's creation comes through here: a batch without slots and without variants launches exactly as it always did
 bool Engine::LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, bool frame_end, const int32_t* list_host, int part_off)
 {
-	if (!var_models_.empty()) {   // (variants and slots exclude each other: dtrl_variants_create / dtrl_slots_create)
-		VariantView m;
-		m.dev = d_var_models_; m.n_variants = static_cast<int32_t>(var_models_.size());
-		m.env_variant_host = env_var_.data(); m.env_list_host = list_host; m.part = var_part_ + part_off;
-		return be_->LaunchVariants(cfg_.run, b, m, d_env_var_, n_envs, n_steps, dt, frame_end);
-	}
-	if (slots_.empty()) return be_->Launch(d_model_, cfg_.run, b, n_envs, n_steps, dt, frame_end);
-	SlotView v;
-	v.dev = d_slot_table_; v.host = slot_table_.data(); v.n_slots = static_cast<int32_t>(slots_.size());
-	v.env_slot_host = env_slot_.data(); v.env_list_host = list_host; v.part = slot_part_ + part_off;
-	return be_->LaunchSlots(d_model_, cfg_.run, b, v, d_env_slot_, n_envs, n_steps, dt, frame_end);
+	const bool variants = !var_models_.empty();   // (variants and slots exclude each other: dtrl_variants_create / dtrl_slots_create)
+	if (!variants && slots_.empty()) return be_->Launch(d_model_, cfg_.run, b, n_envs, n_steps, dt, frame_end);
+	EnvKeyView v = (variants ? variant_keys_ : slot_keys_).View(list_host, part_off);
+	if (variants) v.models_dev = d_var_models_;
+	else { v.slots_dev = d_slot_table_; v.slots_host = slot_table_.data(); }
+	return be_->LaunchKeyed(variants ? d_var_models_ : d_model_, cfg_.run, b, v, n_envs, n_steps, dt, frame_end);
 }
 
 int Engine::UploadTerrainCfg(const double* params)
@@ -1748,19 +1742,78 @@ int Engine::ExtEnvInfo(const int32_t* env_ids, int n, int32_t* park, int32_t* st
 	return DTRL_OK;
 }
 
+// ---- per-env keys: what policy slots and model variants share (dtrl_engine.h EnvAssignment) ----
+void* Engine::KeysAllocate(EnvAssignment& a, size_t table_bytes)
+{
+	void* table = be_->Alloc(table_bytes); if (table) allocs_.push_back(table);
+	a.d_env_key = static_cast<int32_t*>(be_->Alloc(sizeof(int32_t) * n_)); if (a.d_env_key) allocs_.push_back(a.d_env_key);   // (zero-filled: every env starts under key 0)
+	a.part = static_cast<int32_t*>(be_->HostStaging(sizeof(int32_t) * 2 * static_cast<size_t>(n_)));
+	if (!table || !a.d_env_key || !a.part || !be_->Sync()) { Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error()); return nullptr; }
+	a.env_key.assign(static_cast<size_t>(n_), 0);
+	return table;
+}
+
+// The order of the checks is part of the behaviour: no keys, key out of range, frame in flight. dtrl_slot_stats is the one call that waits for a frame in
+// flight instead of refusing it (wait_in_flight): train_loop's overlapped loop logs its greedy envs through it while the next frame runs, as it does with
+// dtrl_eval_stats. dtrl_variant_stats refuses like every other variant call; nothing is known to need either behaviour of the other family, so both stay.
+int Engine::KeysIdle(const EnvAssignment& a, const char* what, int key, bool wait_in_flight)
+{
+	if (a.filled.empty()) return Fail(DTRL_ERR_ARG, std::string(what) + ": " + a.none_text);
+	if (key < 0 || key >= a.n_keys()) return Fail(DTRL_ERR_ARG, std::string(what) + ": " + a.noun + " " + std::to_string(key) + " out of range (0 .. " + std::to_string(a.n_keys() - 1) + ")");
+	if (!wait_in_flight) return RequireIdle(std::string(what) + kFrameInFlight);
+	be_->SelectStream(0);
+	return be_->Sync() ? DTRL_OK : Fail(DTRL_ERR_DEVICE, be_->error());
+}
+
+int Engine::KeysAssign(EnvAssignment& a, const char* what, const int32_t* env_ids, int n, const int32_t* keys)
+{
+	int rc = KeysIdle(a, what, 0);
+	if (rc != DTRL_OK) return rc;
+	const std::string w = std::string(what) + ": ";
+	if (n < 0 || n > n_ || (n > 0 && !keys)) return Fail(DTRL_ERR_ARG, w + a.noun + "s is required and the env count must be 0 .. num_envs");
+	for (int i = 0; i < n; ++i) {   // all or nothing
+		const int e = EnvIndex(env_ids, i), k = keys[i];
+		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range; nothing assigned");
+		if (k < 0 || k >= a.n_keys()) return Fail(DTRL_ERR_ARG, w + a.noun + " " + std::to_string(k) + " out of range (0 .. " + std::to_string(a.n_keys() - 1) + "); nothing assigned");
+		if (!a.filled[k]) return Fail(DTRL_ERR_ARG, w + a.noun + " " + std::to_string(k) + " " + a.empty_text + "; nothing assigned");
+	}
+	for (int i = 0; i < n; ++i) a.env_key[EnvIndex(env_ids, i)] = keys[i];
+	if (!be_->H2D(a.d_env_key, a.env_key.data(), sizeof(int32_t) * a.env_key.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::KeysGet(const EnvAssignment& a, const char* what, const int32_t* env_ids, int n, int32_t* keys_out)
+{
+	const std::string w = std::string(what) + ": ";
+	if (a.filled.empty()) return Fail(DTRL_ERR_ARG, w + a.none_text);
+	if (n < 0 || n > n_ || (n > 0 && !keys_out)) return Fail(DTRL_ERR_ARG, w + a.noun + "s_out is required and the env count must be 0 .. num_envs");
+	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range"); }
+	for (int i = 0; i < n; ++i) keys_out[i] = a.env_key[EnvIndex(env_ids, i)];
+	return DTRL_OK;
+}
+
+// Backend::SlotReduce over the family's per-env array; its kernels are sized by kMaxSlots, so the window of kMaxSlots keys that holds `key` (policy slots: the one window)
+int Engine::KeysStats(const EnvAssignment& a, const char* what, bool wait_in_flight, int key, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets)
+{
+	if (int rc = KeysIdle(a, what, key, wait_in_flight); rc != DTRL_OK) return rc;
+	const int base = key / kMaxSlots * kMaxSlots, cnt = std::min(kMaxSlots, a.n_keys() - base);
+	SlotSums sums[kMaxSlots];
+	if (!be_->SlotReduce(buf_.st, a.d_env_key, n_, cnt, sums, base)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	const SlotSums& t = sums[key - base];
+	if (n_envs) *n_envs = t.n_envs;
+	if (avg_dist) *avg_dist = t.episodes > 0 ? t.dist_sum / static_cast<double>(t.episodes) : 0.0;
+	if (episodes) *episodes = t.episodes;
+	if (cycles) *cycles = t.cycles;
+	if (resets) *resets = t.resets;
+	return DTRL_OK;
+}
+
 // ---- policy slots (include/dtrl.h: dtrl_slots_create ... dtrl_slot_stats) ----
 // Two things keep a launch in flight from ever reading a half-written record. (1) The table and the per-env array change only in calls that refuse a frame in
-// flight and then wait for every stream (SlotsIdle) -- with dtrl_step_poll or -terrain_gen= device the host has not otherwise waited for the launches it queued.
+// flight and then wait for every stream (KeysIdle) -- with dtrl_step_poll or -terrain_gen= device the host has not otherwise waited for the launches it queued.
 // (2) What DOES change while launches run -- slot 0's weight buffer (the double-buffered hand-over) and dtrl_set_explore -- is not in the table at all: slot 0
 // and its aliases carry kSlotLaunchPolicy / kSlotLaunchExplore and take those values from the launch's own by-value arguments, exactly where the single-policy
 // kernels take them. So MarkWeightReader / WaitWeightReaders / WaitPolicyReady and the flip order a hand-over for slot 0 and for every alias of it at once.
-int Engine::SlotsIdle(const char* what, int slot)
-{
-	if (slots_.empty()) return Fail(DTRL_ERR_ARG, std::string(what) + ": the batch has no policy slots (call dtrl_slots_create first)");
-	if (slot < 0 || slot >= static_cast<int>(slots_.size())) return Fail(DTRL_ERR_ARG, std::string(what) + ": slot " + std::to_string(slot) + " out of range (0 .. " + std::to_string(slots_.size() - 1) + ")");
-	return RequireIdle(std::string(what) + kFrameInFlight);
-}
-
 int Engine::UploadSlotTable()
 {
 	for (size_t s = 0; s < slots_.size(); ++s) {
@@ -1787,24 +1840,21 @@ int Engine::SlotsCreate(int n_slots)
 		return Fail(DTRL_ERR_ARG, "dtrl_slots_create: the batch already has " + std::to_string(slots_.size()) + " slots; a second call with another count (" + std::to_string(n_slots) + ") is refused");
 	}
 	if (int rc = RequireIdle(std::string("dtrl_slots_create") + kFrameInFlight); rc != DTRL_OK) return rc;
-	d_slot_table_ = static_cast<SlotRec*>(be_->Alloc(sizeof(SlotRec) * n_slots)); if (d_slot_table_) allocs_.push_back(d_slot_table_);
-	d_env_slot_ = static_cast<int32_t*>(be_->Alloc(sizeof(int32_t) * n_)); if (d_env_slot_) allocs_.push_back(d_env_slot_);   // (zero-filled: every env starts in slot 0)
-	slot_part_ = static_cast<int32_t*>(be_->HostStaging(sizeof(int32_t) * 2 * static_cast<size_t>(n_)));
-	if (!d_slot_table_ || !d_env_slot_ || !slot_part_ || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+	d_slot_table_ = static_cast<SlotRec*>(KeysAllocate(slot_keys_, sizeof(SlotRec) * n_slots));
+	if (!d_slot_table_) return DTRL_ERR_DEVICE;
 	slots_.assign(static_cast<size_t>(n_slots), SlotHost());
-	slots_[0].set = true;
 	for (SlotHost& h : slots_) { h.enable_exp = cfg_.run.enable_exp; h.rate = cfg_.run.exp_rate; h.temp = cfg_.run.exp_temp; h.base_rate = cfg_.run.exp_base_rate; }   // every slot starts with the batch's exploration settings
 	slot_table_.assign(static_cast<size_t>(n_slots), SlotRec{});
-	env_slot_.assign(static_cast<size_t>(n_), 0);
 	int rc = UploadSlotTable();
 	if (rc != DTRL_OK) { slots_.clear(); return rc; }
+	slot_keys_.filled.assign(static_cast<size_t>(n_slots), 0); slot_keys_.filled[0] = 1;
 	return DTRL_OK;
 }
 
 int Engine::SlotSetPolicy(int slot, const float* w, size_t n, const double* io, const double* is, const double* oo, const double* os, bool device)
 {
 	const char* what = device ? "dtrl_slot_set_policy_device" : "dtrl_slot_set_policy";
-	int rc = SlotsIdle(what, slot);
+	int rc = KeysIdle(slot_keys_, what, slot);
 	if (rc != DTRL_OK) return rc;
 	if (slot == 0) return device ? SetPolicyDevice(w, n, io, is, oo, os) : SetPolicy(w, n, io, is, oo, os);
 	const NetDesc& d = cfg_.net;
@@ -1844,86 +1894,36 @@ int Engine::SlotSetPolicy(int slot, const float* w, size_t n, const double* io, 
 		ok = ok && be_->H2D(h.weights, dev_w.data(), sizeof(float) * dev_w.size());
 	}
 	if (!ok) return Fail(DTRL_ERR_DEVICE, be_->error());
-	h.set = true; h.alias = -1;
+	h.alias = -1; slot_keys_.filled[slot] = 1;
 	return UploadSlotTable();
 }
 
 int Engine::SlotAlias(int slot, int src_slot)
 {
-	int rc = SlotsIdle("dtrl_slot_alias", slot);
+	int rc = KeysIdle(slot_keys_, "dtrl_slot_alias", slot);
 	if (rc != DTRL_OK) return rc;
 	if (slot == 0) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: slot 0 is the batch's own policy and cannot be an alias");
 	if (src_slot < 0 || src_slot >= static_cast<int>(slots_.size())) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: source slot " + std::to_string(src_slot) + " out of range (0 .. " + std::to_string(slots_.size() - 1) + ")");
 	if (src_slot == slot) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: slot " + std::to_string(slot) + " cannot be an alias of itself");
-	if (!slots_[src_slot].set && slots_[src_slot].alias < 0) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: source slot " + std::to_string(src_slot) + " is empty (it has neither a policy nor an alias)");
+	if (!slot_keys_.filled[src_slot]) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: source slot " + std::to_string(src_slot) + " " + slot_keys_.empty_text);
 	for (int s = src_slot; s >= 0; s = slots_[s].alias) if (s == slot) return Fail(DTRL_ERR_ARG, "dtrl_slot_alias: slot " + std::to_string(src_slot) + " reads slot " + std::to_string(slot) + " itself: the alias would be an alias of itself");
-	slots_[slot].alias = src_slot; slots_[slot].set = false;
+	slots_[slot].alias = src_slot; slot_keys_.filled[slot] = 1;
 	return UploadSlotTable();
 }
 
 int Engine::SlotSetExplore(int slot, int enable, double rate, double temp, double base_rate)
 {
 	if (slot == 0 && !slots_.empty()) return SetExplore(enable, rate, temp, base_rate);   // (valid at any time, as dtrl_set_explore is: it travels by value with every launch)
-	int rc = SlotsIdle("dtrl_slot_set_explore", slot);
+	int rc = KeysIdle(slot_keys_, "dtrl_slot_set_explore", slot);
 	if (rc != DTRL_OK) return rc;
 	SlotHost& h = slots_[slot];
 	h.enable_exp = enable ? 1 : 0; h.rate = rate; h.temp = temp; h.base_rate = base_rate;
 	return UploadSlotTable();
 }
 
-int Engine::AssignSlots(const int32_t* env_ids, int n, const int32_t* slots)
-{
-	int rc = SlotsIdle("dtrl_assign_slots", 0);
-	if (rc != DTRL_OK) return rc;
-	if (n < 0 || n > n_ || (n > 0 && !slots)) return Fail(DTRL_ERR_ARG, "dtrl_assign_slots: slots is required and the env count must be 0 .. num_envs");
-	for (int i = 0; i < n; ++i) {   // all or nothing
-		const int e = EnvIndex(env_ids, i), s = slots[i];
-		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "dtrl_assign_slots: env id " + std::to_string(e) + " out of range; nothing assigned");
-		if (s < 0 || s >= static_cast<int>(slots_.size())) return Fail(DTRL_ERR_ARG, "dtrl_assign_slots: slot " + std::to_string(s) + " out of range (0 .. " + std::to_string(slots_.size() - 1) + "); nothing assigned");
-		if (!slots_[s].set && slots_[s].alias < 0) return Fail(DTRL_ERR_ARG, "dtrl_assign_slots: slot " + std::to_string(s) + " is empty (it has neither a policy nor an alias); nothing assigned");
-	}
-	for (int i = 0; i < n; ++i) env_slot_[EnvIndex(env_ids, i)] = slots[i];
-	if (!be_->H2D(d_env_slot_, env_slot_.data(), sizeof(int32_t) * env_slot_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
-}
-
-int Engine::GetSlots(const int32_t* env_ids, int n, int32_t* slots_out)
-{
-	if (slots_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_get_slots: the batch has no policy slots (call dtrl_slots_create first)");
-	if (n < 0 || n > n_ || (n > 0 && !slots_out)) return Fail(DTRL_ERR_ARG, "dtrl_get_slots: slots_out is required and the env count must be 0 .. num_envs");
-	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "dtrl_get_slots: env id " + std::to_string(e) + " out of range"); }
-	for (int i = 0; i < n; ++i) slots_out[i] = env_slot_[EnvIndex(env_ids, i)];
-	return DTRL_OK;
-}
-
-int Engine::SlotStats(int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets)
-{
-	if (slots_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_slot_stats: the batch has no policy slots (call dtrl_slots_create first)");
-	if (slot < 0 || slot >= static_cast<int>(slots_.size())) return Fail(DTRL_ERR_ARG, "dtrl_slot_stats: slot " + std::to_string(slot) + " out of range (0 .. " + std::to_string(slots_.size() - 1) + ")");
-	be_->SelectStream(0);
-	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
-	SlotSums sums[kMaxSlots];
-	if (!be_->SlotReduce(buf_.st, d_env_slot_, n_, static_cast<int>(slots_.size()), sums, 0)) return Fail(DTRL_ERR_DEVICE, be_->error());
-	const SlotSums& a = sums[slot];
-	if (n_envs) *n_envs = a.n_envs;
-	if (avg_dist) *avg_dist = a.episodes > 0 ? a.dist_sum / static_cast<double>(a.episodes) : 0.0;
-	if (episodes) *episodes = a.episodes;
-	if (cycles) *cycles = a.cycles;
-	if (resets) *resets = a.resets;
-	return DTRL_OK;
-}
-
 // ---- model variants (include/dtrl.h: dtrl_variants_create ... dtrl_variant_stats) ----
-// The timing rules are those of the slot calls: the table and the per-env array are read by launches in flight, so every call that rewrites them refuses a frame
-// in flight and then waits for every stream (VariantsIdle). Nothing of a variant changes while launches run: unlike slot 0's weights, the batch's own model is
+// The timing rules are those of the slot calls (KeysIdle). Nothing of a variant changes while launches run: unlike slot 0's weights, the batch's own model is
 // fixed at creation, so the table holds a plain copy of it as record 0 and no launch argument has to stand in for a table entry.
-int Engine::VariantsIdle(const char* what, int v)
-{
-	if (var_models_.empty()) return Fail(DTRL_ERR_ARG, std::string(what) + ": the batch has no model variants (call dtrl_variants_create first)");
-	if (v < 0 || v >= static_cast<int>(var_models_.size())) return Fail(DTRL_ERR_ARG, std::string(what) + ": variant " + std::to_string(v) + " out of range (0 .. " + std::to_string(var_models_.size() - 1) + ")");
-	return RequireIdle(std::string(what) + kFrameInFlight);
-}
-
 int Engine::VariantsCreate(int n_variants)
 {
 	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, "dtrl_variants_create: not available with -policy_mode= external (model variants together with external policy mode are not supported)");
@@ -1931,14 +1931,11 @@ int Engine::VariantsCreate(int n_variants)
 	if (!var_models_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_variants_create: the batch already has " + std::to_string(var_models_.size()) + " variants; it is called once per batch");
 	if (n_variants < 1 || n_variants > n_) return Fail(DTRL_ERR_ARG, "dtrl_variants_create: n_variants must be 1 .. num_envs (" + std::to_string(n_) + "), not " + std::to_string(n_variants));
 	if (int rc = RequireIdle(std::string("dtrl_variants_create") + kFrameInFlight); rc != DTRL_OK) return rc;
-	d_var_models_ = static_cast<DevModel*>(be_->Alloc(sizeof(DevModel) * static_cast<size_t>(n_variants))); if (d_var_models_) allocs_.push_back(d_var_models_);
-	d_env_var_ = static_cast<int32_t*>(be_->Alloc(sizeof(int32_t) * n_)); if (d_env_var_) allocs_.push_back(d_env_var_);   // (zero-filled: every env starts in variant 0)
-	var_part_ = static_cast<int32_t*>(be_->HostStaging(sizeof(int32_t) * 2 * static_cast<size_t>(n_)));
-	if (!d_var_models_ || !d_env_var_ || !var_part_ || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+	d_var_models_ = static_cast<DevModel*>(KeysAllocate(variant_keys_, sizeof(DevModel) * static_cast<size_t>(n_variants)));
+	if (!d_var_models_) return DTRL_ERR_DEVICE;
 	if (!be_->H2D(d_var_models_, &cfg_.model, sizeof(DevModel))) return Fail(DTRL_ERR_DEVICE, be_->error());
 	var_models_.assign(static_cast<size_t>(n_variants), cfg_.model);   // (an empty variant holds the batch's model until it is loaded; it cannot be assigned)
-	var_set_.assign(static_cast<size_t>(n_variants), 0); var_set_[0] = 1;
-	env_var_.assign(static_cast<size_t>(n_), 0);
+	variant_keys_.filled.assign(static_cast<size_t>(n_variants), 0); variant_keys_.filled[0] = 1;
 	return DTRL_OK;
 }
 
@@ -1958,7 +1955,7 @@ static const char* VariantMisfit(const DevModel& a, const DevModel& b)
 int Engine::VariantLoad(int v, const char* character_file, const char* text, size_t bytes)
 {
 	const char* what = text ? "dtrl_variant_load_json" : "dtrl_variant_load_file";
-	int rc = VariantsIdle(what, v);
+	int rc = KeysIdle(variant_keys_, what, v);
 	if (rc != DTRL_OK) return rc;
 	if (v == 0) return Fail(DTRL_ERR_ARG, std::string(what) + ": variant 0 is the batch's own model and cannot be replaced");
 	std::string doc; CharSource src;
@@ -1987,53 +1984,7 @@ int Engine::VariantLoad(int v, const char* character_file, const char* text, siz
 	if (const char* f = VariantMisfit(vc.model, cfg_.model))
 		return Fail(DTRL_ERR_ARG, std::string(what) + ": variant " + std::to_string(v) + " does not fit the batch: " + f + " differs from the batch's model (the skeleton, the scene and the controller part -- parameters, actions, default action -- are one per batch)");
 	if (!be_->H2D(d_var_models_ + v, &vc.model, sizeof(DevModel))) return Fail(DTRL_ERR_DEVICE, be_->error());
-	var_models_[v] = vc.model; var_set_[v] = 1;
-	return DTRL_OK;
-}
-
-int Engine::AssignVariants(const int32_t* env_ids, int n, const int32_t* variants)
-{
-	int rc = VariantsIdle("dtrl_assign_variants", 0);
-	if (rc != DTRL_OK) return rc;
-	if (n < 0 || n > n_ || (n > 0 && !variants)) return Fail(DTRL_ERR_ARG, "dtrl_assign_variants: variants is required and the env count must be 0 .. num_envs");
-	const int cnt = n;
-	for (int i = 0; i < cnt; ++i) {
-		const int e = EnvIndex(env_ids, i), v = variants[i];
-		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "dtrl_assign_variants: env id " + std::to_string(e) + " out of range; nothing assigned");
-		if (v < 0 || v >= static_cast<int>(var_models_.size())) return Fail(DTRL_ERR_ARG, "dtrl_assign_variants: variant " + std::to_string(v) + " out of range (0 .. " + std::to_string(var_models_.size() - 1) + "); nothing assigned");
-		if (!var_set_[v]) return Fail(DTRL_ERR_ARG, "dtrl_assign_variants: variant " + std::to_string(v) + " is empty (no dtrl_variant_load_* has filled it); nothing assigned");
-	}
-	for (int i = 0; i < cnt; ++i) env_var_[EnvIndex(env_ids, i)] = variants[i];
-	if (!be_->H2D(d_env_var_, env_var_.data(), sizeof(int32_t) * env_var_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
-}
-
-int Engine::GetVariants(const int32_t* env_ids, int n, int32_t* variants_out)
-{
-	if (var_models_.empty()) return Fail(DTRL_ERR_ARG, "dtrl_get_variants: the batch has no model variants (call dtrl_variants_create first)");
-	const int cnt = n;
-	if (cnt < 0 || cnt > n_ || (cnt > 0 && !variants_out)) return Fail(DTRL_ERR_ARG, "dtrl_get_variants: variants_out is required and the env count must be 0 .. num_envs");
-	for (int i = 0; i < cnt; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "dtrl_get_variants: env id " + std::to_string(e) + " out of range"); }
-	for (int i = 0; i < cnt; ++i) variants_out[i] = env_var_[EnvIndex(env_ids, i)];
-	return DTRL_OK;
-}
-
-// Backend::SlotReduce with the variant array in place of the slot array; its kernels are sized by kMaxSlots, so the window of kMaxSlots variants that holds `v`
-int Engine::VariantStats(int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets)
-{
-	const int nv = static_cast<int>(var_models_.size());
-	if (nv == 0) return Fail(DTRL_ERR_ARG, "dtrl_variant_stats: the batch has no model variants (call dtrl_variants_create first)");
-	if (v < 0 || v >= nv) return Fail(DTRL_ERR_ARG, "dtrl_variant_stats: variant " + std::to_string(v) + " out of range (0 .. " + std::to_string(nv - 1) + ")");
-	if (int rc = RequireIdle(std::string("dtrl_variant_stats") + kFrameInFlight); rc != DTRL_OK) return rc;
-	const int base = v / kMaxSlots * kMaxSlots, cnt = std::min(kMaxSlots, nv - base);
-	SlotSums sums[kMaxSlots];
-	if (!be_->SlotReduce(buf_.st, d_env_var_, n_, cnt, sums, base)) return Fail(DTRL_ERR_DEVICE, be_->error());
-	const SlotSums& a = sums[v - base];
-	if (n_envs) *n_envs = a.n_envs;
-	if (avg_dist) *avg_dist = a.episodes > 0 ? a.dist_sum / static_cast<double>(a.episodes) : 0.0;
-	if (episodes) *episodes = a.episodes;
-	if (cycles) *cycles = a.cycles;
-	if (resets) *resets = a.resets;
+	var_models_[v] = vc.model; variant_keys_.filled[v] = 1;
 	return DTRL_OK;
 }
 

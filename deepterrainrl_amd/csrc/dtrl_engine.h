@@ -40,41 +40,30 @@ DTRL_HD_INLINE void slot_patch(const SlotRec& r, RunParams& rp, DevBuffers& buf)
 	if (!(r.flags & kSlotLaunchPolicy)) { buf.weights = r.weights; buf.in_off = r.in_off; buf.in_scale = r.in_scale; buf.out_off = r.out_off; buf.out_scale = r.out_scale; }
 	if (!(r.flags & kSlotLaunchExplore)) { rp.enable_exp = r.enable_exp; rp.exp_rate = r.exp_rate; rp.exp_temp = r.exp_temp; rp.exp_base_rate = r.exp_base_rate; }
 }
-// what a slotted launch is given: the table as the kernels read it (device memory) and as the host loops read it, the same for the per-env slot array (indexed
-// by local env id), and what the per-slot default needs to split a launch list: the list in host-readable form (nullptr: it exists on the device only and is
-// read back; ignored when the launch has no list) and `part`, HostStaging() memory for the launch's n_envs entries regrouped by slot.
-struct SlotView {
-	const SlotRec* dev = nullptr; const SlotRec* host = nullptr; int32_t n_slots = 0;
-	const int32_t* env_slot_host = nullptr;
+// what a launch over envs of several keys is given, a key being the env's policy slot or its model variant (the two exclude each other): the per-env key array
+// (indexed by local env id) as the kernels read it (device memory) and as the host loops read it, and what the per-key default needs to split a launch list:
+// the list in host-readable form (nullptr: it exists on the device only and is read back; ignored when the launch has no list) and `part`, HostStaging()
+// memory for the launch's n_envs entries regrouped by key. Policy slots add the slot table in both forms, model variants the table of complete DevModel
+// records (device memory; record 0 is a copy of the batch's own model); the other family's pointers stay null.
+struct EnvKeyView {
+	int32_t n_keys = 0;
+	const int32_t* env_key_dev = nullptr; const int32_t* env_key_host = nullptr;
 	const int32_t* env_list_host = nullptr;
 	int32_t* part = nullptr;
+	const SlotRec* slots_dev = nullptr; const SlotRec* slots_host = nullptr;
+	const DevModel* models_dev = nullptr;
 };
 // per-slot totals of dtrl_slot_stats (Backend::SlotReduce): envs in the slot, and over them the sums dtrl_eval_stats takes over the batch
 struct SlotSums { int64_t n_envs, episodes, cycles, resets; double dist_sum; };   // dist_sum = sum of avg_dist * num_episodes
 
-// ---- model variants (include/dtrl.h: dtrl_variants_create ...) ----
-// what a launch over envs of several character models is given: the table of complete DevModel records (device memory; record 0 is a copy of the batch's own
-// model) and the per-env variant array (indexed by local env id) in host-readable form, and what the per-variant default needs to split a launch list:
-// env_list_host / part as in SlotView.
-struct VariantView {
-	const DevModel* dev = nullptr; int32_t n_variants = 0;
-	const int32_t* env_variant_host = nullptr;
-	const int32_t* env_list_host = nullptr;
-	int32_t* part = nullptr;
-};
-
 class Backend {
 public:
 	virtual ~Backend() {}
-	// A launch over envs of several model variants (env e runs under models.dev[env_variant[e]]; env_variant is device memory). The default is one Launch per
-	// non-empty variant over that variant's part of the launch list with that variant's record as `gm`, list order kept inside a variant (what the lane-loop check
-	// build runs, and DTRL_VARIANTS_FALLBACK=1 on HIP; it waits for the selected stream before it reuses models.part). The HIP backend overrides it with ONE
-	// launch of the variant kernels (dtrl_backend_hip_variants.hip).
-	virtual bool LaunchVariants(const RunParams& rp, const DevBuffers& buf, const VariantView& models, const int32_t* env_variant, int n_envs, int n_steps, real dt, bool frame_end);
-	// A launch over envs of several policy slots (env e runs slot env_slot[e]'s record patched over rp / buf: slot_patch). The default is one Launch per
-	// non-empty slot over that slot's part of the launch list, list order kept inside a slot (what the lane-loop check build runs, and DTRL_SLOTS_FALLBACK=1 on
-	// HIP; it waits for the selected stream before it reuses slots.part). The HIP backend overrides it with ONE launch of the slot kernels (dtrl_backend_hip_slots.hip).
-	virtual bool LaunchSlots(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const SlotView& slots, const int32_t* env_slot, int n_envs, int n_steps, real dt, bool frame_end);
+	// A launch over envs of several keys: env e runs slot keys.env_key[e]'s record patched over rp / buf (slot_patch), or under the model keys.models_dev[keys.env_key[e]]
+	// (gm is then record 0). The default is one Launch per non-empty key over that key's part of the launch list, list order kept inside a key (what the lane-loop
+	// check build runs, and DTRL_SLOTS_FALLBACK=1 / DTRL_VARIANTS_FALLBACK=1 on HIP; it waits for the selected stream before it reuses keys.part). The HIP backend
+	// overrides it with ONE launch of the family's kernels (dtrl_backend_hip_slots.hip, dtrl_backend_hip_variants.hip).
+	virtual bool LaunchKeyed(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const EnvKeyView& keys, int n_envs, int n_steps, real dt, bool frame_end);
 	// sums[s] for s < n_slots (<= kMaxSlots) over the envs e < n_envs with env_slot[e] == slot_base + s (an env outside the window counts nowhere: the per-variant
 	// statistics take a table of any size in windows of kMaxSlots); st / env_slot are device memory, sums host memory. Synchronised. The default is a
 	// host loop over a D2H of the records; the HIP backend reduces on the device (two launches, fixed summation order: the same bytes from call to call)
@@ -99,8 +88,6 @@ public:
 	virtual bool ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labels, const int32_t* ids, int n, const int32_t* action_ids, const void* params, bool f32, const uint32_t* flags, bool apply, int32_t* rejected);
 	virtual double ExtLaunchMs(int which) { (void)which; return -1.0; }   // device time of the collection (0) / scatter (1) launches since the last call (HIP events)
 	virtual double SnapLaunchMs() { return -1.0; }   // device time of the snapshot launches since the last call (HIP events; -1: this backend launches nothing)
-	// the list splitting LaunchSlots' and LaunchVariants' defaults share (dtrl_backend_defaults.cpp)
-	bool SplitLaunchList(const DevBuffers& buf, int n_envs, const int32_t* list_host, const int32_t* key_of_env, int n_keys, int32_t* part, std::vector<int32_t>& n_of);
 	virtual bool Init(int device_id, std::string& err) = 0;
 	// -reserve_cus= k (before Init): keep k compute units per XCD out of the frame launches (HIP backend; see dtrl_side_stream in include/dtrl.h)
 	virtual void SetReserveCus(int) {}
@@ -211,18 +198,19 @@ public:
 	int SlotSetPolicy(int slot, const float* w, size_t n, const double* io, const double* is, const double* oo, const double* os, bool device);
 	int SlotAlias(int slot, int src_slot);
 	int SlotSetExplore(int slot, int enable, double rate, double temp, double base_rate);
-	int AssignSlots(const int32_t* env_ids, int n, const int32_t* slots);
-	int GetSlots(const int32_t* env_ids, int n, int32_t* slots_out);
-	int SlotStats(int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+	int AssignSlots(const int32_t* env_ids, int n, const int32_t* slots) { return KeysAssign(slot_keys_, "dtrl_assign_slots", env_ids, n, slots); }
+	int GetSlots(const int32_t* env_ids, int n, int32_t* slots_out) { return KeysGet(slot_keys_, "dtrl_get_slots", env_ids, n, slots_out); }
+	// (the one asymmetry of the two families: dtrl_slot_stats WAITS for a frame in flight, dtrl_variant_stats REFUSES one -- DESIGN 6d)
+	int SlotStats(int slot, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) { return KeysStats(slot_keys_, "dtrl_slot_stats", true, slot, n_envs, avg_dist, episodes, cycles, resets); }
 	// model variants (include/dtrl.h)
 	int VariantsCreate(int n_variants);
 	int VariantLoad(int v, const char* character_file, const char* text, size_t bytes);   // text == nullptr: the file, resolved like -character_file=
-	int AssignVariants(const int32_t* env_ids, int n, const int32_t* variants);
-	int GetVariants(const int32_t* env_ids, int n, int32_t* variants_out);
-	int VariantStats(int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+	int AssignVariants(const int32_t* env_ids, int n, const int32_t* variants) { return KeysAssign(variant_keys_, "dtrl_assign_variants", env_ids, n, variants); }
+	int GetVariants(const int32_t* env_ids, int n, int32_t* variants_out) { return KeysGet(variant_keys_, "dtrl_get_variants", env_ids, n, variants_out); }
+	int VariantStats(int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) { return KeysStats(variant_keys_, "dtrl_variant_stats", false, v, n_envs, avg_dist, episodes, cycles, resets); }
 	int num_variants() const { return static_cast<int>(var_models_.size()); }
 	// the model env e (local id, in range) runs under: what host-side readers of per-env geometry use (dtrl_get_link_states, AddPerturb)
-	const DevModel& ModelOf(int e) const { return var_models_.empty() ? cfg_.model : var_models_[env_var_[e]]; }
+	const DevModel& ModelOf(int e) const { return var_models_.empty() ? cfg_.model : var_models_[variant_keys_.env_key[e]]; }
 	~Engine();
 	int Create(const char* const* argv, int argc, int num_envs, int device_id);
 	int Reset(const int32_t* env_ids, int n, const uint64_t* seeds);
@@ -356,27 +344,37 @@ private:
 	int32_t* d_ext_ids_ = nullptr;                         // device [n]
 	double* d_ext_states_ = nullptr;                       // device [n][S] (host call)
 	int32_t* d_ext_action_ids_ = nullptr; uint32_t* d_ext_flags_ = nullptr; double* d_ext_params_ = nullptr;   // device [n], [n], [n][n_opt]: the rows of a host call
-	// policy slots. Slot 0 is the batch's policy (buf_'s five pointers, cfg_.run's exploration); a slot >= 1 owns storage (own_[s]) or is an alias (alias_[s] >= 0).
-	// The table and the per-env array are rewritten only by calls that have refused a frame in flight and waited for every stream (SlotsIdle)
-	struct SlotHost { float* weights = nullptr; real* norm[4] = {nullptr, nullptr, nullptr, nullptr}; int alias = -1; bool set = false; int enable_exp = 0; double rate = 0, temp = 1, base_rate = 0; };
-	std::vector<SlotHost> slots_;            // empty: no slots, every launch is Backend::Launch as it always was
-	std::vector<SlotRec> slot_table_;        // host form of the table
-	std::vector<int32_t> env_slot_;          // host form of the per-env array
-	SlotRec* d_slot_table_ = nullptr; int32_t* d_env_slot_ = nullptr; int32_t* slot_part_ = nullptr;   // device table [n_slots], device array [n], page-locked [2 n]
-	int SlotsIdle(const char* what, int slot);   // DTRL_ERR_ARG without slots / slot out of range / frame in flight, else every stream idle
+	// Per-env keys: what policy slots and model variants share (at most one of the two is live). A key is a slot or a variant number; every env starts under
+	// key 0. The family's table and the per-env array are read by launches in flight and are therefore rewritten only by calls that have refused a frame in flight and
+	// waited for every stream (KeysIdle). The three texts are the family's own words in the refusals (they differ in more than the noun).
+	struct EnvAssignment {
+		const char* noun; const char* none_text; const char* empty_text;
+		std::vector<char> filled;                // per key: it may be assigned. Empty: the family was not created, every launch is Backend::Launch as it always was
+		std::vector<int32_t> env_key;            // host form of the per-env array
+		int32_t* d_env_key = nullptr; int32_t* part = nullptr;   // device array [n], page-locked [2 n] (the scratch of the per-key default's list split)
+		int n_keys() const { return static_cast<int>(filled.size()); }
+		EnvKeyView View(const int32_t* list_host, int part_off) const { EnvKeyView v; v.n_keys = n_keys(); v.env_key_dev = d_env_key; v.env_key_host = env_key.data(); v.env_list_host = list_host; v.part = part + part_off; return v; }
+	};
+	void* KeysAllocate(EnvAssignment& a, size_t table_bytes);   // the family's device table (returned; nullptr: failed, error set), the per-env array and the scratch
+	// DTRL_ERR_ARG without keys / key out of range / frame in flight, else every stream idle. wait_in_flight (dtrl_slot_stats alone): a frame in flight is waited for
+	int KeysIdle(const EnvAssignment& a, const char* what, int key, bool wait_in_flight = false);
+	int KeysAssign(EnvAssignment& a, const char* what, const int32_t* env_ids, int n, const int32_t* keys);   // all or nothing
+	int KeysGet(const EnvAssignment& a, const char* what, const int32_t* env_ids, int n, int32_t* keys_out);
+	int KeysStats(const EnvAssignment& a, const char* what, bool wait_in_flight, int key, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+	// policy slots. Slot 0 is the batch's policy (buf_'s five pointers, cfg_.run's exploration); a slot >= 1 owns storage (weights) or is an alias (alias >= 0) or is empty
+	struct SlotHost { float* weights = nullptr; real* norm[4] = {nullptr, nullptr, nullptr, nullptr}; int alias = -1; int enable_exp = 0; double rate = 0, temp = 1, base_rate = 0; };
+	EnvAssignment slot_keys_{"slot", "the batch has no policy slots (call dtrl_slots_create first)", "is empty (it has neither a policy nor an alias)"};
+	std::vector<SlotHost> slots_;            // empty: no slots
+	std::vector<SlotRec> slot_table_; SlotRec* d_slot_table_ = nullptr;   // the table: host form, device memory [n_slots]
 	int SlotRoot(int slot) const { while (slots_[slot].alias >= 0) slot = slots_[slot].alias; return slot; }
 	int UploadSlotTable();
-	// every frame-kernel launch of the batch: Backend::Launch, or -- once slots exist -- Backend::LaunchSlots. list_host: b.env_list in host-readable form or
-	// nullptr; part_off: offset of the launch's scratch inside slot_part_
+	// every frame-kernel launch of the batch: Backend::Launch, or -- once slots or variants exist -- Backend::LaunchKeyed. list_host: b.env_list in host-readable
+	// form or nullptr; part_off: offset of the launch's scratch inside the family's `part`
 	bool LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, bool frame_end, const int32_t* list_host, int part_off);
-	// model variants. Variant 0 is the batch's own model; a variant >= 1 is empty until dtrl_variant_load_* fills it. Table and per-env array are rewritten only
-	// by calls that have refused a frame in flight and waited for every stream (VariantsIdle)
+	// model variants. Variant 0 is the batch's own model; a variant >= 1 is empty until dtrl_variant_load_* fills it
 	ArgParser args_;                         // the creation arguments (command line + arg file): a variant is loaded through them with another character description
-	std::vector<DevModel> var_models_;       // empty: no variants, every launch is Backend::Launch (or LaunchSlots) as it always was
-	std::vector<char> var_set_;
-	std::vector<int32_t> env_var_;           // host form of the per-env array
-	DevModel* d_var_models_ = nullptr; int32_t* d_env_var_ = nullptr; int32_t* var_part_ = nullptr;   // device table [n_variants], device array [n], page-locked [2 n]
-	int VariantsIdle(const char* what, int v);   // DTRL_ERR_ARG without variants / variant out of range / frame in flight, else every stream idle
+	EnvAssignment variant_keys_{"variant", "the batch has no model variants (call dtrl_variants_create first)", "is empty (no dtrl_variant_load_* has filled it)"};
+	std::vector<DevModel> var_models_; DevModel* d_var_models_ = nullptr;   // the table: host form (empty: no variants), device memory [n_variants]
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

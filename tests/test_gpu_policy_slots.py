@@ -51,6 +51,10 @@ def test_refusals(da, om):
     T.test_refusals(da, om)
 
 
+def test_slot_stats_waits_for_a_frame_in_flight(da, om):
+    T.test_slot_stats_waits_for_a_frame_in_flight(da, om)
+
+
 def test_batch_without_slots_launches_as_before(da, om):
     T.test_batch_without_slots_launches_as_before(da, om)
 

@@ -1,7 +1,7 @@
 """Model variants (include/dtrl.h dtrl_variants_create ...): several character models in one batch, one per env. The yardstick is always the single-model path:
 env e of a K-variant batch, sitting in variant v, must equal -- bit for bit, every field of its EnvState record, its policy state, its ground window and build
 count -- env e of a plain batch of the same size, arguments and seeds that was created with variant v's character file and continues from the same state.
-Runs on the lane-loop check build of the kernel source (tests/emul: the per-variant default of Backend::LaunchVariants); tests/test_gpu_model_variants.py points
+Runs on the lane-loop check build of the kernel source (tests/emul: the per-key default of Backend::LaunchKeyed); tests/test_gpu_model_variants.py points
 `Scenario` at the product library (one launch of the variant kernels). The variant character files are written at run time from the committed nominal ones."""
 import copy
 import json

@@ -1,7 +1,7 @@
 """Policy slots (include/dtrl.h dtrl_slots_create ...): several policies in one batch, one per env. The yardstick is always the single-policy path: env e of a
 K-slot batch, sitting in slot s, must equal -- bit for bit, every field of its EnvState record, its policy state, its ground window and build count -- env e of a
 single-policy batch of the same size, arguments and seeds that runs slot s's policy and exploration.
-Runs on the lane-loop check build of the kernel source (tests/emul: the per-slot default of Backend::LaunchSlots); tests/test_gpu_policy_slots.py points `Scenario`
+Runs on the lane-loop check build of the kernel source (tests/emul: the per-key default of Backend::LaunchKeyed); tests/test_gpu_policy_slots.py points `Scenario`
 at the product library (one launch of the slot kernels)."""
 import numpy as np
 import pytest
@@ -294,6 +294,17 @@ def test_refusals(da, om, n=4):
     b.AssignSlots([1, 3], [1, 2])
     assert list(b.GetSlots()) == [0, 1, 0, 2]
     b.Update()
+
+
+def test_slot_stats_waits_for_a_frame_in_flight(da, om, n=4):
+    """7b. The one asymmetry between slots and variants: between UpdateBegin and UpdateEnd dtrl_slot_stats is not refused -- it waits for the frame and
+    answers, every env counted once -- where dtrl_variant_stats is refused (test_model_variants.test_refusals). AssignSlots in the same window is refused."""
+    b = slotted(DOG, n, policies(om, DOG)[:2], EXPLORE[:2], [e % 2 for e in range(n)], dict(terrain_seed=11))
+    b.UpdateBegin()
+    got = [b.SlotStats(s) for s in range(2)]
+    refused(da, lambda: b.AssignSlots(None, [0] * n), "dtrl_step_begin")
+    b.UpdateEnd()
+    assert got[0]["n_envs"] + got[1]["n_envs"] == n, got
 
 
 def test_batch_without_slots_launches_as_before(da, om, n=6, frames=30):
