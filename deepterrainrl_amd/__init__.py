@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "dtrl_snapshot_save", "dtrl_snapshot_restore", "dtrl_clone_envs", "dtrl_snapshot_export", "dtrl_snapshot_import", "dtrl_snapshot_info", "dtrl_snapshot_free",
     "dtrl_slots_create", "dtrl_slot_set_policy", "dtrl_slot_set_policy_device", "dtrl_slot_alias", "dtrl_slot_set_explore", "dtrl_assign_slots", "dtrl_get_slots", "dtrl_slot_stats",
     "dtrl_variants_create", "dtrl_variant_load_file", "dtrl_variant_load_json", "dtrl_assign_variants", "dtrl_get_variants", "dtrl_variant_stats",
+    "dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
 
@@ -159,6 +160,13 @@ def _bind(path):
     L.dtrl_assign_variants.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_get_variants.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_variant_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.dtrl_terrains_create.argtypes = [vp, C.c_int]
+    L.dtrl_terrain_set_file.argtypes = [vp, C.c_int, C.c_char_p, C.c_double]
+    L.dtrl_terrain_set_params.argtypes = [vp, C.c_int, C.c_char_p, vp]
+    L.dtrl_terrain_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, vp, C.POINTER(C.c_int)]
+    L.dtrl_assign_terrains.argtypes = [vp, vp, C.c_int, vp, C.c_int]
+    L.dtrl_get_terrains.argtypes = [vp, vp, C.c_int, vp]
+    L.dtrl_terrain_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dtrl_last_error.restype = C.c_char_p
     L.dtrl_last_error.argtypes = [vp]
     L.dtrl_version.restype = C.c_char_p
@@ -325,12 +333,12 @@ class BatchScenario:
         a = np.ascontiguousarray(env_ids, np.int32)
         return a, len(a)
 
-    def _assign_keys(self, fn, who, noun, env_ids, keys):   # the ctypes marshalling policy slots and model variants share; fn: the family's entry point
+    def _assign_keys(self, fn, who, noun, env_ids, keys, *more):   # the ctypes marshalling policy slots, model variants and terrain sets share; fn: the family's entry point
         ka = np.ascontiguousarray(keys, np.int32)
         ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32)
         if ids is not None and ids.shape != ka.shape:
             raise DtrlError("%s: env_ids and %s must have the same length" % (who, noun))
-        self._chk(fn(self._h, _p(ids), len(ka), _p(ka)))
+        self._chk(fn(self._h, _p(ids), len(ka), _p(ka), *more))
 
     def _get_keys(self, fn, env_ids):
         ids, n = self._ids(env_ids)
@@ -799,6 +807,46 @@ class BatchScenario:
     def VariantStats(self, v):
         """EvalStats restricted to the envs currently in variant v (plus their number), reduced on the device in a fixed order."""
         return self._key_stats(self._lib.dtrl_variant_stats, v)
+
+    # ---- terrain sets: several terrains in one batch, one per env (no counterpart in the reference, which keeps one terrain per scene object) ----
+    num_terrains = 0
+
+    def CreateTerrains(self, n_terrains):
+        """dtrl_terrains_create: a table of 1 .. num_envs terrains (type + 40 parameters), once per batch. Terrain 0 is the batch's own terrain (SetTerrainLerp keeps
+        acting on it) and every env starts in it; terrains >= 1 are empty until SetTerrainFile / SetTerrainParams fills them. Combines with policy slots, model
+        variants and external policy mode."""
+        self._chk(self._lib.dtrl_terrains_create(self._h, int(n_terrains)))
+        self.num_terrains = int(n_terrains)
+
+    def SetTerrainFile(self, t, path, lerp=0.0):
+        """dtrl_terrain_set_file: terrain t >= 1 from a terrain file (resolved like -terrain_file=) at `lerp` over that file's parameter sets. Calling it again for a
+        filled terrain moves that terrain's curriculum: its envs build their next segments under the new parameters."""
+        self._chk(self._lib.dtrl_terrain_set_file(self._h, int(t), os.fsencode(str(path)), float(lerp)))
+
+    def SetTerrainParams(self, t, type_name, params40):
+        """dtrl_terrain_set_params: the same from memory (a type name and 40 parameters in cTerrainGen2D::eParams order, what terrain_build takes)."""
+        p = np.ascontiguousarray(params40, np.float64)
+        if p.shape != (40,):
+            raise DtrlError("SetTerrainParams: params40 must hold 40 values")
+        self._chk(self._lib.dtrl_terrain_set_params(self._h, int(t), str(type_name).encode(), _p(p)))
+
+    def TerrainInfo(self, t):
+        """dtrl_terrain_info: {"type", "params" (40 doubles), "filled"} of terrain t; terrain 0 reports the lerped parameters in force."""
+        name = C.create_string_buffer(64); p = np.zeros(40, np.float64); filled = C.c_int()
+        self._chk(self._lib.dtrl_terrain_info(self._h, int(t), name, 64, _p(p), C.byref(filled)))
+        return {"type": name.value.decode(), "params": p, "filled": bool(filled.value)}
+
+    def AssignTerrains(self, env_ids, terrains, restart=False):
+        """env_ids[i] -> terrains[i] (env_ids None: the first len(terrains) envs). restart=False: takes effect with the env's next segment build, the window in place
+        stays. restart=True: the listed envs start over as at creation under their new terrain (terrain stream re-seeded, fresh window, reset), in the same call."""
+        self._assign_keys(self._lib.dtrl_assign_terrains, "AssignTerrains", "terrains", env_ids, terrains, 1 if restart else 0)
+
+    def GetTerrains(self, env_ids=None):
+        return self._get_keys(self._lib.dtrl_get_terrains, env_ids)
+
+    def TerrainStats(self, t):
+        """EvalStats restricted to the envs currently in terrain t (plus their number), reduced on the device in a fixed order."""
+        return self._key_stats(self._lib.dtrl_terrain_stats, t)
 
     # ---- full env snapshots (no counterpart in the reference: it keeps one scene per object) ----
     def SaveState(self, env_ids=None):

@@ -1,9 +1,10 @@
 // dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, launches over
-// envs of several slots or variants and the per-slot sums, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
-// of them with kernels and keeps these as its cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1).
+// envs of several slots or variants and the per-slot sums, the frame-boundary terrain work of envs under several terrains, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
+// of them with kernels and keeps these as its cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1).
 // Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
 // lane-loop check build of any tests/ tree, the sanitizer scripts -- has the defaults, and no source list can lack them.
 #include "dtrl_engine.h"
+#include "dtrl_terrain_dev.h"
 
 namespace dtrl {
 
@@ -128,6 +129,31 @@ bool Backend::SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs
 		++a.n_envs; a.episodes += host[e].num_episodes; a.cycles += host[e].num_cycles; a.resets += host[e].num_resets;
 		a.dist_sum += static_cast<double>(host[e].avg_dist) * static_cast<double>(host[e].num_episodes);
 	}
+	return true;
+}
+// Terrain sets: tg_env_boundary on the host, env by env, under the env's own table entry. A finished episode goes to the device distance ring as the kernel
+// would have put it there (one cursor read at the start, one write at the end: nothing else runs on this stream meanwhile -- D2H waits for it).
+bool Backend::TerrainBoundaryKeyed(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, const int32_t* env_terrain)
+{
+	if (n <= 0) return true;
+	std::vector<int32_t> list(static_cast<size_t>(n));
+	if (!env_list) { for (int k = 0; k < n; ++k) list[k] = e0 + k; }
+	else if (!D2H(list.data(), env_list, sizeof(int32_t) * list.size())) return false;
+	int32_t cursor = 0;
+	if (buf.dist_ring && !D2H(&cursor, buf.dist_count, sizeof(cursor))) return false;
+	const int32_t cursor0 = cursor;
+	GroundRec rec; GroundGen gen; EnvStatus st; TerrainCfg cfg; int32_t key = 0;
+	for (int32_t e : list) {
+		if (!D2H(&key, env_terrain + e, sizeof(key)) || !D2H(&cfg, table + key, sizeof(cfg)) || !D2H(&gen, buf.gen + e, sizeof(gen)) || !D2H(&st, buf.status + e, sizeof(st))) return false;
+		if (!D2H(&rec, buf.gr + e, sizeof(rec))) return false;
+		const GroundGen gen0 = gen;
+		DistRec one; int32_t got = 0;
+		tg_env_boundary(rec, gen, st, cfg, mode, e, buf.dist_ring ? &one : nullptr, &got, 1);
+		if (got > 0) { if (cursor < buf.dist_cap && !H2D(buf.dist_ring + cursor, &one, sizeof(one))) return false; ++cursor; }
+		if (gen.builds == gen0.builds && gen.ctr == gen0.ctr && mode == 0) continue;   // the window stayed: nothing to write back
+		if (!H2D(buf.gr + e, &rec, sizeof(rec)) || !H2D(buf.gen + e, &gen, sizeof(gen))) return false;
+	}
+	if (cursor != cursor0 && !H2D(buf.dist_count, &cursor, sizeof(cursor))) return false;
 	return true;
 }
 

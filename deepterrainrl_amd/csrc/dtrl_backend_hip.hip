@@ -152,6 +152,17 @@ __global__ void dtrl_terrain_boundary(DevBuffers buf, int e0, int n, int mode, c
 	const int e = env_list ? env_list[k] : e0 + k;
 	tg_env_boundary(buf.gr[e], buf.gen[e], buf.status[e], *buf.tcfg, mode, e, buf.dist_ring, buf.dist_count, buf.dist_cap);
 }
+// Terrain sets (include/dtrl.h dtrl_terrains_create ...): the same thread-per-env boundary with one TerrainCfg per env. The table and the per-env terrain array
+// are two extra pointer ARGUMENTS -- DevBuffers keeps its size and layout, so the by-value argument block of every other kernel is what it was. A terrain record
+// is read through the pointer where it is used (type, then the parameters the type's generator draws from); lanes whose envs sit in terrains of different types
+// part ways in tgen::build_terrain's type dispatch and run their generators one type after the other (docs/EXPERIMENTS.md, terrain sets).
+__global__ void dtrl_terrain_boundary_keyed(DevBuffers buf, int e0, int n, int mode, const int32_t* __restrict__ env_list, const TerrainCfg* __restrict__ table, const int32_t* __restrict__ env_terrain)
+{
+	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+	if (k >= n) return;
+	const int e = env_list ? env_list[k] : e0 + k;
+	tg_env_boundary(buf.gr[e], buf.gen[e], buf.status[e], table[env_terrain[e]], mode, e, buf.dist_ring, buf.dist_count, buf.dist_cap);
+}
 // launch order of a group's next frame: counting sort on cost / 16, costliest first (one workgroup; the order inside a bucket is whatever the
 // atomics produce -- it only decides which wavefront starts first)
 constexpr int kOrderBuckets = 1024;
@@ -548,6 +559,14 @@ public:
 		if (n <= 0) return true;
 		hipLaunchKernelGGL(dtrl_terrain_boundary, dim3((n + 63) / 64), dim3(64), 0, stream_, buf, e0, n, mode, env_list);
 		return Check(hipGetLastError(), "terrain boundary launch");
+	}
+	// terrain sets: ONE launch over the listed envs, each under its own table entry. DTRL_TERRAINS_FALLBACK=1 takes the host default instead (A/B and cross-check)
+	bool TerrainBoundaryKeyed(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, const int32_t* env_terrain) override
+	{
+		if (EnvFlag("DTRL_TERRAINS_FALLBACK")) return Backend::TerrainBoundaryKeyed(buf, e0, n, mode, env_list, table, env_terrain);
+		if (n <= 0) return true;
+		hipLaunchKernelGGL(dtrl_terrain_boundary_keyed, dim3((n + 63) / 64), dim3(64), 0, stream_, buf, e0, n, mode, env_list, table, env_terrain);
+		return Check(hipGetLastError(), "keyed terrain boundary launch");
 	}
 	bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) override
 	{

@@ -283,6 +283,14 @@ try {
 dtrl_status dtrl_assign_variants(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* variants) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.AssignVariants(env_ids, n, variants)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_get_variants(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* variants_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.GetVariants(env_ids, n, variants_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_variant_stats(dtrl_batch* b, int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantStats(v, n_envs, avg_dist, episodes, cycles, resets)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+// terrain sets
+dtrl_status dtrl_terrains_create(dtrl_batch* b, int n_terrains) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainsCreate(n_terrains)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_terrain_set_file(dtrl_batch* b, int t, const char* terrain_file, double lerp) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainSetFile(t, terrain_file, lerp)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_terrain_set_params(dtrl_batch* b, int t, const char* type_name, const double* params40) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainSetParams(t, type_name, params40)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_terrain_info(dtrl_batch* b, int t, char* type_out, int type_cap, double* params40_out, int* filled_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainInfo(t, type_out, type_cap, params40_out, filled_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_assign_terrains(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* terrains, int restart) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.AssignTerrains(env_ids, n, terrains, restart != 0)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_get_terrains(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* terrains_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.GetTerrains(env_ids, n, terrains_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_terrain_stats(dtrl_batch* b, int t, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainStats(t, n_envs, avg_dist, episodes, cycles, resets)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_action_dims(const dtrl_batch* b, int* n_opt, int* n_labels, int* num_update_steps, int* external)
 try {
 	CHECK_B();

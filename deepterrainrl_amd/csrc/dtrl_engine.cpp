@@ -119,7 +119,7 @@ Engine::~Engine()
 		be_->Sync();
 		for (Snapshot* s : snapshots_) { be_->Free(s->payload); s->payload = nullptr; s->owner = nullptr; }   // (the handles stay valid for dtrl_snapshot_info / _free)
 		be_->FreeHostStaging(snap_ids_);
-		be_->FreeHostStaging(slot_keys_.part); be_->FreeHostStaging(variant_keys_.part);
+		be_->FreeHostStaging(slot_keys_.part); be_->FreeHostStaging(variant_keys_.part); be_->FreeHostStaging(terrain_keys_.part);
 		if (ext_meta_) be_->FreeHostStaging(ext_meta_);
 		for (void* p : allocs_) be_->Free(p);
 		for (void* p : host_allocs_) be_->FreeHostStaging(p);
@@ -269,6 +269,7 @@ int Engine::Create(const char* const* argv, int argc, int num_envs, int device_i
 	}
 	double params[kNumTerrainParams];
 	LerpTerrainParams(cfg_, cfg_.terrain_blend, params);
+	terrain_lerp_ = cfg_.terrain_blend;
 	if (cfg_.device_terrain) {
 		// every env's window is built by the GPU from its own counter stream (key: terrain seed + global env id)
 		grounds_.clear();
@@ -277,7 +278,7 @@ int Engine::Create(const char* const* argv, int argc, int num_envs, int device_i
 		std::vector<GroundGen> gen(n_);
 		for (int e = 0; e < n_; ++e) { gen[e].key = terrain_stream_key(cfg_.terrain_seed, cfg_.run.env_id_base + e); gen[e].ctr = 0; gen[e].builds = 0; gen[e].overflow = 0; }
 		if (!be_->H2D(buf_.gen, gen.data(), sizeof(GroundGen) * n_)) return Fail(DTRL_ERR_DEVICE, be_->error());
-		if (!be_->TerrainBoundary(buf_, 0, n_, 1, nullptr) || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+		if (!Boundary(0, n_, 1, nullptr) || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	} else {
 	std::vector<GroundRec> recs(n_);
 	for (int e = 0; e < n_; ++e) {
@@ -373,16 +374,22 @@ bool Engine::LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, b
 	return be_->LaunchKeyed(variants ? d_var_models_ : d_model_, cfg_.run, b, v, n_envs, n_steps, dt, frame_end);
 }
 
-int Engine::UploadTerrainCfg(const double* params)
+TerrainCfg Engine::MakeTerrainCfg(int type, const double* params) const
 {
 	TerrainCfg c{};
-	c.type = cfg_.terrain_type;
+	c.type = type;
 	std::memcpy(c.params, params, sizeof(c.params));
 	c.world_scale = cfg_.model.world_scale; c.segment_width = 2 * kViewDist;
 	c.view_min = -2; c.view_max = kViewDist + kViewPad;
 	c.spawn_min = -kViewDist + kGroundSpawnOffset; c.spawn_max = kViewDist + kGroundSpawnOffset;
+	return c;
+}
+int Engine::UploadTerrainCfg(const double* params)
+{
+	const TerrainCfg c = MakeTerrainCfg(cfg_.terrain_type, params);
 	be_->Sync();
 	if (!be_->H2D(d_tcfg_, &c, sizeof(c))) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (d_terrain_table_ && !be_->H2D(d_terrain_table_, &c, sizeof(c))) return Fail(DTRL_ERR_DEVICE, be_->error());   // terrain 0 of a batch with terrain sets
 	return DTRL_OK;
 }
 
@@ -398,7 +405,7 @@ int Engine::DeviceFrameWork(int group)
 	struct Restore { Backend* b; ~Restore() { b->SelectStream(0); } } restore{be_};
 	DevBuffers b = buf_;
 	b.env_list = nullptr; b.reset_listed = 2;
-	if (!be_->TerrainBoundary(buf_, grp.e0, grp.n, 0, nullptr) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (!Boundary(grp.e0, grp.n, 0, nullptr) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	b.env_list = d_order_ + grp.e0;
 	if (!LaunchEnvs(b, grp.n, 0, 0.0, false, nullptr, grp.e0)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
@@ -668,7 +675,7 @@ int Engine::Reset(const int32_t* env_ids, int n, const uint64_t* seeds)
 	}
 	if (cfg_.device_terrain && !reset_ids_.empty()) {
 		std::memcpy(pin_ids_, reset_ids_.data(), sizeof(int32_t) * reset_ids_.size());
-		if (!be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size()) || !be_->TerrainBoundary(buf_, 0, static_cast<int>(reset_ids_.size()), 1, d_env_list_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+		if (!be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size()) || !Boundary(0, static_cast<int>(reset_ids_.size()), 1, d_env_list_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
 	int rc = ApplyResets(reset_ids_, -1);
 	if (rc != DTRL_OK) return rc;
@@ -889,8 +896,10 @@ int Engine::SetTerrainLerp(double lerp)
 {
 	double params[kNumTerrainParams];
 	LerpTerrainParams(cfg_, lerp, params);
+	terrain_lerp_ = lerp;
+	if (!terrain_table_.empty()) terrain_table_[0] = MakeTerrainCfg(cfg_.terrain_type, params);   // terrain sets: this is entry 0, and only its envs move
 	if (cfg_.device_terrain) return UploadTerrainCfg(params);
-	for (GroundWindow& g : grounds_) g.SetParams(params);   // takes effect at the next segment build, as in the reference
+	for (int e = 0; e < n_; ++e) if (terrain_table_.empty() || terrain_keys_.env_key[e] == 0) grounds_[e].SetParams(params);   // takes effect at the next segment build, as in the reference
 	return DTRL_OK;
 }
 
@@ -1567,7 +1576,10 @@ int Engine::CloneEnvs(const int32_t* src_ids, const int32_t* dst_ids, int n)
 		ok = ok && be_->SnapScatter(plan, snap_scratch_, dst, n);
 	}
 	if (!ok) return Fail(DTRL_ERR_DEVICE, be_->error());
-	for (size_t i = 0; i < tmp.size(); ++i) grounds_[dst[i]] = tmp[i];
+	for (size_t i = 0; i < tmp.size(); ++i) {
+		grounds_[dst[i]] = tmp[i];
+		if (!terrain_table_.empty()) { const TerrainCfg& c = terrain_table_[terrain_keys_.env_key[dst[i]]]; grounds_[dst[i]].SetTerrain(c.type, c.params); }   // the window moves, the env's terrain stays
+	}
 	return DTRL_OK;
 }
 
@@ -1985,6 +1997,118 @@ int Engine::VariantLoad(int v, const char* character_file, const char* text, siz
 		return Fail(DTRL_ERR_ARG, std::string(what) + ": variant " + std::to_string(v) + " does not fit the batch: " + f + " differs from the batch's model (the skeleton, the scene and the controller part -- parameters, actions, default action -- are one per batch)");
 	if (!be_->H2D(d_var_models_ + v, &vc.model, sizeof(DevModel))) return Fail(DTRL_ERR_DEVICE, be_->error());
 	var_models_[v] = vc.model; variant_keys_.filled[v] = 1;
+	return DTRL_OK;
+}
+
+// ---- terrain sets (include/dtrl.h: dtrl_terrains_create ... dtrl_terrain_stats) ----
+// The third per-env key family, and the one no frame launch reads: a terrain decides what an env's NEXT segments look like, and segments are built at the frame
+// boundary -- by the env's GroundWindow on the host, or by the boundary kernel (-terrain_gen= device), which takes the table and the per-env array as two extra
+// pointers. So terrains neither touch LaunchEnvs nor exclude slots, variants or external policy mode. The timing rules are those of the other families (KeysIdle).
+int Engine::TerrainsCreate(int n_terrains)
+{
+	if (n_terrains < 1 || n_terrains > n_) return Fail(DTRL_ERR_ARG, "dtrl_terrains_create: n_terrains must be 1 .. num_envs (" + std::to_string(n_) + "), not " + std::to_string(n_terrains));
+	if (!terrain_table_.empty()) {
+		if (n_terrains == static_cast<int>(terrain_table_.size())) return DTRL_OK;
+		return Fail(DTRL_ERR_ARG, "dtrl_terrains_create: the batch already has " + std::to_string(terrain_table_.size()) + " terrains; a second call with another count (" + std::to_string(n_terrains) + ") is refused");
+	}
+	if (int rc = RequireIdle(std::string("dtrl_terrains_create") + kFrameInFlight); rc != DTRL_OK) return rc;
+	TerrainCfg* table = static_cast<TerrainCfg*>(KeysAllocate(terrain_keys_, sizeof(TerrainCfg) * static_cast<size_t>(n_terrains)));
+	if (!table) return DTRL_ERR_DEVICE;
+	double params[kNumTerrainParams];
+	LerpTerrainParams(cfg_, terrain_lerp_, params);
+	std::vector<TerrainCfg> host(static_cast<size_t>(n_terrains), MakeTerrainCfg(cfg_.terrain_type, params));   // (an empty terrain holds the batch's until it is filled; it cannot be assigned)
+	if (!be_->H2D(table, host.data(), sizeof(TerrainCfg) * host.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	d_terrain_table_ = table; terrain_table_.swap(host);
+	terrain_src_.assign(static_cast<size_t>(n_terrains), TerrainSource());
+	terrain_keys_.filled.assign(static_cast<size_t>(n_terrains), 0); terrain_keys_.filled[0] = 1;
+	return DTRL_OK;
+}
+
+int Engine::TerrainFill(const char* what, int t, int type, const double* params)
+{
+	const TerrainCfg c = MakeTerrainCfg(type, params);
+	if (!be_->H2D(d_terrain_table_ + t, &c, sizeof(c))) return Fail(DTRL_ERR_DEVICE, std::string(what) + ": " + be_->error());
+	terrain_table_[t] = c; terrain_keys_.filled[t] = 1;
+	if (!cfg_.device_terrain) for (int e = 0; e < n_; ++e) if (terrain_keys_.env_key[e] == t) grounds_[e].SetTerrain(type, params);   // next segment build, like a curriculum step
+	return DTRL_OK;
+}
+
+int Engine::TerrainSetFile(int t, const char* terrain_file, double lerp)
+{
+	const char* what = "dtrl_terrain_set_file";
+	if (int rc = KeysIdle(terrain_keys_, what, t); rc != DTRL_OK) return rc;
+	if (t == 0) return Fail(DTRL_ERR_ARG, std::string(what) + ": terrain 0 is the batch's own terrain (-terrain_file=) and cannot be replaced; dtrl_set_terrain_lerp moves it");
+	if (!terrain_file || !*terrain_file) return Fail(DTRL_ERR_ARG, std::string(what) + ": terrain_file is required");
+	const std::string path = ResolveDataPath(cfg_.data_root, terrain_file);
+	TerrainSource src; int type = 0; std::string lerr;
+	const int bad = LoadTerrainFile(path, type, src.sets, lerr);
+	if (bad == 1) return Fail(DTRL_ERR_IO, std::string(what) + ": terrain " + std::to_string(t) + ": " + lerr);
+	if (bad) return Fail(DTRL_ERR_ARG, std::string(what) + ": terrain " + std::to_string(t) + ": " + path + ": " + lerr);
+	double params[kNumTerrainParams];
+	LerpTerrainParams(src.sets, lerp, params);
+	src.lerp = lerp;
+	if (int rc = TerrainFill(what, t, type, params); rc != DTRL_OK) return rc;
+	terrain_src_[t] = src;
+	return DTRL_OK;
+}
+
+int Engine::TerrainSetParams(int t, const char* type_name, const double* params40)
+{
+	const char* what = "dtrl_terrain_set_params";
+	if (int rc = KeysIdle(terrain_keys_, what, t); rc != DTRL_OK) return rc;
+	if (t == 0) return Fail(DTRL_ERR_ARG, std::string(what) + ": terrain 0 is the batch's own terrain (-terrain_file=) and cannot be replaced; dtrl_set_terrain_lerp moves it");
+	if (!type_name || !params40) return Fail(DTRL_ERR_ARG, std::string(what) + ": type_name and params40 are required");
+	const int type = TerrainTypeByName(type_name);
+	if (type < 0) return Fail(DTRL_ERR_ARG, std::string(what) + ": terrain " + std::to_string(t) + ": unsupported terrain type " + type_name);
+	if (int rc = TerrainFill(what, t, type, params40); rc != DTRL_OK) return rc;
+	terrain_src_[t] = TerrainSource();
+	return DTRL_OK;
+}
+
+int Engine::TerrainInfo(int t, char* type_out, int type_cap, double* params40_out, int* filled_out)
+{
+	const EnvAssignment& a = terrain_keys_;
+	if (a.filled.empty()) return Fail(DTRL_ERR_ARG, std::string("dtrl_terrain_info: ") + a.none_text);
+	if (t < 0 || t >= a.n_keys()) return Fail(DTRL_ERR_ARG, "dtrl_terrain_info: terrain " + std::to_string(t) + " out of range (0 .. " + std::to_string(a.n_keys() - 1) + ")");
+	const TerrainCfg& c = terrain_table_[t];
+	if (type_out && type_cap > 0) std::snprintf(type_out, static_cast<size_t>(type_cap), "%s", kTerrainTypeNames[c.type]);
+	if (params40_out) std::memcpy(params40_out, c.params, sizeof(c.params));
+	if (filled_out) *filled_out = a.filled[t] ? 1 : 0;
+	return DTRL_OK;
+}
+
+// restart: the listed envs start over as at creation, under their new terrain -- the terrain stream from (terrain seed, GLOBAL env id), build count 0, a fresh
+// two-segment window around the spawn point, then the device half of a reset. The exploration counter rng_ctr is not rewound (a reset never rewinds it).
+int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrains, bool restart)
+{
+	const char* what = "dtrl_assign_terrains";
+	if (int rc = KeysAssign(terrain_keys_, what, env_ids, n, terrains); rc != DTRL_OK) return rc;
+	reset_ids_.clear();
+	std::vector<char> seen(static_cast<size_t>(n_), 0);
+	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (!seen[e]) { seen[e] = 1; reset_ids_.push_back(e); } }   // (an env listed twice: its last terrain holds, it restarts once)
+	if (!cfg_.device_terrain) {
+		for (int32_t e : reset_ids_) {
+			GroundWindow& g = grounds_[e];
+			const TerrainCfg& c = terrain_table_[terrain_keys_.env_key[e]];
+			g.SetTerrain(c.type, c.params);
+			if (!restart) continue;
+			g.SeedRand(static_cast<unsigned long>(cfg_.terrain_seed + static_cast<uint64_t>(cfg_.run.env_id_base) + e));
+			g.Clear(); g.ResetBuilds();
+			g.InitSegments(-kViewDist + kGroundSpawnOffset, kViewDist + kGroundSpawnOffset);
+			if (!UploadGround(e)) return DTRL_ERR_CAPACITY;
+		}
+	}
+	if (!restart || reset_ids_.empty()) return DTRL_OK;
+	if (cfg_.device_terrain) {
+		std::vector<GroundGen> gen(static_cast<size_t>(n_));
+		if (!be_->D2H(gen.data(), buf_.gen, sizeof(GroundGen) * gen.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+		for (int32_t e : reset_ids_) gen[e].key = terrain_stream_key(cfg_.terrain_seed, cfg_.run.env_id_base + e);
+		std::memcpy(pin_ids_, reset_ids_.data(), sizeof(int32_t) * reset_ids_.size());
+		if (!be_->H2D(buf_.gen, gen.data(), sizeof(GroundGen) * gen.size()) || !be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size())
+			|| !Boundary(0, static_cast<int>(reset_ids_.size()), 2, d_env_list_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	}
+	if (int rc = ApplyResets(reset_ids_, -1); rc != DTRL_OK) return rc;
+	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
 }
 

@@ -113,6 +113,11 @@ public:
 	// -terrain_gen= device: the frame-boundary terrain work of envs [e0, e0 + n) (or of env_list[0 .. n) when given), queued on the selected stream
 	// (tg_env_boundary, dtrl_terrain_dev.h); mode 0 = after a frame, 1 = (re)initialise
 	virtual bool TerrainBoundary(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list) = 0;
+	// Terrain sets (include/dtrl.h dtrl_terrains_create ...): the same work with one TerrainCfg per env -- env e is built under table[env_terrain[e]] instead of
+	// *buf.tcfg (table / env_terrain / env_list: device memory, env_terrain indexed by local env id); mode 2 = re-seed + initialise (tg_env_boundary). The default
+	// fetches each listed env's GroundRec / GroundGen / EnvStatus, runs tg_env_boundary on the host and writes the records back, synchronised (what the lane-loop
+	// check build runs, and DTRL_TERRAINS_FALLBACK=1 on HIP); the HIP backend overrides it with one launch of dtrl_terrain_boundary_keyed on the selected stream.
+	virtual bool TerrainBoundaryKeyed(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, const int32_t* env_terrain);
 	// order[e0 .. e0 + n) = the envs e0 .. e0 + n - 1 sorted by status[].cost, costliest first (launch order of the group's next frame), on the selected stream
 	virtual bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) = 0;
 	// pending tuples -> block [block_rows + 1][W + 2] (header row + rows sorted by env id, flag word and global env id as the two extra columns); rows
@@ -209,6 +214,15 @@ public:
 	int GetVariants(const int32_t* env_ids, int n, int32_t* variants_out) { return KeysGet(variant_keys_, "dtrl_get_variants", env_ids, n, variants_out); }
 	int VariantStats(int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) { return KeysStats(variant_keys_, "dtrl_variant_stats", false, v, n_envs, avg_dist, episodes, cycles, resets); }
 	int num_variants() const { return static_cast<int>(var_models_.size()); }
+	// terrain sets (include/dtrl.h)
+	int TerrainsCreate(int n_terrains);
+	int TerrainSetFile(int t, const char* terrain_file, double lerp);
+	int TerrainSetParams(int t, const char* type_name, const double* params40);
+	int TerrainInfo(int t, char* type_out, int type_cap, double* params40_out, int* filled_out);
+	int AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrains, bool restart);
+	int GetTerrains(const int32_t* env_ids, int n, int32_t* terrains_out) { return KeysGet(terrain_keys_, "dtrl_get_terrains", env_ids, n, terrains_out); }
+	int TerrainStats(int t, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) { return KeysStats(terrain_keys_, "dtrl_terrain_stats", false, t, n_envs, avg_dist, episodes, cycles, resets); }
+	int num_terrains() const { return terrain_keys_.n_keys(); }
 	// the model env e (local id, in range) runs under: what host-side readers of per-env geometry use (dtrl_get_link_states, AddPerturb)
 	const DevModel& ModelOf(int e) const { return var_models_.empty() ? cfg_.model : var_models_[variant_keys_.env_key[e]]; }
 	~Engine();
@@ -266,6 +280,9 @@ private:
 	int DeviceFrameWork(int group);   // -terrain_gen= device: the same frame-boundary work queued as device kernels, no host sync
 	int DrainDeviceDistLog();
 	int UploadTerrainCfg(const double* params);
+	TerrainCfg MakeTerrainCfg(int type, const double* params) const;   // the scene constants of a TerrainCfg are the batch's
+	// -terrain_gen= device: the boundary work of every caller -- Backend::TerrainBoundary as it always was, or, once terrains exist, the keyed form
+	bool Boundary(int e0, int n, int mode, const int32_t* env_list) { return terrain_keys_.filled.empty() ? be_->TerrainBoundary(buf_, e0, n, mode, env_list) : be_->TerrainBoundaryKeyed(buf_, e0, n, mode, env_list, d_terrain_table_, terrain_keys_.d_env_key); }
 	int ApplyResets(const std::vector<int32_t>& ids, int group);
 	int LaunchGroup(int group, int n_steps, double dt_step, bool frame_end);
 	// env groups: contiguous env ranges, each with its own stream, launch order and staging slices. Envs are independent, so a group
@@ -344,7 +361,7 @@ private:
 	int32_t* d_ext_ids_ = nullptr;                         // device [n]
 	double* d_ext_states_ = nullptr;                       // device [n][S] (host call)
 	int32_t* d_ext_action_ids_ = nullptr; uint32_t* d_ext_flags_ = nullptr; double* d_ext_params_ = nullptr;   // device [n], [n], [n][n_opt]: the rows of a host call
-	// Per-env keys: what policy slots and model variants share (at most one of the two is live). A key is a slot or a variant number; every env starts under
+	// Per-env keys: what policy slots, model variants and terrain sets share (slots and variants exclude each other; terrains combine with either). A key is a slot, a variant or a terrain number; every env starts under
 	// key 0. The family's table and the per-env array are read by launches in flight and are therefore rewritten only by calls that have refused a frame in flight and
 	// waited for every stream (KeysIdle). The three texts are the family's own words in the refusals (they differ in more than the noun).
 	struct EnvAssignment {
@@ -375,6 +392,15 @@ private:
 	ArgParser args_;                         // the creation arguments (command line + arg file): a variant is loaded through them with another character description
 	EnvAssignment variant_keys_{"variant", "the batch has no model variants (call dtrl_variants_create first)", "is empty (no dtrl_variant_load_* has filled it)"};
 	std::vector<DevModel> var_models_; DevModel* d_var_models_ = nullptr;   // the table: host form (empty: no variants), device memory [n_variants]
+	// terrain sets. Terrain 0 is the batch's terrain (cfg_.terrain_type / terrain_param_sets at terrain_lerp_: what dtrl_set_terrain_lerp moves); a terrain >= 1 is
+	// empty until dtrl_terrain_set_* fills it. No frame launch reads the table: the consumers are the frame-boundary paths (host: each env's GroundWindow carries its
+	// terrain's type and parameters; device: Backend::TerrainBoundaryKeyed), so terrains combine with slots, variants and external policy mode
+	struct TerrainSource { std::vector<std::vector<double>> sets; double lerp = 0; };   // where a terrain's parameters came from (a file's sets; empty: given directly)
+	EnvAssignment terrain_keys_{"terrain", "the batch has no terrain sets (call dtrl_terrains_create first)", "is empty (no dtrl_terrain_set_file / dtrl_terrain_set_params has filled it)"};
+	std::vector<TerrainCfg> terrain_table_; TerrainCfg* d_terrain_table_ = nullptr;   // the table: host form (empty: no terrains), device memory [n_terrains]
+	std::vector<TerrainSource> terrain_src_;
+	double terrain_lerp_ = 0;                // terrain 0's lerp in force
+	int TerrainFill(const char* what, int t, int type, const double* params);   // table entry t (>= 1) in both forms, and the windows of the envs under it
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

@@ -355,15 +355,40 @@ bool ParseDeployPrototxt(const std::string& path, NetDesc& d, std::string& err, 
 	return true;
 }
 
-void LerpTerrainParams(const ScenarioConfig& cfg, double lerp, double* out)
+int TerrainTypeByName(const std::string& name)
+{
+	if (name.empty()) return kTerrFlat;
+	for (int i = 0; i < kTerrTypeMax; ++i) if (name == kTerrainTypeNames[i]) return i;
+	return -1;
+}
+int LoadTerrainFile(const std::string& path, int& type, std::vector<std::vector<double>>& sets, std::string& err)
+{
+	Json tf;
+	if (!Json::parse_file(path, tf, err)) return 1;
+	const Json* ty = tf.find("Type");
+	const std::string tname = ty ? ty->str : "";
+	const int found = TerrainTypeByName(tname);
+	if (found < 0) { err = "unsupported terrain type " + tname; return 2; }
+	type = found; sets.clear();
+	const Json* ps = tf.find("Params");
+	if (ps) for (const Json& obj : ps->arr) {
+		std::vector<double> v(kNumTerrainParams);
+		for (int k = 0; k < kNumTerrainParams; ++k) v[k] = obj.get_num(kTerrainParamNames[k], kTerrainParamDefaults[k]);
+		sets.push_back(v);
+	}
+	return 0;
+}
+
+void LerpTerrainParams(const ScenarioConfig& cfg, double lerp, double* out) { LerpTerrainParams(cfg.terrain_param_sets, lerp, out); }
+void LerpTerrainParams(const std::vector<std::vector<double>>& sets, double lerp, double* out)
 {
 	// scenarios/ScenarioSimChar.cpp:255-272
-	const int n = static_cast<int>(cfg.terrain_param_sets.size());
+	const int n = static_cast<int>(sets.size());
 	if (n == 0) { std::memcpy(out, kTerrainParamDefaults, sizeof(kTerrainParamDefaults)); return; }
 	lerp = std::min(std::max(lerp, 0.0), n - 1.0);
 	int i0 = static_cast<int>(lerp), i1 = std::min(i0 + 1, n - 1);
 	lerp -= i0;
-	for (int k = 0; k < kNumTerrainParams; ++k) out[k] = (1 - lerp) * cfg.terrain_param_sets[i0][k] + lerp * cfg.terrain_param_sets[i1][k];
+	for (int k = 0; k < kNumTerrainParams; ++k) out[k] = (1 - lerp) * sets[i0][k] + lerp * sets[i1][k];
 }
 
 void BuildOutputOffsetScale(const DevModel& m, const NetDesc& d, std::vector<double>& off, std::vector<double>& scale)
@@ -620,23 +645,7 @@ bool LoadScenario(const ArgParser& args, ScenarioConfig& cfg, std::string& err, 
 
 	// terrain (scenarios/ScenarioSimChar.cpp:670-706, sim/TerrainGen2D.cpp:58-146)
 	cfg.terrain_type = kTerrFlat; cfg.terrain_param_sets.clear();
-	if (!terrain_file.empty()) {
-		Json tf;
-		if (!Json::parse_file(JoinPath(root, terrain_file), tf, err)) return false;
-		const Json* ty = tf.find("Type");
-		std::string tname = ty ? ty->str : "";
-		if (tname.empty()) tname = "flat";
-		int found = -1;
-		for (int i = 0; i < kTerrTypeMax; ++i) if (tname == kTerrainTypeNames[i]) found = i;
-		if (found < 0) { err = "unsupported terrain type " + tname; return false; }
-		cfg.terrain_type = found;
-		const Json* ps = tf.find("Params");
-		if (ps) for (const Json& obj : ps->arr) {
-			std::vector<double> v(kNumTerrainParams);
-			for (int k = 0; k < kNumTerrainParams; ++k) v[k] = obj.get_num(kTerrainParamNames[k], kTerrainParamDefaults[k]);
-			cfg.terrain_param_sets.push_back(v);
-		}
-	}
+	if (!terrain_file.empty() && LoadTerrainFile(JoinPath(root, terrain_file), cfg.terrain_type, cfg.terrain_param_sets, err) != 0) return false;
 	args.ParseDouble("terrain_blend", cfg.terrain_blend);
 	args.ParseDouble("min_perturb", cfg.min_perturb); args.ParseDouble("max_perturb", cfg.max_perturb);
 	args.ParseDouble("min_pertrub_duration", cfg.min_perturb_duration); args.ParseDouble("max_perturb_duration", cfg.max_perturb_duration);

@@ -94,6 +94,9 @@ public:
 	bool LoadState(const GroundWindowState& in);    // false: malformed record (vertex counts, generator state)
 	void Configure(int type, const double* params, double world_scale, double segment_width);
 	void SetParams(const double* params);
+	// another terrain for the segments built from now on (terrain sets: dtrl_assign_terrains); like SetParams it leaves the built segments and the generator alone
+	void SetTerrain(int type, const double* params) { type_ = type; SetParams(params); }
+	void ResetBuilds() { builds_ = 0; }
 	void SeedRand(unsigned long seed) { rand_.Seed(seed); }
 	void Clear();
 	// returns true when a segment was (re)built, i.e. the device record must be refreshed
@@ -151,5 +154,10 @@ bool ParseDeployPrototxt(const std::string& path, NetDesc& d, std::string& err, 
 // cBaseControllerMACE::BuildNNOutputOffsetScale + cDogControllerMACE::BuildActorBias
 void BuildOutputOffsetScale(const DevModel& m, const NetDesc& d, std::vector<double>& off, std::vector<double>& scale);
 void LerpTerrainParams(const ScenarioConfig& cfg, double lerp, double* out);
+void LerpTerrainParams(const std::vector<std::vector<double>>& sets, double lerp, double* out);   // the same over any file's parameter sets (terrain sets)
+// the terrain-file reader of creation (scenarios/ScenarioSimChar.cpp:670-706, sim/TerrainGen2D.cpp:69-81): "Type" and every 40-vector of "Params" with the
+// defaults of kTerrainParamDefaults. 0 = read, 1 = the file cannot be read or parsed, 2 = unknown type name (err set)
+int LoadTerrainFile(const std::string& path, int& type, std::vector<std::vector<double>>& sets, std::string& err);
+int TerrainTypeByName(const std::string& name);   // "" == flat (cTerrainGen2D::ParseType); -1: unknown
 
 }  // namespace dtrl

@@ -96,10 +96,18 @@ DTRL_TG_HD inline bool tg_window_update(GroundRec& rec, double bmin, double bmax
 //   mode 0: after a frame -- a fallen env (status.need_reset) gets a fresh window around the spawn point (cScenarioSimChar::ResetGround: Clear + Update),
 //           any other env has its window slid along with the character; a finished poli_eval episode (bit 1) is appended to the distance log
 //   mode 1: (re)initialise unconditionally (Init, user resets)
+//   mode 2: re-seed + initialise (dtrl_assign_terrains with restart): the env's stream starts over at its key (the host has written it: terrain seed + GLOBAL
+//           env id), the build count goes to 0, then as mode 1 -- the env's window is what creation would have built under this terrain
+// (always inlined on the device: with two kernels calling it -- dtrl_terrain_boundary and dtrl_terrain_boundary_keyed -- the compiler would otherwise keep ONE copy
+// behind a call, and the shipped kernel would get a stack frame and the callee's register count; inlined, each kernel is compiled as the shipped one always was)
+#if defined(__HIPCC__)
+__attribute__((always_inline))
+#endif
 DTRL_TG_HD inline void tg_env_boundary(GroundRec& rec, GroundGen& gen, const EnvStatus& st, const TerrainCfg& c, int mode, int env, DistRec* dist_ring, int32_t* dist_count, int32_t dist_cap)
 {
 	CtrRand rnd{gen.key, &gen.ctr};
-	if (mode == 1) { tg_init_segments(rec, c.spawn_min, c.spawn_max, c, rnd, &gen); return; }
+	if (mode == 2) { gen.ctr = 0; gen.builds = 0; gen.overflow = 0; }   // (the stream reads its counter through the pointer: it starts over)
+	if (mode == 1 || mode == 2) { tg_init_segments(rec, c.spawn_min, c.spawn_max, c, rnd, &gen); return; }
 	if (st.need_reset & 2) {
 		if (dist_ring) {
 #if defined(__HIP_DEVICE_COMPILE__)

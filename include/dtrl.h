@@ -340,7 +340,8 @@ dtrl_status dtrl_slot_stats(dtrl_batch* b, int slot, int64_t* n_envs, double* av
  * that never calls dtrl_variants_create runs exactly the kernels and launches it ran before. The assignment is batch state like the slot assignment: snapshots,
  * restores, clones and blobs do not carry it and a reset does not change it. An env that changes variant keeps every byte of its state and simply runs its next
  * launch under the other model; a caller who wants episodes to START under the new model resets those envs (dtrl_reset) after assigning. Variants use local
- * env ids. Not available together with policy slots or with -policy_mode= external, in either order (each combination would be one more kernel family).
+ * env ids. Not available together with policy slots or with -policy_mode= external, in either order (each combination would be one more kernel family);
+ * terrain sets (below) combine with all three.
  * The calls below are refused with DTRL_ERR_ARG between dtrl_step_begin and dtrl_step_end (they never wait for a frame) and then -- dtrl_get_variants
  * excepted, which is valid at any time -- wait for everything the batch has queued on the device before they change or read anything. */
 /* No counterpart in the reference, which keeps one character per scene object. 1 <= n_variants <= num_envs, once per batch, between frames. Refused with
@@ -363,6 +364,45 @@ dtrl_status dtrl_get_variants(dtrl_batch* b, const int32_t* env_ids, int n, int3
 /* No counterpart in the reference, which keeps one character per scene object. dtrl_eval_stats restricted to the envs currently in variant v (n_envs of them),
  * reduced on the device in a fixed order: two calls without a step between them return the same bits. Any output may be NULL. */
 dtrl_status dtrl_variant_stats(dtrl_batch* b, int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+
+/* ---- Terrain sets: several terrains in one batch, one per env ----
+ * No counterpart in the reference, which keeps one terrain per scene object (cScenarioSimChar::ParseTerrainParams reads ONE -terrain_file= into the scene's
+ * cGroundVar2D, scenarios/ScenarioSimChar.cpp:670-706): measuring a policy on flat / slopes_mixed / narrow_gaps / cliffs there means one scenario per terrain, and
+ * neither a mixture of terrains nor a per-env curriculum can be expressed. A terrain is the type plus the 40 parameters of cTerrainGen2D::eParams; the scene
+ * constants (world scale, segment width, view and spawn bounds) stay the batch's. A batch holds a table of n_terrains of them, up to one per env, and a per-env
+ * index says which terrain builds an env's NEXT segments. Terrain 0 IS the batch's terrain: dtrl_set_terrain_lerp and -terrain_blend= keep acting on it (and
+ * on the envs in it alone), every env starts in it; terrains >= 1 start empty. No frame kernel reads terrain parameters (they read the env's ground record), so a
+ * batch that never calls dtrl_terrains_create runs exactly the launches it ran before, and terrains combine freely with policy slots, model variants and
+ * -policy_mode= external, in either order of creation. The assignment is batch state like the slot and variant assignments: snapshots, restores, clones, blobs
+ * and dtrl_reset neither carry nor change it; a restored window keeps its segments and generator state and builds its next segment under the env's current
+ * terrain. Terrains use local env ids. The calls below are refused with DTRL_ERR_ARG between dtrl_step_begin and dtrl_step_end (they never wait for a frame)
+ * and then -- dtrl_get_terrains and dtrl_terrain_info excepted, which are valid at any time -- wait for everything the batch has queued on the device before
+ * they change or read anything. */
+/* No counterpart in the reference, which keeps one terrain per scene object. 1 <= n_terrains <= num_envs, once per batch (the same count again is accepted), between frames. */
+dtrl_status dtrl_terrains_create(dtrl_batch* b, int n_terrains);
+/* No counterpart in the reference, which keeps one terrain per scene object. Fill terrain t >= 1 from a terrain file, in place of the file reader of cScenarioSimChar::ParseTerrainParams
+ * (scenarios/ScenarioSimChar.cpp:670-706) + cTerrainGen2D::LoadParams (sim/TerrainGen2D.cpp:69-81): the reader creation uses ("Type" plus every 40-vector of
+ * "Params", missing values from the defaults), the path resolved like -terrain_file=. `lerp` blends THAT file's parameter sets as dtrl_set_terrain_lerp blends
+ * the batch's (scenarios/ScenarioSimChar.cpp:255-272). May be called again for a filled terrain -- that is how a per-terrain curriculum moves: the envs in the
+ * terrain build their next segments under the new parameters. DTRL_ERR_IO: the file cannot be read or parsed; DTRL_ERR_ARG: unknown type name, t out of range or 0. */
+dtrl_status dtrl_terrain_set_file(dtrl_batch* b, int t, const char* terrain_file, double lerp);
+/* No counterpart in the reference, which keeps one terrain per scene object. The same from memory, in place of the file reader (scenarios/ScenarioSimChar.cpp:670-706, sim/TerrainGen2D.cpp:69-81): a type name
+ * ("" == flat) and params40 in cTerrainGen2D::eParams order -- what dtrl_terrain_build takes. */
+dtrl_status dtrl_terrain_set_params(dtrl_batch* b, int t, const char* type_name, const double* params40);
+/* No counterpart in the reference, which keeps one terrain per scene object. What terrain t currently holds: its type name (up to type_cap bytes), its 40 parameters, and whether it has been filled (an empty
+ * terrain reports the batch's). For terrain 0: the lerped parameters in force. Any output may be NULL. */
+dtrl_status dtrl_terrain_info(dtrl_batch* b, int t, char* type_out, int type_cap, double* params40_out, int* filled_out);
+/* No counterpart in the reference, which keeps one terrain per scene object. env_ids[i] -> terrains[i]; env_ids == NULL means the first n envs. All or nothing: an env id or terrain out of range, or an empty
+ * terrain, is DTRL_ERR_ARG. restart == 0: takes effect with the env's next segment build -- the window in place stays and the new terrain joins it at the seam
+ * height, as a curriculum step does. restart != 0: in the same call the listed envs start over as at creation under their new terrain: the terrain stream is
+ * re-seeded from (terrain seed, GLOBAL env id), the build count goes to 0, a fresh two-segment window is built around the spawn point, and the device half of a
+ * reset runs (as dtrl_reset). The exploration counter is not rewound. */
+dtrl_status dtrl_assign_terrains(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* terrains, int restart);
+/* No counterpart in the reference, which keeps one terrain per scene object. The terrains of the listed envs (valid at any time). */
+dtrl_status dtrl_get_terrains(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* terrains_out);
+/* No counterpart in the reference, which keeps one terrain per scene object. dtrl_eval_stats restricted to the envs currently in terrain t (n_envs of them), reduced on the device in a fixed order: two calls
+ * without a step between them return the same bits. Refuses a frame in flight, like dtrl_variant_stats. Any output may be NULL. */
+dtrl_status dtrl_terrain_stats(dtrl_batch* b, int t, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
 
 /* Replaces: cScenarioSimChar::AddPerturb -> cWorld::AddPerturb (scenarios/ScenarioSimChar.cpp:204-207, sim/World.cpp:256-259) with a
  * tPerturb of type ePerturbForce (sim/Perturb.cpp:52-79, sim/World.cpp:445-470): a world-frame force[n][2] on body part link[n] at the
