@@ -230,6 +230,16 @@ struct WSFast : WSBase {
 // fused multiply-add a*b + c, spelled out (the build runs with -ffp-contract=off): the SAME fused operations in the lane-loop,
 // reference and register-resident builds keep the three bit-identical, and the solver's dependent chains are one op shorter per step
 DTRL_HD_INLINE real fmadd(real a, real b, real c) { return __builtin_fma(a, b, c); }
+// a lane-derived index the device optimiser cannot see through: the address built from it is computed where it is used (one base + lane offset) instead of being
+// hoisted out of the env-step loop as a loop-invariant 64-bit pointer per array, spilled, and reloaded from scratch in front of every load (opaque_lane() of
+// dtrl_kernel_fast.h, for code both kernel forms and the lane-loop build share). No instruction.
+DTRL_HD_INLINE int opaque_index(int v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	asm volatile("" : "+v"(v));
+#endif
+	return v;
+}
 DTRL_HD_INLINE void sincos_r(real x, real* s, real* c)
 {
 #if defined(DTRL_REAL_F32)
@@ -345,7 +355,10 @@ DTRL_HD_INLINE GroundHdr ground_header(const GroundRec& g)
 	h.o0 = g.origin_x[0]; h.o1 = g.origin_x[1]; h.sc0 = g.scale_x[0]; h.sc1 = g.scale_x[1];
 	return h;
 }
-DTRL_HD_INLINE real sample_ground(const GroundRec& g, const GroundHdr& gh, real x, real* slope, int* oi, int* oj, int* oseg)
+// The sample in two halves, so that a caller with several positions (the fast path's eval_points(), dtrl_kernel_fast.h) can run the first half for all of them, issue all
+// height loads together and finish afterwards: ground_cell() is everything in front of the two height loads, ground_height() everything behind them
+struct GroundCell { int seg, i, j; real lerp, inv_run; };
+DTRL_HD_INLINE GroundCell ground_cell(const GroundHdr& gh, real x)
 {
 	const real mx0 = gh.mx0;
 	const int w0 = gh.w0, w1 = gh.w1;
@@ -359,17 +372,28 @@ DTRL_HD_INLINE real sample_ground(const GroundRec& g, const GroundHdr& gh, real 
 	c += ((w - 1) * 0.5);
 	if (c > -tol && c < w - 1 + tol) { c = c < 0.0 ? 0.0 : (c > w - 1.0 ? w - 1.0 : c); }
 	c = !(c > 0.0) ? 0.0 : (c > w - 1.0 ? w - 1.0 : c);   // (written so that a NaN coordinate -- a state that has already blown up -- still indexes inside the segment)
-	int i = static_cast<int>(c);
-	int j = (i + 1 < w - 1) ? i + 1 : w - 1;
-	real lerp = c - i;
-	const real inv_run = fast_recip(scale * ((j - i) > 0 ? (j - i) : 1));   // ready before the height samples arrive
-	real a = g.data[seg][i];
-	real b = g.data[seg][j];
-	if (slope) *slope = (j == i) ? 0.0 : (b - a) * inv_run;
-	if (oi) *oi = i;
-	if (oj) *oj = j;
-	if (oseg) *oseg = seg;
-	return (1 - lerp) * a + lerp * b;
+	GroundCell k;
+	k.seg = seg;
+	k.i = static_cast<int>(c);
+	k.j = (k.i + 1 < w - 1) ? k.i + 1 : w - 1;
+	k.lerp = c - k.i;
+	k.inv_run = fast_recip(scale * ((k.j - k.i) > 0 ? (k.j - k.i) : 1));   // ready before the height samples arrive
+	return k;
+}
+DTRL_HD_INLINE real ground_height(const GroundCell& k, real a, real b, real* slope)
+{
+	if (slope) *slope = (k.j == k.i) ? 0.0 : (b - a) * k.inv_run;
+	return (1 - k.lerp) * a + k.lerp * b;
+}
+DTRL_HD_INLINE real sample_ground(const GroundRec& g, const GroundHdr& gh, real x, real* slope, int* oi, int* oj, int* oseg)
+{
+	const GroundCell k = ground_cell(gh, x);
+	real a = g.data[k.seg][k.i];
+	real b = g.data[k.seg][k.j];
+	if (oi) *oi = k.i;
+	if (oj) *oj = k.j;
+	if (oseg) *oseg = k.seg;
+	return ground_height(k, a, b, slope);
 }
 DTRL_HD_INLINE real sample_ground(const GroundRec& g, real x, real* slope, int* oi, int* oj, int* oseg)
 {
@@ -1806,26 +1830,29 @@ DTRL_HD inline void controller_update(W& ws, const DevModel& gm, const RunParams
 	LANES_BEGIN
 	if (lane < D) {
 		const int i = lane;
-		real kp = 0, kd = 0, kdm = 0, pe = 0, ve = 0;
-		if (i >= 3) {
-			const int j = i - 2;
-			kdm = gm.kd[j];
-			if ((ws.st.pd_active_bits >> j) & 1u) { kp = gm.kp[j]; kd = kdm; }
-			// relative joint: -getHingeAngle() - ref_theta, an atan2 window (sim/World.cpp:543-553). World-coordinate joint (dog shoulder / hip):
-			// btQuaternion::getAngle() * (axis . z) of the quaternion btMatrix3x3::getRotation extracts from the link's world basis (sim/World.cpp:374-384):
-			// phi while 1 + 2 cos(phi) > 0 or phi > 0, phi + 2 pi for phi in (-pi, -2 pi / 3] (w < 0 in the largest-diagonal branch)
-			real theta;
-			if (gm.use_world[j]) {
-				theta = wrap_pi(ws.phi[j] + gm.body_theta[j]);
-				if (theta <= real(-2.0943951023931954923084289221863)) theta += real(6.283185307179586476925286766559);
-			} else {
-				theta = wrap_pi(ws.st.q[i] + gm.ref_theta[j]) - gm.ref_theta[j];
-			}
-			pe = ws.st.pd_target[j] - theta;
-			ve = 0 - ws.st.qd[i];
-		}
+		// The five per-DoF controller constants travel in ONE batch at the head of the phase: every lane loads them unconditionally (the root's DoFs from joint 1:
+		// a valid address, the values are dropped) and the hinge / active / world-joint cases are SELECTED afterwards. Written with the loads under the branches
+		// that use them, each load is a memory round trip of its own on the env-step's dependent chain (load, wait, branch, load, wait ...), and each goes through
+		// a 64-bit address that is loop-invariant, hoisted out of the env-step loop and reloaded from scratch in front of its load. The index is opaque for that
+		// reason: base + lane offset is then computed where it is used. Keep the loads out of the branches.
+		const bool hinge = i >= 3;
+		const int j = opaque_index(hinge ? i - 2 : 1);
+		const real c_kd = gm.kd[j], c_kp = gm.kp[j], c_body = gm.body_theta[j], c_ref = gm.ref_theta[j];
+		const bool world = gm.use_world[j] != 0;
+		const real qd_i = ws.st.qd[i];
+		const bool active = ((ws.st.pd_active_bits >> j) & 1u) != 0;
+		const real kdm = hinge ? c_kd : 0;
+		const real kp = (hinge && active) ? c_kp : 0, kd = (hinge && active) ? c_kd : 0;
+		// relative joint: -getHingeAngle() - ref_theta, an atan2 window (sim/World.cpp:543-553). World-coordinate joint (dog shoulder / hip):
+		// btQuaternion::getAngle() * (axis . z) of the quaternion btMatrix3x3::getRotation extracts from the link's world basis (sim/World.cpp:374-384):
+		// phi while 1 + 2 cos(phi) > 0 or phi > 0, phi + 2 pi for phi in (-pi, -2 pi / 3] (w < 0 in the largest-diagonal branch)
+		// (one wrap_pi() of the selected argument: the same operation on the same operand as either case's own)
+		const real wr = wrap_pi(world ? ws.phi[j] + c_body : ws.st.q[i] + c_ref);
+		const real theta = world ? ((wr <= real(-2.0943951023931954923084289221863)) ? wr + real(6.283185307179586476925286766559) : wr) : wr - c_ref;
+		const real pe = hinge ? ws.st.pd_target[j] - theta : 0;
+		const real ve = hinge ? 0 - qd_i : 0;
 		ws.kpv[i] = kp; ws.kdv[i] = kd; ws.kdm[i] = kdm; ws.perr[i] = pe; ws.verr[i] = ve;
-		ws.u[i] = kp * (pe - dt * ws.st.qd[i]) + kd * ve - quirk_bias(ws, i);
+		ws.u[i] = kp * (pe - dt * qd_i) + kd * ve - quirk_bias(ws, i);
 	}
 	LANES_END
 	PROF_ADD_SINCE(ws, kProfC_PdSetup, pc_t); pc_t = PROF_NOW();

@@ -34,6 +34,9 @@ __device__ __forceinline__ int opaque_lane()
 	asm volatile("" : "+v"(lane));
 	return lane;
 }
+// a loaded value the optimiser must have in a register HERE: the load behind it can neither be sunk into a later branch nor be moved behind this point. No instruction
+template <class T>
+__device__ __forceinline__ void pin_loaded(T& v) { asm volatile("" : "+v"(v)); }
 // the EXEC-window helpers below are spelled per arithmetic type (dtrl_types.h: fp64 shipped, fp32 opt-in build)
 #if defined(DTRL_REAL_F32)
 #define DTRL_VFMA "v_fma_f32"
@@ -298,18 +301,23 @@ __device__ __forceinline__ real utsolve_regs(const real (&h)[D], real u)
 	return u;
 }
 
-// contact sample points in registers: lane owns points lane, lane + 64, lane + 128; wave ballots give the per-link contact
+// contact sample points in registers: lane owns points lane, lane + 64 (, lane + 128); wave ballots give the per-link contact
 // flags and the ordered constraint-row list (same order as detect_contacts()/build_rows()) without touching LDS.
 // (three named values, not an array: the struct must stay in VGPRs, never in scratch)
-static_assert((kMaxPts + kGroup - 1) / kGroup == 3, "written for 3 sample points per lane");
+// A kernel instance knows its skeleton, hence how many sample points a lane owns: NP = pts_per_lane(Topo::L), two for both shipped skeletons. Everything below is
+// instantiated for NP; the fields of the points an instance does not have stay the constants they are initialised with and fold away (no third point's
+// zero-init, branch, ballots, link_field() word or row emitter in the physics loop).
+static_assert((kMaxPts + kGroup - 1) / kGroup == 3, "written for up to 3 sample points per lane");
+constexpr int pts_per_lane(int L) { return (L * kPtsPerLink + kGroup - 1) / kGroup; }
 struct ContactPts { PtVal p0, p1, p2; unsigned long long m0, m1, m2; /* constraint-carrying points */ unsigned long long f0, f1, f2; /* points near the surface: contact flags */ };
-// the kPtsPerLink ballot bits of link `link`'s sample points (points link * 6 .. link * 6 + 5 of the three 64-point ballots)
+// the kPtsPerLink ballot bits of link `link`'s sample points (points link * 6 .. link * 6 + 5 of the NP 64-point ballots)
+template <int NP>
 __device__ __forceinline__ unsigned link_field(unsigned long long m0, unsigned long long m1, unsigned long long m2, int link)
 {
 	const int b = link * kPtsPerLink, word = b >> 6, off = b & 63;
-	unsigned long long lo = m0, hi = m1;   // (plain selects on by-value scalars: an indexable aggregate here would be demoted to scratch)
-	if (word == 1) { lo = m1; hi = m2; }
-	if (word == 2) { lo = m2; hi = 0ull; }
+	unsigned long long lo = m0, hi = NP > 1 ? m1 : 0ull;   // (plain selects on by-value scalars: an indexable aggregate here would be demoted to scratch)
+	if constexpr (NP > 1) if (word == 1) { lo = m1; hi = NP > 2 ? m2 : 0ull; }
+	if constexpr (NP > 2) if (word == 2) { lo = m2; hi = 0ull; }
 	unsigned long long bits = lo >> off;
 	if (off + kPtsPerLink > 64) bits |= hi << (64 - off);
 	return static_cast<unsigned>(bits & ((1ull << kPtsPerLink) - 1ull));
@@ -318,17 +326,18 @@ __device__ __forceinline__ unsigned link_field(unsigned long long m0, unsigned l
 // ground with five or six of its sample points below the surface): the depths go once through LDS (the packed-matrix storage is dead between
 // the factorisation and the Delassus build, and before the controller's mass rows) so that a point sees the other sample points of its link
 // Takes and returns scalars only (an aggregate passed by reference to a non-inlined function would live in scratch memory on the hot path):
-// d0..d2 = depth of the lane's three sample points or kNoPoint when the point carries no rows (a row-carrying point within the breaking threshold above
-// the surface has a small negative depth); returns bit k set when point k is dropped
+// d0..d2 = depth of the lane's sample points or kNoPoint when the point carries no rows (a row-carrying point within the breaking threshold above
+// the surface has a small negative depth; the points an instance does not have: kNoPoint, not looked at); returns bit k set when point k is dropped
 constexpr real kNoPoint = -1.0e30;
+template <int NP>
 __device__ __noinline__ unsigned link_cap_drop_mask(WSFast& ws, real d0, real d1, real d2)
 {
 	const int lane = opaque_lane();
 	const int npts = ws.M.L * kPtsPerLink;
 	real* S = ws.Apk;
 	if (lane < npts) S[lane] = d0;
-	if (lane + kGroup < npts) S[lane + kGroup] = d1;
-	if (lane + 2 * kGroup < npts) S[lane + 2 * kGroup] = d2;
+	if constexpr (NP > 1) if (lane + kGroup < npts) S[lane + kGroup] = d1;
+	if constexpr (NP > 2) if (lane + 2 * kGroup < npts) S[lane + 2 * kGroup] = d2;
 	env_sync();
 	auto over = [&](real d, int pt) -> unsigned {
 		if (!(d > kNoPoint)) return 0u;
@@ -337,47 +346,125 @@ __device__ __noinline__ unsigned link_cap_drop_mask(WSFast& ws, real d0, real d1
 		for (int k = 0; k < kPtsPerLink; ++k) { const int o = base + k; const real od = S[o]; rank += (o != pt && (od > d || (od == d && o < pt))) ? 1 : 0; }
 		return rank >= kMaxPtsPerLink ? 1u : 0u;
 	};
-	const unsigned m = over(d0, lane) | (over(d1, lane + kGroup) << 1) | (over(d2, lane + 2 * kGroup) << 2);
+	unsigned m = over(d0, lane);
+	if constexpr (NP > 1) m |= over(d1, lane + kGroup) << 1;
+	if constexpr (NP > 2) m |= over(d2, lane + 2 * kGroup) << 2;
 	env_sync();
 	return m;
 }
+// The ground test of all of a lane's sample points in ONE interleaved pass: contact_point_eval() of dtrl_kernel.h cut into stages, every stage run for all NP
+// points before the next one starts. Per point the operations, their operands and their order are exactly contact_point_eval()'s (IEEE division, fmadd where
+// it is, nothing reassociated: ground_cell() / ground_height() are the two halves of the one sample_ground()), so the bits are the reference path's.
+//   (a) everything that depends on nothing but the lane, issued together: the ground header ONCE (it is the same for every point), and per point the link's
+//       collision flag and frame from LDS, its local coordinates, margin and breaking threshold from the model
+//   (b) world position, segment pick, grid coordinate, cell indices (ground_cell(): the division is here)
+//   (c) the two height loads of every point together
+//   (d) gap, margin test, normal, depth, flags
+// There is NO branch in here, on purpose. A lane without a point e (pt >= npts) evaluates the last point again, a point of a non-colliding link is evaluated like
+// any other (all addresses valid, a NaN coordinate still indexes inside the segment: ground_cell()), and `active` / `near` are SELECTED at the end. With the
+// point's evaluation under `if (pt < npts)` and early returns inside, the compiler emits the points strictly one after the other and waits for memory two to three
+// times per point -- LDS for the collision flag, the constants + header, the heights, the margins -- which is four to six dependent global round trips and two
+// copies of a 65-instruction chain per pass where two trips and one chain at ILP 2 do the same work; the pass runs five times per env-step, all of it on the wave's
+// dependent chain. The 1/sqrt of a point that fails the margin test is off that chain and cheap. Do not put the branches back.
+// x, y, depth, nx, ny of a point that is not `active` are whatever the evaluation left (nobody reads them: emit_contact_rows(), the drop masks).
 // kFlags: also find the points within contact_tol of the surface (the per-link contact flags the controller reads: only the post-step pass needs them)
-template <bool kFlags>
+template <int L, bool kFlags>
 __device__ __forceinline__ ContactPts eval_points(WSFast& ws, const DevModel& gm, const GroundRec& g)
 {
+	constexpr int NP = pts_per_lane(L), npts = L * kPtsPerLink;
 	const int lane = opaque_lane();
-	const int npts = ws.M.L * kPtsPerLink;
+	// (a)
+	const GroundHdr gh = ground_header(g);
+	const real q0 = ws.st.q[0], q1 = ws.st.q[1];
+	const real tol = kFlags ? gm.contact_tol : real(0);
+	bool have[NP]; int col[NP]; real lx[NP], ly[NP], margin[NP], brk[NP], cs[NP], sn[NP], px[NP], py[NP];   // (constant indices only: registers)
+	static_for<0, NP>([&](auto ec) {
+		constexpr int e = decltype(ec)::value;
+		const int pt = lane + e * kGroup;
+		have[e] = (e + 1) * kGroup <= npts || pt < npts;
+		const int ptc = ((e + 1) * kGroup <= npts || pt < npts) ? pt : npts - 1;
+		const int j = ptc / kPtsPerLink;
+		col[e] = ws.M.col[j];
+		cs[e] = ws.cs[j]; sn[e] = ws.sn[j]; px[e] = ws.px[j]; py[e] = ws.py[j];
+		const real* lp = &gm.pt_ground[0][0][0] + 2 * ptc;   // = pt_ground[j][k], k = ptc - j kPtsPerLink: point of the margin-shrunk box
+		lx[e] = lp[0]; ly[e] = lp[1];
+		margin[e] = gm.link_margin[j]; brk[e] = gm.link_brk[j];
+	});
+	// every value of stage (a) is pinned here, behind the last of its loads: left alone, the compiler sinks the loads that only the final select reads (the breaking
+	// threshold, the collision flag of a lane's last point) into a branch of its own making behind the heights -- a third round trip on the chain
+	static_for<0, NP>([&](auto ec) {
+		constexpr int e = decltype(ec)::value;
+		pin_loaded(col[e]); pin_loaded(lx[e]); pin_loaded(ly[e]); pin_loaded(margin[e]); pin_loaded(brk[e]);
+	});
+	// (b)
+	real x[NP], y[NP]; GroundCell cell[NP];
+	static_for<0, NP>([&](auto ec) {
+		constexpr int e = decltype(ec)::value;
+		x[e] = px[e] + cs[e] * lx[e] - sn[e] * ly[e];
+		y[e] = py[e] + sn[e] * lx[e] + cs[e] * ly[e];
+		cell[e] = ground_cell(gh, q0 + x[e]);
+	});
+	// (c)
+	real ha[NP], hb[NP];
+	static_for<0, NP>([&](auto ec) {
+		constexpr int e = decltype(ec)::value;
+		ha[e] = g.data[cell[e].seg][cell[e].i];
+		hb[e] = g.data[cell[e].seg][cell[e].j];
+	});
+	// (d)
+	PtVal r[3];
+	static_for<0, 3>([&](auto ec) {
+		constexpr int e = decltype(ec)::value;
+		r[e].x = 0; r[e].y = 0; r[e].depth = 0; r[e].nx = 0; r[e].ny = 0; r[e].active = 0; r[e].near = 0;
+		if constexpr (e < NP) {
+			real slope;
+			const real h = ground_height(cell[e], ha[e], hb[e], &slope);
+			const real gap = h - (q1 + y[e]);
+			// inside a substep only the points that carry rows matter: penetrating ones and -- Bullet's persistent manifold -- those within the breaking threshold above the surface
+			// (rows: depth = gap * ny + margin > -brk needs gap > -(margin + brk) / ny, and 1 / ny = sqrt(1 + slope^2) <= 1 + |slope|)
+			const bool in_reach = kFlags || (gap + (margin[e] + brk[e]) * (1.0 + fabs(slope)) > 0);
+			const real inv = fast_rsqrt(1.0 + slope * slope);
+			const real depth = fmadd(gap, inv, margin[e]);   // along the cell normal (ny = inv > 0), to the ROUNDED surface of the box (Bullet's collision margin)
+			const bool live = have[e] & (col[e] != 0);   // (& not &&: a select, never a branch)
+			if (kFlags) r[e].near = (live & (depth >= -tol)) ? 1 : 0;   // cContactManager::Update: getDistance() <= dist_tol
+			r[e].active = (live & in_reach & (depth > -brk[e])) ? 1 : 0;
+			r[e].nx = -slope * inv; r[e].ny = inv;
+			r[e].depth = depth;
+			r[e].x = x[e]; r[e].y = y[e];
+		}
+	});
 	ContactPts c;
-	PtVal z; z.x = 0; z.y = 0; z.depth = 0; z.nx = 0; z.ny = 0; z.active = 0; z.near = 0;
-	c.p0 = z; c.p1 = z; c.p2 = z;
-	if (lane < npts) c.p0 = contact_point_eval<kFlags>(ws, gm, g, lane);
-	if (lane + kGroup < npts) c.p1 = contact_point_eval<kFlags>(ws, gm, g, lane + kGroup);
-	if (lane + 2 * kGroup < npts) c.p2 = contact_point_eval<kFlags>(ws, gm, g, lane + 2 * kGroup);
+	c.p0 = r[0]; c.p1 = r[1]; c.p2 = r[2];
 	c.f0 = 0; c.f1 = 0; c.f2 = 0;
-	if (kFlags) { c.f0 = __ballot(c.p0.near); c.f1 = __ballot(c.p1.near); c.f2 = __ballot(c.p2.near); }
-	c.m0 = __ballot(c.p0.active); c.m1 = __ballot(c.p1.active); c.m2 = __ballot(c.p2.active);
+	if (kFlags) { c.f0 = __ballot(c.p0.near); if constexpr (NP > 1) c.f1 = __ballot(c.p1.near); if constexpr (NP > 2) c.f2 = __ballot(c.p2.near); }
+	c.m0 = __ballot(c.p0.active); c.m1 = 0; c.m2 = 0;
+	if constexpr (NP > 1) c.m1 = __ballot(c.p1.active);
+	if constexpr (NP > 2) c.m2 = __ballot(c.p2.active);
 	if ((c.m0 | c.m1 | c.m2) != 0ull) {   // wave-uniform: somebody penetrates; does any link have more than kMaxPtsPerLink such points?
-		const int many = (lane < ws.M.L) && __popc(link_field(c.m0, c.m1, c.m2, lane)) > kMaxPtsPerLink;
+		const int many = (lane < L) && __popc(link_field<NP>(c.m0, c.m1, c.m2, lane)) > kMaxPtsPerLink;
 		if (__builtin_expect(__ballot(many) != 0ull, 0)) {
-			const unsigned drop = link_cap_drop_mask(ws, c.p0.active ? c.p0.depth : kNoPoint, c.p1.active ? c.p1.depth : kNoPoint, c.p2.active ? c.p2.depth : kNoPoint);
+			const unsigned drop = link_cap_drop_mask<NP>(ws, c.p0.active ? c.p0.depth : kNoPoint, (NP > 1 && c.p1.active) ? c.p1.depth : kNoPoint, (NP > 2 && c.p2.active) ? c.p2.depth : kNoPoint);
 			if (drop & 1u) c.p0.active = 0;
 			if (drop & 2u) c.p1.active = 0;
 			if (drop & 4u) c.p2.active = 0;
-			c.m0 = __ballot(c.p0.active); c.m1 = __ballot(c.p1.active); c.m2 = __ballot(c.p2.active);
+			c.m0 = __ballot(c.p0.active);
+			if constexpr (NP > 1) c.m1 = __ballot(c.p1.active);
+			if constexpr (NP > 2) c.m2 = __ballot(c.p2.active);
 		}
 	}
 	return c;
 }
 // more penetrating points than constraint rows: the deepest `cap` points overall keep theirs (ties: lower sample-point index). Cold path
 // (a character lying on the ground with a dozen points in it)
+template <int NP>
 __device__ __noinline__ unsigned row_cap_drop_mask(WSFast& ws, real d0, real d1, real d2, int cap)
 {
 	const int lane = opaque_lane();
 	const int npts = ws.M.L * kPtsPerLink;
 	real* S = ws.Apk;
 	if (lane < npts) S[lane] = d0;
-	if (lane + kGroup < npts) S[lane + kGroup] = d1;
-	if (lane + 2 * kGroup < npts) S[lane + 2 * kGroup] = d2;
+	if constexpr (NP > 1) if (lane + kGroup < npts) S[lane + kGroup] = d1;
+	if constexpr (NP > 2) if (lane + 2 * kGroup < npts) S[lane + 2 * kGroup] = d2;
 	env_sync();
 	auto over = [&](real d, int pt) -> unsigned {
 		if (!(d > kNoPoint)) return 0u;
@@ -385,7 +472,9 @@ __device__ __noinline__ unsigned row_cap_drop_mask(WSFast& ws, real d0, real d1,
 		for (int o = 0; o < npts; ++o) { const real od = S[o]; rank += (o != pt && (od > d || (od == d && o < pt))) ? 1 : 0; }
 		return rank >= cap ? 1u : 0u;
 	};
-	const unsigned m = over(d0, lane) | (over(d1, lane + kGroup) << 1) | (over(d2, lane + 2 * kGroup) << 2);
+	unsigned m = over(d0, lane);
+	if constexpr (NP > 1) m |= over(d1, lane + kGroup) << 1;
+	if constexpr (NP > 2) m |= over(d2, lane + 2 * kGroup) << 2;
 	env_sync();
 	return m;
 }
@@ -447,19 +536,14 @@ __device__ __noinline__ int append_pair_rows_fast(WSFast& ws, const DevModel& gm
 	}
 	return R;
 }
+template <int NP>
 __device__ __forceinline__ void contact_bits_fast(WSFast& ws, unsigned long long m0, unsigned long long m1, unsigned long long m2)
 {
 	const int lane = static_cast<int>(threadIdx.x);
 	int any = 0;
-	if (lane < ws.M.L) any = link_field(m0, m1, m2, lane) != 0u;
+	if (lane < ws.M.L) any = link_field<NP>(m0, m1, m2, lane) != 0u;
 	const unsigned long long lm = __ballot(any);
 	if (lane == 0) ws.st.contact_bits = static_cast<uint32_t>(lm);
-}
-__device__ __forceinline__ void detect_contacts_fast(WSFast& ws, const DevModel& gm, const GroundRec& g)
-{
-	const ContactPts c = eval_points<true>(ws, gm, g);
-	contact_bits_fast(ws, c.f0, c.f1, c.f2);
-	env_sync();
 }
 __device__ __forceinline__ void emit_contact_rows(WSFast& ws, const PtVal& p, int pt, int rank, int cap, int R0, real inv_h)
 {
@@ -473,6 +557,7 @@ __device__ __forceinline__ void emit_contact_rows(WSFast& ws, const PtVal& p, in
 		ws.row_dx[R + 1] = p.ny; ws.row_dy[R + 1] = -p.nx; ws.row_tgt[R + 1] = 0;
 	}
 }
+template <int NP>
 __device__ __forceinline__ void build_rows_fast(WSFast& ws, const DevModel& gm, const ContactPts& c_in, real h)
 {
 	ContactPts c = c_in;
@@ -493,16 +578,18 @@ __device__ __forceinline__ void build_rows_fast(WSFast& ws, const DevModel& gm, 
 	// contacts, ordered by sample-point index
 	const int cap = (kMaxRows - R0) / 2;
 	if (__builtin_expect(__popcll(c.m0) + __popcll(c.m1) + __popcll(c.m2) > cap, 0)) {   // wave-uniform
-		const unsigned drop = row_cap_drop_mask(ws, c.p0.active ? c.p0.depth : kNoPoint, c.p1.active ? c.p1.depth : kNoPoint, c.p2.active ? c.p2.depth : kNoPoint, cap);
+		const unsigned drop = row_cap_drop_mask<NP>(ws, c.p0.active ? c.p0.depth : kNoPoint, (NP > 1 && c.p1.active) ? c.p1.depth : kNoPoint, (NP > 2 && c.p2.active) ? c.p2.depth : kNoPoint, cap);
 		if (drop & 1u) c.p0.active = 0;
 		if (drop & 2u) c.p1.active = 0;
 		if (drop & 4u) c.p2.active = 0;
-		c.m0 = __ballot(c.p0.active); c.m1 = __ballot(c.p1.active); c.m2 = __ballot(c.p2.active);
+		c.m0 = __ballot(c.p0.active);
+		if constexpr (NP > 1) c.m1 = __ballot(c.p1.active);
+		if constexpr (NP > 2) c.m2 = __ballot(c.p2.active);
 	}
 	const int n0 = __popcll(c.m0), n1 = __popcll(c.m1), n2 = __popcll(c.m2);
 	emit_contact_rows(ws, c.p0, lane, __popcll(c.m0 & below), cap, R0, inv_h);
-	emit_contact_rows(ws, c.p1, lane + kGroup, n0 + __popcll(c.m1 & below), cap, R0, inv_h);
-	emit_contact_rows(ws, c.p2, lane + 2 * kGroup, n0 + n1 + __popcll(c.m2 & below), cap, R0, inv_h);
+	if constexpr (NP > 1) emit_contact_rows(ws, c.p1, lane + kGroup, n0 + __popcll(c.m1 & below), cap, R0, inv_h);
+	if constexpr (NP > 2) emit_contact_rows(ws, c.p2, lane + 2 * kGroup, n0 + n1 + __popcll(c.m2 & below), cap, R0, inv_h);
 	int nc = n0 + n1 + n2; if (nc > cap) nc = cap;
 	int R = R0 + 2 * nc;
 	// link--link contacts take what is left of the row budget
@@ -825,6 +912,7 @@ __device__ __forceinline__ int prof_row_bucket(int R) { return R == 0 ? 0 : (R <
 template <class Topo>
 struct FastPath {
 	static constexpr int D = Topo::L + 2;
+	static constexpr int NP = pts_per_lane(Topo::L);   // contact sample points per lane
 	static __device__ void substep(WSFast& ws, const DevModel& gm, const GroundRec& g, real h, bool kin_valid)
 	{
 		const int lane = static_cast<int>(threadIdx.x);
@@ -842,8 +930,8 @@ struct FastPath {
 			env_sync();
 		} else {
 			ContactPts cp;
-			{ PROF_T0(); cp = eval_points<false>(ws, gm, g); PROF_ADD(ws, kProfDetect); }   // the per-link contact flags are the post-step pass's business (contacts() below)
-			{ PROF_T0(); build_rows_fast(ws, gm, cp, h); PROF_ADD(ws, kProfRows); }
+			{ PROF_T0(); cp = eval_points<Topo::L, false>(ws, gm, g); PROF_ADD(ws, kProfDetect); }   // the per-link contact flags are the post-step pass's business (contacts() below)
+			{ PROF_T0(); build_rows_fast<NP>(ws, gm, cp, h); PROF_ADD(ws, kProfRows); }
 		}
 		{ PROF_T0(); warm_match_fast(ws); PROF_ADD(ws, kProfRows); }
 		real hrow[D];
@@ -938,9 +1026,9 @@ struct FastPath {
 	// the next env-step's first substep (same q, same heightfield window within a launch)
 	static __device__ void contacts(WSFast& ws, const DevModel& gm, const GroundRec& g, real h)
 	{
-		const ContactPts cp = eval_points<true>(ws, gm, g);
-		contact_bits_fast(ws, cp.f0, cp.f1, cp.f2);
-		build_rows_fast(ws, gm, cp, h);
+		const ContactPts cp = eval_points<Topo::L, true>(ws, gm, g);
+		contact_bits_fast<NP>(ws, cp.f0, cp.f1, cp.f2);
+		build_rows_fast<NP>(ws, gm, cp, h);
 		if (threadIdx.x == 0) ws.n_pts_active = ws.R;
 		env_sync();
 	}
