@@ -64,7 +64,7 @@ ABI_SYMBOLS = [
     "dtrl_snapshot_save", "dtrl_snapshot_restore", "dtrl_clone_envs", "dtrl_snapshot_export", "dtrl_snapshot_import", "dtrl_snapshot_info", "dtrl_snapshot_free",
     "dtrl_slots_create", "dtrl_slot_set_policy", "dtrl_slot_set_policy_device", "dtrl_slot_alias", "dtrl_slot_set_explore", "dtrl_assign_slots", "dtrl_get_slots", "dtrl_slot_stats",
     "dtrl_variants_create", "dtrl_variant_load_file", "dtrl_variant_load_json", "dtrl_assign_variants", "dtrl_get_variants", "dtrl_variant_stats",
-    "dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats",
+    "dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats", "dtrl_terrain_ladder", "dtrl_ladder_info",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
 
@@ -167,6 +167,8 @@ def _bind(path):
     L.dtrl_assign_terrains.argtypes = [vp, vp, C.c_int, vp, C.c_int]
     L.dtrl_get_terrains.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_terrain_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.dtrl_terrain_ladder.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]
+    L.dtrl_ladder_info.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.dtrl_last_error.restype = C.c_char_p
     L.dtrl_last_error.argtypes = [vp]
     L.dtrl_version.restype = C.c_char_p
@@ -847,6 +849,21 @@ class BatchScenario:
     def TerrainStats(self, t):
         """EvalStats restricted to the envs currently in terrain t (plus their number), reduced on the device in a fixed order."""
         return self._key_stats(self._lib.dtrl_terrain_stats, t)
+
+    # ---- terrain ladder: envs climb and descend terrains lo .. hi by their own episodes (no counterpart in the reference, which keeps one terrain per scene object) ----
+    def TerrainLadder(self, lo, hi, up_dist, down_dist, at_top=False):
+        """dtrl_terrain_ladder: terrains lo .. hi (filled, ordered easy to hard) become a ladder. At each frame boundary an env that has come up_dist past its mark
+        goes one level up (at the top: stays, or with at_top=True is dealt a level of the ladder at random), an env that falls within down_dist of its mark goes one
+        down; envs in terrains outside lo .. hi are left alone. With -terrain_gen= device this happens inside the boundary launch, without the host. lo > hi removes
+        the ladder. With a ladder, GetTerrains / LadderInfo report the state as of the last completed frame boundary (not between UpdateBegin and UpdateEnd)."""
+        self._chk(self._lib.dtrl_terrain_ladder(self._h, int(lo), int(hi), float(up_dist), float(down_dist), 1 if at_top else 0))
+
+    def LadderInfo(self, env_ids=None):
+        """dtrl_ladder_info: {"mark_x" (float64: root x at the env's last spawn or level change), "ups", "downs" (int32)} of the listed envs (all by default)."""
+        ids, n = self._ids(env_ids)
+        mark, ups, downs = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._chk(self._lib.dtrl_ladder_info(self._h, _p(ids), n, _p(mark), _p(ups), _p(downs)))
+        return {"mark_x": mark, "ups": ups, "downs": downs}
 
     # ---- full env snapshots (no counterpart in the reference: it keeps one scene per object) ----
     def SaveState(self, env_ids=None):

@@ -135,6 +135,13 @@ bool Backend::SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs
 // would have put it there (one cursor read at the start, one write at the end: nothing else runs on this stream meanwhile -- D2H waits for it).
 bool Backend::TerrainBoundaryKeyed(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, const int32_t* env_terrain)
 {
+	// (this class's loop, not a backend's override of it; without ladder records it writes nothing to the key array)
+	return Backend::TerrainBoundaryLadder(buf, e0, n, mode, env_list, table, const_cast<int32_t*>(env_terrain), nullptr, LadderCfg{});
+}
+// Terrain ladder: the same loop with the rule (tg_ladder_step) in front of each env's terrain work; key and ladder record go back where they changed.
+// ladder == nullptr: no rule, the keyed form.
+bool Backend::TerrainBoundaryLadder(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, int32_t* env_terrain, LadderRec* ladder, const LadderCfg& lc)
+{
 	if (n <= 0) return true;
 	std::vector<int32_t> list(static_cast<size_t>(n));
 	if (!env_list) { for (int k = 0; k < n; ++k) list[k] = e0 + k; }
@@ -144,8 +151,17 @@ bool Backend::TerrainBoundaryKeyed(const DevBuffers& buf, int e0, int n, int mod
 	const int32_t cursor0 = cursor;
 	GroundRec rec; GroundGen gen; EnvStatus st; TerrainCfg cfg; int32_t key = 0;
 	for (int32_t e : list) {
-		if (!D2H(&key, env_terrain + e, sizeof(key)) || !D2H(&cfg, table + key, sizeof(cfg)) || !D2H(&gen, buf.gen + e, sizeof(gen)) || !D2H(&st, buf.status + e, sizeof(st))) return false;
-		if (!D2H(&rec, buf.gr + e, sizeof(rec))) return false;
+		if (!D2H(&key, env_terrain + e, sizeof(key)) || !D2H(&st, buf.status + e, sizeof(st))) return false;
+		if (ladder) {
+			LadderRec lr;
+			if (!D2H(&lr, ladder + e, sizeof(lr))) return false;
+			const LadderRec lr0 = lr;
+			const int32_t next = tg_ladder_step(lr, key, st, lc, mode, e);
+			if (next != key && !H2D(env_terrain + e, &next, sizeof(next))) return false;
+			if ((lr.mark_x != lr0.mark_x || lr.ups != lr0.ups || lr.downs != lr0.downs) && !H2D(ladder + e, &lr, sizeof(lr))) return false;
+			key = next;
+		}
+		if (!D2H(&cfg, table + key, sizeof(cfg)) || !D2H(&gen, buf.gen + e, sizeof(gen)) || !D2H(&rec, buf.gr + e, sizeof(rec))) return false;
 		const GroundGen gen0 = gen;
 		DistRec one; int32_t got = 0;
 		tg_env_boundary(rec, gen, st, cfg, mode, e, buf.dist_ring ? &one : nullptr, &got, 1);

@@ -163,6 +163,23 @@ __global__ void dtrl_terrain_boundary_keyed(DevBuffers buf, int e0, int n, int m
 	const int e = env_list ? env_list[k] : e0 + k;
 	tg_env_boundary(buf.gr[e], buf.gen[e], buf.status[e], table[env_terrain[e]], mode, e, buf.dist_ring, buf.dist_count, buf.dist_cap);
 }
+// Terrain ladder (include/dtrl.h dtrl_terrain_ladder): the keyed boundary with the rule in front of it, in the same launch -- the env's level moves by its own
+// status record (tg_ladder_step, dtrl_terrain_dev.h), the key and the ladder record are written back where they changed, and the terrain work runs under the NEW
+// level's table entry. The ladder records and settings are arguments like the table and the key array. Thread per env, every word per env: no atomics of its own.
+__global__ void dtrl_terrain_boundary_ladder(DevBuffers buf, int e0, int n, int mode, const int32_t* __restrict__ env_list, const TerrainCfg* __restrict__ table, int32_t* __restrict__ env_terrain,
+	LadderRec* __restrict__ ladder, LadderCfg lc)
+{
+	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+	if (k >= n) return;
+	const int e = env_list ? env_list[k] : e0 + k;
+	const int32_t level = env_terrain[e];
+	LadderRec lr = ladder[e];
+	const LadderRec lr0 = lr;
+	const int32_t next = tg_ladder_step(lr, level, buf.status[e], lc, mode, e);
+	if (next != level) env_terrain[e] = next;
+	if (lr.mark_x != lr0.mark_x || lr.ups != lr0.ups || lr.downs != lr0.downs) ladder[e] = lr;
+	tg_env_boundary(buf.gr[e], buf.gen[e], buf.status[e], table[next], mode, e, buf.dist_ring, buf.dist_count, buf.dist_cap);
+}
 // launch order of a group's next frame: counting sort on cost / 16, costliest first (one workgroup; the order inside a bucket is whatever the
 // atomics produce -- it only decides which wavefront starts first)
 constexpr int kOrderBuckets = 1024;
@@ -567,6 +584,14 @@ public:
 		if (n <= 0) return true;
 		hipLaunchKernelGGL(dtrl_terrain_boundary_keyed, dim3((n + 63) / 64), dim3(64), 0, stream_, buf, e0, n, mode, env_list, table, env_terrain);
 		return Check(hipGetLastError(), "keyed terrain boundary launch");
+	}
+	// terrain ladder: still ONE launch per group and frame -- the rule runs inside it. DTRL_TERRAINS_FALLBACK=1 takes the host default
+	bool TerrainBoundaryLadder(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, int32_t* env_terrain, LadderRec* ladder, const LadderCfg& lc) override
+	{
+		if (EnvFlag("DTRL_TERRAINS_FALLBACK")) return Backend::TerrainBoundaryLadder(buf, e0, n, mode, env_list, table, env_terrain, ladder, lc);
+		if (n <= 0) return true;
+		hipLaunchKernelGGL(dtrl_terrain_boundary_ladder, dim3((n + 63) / 64), dim3(64), 0, stream_, buf, e0, n, mode, env_list, table, env_terrain, ladder, lc);
+		return Check(hipGetLastError(), "ladder terrain boundary launch");
 	}
 	bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) override
 	{

@@ -291,6 +291,8 @@ dtrl_status dtrl_terrain_info(dtrl_batch* b, int t, char* type_out, int type_cap
 dtrl_status dtrl_assign_terrains(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* terrains, int restart) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.AssignTerrains(env_ids, n, terrains, restart != 0)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_get_terrains(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* terrains_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.GetTerrains(env_ids, n, terrains_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_terrain_stats(dtrl_batch* b, int t, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainStats(t, n_envs, avg_dist, episodes, cycles, resets)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_terrain_ladder(dtrl_batch* b, int lo, int hi, double up_dist, double down_dist, int at_top) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainLadder(lo, hi, up_dist, down_dist, at_top)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_ladder_info(dtrl_batch* b, const int32_t* env_ids, int n, double* mark_x_out, int32_t* ups_out, int32_t* downs_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.LadderInfo(env_ids, n, mark_x_out, ups_out, downs_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_action_dims(const dtrl_batch* b, int* n_opt, int* n_labels, int* num_update_steps, int* external)
 try {
 	CHECK_B();

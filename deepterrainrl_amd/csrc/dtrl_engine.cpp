@@ -446,12 +446,20 @@ int Engine::HostFrameWork(int group)
 	const double ht1 = g_ht.on ? now_s() : 0;
 	reset_ids_.clear();
 	work_.clear();
+	bool level_moved = false;
 	for (int e = e0; e < e1; ++e) {
 		const EnvStatus& s = status_[e];
+		if (ladder_on_) {   // the ladder's rule, in front of the env's terrain work: the window built or slid below is already the new level's
+			int32_t& k = terrain_keys_.env_key[e];
+			const int32_t next = tg_ladder_step(ladder_rec_[e], k, s, ladder_, 0, e);
+			if (next != k) { k = next; const TerrainCfg& c = terrain_table_[k]; grounds_[e].SetTerrain(c.type, c.params); level_moved = true; }
+		}
 		if (s.need_reset & 2) dist_log_.emplace_back(e, s.episode_dist);   // cScenarioPoliEval::RecordDistTraveled -> mDistLog
 		if (s.need_reset) { reset_ids_.push_back(e); work_.push_back(e); }
 		else if (grounds_[e].NeedsUpdate(s.root_x - 2, s.root_x + kViewDist + kViewPad)) work_.push_back(e);
 	}
+	// (the device copy of the keys, which dtrl_terrain_stats reduces over: the group's slice, when a level in it moved; no launch reads it)
+	if (level_moved && !be_->H2D(terrain_keys_.d_env_key + e0, terrain_keys_.env_key.data() + e0, sizeof(int32_t) * static_cast<size_t>(grp.n))) return Fail(DTRL_ERR_DEVICE, be_->error());
 	const int used = static_cast<int>(work_.size());
 	if (used > 0) {
 		// the rebuilds of one frame are independent (own RNG stream, own window per env): host workers share them; every rebuilt record goes into
@@ -667,6 +675,7 @@ int Engine::Reset(const int32_t* env_ids, int n, const uint64_t* seeds)
 			continue;
 		}
 		GroundWindow& g = grounds_[e];
+		if (ladder_on_) tg_ladder_step(ladder_rec_[e], terrain_keys_.env_key[e], status_[e], ladder_, 1, e);   // (device terrain: the boundary launch below does it)
 		if (seeds) g.SeedRand(static_cast<unsigned long>(seeds[i]));
 		g.Clear();
 		g.Update(-kViewDist + kGroundSpawnOffset, kViewDist + kGroundSpawnOffset);
@@ -2004,6 +2013,7 @@ int Engine::VariantLoad(int v, const char* character_file, const char* text, siz
 // The third per-env key family, and the one no frame launch reads: a terrain decides what an env's NEXT segments look like, and segments are built at the frame
 // boundary -- by the env's GroundWindow on the host, or by the boundary kernel (-terrain_gen= device), which takes the table and the per-env array as two extra
 // pointers. So terrains neither touch LaunchEnvs nor exclude slots, variants or external policy mode. The timing rules are those of the other families (KeysIdle).
+// With a terrain ladder on device terrain the DEVICE key array is the truth while frames run: the calls that read or upload it refresh the host copy first (LadderIdle).
 int Engine::TerrainsCreate(int n_terrains)
 {
 	if (n_terrains < 1 || n_terrains > n_) return Fail(DTRL_ERR_ARG, "dtrl_terrains_create: n_terrains must be 1 .. num_envs (" + std::to_string(n_) + "), not " + std::to_string(n_terrains));
@@ -2082,10 +2092,19 @@ int Engine::TerrainInfo(int t, char* type_out, int type_cap, double* params40_ou
 int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrains, bool restart)
 {
 	const char* what = "dtrl_assign_terrains";
+	if (int rc = LadderIdle(what); rc != DTRL_OK) return rc;   // (with a ladder on device terrain the upload below would otherwise overwrite every move the kernel made)
 	if (int rc = KeysAssign(terrain_keys_, what, env_ids, n, terrains); rc != DTRL_OK) return rc;
 	reset_ids_.clear();
 	std::vector<char> seen(static_cast<size_t>(n_), 0);
 	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (!seen[e]) { seen[e] = 1; reset_ids_.push_back(e); } }   // (an env listed twice: its last terrain holds, it restarts once)
+	if (ladder_on_) {
+		// the listed envs' marks: the env's current root x, or -- restart -- the spawn point (host terrain here; device terrain: the mode-2 boundary launch below)
+		for (int32_t e : reset_ids_) {
+			if (restart) { if (!cfg_.device_terrain) tg_ladder_step(ladder_rec_[e], terrain_keys_.env_key[e], status_[e], ladder_, 2, e); }
+			else if (int rc = RootX(e, &ladder_rec_[e].mark_x); rc != DTRL_OK) return rc;
+		}
+		if (int rc = LadderUpload(); rc != DTRL_OK) return rc;
+	}
 	if (!cfg_.device_terrain) {
 		for (int32_t e : reset_ids_) {
 			GroundWindow& g = grounds_[e];
@@ -2109,6 +2128,89 @@ int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrain
 	}
 	if (int rc = ApplyResets(reset_ids_, -1); rc != DTRL_OK) return rc;
 	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::GetTerrains(const int32_t* env_ids, int n, int32_t* terrains_out)
+{
+	if (int rc = LadderIdle("dtrl_get_terrains"); rc != DTRL_OK) return rc;   // with a ladder: the levels as of the last completed boundary
+	return KeysGet(terrain_keys_, "dtrl_get_terrains", env_ids, n, terrains_out);
+}
+
+// ---- terrain ladder (include/dtrl.h: dtrl_terrain_ladder, dtrl_ladder_info) ----
+// The rule is tg_ladder_step (dtrl_terrain_dev.h), run at every frame boundary in front of the env's terrain work: by HostFrameWork / Reset / AssignTerrains on
+// the host (host terrain), inside the boundary launch (-terrain_gen= device, Backend::TerrainBoundaryLadder). dtrl_engine.h says who owns the key array when.
+int Engine::RootX(int e, double* x)
+{
+	real q0 = 0;
+	if (!be_->D2H(&q0, &buf_.st[e].q[0], sizeof(q0))) return Fail(DTRL_ERR_DEVICE, be_->error());
+	*x = static_cast<double>(q0);
+	return DTRL_OK;
+}
+int Engine::LadderRefresh()
+{
+	if (!ladder_on_ || !cfg_.device_terrain) return DTRL_OK;
+	if (!be_->D2H(terrain_keys_.env_key.data(), terrain_keys_.d_env_key, sizeof(int32_t) * terrain_keys_.env_key.size())
+		|| !be_->D2H(ladder_rec_.data(), d_ladder_, sizeof(LadderRec) * ladder_rec_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+int Engine::LadderUpload()
+{
+	if (!ladder_on_ || !cfg_.device_terrain) return DTRL_OK;
+	if (!be_->H2D(d_ladder_, ladder_rec_.data(), sizeof(LadderRec) * ladder_rec_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+int Engine::LadderIdle(const char* what)
+{
+	if (!ladder_on_) return DTRL_OK;
+	if (int rc = KeysIdle(terrain_keys_, what, 0); rc != DTRL_OK) return rc;
+	return LadderRefresh();
+}
+
+int Engine::TerrainLadder(int lo, int hi, double up_dist, double down_dist, int at_top)
+{
+	const std::string w = "dtrl_terrain_ladder: ";
+	if (int rc = KeysIdle(terrain_keys_, "dtrl_terrain_ladder", 0); rc != DTRL_OK) return rc;
+	if (int rc = LadderRefresh(); rc != DTRL_OK) return rc;   // (a ladder in place: the host keys are current again before it goes or is replaced)
+	if (lo > hi) { ladder_on_ = false; return DTRL_OK; }       // the levels stay where they are
+	const int T = terrain_keys_.n_keys();
+	if (lo < 0 || hi >= T) return Fail(DTRL_ERR_ARG, w + "levels " + std::to_string(lo) + " .. " + std::to_string(hi) + " out of range (terrains 0 .. " + std::to_string(T - 1) + ")");
+	for (int t = lo; t <= hi; ++t) if (!terrain_keys_.filled[t]) return Fail(DTRL_ERR_ARG, w + "terrain " + std::to_string(t) + " " + terrain_keys_.empty_text + ": every level of the ladder must be filled");
+	if (!(up_dist > 0)) return Fail(DTRL_ERR_ARG, w + "up_dist must be > 0, not " + std::to_string(up_dist));
+	if (!(down_dist >= 0)) return Fail(DTRL_ERR_ARG, w + "down_dist must be >= 0, not " + std::to_string(down_dist));
+	if (at_top != 0 && at_top != 1) return Fail(DTRL_ERR_ARG, w + "at_top must be 0 or 1, not " + std::to_string(at_top));
+	// the x a reset leaves in q[0] (dtrl_kernel.h reset_env, cScenarioSimChar::InitCharacterPos): one value for the batch
+	auto spawn_of = [](const DevModel& m) { return static_cast<double>(m.valid_init_pos_x ? m.init_pos_x : m.pose0[0]); };
+	const double spawn_x = spawn_of(cfg_.model);
+	for (size_t v = 0; v < var_models_.size(); ++v)
+		if (spawn_of(var_models_[v]) != spawn_x) return Fail(DTRL_ERR_ARG, w + "model variant " + std::to_string(v) + " spawns at another root x (" + std::to_string(spawn_of(var_models_[v])) + ") than the batch's model (" + std::to_string(spawn_x) + "): the ladder keeps one spawn x per batch");
+	if (cfg_.device_terrain && !d_ladder_) {
+		d_ladder_ = static_cast<LadderRec*>(be_->Alloc(sizeof(LadderRec) * static_cast<size_t>(n_)));
+		if (!d_ladder_) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+		allocs_.push_back(d_ladder_);
+	}
+	std::vector<LadderRec> rec(static_cast<size_t>(n_));
+	for (int e = 0; e < n_; ++e) { rec[e].ups = 0; rec[e].downs = 0; if (int rc = RootX(e, &rec[e].mark_x); rc != DTRL_OK) return rc; }
+	ladder_rec_.swap(rec);
+	ladder_ = LadderCfg{lo, hi, at_top, 0, up_dist, down_dist, spawn_x, cfg_.terrain_seed, static_cast<int64_t>(cfg_.run.env_id_base)};
+	ladder_on_ = true;
+	return LadderUpload();
+}
+
+int Engine::LadderInfo(const int32_t* env_ids, int n, double* mark_x_out, int32_t* ups_out, int32_t* downs_out)
+{
+	const std::string w = "dtrl_ladder_info: ";
+	if (terrain_keys_.filled.empty()) return Fail(DTRL_ERR_ARG, w + terrain_keys_.none_text);
+	if (!ladder_on_) return Fail(DTRL_ERR_ARG, w + "the batch has no terrain ladder (call dtrl_terrain_ladder first)");
+	if (int rc = LadderIdle("dtrl_ladder_info"); rc != DTRL_OK) return rc;
+	if (n < 0 || n > n_) return Fail(DTRL_ERR_ARG, w + "the env count must be 0 .. num_envs");
+	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range"); }
+	for (int i = 0; i < n; ++i) {
+		const LadderRec& r = ladder_rec_[EnvIndex(env_ids, i)];
+		if (mark_x_out) mark_x_out[i] = r.mark_x;
+		if (ups_out) ups_out[i] = r.ups;
+		if (downs_out) downs_out[i] = r.downs;
+	}
 	return DTRL_OK;
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 #include "dtrl_host.h"
 #include "dtrl_kernel.h"
+#include "dtrl_terrain_dev.h"
 #include <string>
 #include <vector>
 
@@ -118,6 +119,11 @@ public:
 	// fetches each listed env's GroundRec / GroundGen / EnvStatus, runs tg_env_boundary on the host and writes the records back, synchronised (what the lane-loop
 	// check build runs, and DTRL_TERRAINS_FALLBACK=1 on HIP); the HIP backend overrides it with one launch of dtrl_terrain_boundary_keyed on the selected stream.
 	virtual bool TerrainBoundaryKeyed(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, const int32_t* env_terrain);
+	// Terrain ladder (include/dtrl.h dtrl_terrain_ladder): the keyed work with the rule in front of it -- env e's level moves by its status record (tg_ladder_step,
+	// dtrl_terrain_dev.h), env_terrain[e] and ladder[e] (device memory, local env id) are written back, and the env is built under table[its new level]. The
+	// default is the keyed default's host loop with the rule in it (the lane-loop check build, DTRL_TERRAINS_FALLBACK=1 on HIP); the HIP backend overrides it with
+	// one launch of dtrl_terrain_boundary_ladder on the selected stream.
+	virtual bool TerrainBoundaryLadder(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, int32_t* env_terrain, LadderRec* ladder, const LadderCfg& lc);
 	// order[e0 .. e0 + n) = the envs e0 .. e0 + n - 1 sorted by status[].cost, costliest first (launch order of the group's next frame), on the selected stream
 	virtual bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) = 0;
 	// pending tuples -> block [block_rows + 1][W + 2] (header row + rows sorted by env id, flag word and global env id as the two extra columns); rows
@@ -220,7 +226,10 @@ public:
 	int TerrainSetParams(int t, const char* type_name, const double* params40);
 	int TerrainInfo(int t, char* type_out, int type_cap, double* params40_out, int* filled_out);
 	int AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrains, bool restart);
-	int GetTerrains(const int32_t* env_ids, int n, int32_t* terrains_out) { return KeysGet(terrain_keys_, "dtrl_get_terrains", env_ids, n, terrains_out); }
+	int GetTerrains(const int32_t* env_ids, int n, int32_t* terrains_out);
+	// terrain ladder (include/dtrl.h)
+	int TerrainLadder(int lo, int hi, double up_dist, double down_dist, int at_top);
+	int LadderInfo(const int32_t* env_ids, int n, double* mark_x_out, int32_t* ups_out, int32_t* downs_out);
 	int TerrainStats(int t, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) { return KeysStats(terrain_keys_, "dtrl_terrain_stats", false, t, n_envs, avg_dist, episodes, cycles, resets); }
 	int num_terrains() const { return terrain_keys_.n_keys(); }
 	// the model env e (local id, in range) runs under: what host-side readers of per-env geometry use (dtrl_get_link_states, AddPerturb)
@@ -281,8 +290,13 @@ private:
 	int DrainDeviceDistLog();
 	int UploadTerrainCfg(const double* params);
 	TerrainCfg MakeTerrainCfg(int type, const double* params) const;   // the scene constants of a TerrainCfg are the batch's
-	// -terrain_gen= device: the boundary work of every caller -- Backend::TerrainBoundary as it always was, or, once terrains exist, the keyed form
-	bool Boundary(int e0, int n, int mode, const int32_t* env_list) { return terrain_keys_.filled.empty() ? be_->TerrainBoundary(buf_, e0, n, mode, env_list) : be_->TerrainBoundaryKeyed(buf_, e0, n, mode, env_list, d_terrain_table_, terrain_keys_.d_env_key); }
+	// -terrain_gen= device: the boundary work of every caller -- Backend::TerrainBoundary as it always was, once terrains exist the keyed form, with a ladder the ladder form
+	bool Boundary(int e0, int n, int mode, const int32_t* env_list)
+	{
+		if (terrain_keys_.filled.empty()) return be_->TerrainBoundary(buf_, e0, n, mode, env_list);
+		if (!ladder_on_) return be_->TerrainBoundaryKeyed(buf_, e0, n, mode, env_list, d_terrain_table_, terrain_keys_.d_env_key);
+		return be_->TerrainBoundaryLadder(buf_, e0, n, mode, env_list, d_terrain_table_, terrain_keys_.d_env_key, d_ladder_, ladder_);
+	}
 	int ApplyResets(const std::vector<int32_t>& ids, int group);
 	int LaunchGroup(int group, int n_steps, double dt_step, bool frame_end);
 	// env groups: contiguous env ranges, each with its own stream, launch order and staging slices. Envs are independent, so a group
@@ -401,6 +415,18 @@ private:
 	std::vector<TerrainSource> terrain_src_;
 	double terrain_lerp_ = 0;                // terrain 0's lerp in force
 	int TerrainFill(const char* what, int t, int type, const double* params);   // table entry t (>= 1) in both forms, and the windows of the envs under it
+	// terrain ladder: settings and per-env records are batch state, like the assignment. WHO OWNS THE TERRAIN KEYS: without a ladder the host array is the truth and
+	// the device array its copy (KeysAssign uploads it). With a ladder, host terrain mode keeps it so (HostFrameWork runs the rule and brings the device copy up to
+	// date), but with -terrain_gen= device the boundary kernel moves the DEVICE array and the device ladder records while frames run: every terrain call that reads
+	// or uploads the key array first waits for every stream (KeysIdle) and then refreshes both host copies from the device (LadderRefresh)
+	bool ladder_on_ = false;
+	LadderCfg ladder_{};
+	std::vector<LadderRec> ladder_rec_;      // host form [n]
+	LadderRec* d_ladder_ = nullptr;          // device [n] (-terrain_gen= device; allocated by the first ladder)
+	int LadderRefresh();                     // device terrain + ladder: host keys and ladder records <- device (call behind KeysIdle); else nothing
+	int LadderUpload();                      // device terrain + ladder: device ladder records <- host
+	int RootX(int e, double* x);             // env e's current root x (q[0] of its state record; call with the streams idle)
+	int LadderIdle(const char* what);        // with a ladder: KeysIdle + LadderRefresh; without: nothing
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

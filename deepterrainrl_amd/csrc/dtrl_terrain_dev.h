@@ -122,4 +122,42 @@ DTRL_TG_HD inline void tg_env_boundary(GroundRec& rec, GroundGen& gen, const Env
 	else tg_window_update(rec, st.root_x + c.view_min, st.root_x + c.view_max, c, rnd, &gen);
 }
 
+// ---- terrain ladder (include/dtrl.h dtrl_terrain_ladder): envs climb and descend a range of the terrain set by their episodes ----
+// per-env record: the root x at which the env last spawned or last changed level, and how often it went up / down
+struct LadderRec { double mark_x; int32_t ups, downs; };
+// the batch's ladder: terrains [lo, hi] ordered easy to hard, the distances, what happens at the top, and what the rule needs besides (the x a reset leaves in
+// q[0], the terrain seed and the env-id base of the at_top draw). A kernel ARGUMENT, like the table and the key array: DevBuffers keeps its layout
+struct LadderCfg {
+	int32_t lo, hi, at_top, pad_;
+	double up_dist, down_dist, spawn_x;
+	uint64_t seed; int64_t env_id_base;
+};
+// the at_top draw: counter-based like the terrain streams, a function of (terrain seed, GLOBAL env id, moves so far) only -- shard-invariant
+DTRL_TG_HD inline uint64_t ladder_draw(uint64_t terrain_seed, int64_t global_env, int32_t moves)
+{
+	return tg_mix(tg_mix(tg_mix(terrain_seed) ^ (0x1ADDE2ULL + static_cast<uint64_t>(global_env))) + static_cast<uint64_t>(moves) * 0xD1342543DE82EF95ULL);
+}
+// The rule, the one body of host and device: the level of env `env` (local id) after its frame boundary, given its level k in front of it. Runs IN FRONT OF the
+// env's terrain work (tg_env_boundary, GroundWindow::Clear / Update), so the window built or slid in the same boundary is the new level's. An env whose level is
+// outside [lo, hi] is not on the ladder: nothing happens. Modes as tg_env_boundary's: 0 = after a frame, 1 / 2 = (re)initialise (the level stays, the mark goes
+// to the spawn point). Every comparison in double; no exploration, no reward, no episode_dist, no other env.
+DTRL_TG_HD inline int32_t tg_ladder_step(LadderRec& lr, int32_t k, const EnvStatus& st, const LadderCfg& lc, int mode, int env)
+{
+	if (k < lc.lo || k > lc.hi) return k;
+	if (mode != 0) { lr.mark_x = lc.spawn_x; return k; }
+	if (st.need_reset) {   // the episode ended: early falls go down
+		if (st.root_x - lr.mark_x < lc.down_dist && k > lc.lo) { k -= 1; lr.downs += 1; }
+		lr.mark_x = lc.spawn_x;
+	} else if (st.root_x - lr.mark_x >= lc.up_dist) {
+		if (k < lc.hi) { k += 1; lr.ups += 1; }
+		else if (lc.at_top == 1) {
+			const uint64_t draw = ladder_draw(lc.seed, lc.env_id_base + env, lr.ups + lr.downs);
+			k = lc.lo + static_cast<int32_t>(draw % static_cast<uint64_t>(lc.hi - lc.lo + 1));
+			lr.ups += 1;
+		}
+		lr.mark_x = st.root_x;
+	}
+	return k;
+}
+
 }  // namespace dtrl

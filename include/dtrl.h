@@ -398,11 +398,38 @@ dtrl_status dtrl_terrain_info(dtrl_batch* b, int t, char* type_out, int type_cap
  * re-seeded from (terrain seed, GLOBAL env id), the build count goes to 0, a fresh two-segment window is built around the spawn point, and the device half of a
  * reset runs (as dtrl_reset). The exploration counter is not rewound. */
 dtrl_status dtrl_assign_terrains(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* terrains, int restart);
-/* No counterpart in the reference, which keeps one terrain per scene object. The terrains of the listed envs (valid at any time). */
+/* No counterpart in the reference, which keeps one terrain per scene object. The terrains of the listed envs. Without a terrain ladder (below): valid at any time.
+ * With a ladder the levels move at the frame boundaries, with -terrain_gen= device on the device: the call then returns the levels as of the last completed
+ * boundary -- it is refused with DTRL_ERR_ARG between dtrl_step_begin and dtrl_step_end, and otherwise waits for everything the batch has queued. */
 dtrl_status dtrl_get_terrains(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* terrains_out);
 /* No counterpart in the reference, which keeps one terrain per scene object. dtrl_eval_stats restricted to the envs currently in terrain t (n_envs of them), reduced on the device in a fixed order: two calls
  * without a step between them return the same bits. Refuses a frame in flight, like dtrl_variant_stats. Any output may be NULL. */
 dtrl_status dtrl_terrain_stats(dtrl_batch* b, int t, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+
+/* ---- Terrain ladder: envs climb and descend a range of the terrain set by their own episodes ----
+ * No counterpart in the reference, which keeps one terrain per scene object and moves it for everybody at once (SetTerrainParamsLerp). A ladder is a contiguous
+ * range [lo, hi] of filled terrains, ordered easy to hard by the caller. Each env carries a record {mark_x, ups, downs}: mark_x is the root x at which it last
+ * spawned or last changed level. At the frame boundary of env e, IN FRONT OF its terrain work (so the window built or slid in the same boundary is already the
+ * new level's), with k = the env's terrain, in double:
+ *   k outside [lo, hi]                                    nothing: the env is not on the ladder (evaluation envs can be held on fixed terrains)
+ *   the episode ended (the env fell)                      root_x - mark_x < down_dist and k > lo: k -= 1, downs += 1. Always mark_x = spawn_x
+ *   it did not, and root_x - mark_x >= up_dist            k < hi: k += 1, ups += 1; else with at_top == 1: k = lo + draw % (hi - lo + 1), ups += 1 (draw: counter-
+ *                                                         based, a function of the terrain seed, the GLOBAL env id and ups + downs alone: shard-invariant); else k
+ *                                                         stays. In all three cases mark_x = root_x
+ *   creation-time init, dtrl_reset, restart               mark_x = spawn_x, the level stays
+ * spawn_x is the root x a reset leaves (the character file's default pose, or -init_pos_x=). The rule looks at nothing else: no exploration, reward, episode
+ * distance or other env. With -terrain_gen= device it runs inside the boundary launch the batch already queues per env group and frame (no host round trip, no
+ * launch more; dtrl_run_frames and the overlapped loops included); in host terrain mode in the host's per-frame status loop. It also runs at the boundary behind
+ * dtrl_step_updates. Settings and records are batch state like the assignment: snapshots, restores, clones and blobs leave them alone -- a restored env that now
+ * stands behind its mark_x therefore counts as "early" at its next fall. Timing as the terrain calls above. */
+/* No counterpart in the reference, which keeps one terrain per scene object. Create or replace the batch's ladder: every env's mark_x becomes its current root x, the counters go to 0, the levels
+ * stay. lo > hi removes the ladder (the levels stay where they are). DTRL_ERR_ARG: no terrain set, lo / hi out of range, an empty terrain inside [lo, hi],
+ * up_dist <= 0, down_dist < 0, at_top not 0 / 1, model variants whose spawn x differ, a frame in flight. */
+dtrl_status dtrl_terrain_ladder(dtrl_batch* b, int lo, int hi, double up_dist, double down_dist, int at_top);
+/* No counterpart in the reference, which keeps one terrain per scene object. The ladder records of the listed envs (env_ids == NULL: the first n), as of the last completed boundary: refused between
+ * dtrl_step_begin and dtrl_step_end, otherwise waits for queued work. Any output may be NULL. With a ladder present dtrl_assign_terrains keeps working: restart
+ * != 0 puts the listed envs' mark_x to spawn_x, restart == 0 to the env's current root x; the counters stay. */
+dtrl_status dtrl_ladder_info(dtrl_batch* b, const int32_t* env_ids, int n, double* mark_x_out, int32_t* ups_out, int32_t* downs_out);
 
 /* Replaces: cScenarioSimChar::AddPerturb -> cWorld::AddPerturb (scenarios/ScenarioSimChar.cpp:204-207, sim/World.cpp:256-259) with a
  * tPerturb of type ePerturbForce (sim/Perturb.cpp:52-79, sim/World.cpp:445-470): a world-frame force[n][2] on body part link[n] at the
