@@ -63,7 +63,7 @@ ABI_SYMBOLS = [
     "dtrl_drain_tuples_device", "dtrl_tuple_stats", "dtrl_set_policy_device", "dtrl_get_dist_log", "dtrl_reset_avg_dist", "dtrl_write_dist_log", "dtrl_get_ground_window", "dtrl_drain_tuples_packed", "dtrl_get_policy_output", "dtrl_set_tuple_pipelining", "dtrl_step_end_begin", "dtrl_command_action", "dtrl_side_stream", "dtrl_step_poll", "dtrl_set_policy_device_on", "dtrl_set_policy_device_async",
     "dtrl_snapshot_save", "dtrl_snapshot_restore", "dtrl_clone_envs", "dtrl_snapshot_export", "dtrl_snapshot_import", "dtrl_snapshot_info", "dtrl_snapshot_free",
     "dtrl_slots_create", "dtrl_slot_set_policy", "dtrl_slot_set_policy_device", "dtrl_slot_alias", "dtrl_slot_set_explore", "dtrl_assign_slots", "dtrl_get_slots", "dtrl_slot_stats",
-    "dtrl_variants_create", "dtrl_variant_load_file", "dtrl_variant_load_json", "dtrl_assign_variants", "dtrl_get_variants", "dtrl_variant_stats",
+    "dtrl_variants_create", "dtrl_variant_load_file", "dtrl_variant_load_json", "dtrl_assign_variants", "dtrl_get_variants", "dtrl_variant_stats", "dtrl_variant_redraw", "dtrl_variant_redraw_info",
     "dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats", "dtrl_terrain_ladder", "dtrl_ladder_info",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
@@ -160,6 +160,8 @@ def _bind(path):
     L.dtrl_assign_variants.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_get_variants.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_variant_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.dtrl_variant_redraw.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, vp]
+    L.dtrl_variant_redraw_info.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     L.dtrl_terrains_create.argtypes = [vp, C.c_int]
     L.dtrl_terrain_set_file.argtypes = [vp, C.c_int, C.c_char_p, C.c_double]
     L.dtrl_terrain_set_params.argtypes = [vp, C.c_int, C.c_char_p, vp]
@@ -809,6 +811,28 @@ class BatchScenario:
     def VariantStats(self, v):
         """EvalStats restricted to the envs currently in variant v (plus their number), reduced on the device in a fixed order."""
         return self._key_stats(self._lib.dtrl_variant_stats, v)
+
+    # ---- variant redraw: envs draw a new model variant at each episode start (no counterpart in the reference, which keeps one character per scene object) ----
+    def VariantRedraw(self, lo, hi, seed=0, weights=None):
+        """dtrl_variant_redraw: from now on an env whose variant is in lo .. hi (filled variants) draws a new variant of that range at every episode start -- the
+        frame boundary at which it fell, or Reset naming it -- in front of the reset, which therefore runs under the new model. weights: None = uniform, else
+        hi - lo + 1 non-negative numbers, not all zero. The draw depends on (seed, global env id, the env's own draw counter) alone. Envs outside lo .. hi are left
+        alone. With -terrain_gen= device this happens on the device, without the host. VariantRedraw(1, 0) removes the redraw (variants and counters stay). With a
+        redraw on device terrain, GetVariants / VariantRedrawInfo report the state as of the last completed frame boundary (not between UpdateBegin and UpdateEnd)."""
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if int(lo) <= int(hi) and w.size != int(hi) - int(lo) + 1:
+                raise DtrlError("VariantRedraw: weights must hold hi - lo + 1 = %d numbers, not %d" % (int(hi) - int(lo) + 1, w.size))
+        self._chk(self._lib.dtrl_variant_redraw(self._h, int(lo), int(hi), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(w) if w is not None else None))
+
+    def VariantRedrawInfo(self, env_ids=None):
+        """dtrl_variant_redraw_info: {"lo", "hi" (the redraw's range), "variant", "draws" (int32 per listed env, all by default)}."""
+        ids, n = self._ids(env_ids)
+        lo, hi = C.c_int32(), C.c_int32()
+        variant, draws = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._chk(self._lib.dtrl_variant_redraw_info(self._h, _p(ids), n, C.byref(lo), C.byref(hi), _p(variant), _p(draws)))
+        return {"lo": int(lo.value), "hi": int(hi.value), "variant": variant, "draws": draws}
 
     # ---- terrain sets: several terrains in one batch, one per env (no counterpart in the reference, which keeps one terrain per scene object) ----
     num_terrains = 0

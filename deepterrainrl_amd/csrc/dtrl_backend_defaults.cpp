@@ -1,10 +1,11 @@
 // dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, launches over
-// envs of several slots or variants and the per-slot sums, the frame-boundary terrain work of envs under several terrains, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
+// envs of several slots or variants and the per-slot sums, the variant redraw, the frame-boundary terrain work of envs under several terrains, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
 // of them with kernels and keeps these as its cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1).
 // Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
 // lane-loop check build of any tests/ tree, the sanitizer scripts -- has the defaults, and no source list can lack them.
 #include "dtrl_engine.h"
 #include "dtrl_terrain_dev.h"
+#include <algorithm>
 
 namespace dtrl {
 
@@ -89,25 +90,34 @@ bool Backend::ExtSupply(const DevBuffers& buf, int n_envs, int n_opt, int n_labe
 }
 // The launch list of `buf` (n_envs entries; no list: envs 0 .. n_envs - 1) regrouped by key_of_env[] into `part`, list order kept inside a key; n_of[k] = entries
 // of key k, in key order. list_host: the list in host-readable form, nullptr = read it back. Waits for the selected stream before it writes `part`.
-static bool SplitLaunchList(Backend& be, const DevBuffers& buf, int n_envs, const int32_t* list_host, const int32_t* key_of_env, int n_keys, int32_t* part, std::vector<int32_t>& n_of)
+// key_dev != nullptr (a variant redraw on device terrain: the device array is the truth): the listed envs' keys are read back from there, behind that wait.
+static bool SplitLaunchList(Backend& be, const DevBuffers& buf, int n_envs, const int32_t* list_host, const int32_t* key_of_env, const int32_t* key_dev, int n_keys, int32_t* part, std::vector<int32_t>& n_of)
 {
 	std::vector<int32_t> list(static_cast<size_t>(n_envs));
 	if (!buf.env_list) { for (int i = 0; i < n_envs; ++i) list[i] = i; }
 	else if (list_host) { for (int i = 0; i < n_envs; ++i) list[i] = list_host[i]; }
 	else if (!be.D2H(list.data(), buf.env_list, sizeof(int32_t) * list.size())) return false;   // (an order computed on the device: behind everything queued, this launch's list included)
 	if (!be.SyncSelected()) return false;   // an earlier launch of this stream may still be reading `part`
+	std::vector<int32_t> fetched; int32_t first = 0;
+	if (key_dev) {   // one copy of the span of the key array that holds the listed envs
+		const auto mm = std::minmax_element(list.begin(), list.end());
+		first = *mm.first;
+		fetched.resize(static_cast<size_t>(*mm.second - first + 1));
+		if (!be.D2H(fetched.data(), key_dev + first, sizeof(int32_t) * fetched.size())) return false;
+		key_of_env = fetched.data();
+	}
 	n_of.assign(static_cast<size_t>(n_keys), 0);
 	std::vector<int32_t> at(static_cast<size_t>(n_keys));
-	for (int32_t e : list) ++n_of[key_of_env[e]];
+	for (int32_t e : list) ++n_of[key_of_env[e - first]];
 	for (int s = 0, k = 0; s < n_keys; ++s) { at[s] = k; k += n_of[s]; }
-	for (int32_t e : list) part[at[key_of_env[e]]++] = e;
+	for (int32_t e : list) part[at[key_of_env[e - first]]++] = e;
 	return true;
 }
 bool Backend::LaunchKeyed(const DevModel* gm, const RunParams& rp, const DevBuffers& buf, const EnvKeyView& keys, int n_envs, int n_steps, real dt, bool frame_end)
 {
 	if (n_envs <= 0) return true;
 	std::vector<int32_t> n_of;
-	if (!SplitLaunchList(*this, buf, n_envs, keys.env_list_host, keys.env_key_host, keys.n_keys, keys.part, n_of)) return false;
+	if (!SplitLaunchList(*this, buf, n_envs, keys.env_list_host, keys.env_key_host, keys.keys_on_device ? keys.env_key_dev : nullptr, keys.n_keys, keys.part, n_of)) return false;
 	for (int k = 0, at = 0; k < keys.n_keys; at += n_of[k], ++k) {
 		if (n_of[k] == 0) continue;
 		RunParams r = rp; DevBuffers b = buf;
@@ -128,6 +138,27 @@ bool Backend::SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs
 		SlotSums& a = sums[s];
 		++a.n_envs; a.episodes += host[e].num_episodes; a.cycles += host[e].num_cycles; a.resets += host[e].num_resets;
 		a.dist_sum += static_cast<double>(host[e].avg_dist) * static_cast<double>(host[e].num_episodes);
+	}
+	return true;
+}
+// Variant redraw: the rule (var_redraw_step) on the host, env by env; key and counter go back where they changed. The first D2H waits for the selected stream.
+bool Backend::VariantRedraw(const EnvStatus* status, int e0, int n, const int32_t* env_list, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg)
+{
+	if (n <= 0) return true;
+	std::vector<int32_t> list(static_cast<size_t>(n));
+	if (!env_list) { for (int k = 0; k < n; ++k) list[k] = e0 + k; }
+	else if (!D2H(list.data(), env_list, sizeof(int32_t) * list.size())) return false;
+	std::vector<double> cum(static_cast<size_t>(cfg.hi - cfg.lo + 1));
+	if (!D2H(cum.data(), cfg.cum, sizeof(double) * cum.size())) return false;
+	EnvStatus st; RedrawRec r; int32_t key = 0;
+	for (int32_t e : list) {
+		if (!D2H(&st, status + e, sizeof(st))) return false;
+		if (!(st.need_reset & 1)) continue;
+		if (!D2H(&key, env_model + e, sizeof(key)) || !D2H(&r, recs + e, sizeof(r))) return false;
+		const int32_t draws0 = r.draws;
+		const int32_t next = var_redraw_step(r, key, true, cfg, cum.data(), e);
+		if (next != key && !H2D(env_model + e, &next, sizeof(next))) return false;
+		if (r.draws != draws0 && !H2D(recs + e, &r, sizeof(r))) return false;
 	}
 	return true;
 }

@@ -180,6 +180,22 @@ __global__ void dtrl_terrain_boundary_ladder(DevBuffers buf, int e0, int n, int 
 	if (lr.mark_x != lr0.mark_x || lr.ups != lr0.ups || lr.downs != lr0.downs) ladder[e] = lr;
 	tg_env_boundary(buf.gr[e], buf.gen[e], buf.status[e], table[next], mode, e, buf.dist_ring, buf.dist_count, buf.dist_cap);
 }
+// Variant redraw (include/dtrl.h dtrl_variant_redraw): the envs of a group that fell draw the model variant of their next episode, behind the group's frame and
+// boundary work and in front of its reset launch (var_redraw_step, dtrl_terrain_dev.h). A kernel of its own: the boundary kernels above stay as they are. Thread
+// per env, every word per env, key and counter written back only where they changed: no atomics. The settings and the cumulative table are arguments.
+__global__ void dtrl_variant_redraw(const EnvStatus* __restrict__ status, int e0, int n, const int32_t* __restrict__ env_list, int32_t* __restrict__ env_model, RedrawRec* __restrict__ recs, RedrawCfg rc)
+{
+	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+	if (k >= n) return;
+	const int e = env_list ? env_list[k] : e0 + k;
+	if (!(status[e].need_reset & 1)) return;
+	const int32_t v = env_model[e];
+	RedrawRec r = recs[e];
+	const int32_t draws0 = r.draws;
+	const int32_t next = var_redraw_step(r, v, true, rc, rc.cum, e);
+	if (next != v) env_model[e] = next;
+	if (r.draws != draws0) recs[e] = r;
+}
 // launch order of a group's next frame: counting sort on cost / 16, costliest first (one workgroup; the order inside a bucket is whatever the
 // atomics produce -- it only decides which wavefront starts first)
 constexpr int kOrderBuckets = 1024;
@@ -592,6 +608,14 @@ public:
 		if (n <= 0) return true;
 		hipLaunchKernelGGL(dtrl_terrain_boundary_ladder, dim3((n + 63) / 64), dim3(64), 0, stream_, buf, e0, n, mode, env_list, table, env_terrain, ladder, lc);
 		return Check(hipGetLastError(), "ladder terrain boundary launch");
+	}
+	// variant redraw: ONE launch per group and frame, queued like the boundary work. DTRL_VARIANTS_FALLBACK=1 takes the host default
+	bool VariantRedraw(const EnvStatus* status, int e0, int n, const int32_t* env_list, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg) override
+	{
+		if (EnvFlag("DTRL_VARIANTS_FALLBACK")) return Backend::VariantRedraw(status, e0, n, env_list, env_model, recs, cfg);
+		if (n <= 0) return true;
+		hipLaunchKernelGGL(dtrl_variant_redraw, dim3((n + 63) / 64), dim3(64), 0, stream_, status, e0, n, env_list, env_model, recs, cfg);
+		return Check(hipGetLastError(), "variant redraw launch");
 	}
 	bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) override
 	{

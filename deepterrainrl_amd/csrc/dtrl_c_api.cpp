@@ -140,6 +140,7 @@ dtrl_status dtrl_get_link_states(dtrl_batch* b, const int32_t* env_ids, int n, d
 try {
 	CHECK_B();
 	std::vector<EnvState> st; int rc = b->eng.GetStates(env_ids, n, st);
+	if (rc == DTRL_OK) rc = b->eng.VariantKeysCurrent();   // (a variant redraw on device terrain: the keys ModelOf reads are the device's; GetStates has waited for the streams)
 	if (rc != DTRL_OK) return static_cast<dtrl_status>(rc);
 	const int L = b->eng.cfg().model.L;
 	for (int e = 0; e < n; ++e) {
@@ -282,6 +283,8 @@ try {
 } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_assign_variants(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* variants) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.AssignVariants(env_ids, n, variants)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_get_variants(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* variants_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.GetVariants(env_ids, n, variants_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_variant_redraw(dtrl_batch* b, int lo, int hi, uint64_t seed, const double* weights) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantRedraw(lo, hi, seed, weights)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_variant_redraw_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* lo, int32_t* hi, int32_t* variant, int32_t* draws) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantRedrawInfo(env_ids, n, lo, hi, variant, draws)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_variant_stats(dtrl_batch* b, int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantStats(v, n_envs, avg_dist, episodes, cycles, resets)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 // terrain sets
 dtrl_status dtrl_terrains_create(dtrl_batch* b, int n_terrains) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainsCreate(n_terrains)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }

@@ -369,7 +369,7 @@ bool Engine::LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, b
 	const bool variants = !var_models_.empty();   // (variants and slots exclude each other: dtrl_variants_create / dtrl_slots_create)
 	if (!variants && slots_.empty()) return be_->Launch(d_model_, cfg_.run, b, n_envs, n_steps, dt, frame_end);
 	EnvKeyView v = (variants ? variant_keys_ : slot_keys_).View(list_host, part_off);
-	if (variants) v.models_dev = d_var_models_;
+	if (variants) { v.models_dev = d_var_models_; v.keys_on_device = RedrawOnDevice(); }
 	else { v.slots_dev = d_slot_table_; v.slots_host = slot_table_.data(); }
 	return be_->LaunchKeyed(variants ? d_var_models_ : d_model_, cfg_.run, b, v, n_envs, n_steps, dt, frame_end);
 }
@@ -397,6 +397,7 @@ int Engine::UploadTerrainCfg(const double* params)
 // one -- the host neither waits nor loops over envs:
 //   dtrl_terrain_boundary  fresh windows for the envs that fell, slid windows where the character got close to an edge, episode distances logged
 //   dtrl_order_by_cost     launch order of the next frame (costliest wavefronts first)
+//   dtrl_variant_redraw    (with a variant redraw) the envs that fell draw the model variant of their next episode
 //   0-step frame launch    the device half of the reset, taken by the envs that fell, skipped by the others (reset_listed = 2)
 int Engine::DeviceFrameWork(int group)
 {
@@ -406,6 +407,8 @@ int Engine::DeviceFrameWork(int group)
 	DevBuffers b = buf_;
 	b.env_list = nullptr; b.reset_listed = 2;
 	if (!Boundary(grp.e0, grp.n, 0, nullptr) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	// variant redraw: the envs that fell draw their next variant behind their frame and in front of the reset launch, which then runs reset_env under the new model
+	if (redraw_on_) { redraw_stale_ = true; if (!be_->VariantRedraw(buf_.status, grp.e0, grp.n, nullptr, variant_keys_.d_env_key, d_redraw_, redraw_)) return Fail(DTRL_ERR_DEVICE, be_->error()); }
 	b.env_list = d_order_ + grp.e0;
 	if (!LaunchEnvs(b, grp.n, 0, 0.0, false, nullptr, grp.e0)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
@@ -446,9 +449,15 @@ int Engine::HostFrameWork(int group)
 	const double ht1 = g_ht.on ? now_s() : 0;
 	reset_ids_.clear();
 	work_.clear();
-	bool level_moved = false;
+	bool level_moved = false, variant_moved = false;
+	RedrawCfg rd = redraw_; rd.cum = redraw_cum_.data();
 	for (int e = e0; e < e1; ++e) {
 		const EnvStatus& s = status_[e];
+		if (redraw_on_) {   // the redraw's rule: an env that fell draws the variant its next episode runs under (the reset launch below reads the key)
+			int32_t& k = variant_keys_.env_key[e];
+			const int32_t next = var_redraw_step(redraw_rec_[e], k, (s.need_reset & 1) != 0, rd, rd.cum, e);
+			if (next != k) { k = next; variant_moved = true; }
+		}
 		if (ladder_on_) {   // the ladder's rule, in front of the env's terrain work: the window built or slid below is already the new level's
 			int32_t& k = terrain_keys_.env_key[e];
 			const int32_t next = tg_ladder_step(ladder_rec_[e], k, s, ladder_, 0, e);
@@ -460,6 +469,8 @@ int Engine::HostFrameWork(int group)
 	}
 	// (the device copy of the keys, which dtrl_terrain_stats reduces over: the group's slice, when a level in it moved; no launch reads it)
 	if (level_moved && !be_->H2D(terrain_keys_.d_env_key + e0, terrain_keys_.env_key.data() + e0, sizeof(int32_t) * static_cast<size_t>(grp.n))) return Fail(DTRL_ERR_DEVICE, be_->error());
+	// (the variant keys are read by a launch: the group's slice goes up on the group's stream in front of the reset launch)
+	if (variant_moved && !be_->H2D(variant_keys_.d_env_key + e0, variant_keys_.env_key.data() + e0, sizeof(int32_t) * static_cast<size_t>(grp.n))) return Fail(DTRL_ERR_DEVICE, be_->error());
 	const int used = static_cast<int>(work_.size());
 	if (used > 0) {
 		// the rebuilds of one frame are independent (own RNG stream, own window per env): host workers share them; every rebuilt record goes into
@@ -686,6 +697,7 @@ int Engine::Reset(const int32_t* env_ids, int n, const uint64_t* seeds)
 		std::memcpy(pin_ids_, reset_ids_.data(), sizeof(int32_t) * reset_ids_.size());
 		if (!be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size()) || !Boundary(0, static_cast<int>(reset_ids_.size()), 1, d_env_list_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
+	if (int rc = RedrawListed(reset_ids_); rc != DTRL_OK) return rc;   // variant redraw: an episode starts, once per listed env, and the reset below runs under the new model
 	int rc = ApplyResets(reset_ids_, -1);
 	if (rc != DTRL_OK) return rc;
 	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
@@ -1225,6 +1237,7 @@ int Engine::AddPerturb(const int32_t* env_ids, int n, const int32_t* link, const
 {
 	if (env_ids && n < 0) return Fail(DTRL_ERR_ARG, "negative env count");
 	be_->Sync();
+	if (int rc = VariantRefresh(); rc != DTRL_OK) return rc;
 	EnvState st;
 	const int cnt = env_ids ? n : n_;
 	for (int i = 0; i < cnt; ++i) {
@@ -2006,6 +2019,100 @@ int Engine::VariantLoad(int v, const char* character_file, const char* text, siz
 		return Fail(DTRL_ERR_ARG, std::string(what) + ": variant " + std::to_string(v) + " does not fit the batch: " + f + " differs from the batch's model (the skeleton, the scene and the controller part -- parameters, actions, default action -- are one per batch)");
 	if (!be_->H2D(d_var_models_ + v, &vc.model, sizeof(DevModel))) return Fail(DTRL_ERR_DEVICE, be_->error());
 	var_models_[v] = vc.model; variant_keys_.filled[v] = 1;
+	return DTRL_OK;
+}
+
+// ---- variant redraw (include/dtrl.h: dtrl_variant_redraw, dtrl_variant_redraw_info) ----
+// The rule is var_redraw_step (dtrl_terrain_dev.h), run at an env's episode start in front of the reset launch: by HostFrameWork's status loop (host terrain), by
+// Backend::VariantRedraw queued between the boundary work and the reset launch (-terrain_gen= device), by RedrawListed under dtrl_reset. dtrl_engine.h says who
+// owns the key array when.
+int Engine::VariantRefresh()
+{
+	if (!RedrawOnDevice() || !redraw_stale_) return DTRL_OK;
+	if (!be_->D2H(variant_keys_.env_key.data(), variant_keys_.d_env_key, sizeof(int32_t) * variant_keys_.env_key.size())
+		|| !be_->D2H(redraw_rec_.data(), d_redraw_, sizeof(RedrawRec) * redraw_rec_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	redraw_stale_ = false;
+	return DTRL_OK;
+}
+int Engine::VariantIdle(const char* what)
+{
+	if (!RedrawOnDevice()) return DTRL_OK;
+	if (int rc = KeysIdle(variant_keys_, what, 0); rc != DTRL_OK) return rc;
+	return VariantRefresh();
+}
+int Engine::AssignVariants(const int32_t* env_ids, int n, const int32_t* variants)
+{
+	if (int rc = VariantIdle("dtrl_assign_variants"); rc != DTRL_OK) return rc;   // (the whole-array upload below would otherwise undo every draw the kernel made)
+	return KeysAssign(variant_keys_, "dtrl_assign_variants", env_ids, n, variants);
+}
+int Engine::GetVariants(const int32_t* env_ids, int n, int32_t* variants_out)
+{
+	if (int rc = VariantIdle("dtrl_get_variants"); rc != DTRL_OK) return rc;   // with a redraw on device terrain: the variants as of the last completed boundary
+	return KeysGet(variant_keys_, "dtrl_get_variants", env_ids, n, variants_out);
+}
+// (dtrl_reset only, never per frame: the streams are idle, and both arrays go up whole with synchronous copies -- O(num_envs) per call, whatever the list's length)
+int Engine::RedrawListed(const std::vector<int32_t>& ids)
+{
+	if (!redraw_on_ || ids.empty()) return DTRL_OK;
+	if (int rc = VariantRefresh(); rc != DTRL_OK) return rc;
+	RedrawCfg rd = redraw_; rd.cum = redraw_cum_.data();
+	for (int32_t e : ids) variant_keys_.env_key[e] = var_redraw_step(redraw_rec_[e], variant_keys_.env_key[e], true, rd, rd.cum, e);
+	if (!be_->H2D(variant_keys_.d_env_key, variant_keys_.env_key.data(), sizeof(int32_t) * variant_keys_.env_key.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (cfg_.device_terrain && !be_->H2D(d_redraw_, redraw_rec_.data(), sizeof(RedrawRec) * redraw_rec_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::VariantRedraw(int lo, int hi, uint64_t seed, const double* weights)
+{
+	const std::string w = "dtrl_variant_redraw: ";
+	if (int rc = KeysIdle(variant_keys_, "dtrl_variant_redraw", 0); rc != DTRL_OK) return rc;
+	if (int rc = VariantRefresh(); rc != DTRL_OK) return rc;   // (a redraw in place: the host keys and counters are current again before it goes or is replaced)
+	if (lo > hi) { redraw_on_ = false; return DTRL_OK; }        // the envs keep the variants they have, the counters stay
+	const int V = variant_keys_.n_keys();
+	if (lo < 0 || hi >= V) return Fail(DTRL_ERR_ARG, w + "variants " + std::to_string(lo) + " .. " + std::to_string(hi) + " out of range (variants 0 .. " + std::to_string(V - 1) + ")");
+	for (int v = lo; v <= hi; ++v) if (!variant_keys_.filled[v]) return Fail(DTRL_ERR_ARG, w + "variant " + std::to_string(v) + " " + variant_keys_.empty_text + ": every variant of the redraw must be filled");
+	const int m = hi - lo + 1;
+	std::vector<double> cum(static_cast<size_t>(m));
+	double sum = 0;
+	for (int j = 0; j < m; ++j) {
+		const double wj = weights ? weights[j] : 1.0;
+		if (!(wj >= 0) || !std::isfinite(wj)) return Fail(DTRL_ERR_ARG, w + "weight " + std::to_string(j) + " (" + std::to_string(wj) + ") must be a non-negative finite number");
+		sum += wj; cum[j] = sum;
+	}
+	if (!(sum > 0)) return Fail(DTRL_ERR_ARG, w + "the weights are all zero");
+	if (!std::isfinite(sum)) return Fail(DTRL_ERR_ARG, w + "the sum of the weights is not a finite number");
+	for (int j = 0; j < m; ++j) cum[j] /= sum;
+	cum[m - 1] = 1.0;
+	if (cfg_.device_terrain && !d_redraw_) {
+		RedrawRec* recs = static_cast<RedrawRec*>(be_->Alloc(sizeof(RedrawRec) * static_cast<size_t>(n_)));
+		double* table = static_cast<double*>(be_->Alloc(sizeof(double) * static_cast<size_t>(V)));
+		if (!recs || !table) { if (recs) be_->Free(recs); if (table) be_->Free(table); return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error()); }
+		allocs_.push_back(recs); allocs_.push_back(table);
+		d_redraw_ = recs; d_redraw_cum_ = table;
+	}
+	if (redraw_rec_.empty()) redraw_rec_.assign(static_cast<size_t>(n_), RedrawRec{0});
+	if (cfg_.device_terrain && (!be_->H2D(d_redraw_cum_, cum.data(), sizeof(double) * cum.size()) || !be_->H2D(d_redraw_, redraw_rec_.data(), sizeof(RedrawRec) * redraw_rec_.size()))) return Fail(DTRL_ERR_DEVICE, be_->error());
+	redraw_cum_.swap(cum);
+	redraw_ = RedrawCfg{lo, hi, seed, static_cast<int64_t>(cfg_.run.env_id_base), d_redraw_cum_};
+	redraw_on_ = true; redraw_stale_ = false;
+	return DTRL_OK;
+}
+
+int Engine::VariantRedrawInfo(const int32_t* env_ids, int n, int32_t* lo, int32_t* hi, int32_t* variant, int32_t* draws)
+{
+	const std::string w = "dtrl_variant_redraw_info: ";
+	if (int rc = KeysIdle(variant_keys_, "dtrl_variant_redraw_info", 0); rc != DTRL_OK) return rc;
+	if (!redraw_on_) return Fail(DTRL_ERR_ARG, w + "the batch has no variant redraw (call dtrl_variant_redraw first)");
+	if (int rc = VariantRefresh(); rc != DTRL_OK) return rc;
+	if (n < 0 || n > n_) return Fail(DTRL_ERR_ARG, w + "the env count must be 0 .. num_envs");
+	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range"); }
+	if (lo) *lo = redraw_.lo;
+	if (hi) *hi = redraw_.hi;
+	for (int i = 0; i < n; ++i) {
+		const int e = EnvIndex(env_ids, i);
+		if (variant) variant[i] = variant_keys_.env_key[e];
+		if (draws) draws[i] = redraw_rec_[e].draws;
+	}
 	return DTRL_OK;
 }
 

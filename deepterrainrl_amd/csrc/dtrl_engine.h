@@ -49,6 +49,7 @@ DTRL_HD_INLINE void slot_patch(const SlotRec& r, RunParams& rp, DevBuffers& buf)
 struct EnvKeyView {
 	int32_t n_keys = 0;
 	const int32_t* env_key_dev = nullptr; const int32_t* env_key_host = nullptr;
+	bool keys_on_device = false;   // a variant redraw on device terrain moves env_key_dev while frames run: the per-key default reads the listed envs' keys from there
 	const int32_t* env_list_host = nullptr;
 	int32_t* part = nullptr;
 	const SlotRec* slots_dev = nullptr; const SlotRec* slots_host = nullptr;
@@ -124,6 +125,11 @@ public:
 	// default is the keyed default's host loop with the rule in it (the lane-loop check build, DTRL_TERRAINS_FALLBACK=1 on HIP); the HIP backend overrides it with
 	// one launch of dtrl_terrain_boundary_ladder on the selected stream.
 	virtual bool TerrainBoundaryLadder(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, int32_t* env_terrain, LadderRec* ladder, const LadderCfg& lc);
+	// Variant redraw (include/dtrl.h dtrl_variant_redraw): the rule (var_redraw_step, dtrl_terrain_dev.h) for envs [e0, e0 + n) (or env_list[0 .. n) when given) at
+	// a frame boundary -- an env with status[e].need_reset & 1 whose variant is inside [cfg.lo, cfg.hi] draws; env_model[e] and recs[e] (device memory, local env
+	// id) are written back where they changed. status / env_list / cfg.cum are device memory too. The default is a host loop with per-env D2H / H2D, synchronised
+	// (the lane-loop check build, DTRL_VARIANTS_FALLBACK=1 on HIP); the HIP backend overrides it with one launch of dtrl_variant_redraw on the selected stream.
+	virtual bool VariantRedraw(const EnvStatus* status, int e0, int n, const int32_t* env_list, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg);
 	// order[e0 .. e0 + n) = the envs e0 .. e0 + n - 1 sorted by status[].cost, costliest first (launch order of the group's next frame), on the selected stream
 	virtual bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) = 0;
 	// pending tuples -> block [block_rows + 1][W + 2] (header row + rows sorted by env id, flag word and global env id as the two extra columns); rows
@@ -216,8 +222,11 @@ public:
 	// model variants (include/dtrl.h)
 	int VariantsCreate(int n_variants);
 	int VariantLoad(int v, const char* character_file, const char* text, size_t bytes);   // text == nullptr: the file, resolved like -character_file=
-	int AssignVariants(const int32_t* env_ids, int n, const int32_t* variants) { return KeysAssign(variant_keys_, "dtrl_assign_variants", env_ids, n, variants); }
-	int GetVariants(const int32_t* env_ids, int n, int32_t* variants_out) { return KeysGet(variant_keys_, "dtrl_get_variants", env_ids, n, variants_out); }
+	int AssignVariants(const int32_t* env_ids, int n, const int32_t* variants);
+	int GetVariants(const int32_t* env_ids, int n, int32_t* variants_out);
+	// variant redraw (include/dtrl.h)
+	int VariantRedraw(int lo, int hi, uint64_t seed, const double* weights);
+	int VariantRedrawInfo(const int32_t* env_ids, int n, int32_t* lo, int32_t* hi, int32_t* variant, int32_t* draws);
 	int VariantStats(int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) { return KeysStats(variant_keys_, "dtrl_variant_stats", false, v, n_envs, avg_dist, episodes, cycles, resets); }
 	int num_variants() const { return static_cast<int>(var_models_.size()); }
 	// terrain sets (include/dtrl.h)
@@ -232,7 +241,9 @@ public:
 	int LadderInfo(const int32_t* env_ids, int n, double* mark_x_out, int32_t* ups_out, int32_t* downs_out);
 	int TerrainStats(int t, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) { return KeysStats(terrain_keys_, "dtrl_terrain_stats", false, t, n_envs, avg_dist, episodes, cycles, resets); }
 	int num_terrains() const { return terrain_keys_.n_keys(); }
-	// the model env e (local id, in range) runs under: what host-side readers of per-env geometry use (dtrl_get_link_states, AddPerturb)
+	// the model env e (local id, in range) runs under: what host-side readers of per-env geometry use (dtrl_get_link_states, AddPerturb). With a redraw on device
+	// terrain the caller brings the host keys up to date first (VariantKeysCurrent, once per call, behind a wait for the streams)
+	int VariantKeysCurrent() { return VariantRefresh(); }
 	const DevModel& ModelOf(int e) const { return var_models_.empty() ? cfg_.model : var_models_[variant_keys_.env_key[e]]; }
 	~Engine();
 	int Create(const char* const* argv, int argc, int num_envs, int device_id);
@@ -427,6 +438,19 @@ private:
 	int LadderUpload();                      // device terrain + ladder: device ladder records <- host
 	int RootX(int e, double* x);             // env e's current root x (q[0] of its state record; call with the streams idle)
 	int LadderIdle(const char* what);        // with a ladder: KeysIdle + LadderRefresh; without: nothing
+	// variant redraw: settings and per-env counters are batch state, like the assignment. WHO OWNS THE VARIANT KEYS: the ladder's protocol. Without a redraw, and
+	// with one in host terrain mode (HostFrameWork runs the rule and uploads the group's slice in front of the reset launch, which reads it), the host array is
+	// the truth. With a redraw and -terrain_gen= device the redraw kernel moves the DEVICE array and the device counters while frames run: every call that reads
+	// or uploads the variant keys first waits for every stream and then refreshes both host copies from the device (VariantRefresh)
+	bool redraw_on_ = false, redraw_stale_ = false;   // stale: a redraw launch was queued since the last refresh
+	RedrawCfg redraw_{};                     // (cum: the DEVICE table)
+	std::vector<double> redraw_cum_;         // host form of the cumulative table
+	std::vector<RedrawRec> redraw_rec_;      // host form [n]; kept when the redraw is replaced or removed
+	RedrawRec* d_redraw_ = nullptr; double* d_redraw_cum_ = nullptr;   // device [n], [n_variants] (allocated by the first redraw)
+	bool RedrawOnDevice() const { return redraw_on_ && cfg_.device_terrain; }
+	int VariantRefresh();                    // redraw on device terrain: host keys and counters <- device (call with the streams idle); else nothing
+	int VariantIdle(const char* what);       // redraw on device terrain: KeysIdle + VariantRefresh; else nothing
+	int RedrawListed(const std::vector<int32_t>& ids);   // dtrl_reset: the rule for the listed envs on the host, keys and counters uploaded (streams idle)
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

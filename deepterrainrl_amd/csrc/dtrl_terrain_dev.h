@@ -160,4 +160,33 @@ DTRL_TG_HD inline int32_t tg_ladder_step(LadderRec& lr, int32_t k, const EnvStat
 	return k;
 }
 
+// ---- variant redraw (include/dtrl.h dtrl_variant_redraw): envs draw a new model variant at each episode start ----
+// per-env record: how many draws the env has made (the counter of its draw stream)
+struct RedrawRec { int32_t draws; };
+// the batch's redraw: variants [lo, hi], the draw's seed and env-id base, and the cumulative weight table cum[hi - lo + 1] (ascending, last entry exactly 1.0;
+// device memory for the kernel and the backend default, host memory for the engine's own loops). A kernel ARGUMENT: DevBuffers and RunParams keep their layout
+struct RedrawCfg {
+	int32_t lo, hi;
+	uint64_t seed; int64_t env_id_base;
+	const double* cum;
+};
+// counter-based like ladder_draw, under a constant of its own: a function of (seed, GLOBAL env id, the env's draws so far) only -- shard-invariant
+DTRL_TG_HD inline uint64_t redraw_bits(uint64_t seed, int64_t global_env, int32_t draws)
+{
+	return tg_mix(tg_mix(tg_mix(seed) ^ (0x5EDBA77ULL + static_cast<uint64_t>(global_env))) + static_cast<uint64_t>(draws) * 0xD1342543DE82EF95ULL);
+}
+// The rule, the one body of host and device: the variant of env `env` (local id) after an episode start, given its variant k in front of it. `start`: the env is
+// at an episode start (a frame boundary with need_reset & 1, or dtrl_reset naming it). Runs IN FRONT OF the reset launch, so reset_env runs under the new model.
+// An env whose variant is outside [lo, hi] is not in the redraw: nothing of it is touched. `cum` is c.cum as the caller can read it. Doubles and integers only.
+DTRL_TG_HD inline int32_t var_redraw_step(RedrawRec& r, int32_t k, bool start, const RedrawCfg& c, const double* cum, int env)
+{
+	if (!start || k < c.lo || k > c.hi) return k;
+	const double u = static_cast<double>(redraw_bits(c.seed, c.env_id_base + env, r.draws) >> 11) * (1.0 / 9007199254740992.0);
+	int32_t a = 0, b = c.hi - c.lo + 1;   // #{ j : cum[j] <= u } by binary search
+	while (a < b) { const int32_t mid = (a + b) >> 1; if (cum[mid] <= u) a = mid + 1; else b = mid; }
+	r.draws += 1;
+	const int32_t next = c.lo + a;
+	return next > c.hi ? c.hi : next;
+}
+
 }  // namespace dtrl

@@ -82,9 +82,46 @@ def feed_chunks(t, rows, flags, chunk, ph=None, poll=None):
     return len(rows)
 
 
+def setup_variants(b, spec):
+    """Domain randomisation while training (BatchScenario.VariantRedraw): a table of spec["count"] model variants -- variant 0 the batch's own model, every other
+    one ScaledVariant under scales drawn uniformly (numpy RandomState(spec["seed"])) from the ranges spec["mass"] / ["torque_lim"] / ["kp"] / ["kd"] ((lo, hi) each;
+    a missing key: 1) -- an initial deal of the envs over the table (AssignVariants + Reset, so that the first episodes already run under the dealt models) and the
+    redraw over the whole table, after which every episode of every env starts under a model drawn afresh. spec["keep_nominal"]: the share of the weight on
+    variant 0 (default: 1 / count, i.e. uniform); spec["mass_body"]: scale that body's mass alone (default: every body by the one factor).
+    Returns {"scales": per variant, "weights"}."""
+    count = int(spec["count"])
+    if count < 2 or count > b.num_envs:
+        raise ValueError("variants: count must be 2 .. num_envs")
+    unknown = set(spec) - {"count", "mass", "torque_lim", "kp", "kd", "seed", "keep_nominal", "mass_body"}
+    if unknown:
+        raise ValueError("variants: unknown keys %s" % ", ".join(sorted(unknown)))
+    seed = int(spec.get("seed", 0))
+    keep = float(spec.get("keep_nominal", 1.0 / count))
+    if not 0.0 <= keep < 1.0:
+        raise ValueError("variants: keep_nominal must be in [0, 1)")
+    rng = np.random.RandomState(seed)
+    keys = ("mass", "torque_lim", "kp", "kd")
+    scales = [dict.fromkeys(keys, 1.0)]
+    b.CreateVariants(count)
+    for v in range(1, count):
+        sc = {}
+        for k in keys:                       # (one draw per key and variant, given or not: a range added later does not move the other keys' scales)
+            u = rng.uniform()
+            lo, hi = spec.get(k, (1.0, 1.0))
+            sc[k] = float(lo + u * (hi - lo))
+        body = spec.get("mass_body")
+        b.ScaledVariant(v, mass={body: sc["mass"]} if body else sc["mass"], kp=sc["kp"], kd=sc["kd"], torque_lim=sc["torque_lim"])
+        scales.append(sc)
+    weights = np.array([keep] + [(1.0 - keep) / (count - 1)] * (count - 1), np.float64)
+    b.AssignVariants(None, rng.choice(count, size=b.num_envs, p=weights / weights.sum()).astype(np.int32))
+    b.Reset()
+    b.VariantRedraw(0, count - 1, seed=seed, weights=weights)
+    return {"scales": scales, "weights": weights}
+
+
 def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, device_id=-1, extra_args=None, seed=0, log_every=0, out_scale_file=None,
           trainer_device=None, overlap=False, frames_per_drain=1, scenario_cls=BatchScenario, trainer="torch", trainer_lib=None, poll=False,
-          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0):
+          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None):
     """extra_args override / extend the arg file (both for the engine and for the -trainer_* keys read here).
     overlap=True trains on frame f's tuples while the GPU already rolls out frame f+1 (dtrl_step_begin / dtrl_step_end): the policy
     each frame runs with is one frame staler, as with the reference's concurrent env threads; overlap=False is the strictly
@@ -97,7 +134,12 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     out_model_file: the trainer's net as a Caffe HDF5 model at the end (cNeuralNetTrainer::OutputModel), next to out_scale_file.
     greedy_envs=k > 0 keeps the last k envs greedy beside the exploring ones (policy slots: an alias of slot 0 with exploration off, so every hand-over reaches
     them too): their tuples are left out of what the trainer is fed, and their falls per 1000 env-steps (SlotStats) are logged with log_every and returned as
-    stats["greedy"]. k = 0 (default) creates no slots and runs exactly as before."""
+    stats["greedy"]. k = 0 (default) creates no slots and runs exactly as before.
+    variants=dict(count=, mass=(lo, hi), torque_lim=, kp=, kd=, seed=, keep_nominal=) trains under domain randomisation (setup_variants: a table of scaled
+    character models, every episode of every env under a model drawn afresh); stats["variants"] then holds the scales, the weights and VariantRedrawInfo() at the
+    end. Not together with greedy_envs: the greedy envs use policy slots, and slots exclude model variants. None (default) runs exactly as before."""
+    if variants is not None and greedy_envs:
+        raise ValueError("greedy_envs > 0 together with variants: the greedy envs use policy slots, and policy slots exclude model variants")
     if overlap:
         extra_args = dict({"tuple_ring": "host"}, **(extra_args or {}))    # drains beside a running frame must not queue copies behind it (include/dtrl.h: dtrl_drain_tuples)
     args = parse_arg_file(os.path.join(data_root, arg_file))
@@ -156,6 +198,7 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
         b.SetTerrainParamsLerp(phase if it > 0 or n_curr < 1 else 0.0)
 
     sync(0)
+    var_info = setup_variants(b, variants) if variants is not None else None   # (behind the first SetPolicy / SetExplore: its Reset runs a launch)
     frames = tuples = 0
     next_eval = [0 if eval_fn else None]
     if eval_fn:
@@ -241,6 +284,8 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
                  trainer_iters_per_s=t.GetIter() / dt, weights=t.GetWeights(), offset_scale=t.GetOffsetScale(), phases=ph, side_stream_delay_us=side[1])
     if greedy_envs:
         stats["greedy"] = dict(b.SlotStats(1), falls_k=greedy_falls())
+    if var_info is not None:
+        stats["variants"] = dict(var_info, **b.VariantRedrawInfo())
     return stats
 
 

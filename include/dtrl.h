@@ -359,11 +359,39 @@ dtrl_status dtrl_variant_load_json(dtrl_batch* b, int v, const char* text, size_
 /* No counterpart in the reference, which keeps one character per scene object. env_ids[i] -> variants[i]; env_ids == NULL means the first n envs (n = num_envs:
  * all). All or nothing: an env id or variant out of range, or an empty variant, is DTRL_ERR_ARG. Takes effect with the env's next launch. */
 dtrl_status dtrl_assign_variants(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* variants);
-/* No counterpart in the reference, which keeps one character per scene object. The variants of the listed envs (valid at any time). */
+/* No counterpart in the reference, which keeps one character per scene object. The variants of the listed envs. Without a variant redraw (below), and with one
+ * in host terrain mode: valid at any time. With a redraw and -terrain_gen= device the variants move on the device at the frame boundaries: the call then returns
+ * them as of the last completed boundary -- it is refused with DTRL_ERR_ARG between dtrl_step_begin and dtrl_step_end, and otherwise waits for everything the
+ * batch has queued. */
 dtrl_status dtrl_get_variants(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* variants_out);
 /* No counterpart in the reference, which keeps one character per scene object. dtrl_eval_stats restricted to the envs currently in variant v (n_envs of them),
  * reduced on the device in a fixed order: two calls without a step between them return the same bits. Any output may be NULL. */
 dtrl_status dtrl_variant_stats(dtrl_batch* b, int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets);
+
+/* ---- Variant redraw: envs draw a new model variant at each episode start (domain randomisation while training) ----
+ * No counterpart in the reference, which keeps one character per scene object. A redraw is a contiguous range [lo, hi] of filled variants, a seed and a weight per
+ * variant of the range. Each env carries a counter `draws`. At env e's EPISODE START -- a frame boundary at which it fell (need_reset bit 0), or dtrl_reset naming
+ * it (once per env, however often it is listed) -- with k = the env's variant:
+ *   k outside [lo, hi]      nothing: the env is not in the redraw (evaluation envs can be held on variant 0 that way)
+ *   else                    bits = mix(mix(mix(seed) ^ (C + global env id)) + draws * 0xD1342543DE82EF95), u = (bits >> 11) * 2^-53,
+ *                           k = lo + #{ j : cum[j] <= u } (clamped to hi), draws += 1
+ * mix is the terrain streams' 64-bit finaliser and C a constant of the redraw's own; cum[j] = (w_0 + .. + w_j) / (w_0 + .. + w_(hi-lo)), summed left to right
+ * in double, the last entry exactly 1.0 (uniform: every w_j = 1). The draw is a function of the seed, the GLOBAL env id (-env_id_base= + local id) and the
+ * env's own counter alone: shard-invariant, and independent of exploration, reward and every other env. The rule runs IN FRONT OF the reset launch, so the
+ * device half of the reset (default pose, centre of mass, forward kinematics) is the new variant's; the frame that ended, with its fall bookkeeping, ran under
+ * the old one. dtrl_assign_terrains with restart != 0 does not draw. With -terrain_gen= device the rule is one more small launch per env group and frame,
+ * queued with the boundary work (no host round trip; dtrl_run_frames and the overlapped loops included); in host terrain mode it runs in the host's per-frame
+ * status loop. Settings and counters are batch state like the assignment: snapshots, restores, clones and blobs leave them alone. Internal policy mode only, as
+ * the variants themselves. */
+/* No counterpart in the reference, which keeps one character per scene object. Turn the redraw on (lo <= hi), replace its settings, or remove it (lo > hi; the
+ * envs keep the variants they have). The counters are kept in all three cases. weights: NULL = uniform over lo..hi, else hi - lo + 1 non-negative finite doubles,
+ * not all zero. DTRL_ERR_ARG, nothing changed: no variants, lo / hi outside the table, an empty variant inside [lo, hi], a negative, NaN or infinite weight, all
+ * weights zero, a frame in flight. */
+dtrl_status dtrl_variant_redraw(dtrl_batch* b, int lo, int hi, uint64_t seed, const double* weights);
+/* No counterpart in the reference, which keeps one character per scene object. Any output may be NULL. The redraw's range, and per listed env (env_ids == NULL:
+ * the first n) its variant now and how many draws it has made, as of the last completed boundary: refused between dtrl_step_begin and dtrl_step_end and without
+ * a redraw, otherwise waits for queued work. */
+dtrl_status dtrl_variant_redraw_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* lo, int32_t* hi, int32_t* variant, int32_t* draws);
 
 /* ---- Terrain sets: several terrains in one batch, one per env ----
  * No counterpart in the reference, which keeps one terrain per scene object (cScenarioSimChar::ParseTerrainParams reads ONE -terrain_file= into the scene's

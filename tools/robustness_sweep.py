@@ -19,13 +19,14 @@ MODELS = {"dog": "dog_mace3_slopes_mixed_model.h5", "raptor": "raptor_mace3_narr
 BODY = {"dog": "torso", "raptor": "root"}
 
 
-def sweep(char, masses, limits, n, frames, seed, root, scenario=None):
-    """[(mass scale, torque-limit scale, dict(falls_k, speed, episodes, cycles, n_envs))] in grid order (mass-major)"""
+def sweep(char, masses, limits, n, frames, seed, root, scenario=None, policy=None):
+    """[(mass scale, torque-limit scale, dict(falls_k, speed, episodes, cycles, n_envs))] in grid order (mass-major). policy: (weights, normalisers) in place of
+    the committed trained net (tools/domain_randomisation.py)"""
     cells = [(m, t) for m in masses for t in limits]
     K = len(cells)
     arg = learn_curve.CHARS[char]["evalf"]
     b = (scenario or learn_curve.SCENARIO)(arg, K * n, data_root=root, extra_args={"terrain_seed": seed})
-    w, norm = eval_policies.load_policy(b, os.path.join(REPO, "tests", "golden", "policies", MODELS[char]))
+    w, norm = policy if policy is not None else eval_policies.load_policy(b, os.path.join(REPO, "tests", "golden", "policies", MODELS[char]))
     b.SetPolicy(w, *norm)
     b.SetExplore(0, 0.0, 1.0, 0.0)
     b.CreateVariants(K + 1)                                        # variant 0 stays the batch's own model and is not used: every cell is loaded the same way

@@ -22,7 +22,21 @@ ap.add_argument("--poll", action="store_true", help="with --overlap: relaunch en
 ap.add_argument("--distributed", action="store_true", help="train_loop.train_distributed: sharded rollout + tuple gather to rank 0 + policy broadcast (RCCL). Start with torch.distributed.run for N ranks; alone it runs a one-rank RCCL group (DTRL_FORCE_COLLECTIVES=1), the config-3/4 loop shape on one GPU")
 ap.add_argument("--data-parallel", action="store_true", help="with --distributed: no trainer rank -- every rank trains on its own tuples, gradients all-reduced (train_distributed(mode=\"data_parallel\"))")
 ap.add_argument("--out", default=None, help="write weights (.npy) and <out>_scale.txt")
+ap.add_argument("--variants", type=int, default=0, help="domain randomisation while training (train_loop.train(variants=...)): a table of this many model variants under seeded scales, every episode of every env under a model drawn afresh (0: off; not with --distributed)")
+ap.add_argument("--variant-mass", type=float, nargs=2, default=[1.0, 1.0], metavar=("LO", "HI"), help="with --variants: range of the body-mass scale")
+ap.add_argument("--variant-torque-lim", type=float, nargs=2, default=[1.0, 1.0], metavar=("LO", "HI"), help="with --variants: range of the torque-limit scale")
+ap.add_argument("--variant-kp", type=float, nargs=2, default=[1.0, 1.0], metavar=("LO", "HI"), help="with --variants: range of the PD controllers' Kp scale")
+ap.add_argument("--variant-kd", type=float, nargs=2, default=[1.0, 1.0], metavar=("LO", "HI"), help="with --variants: range of the PD controllers' Kd scale")
+ap.add_argument("--variant-seed", type=int, default=0, help="with --variants: seed of the scales, the initial deal and the redraw")
+ap.add_argument("--keep-nominal", type=float, default=None, help="with --variants: share of the draw's weight on the nominal model (default: 1 / variants)")
 a = ap.parse_args()
+if a.variants and a.distributed:
+    ap.error("--variants is not available with --distributed")
+variants = None
+if a.variants:
+    variants = dict(count=a.variants, mass=tuple(a.variant_mass), torque_lim=tuple(a.variant_torque_lim), kp=tuple(a.variant_kp), kd=tuple(a.variant_kd), seed=a.variant_seed)
+    if a.keep_nominal is not None:
+        variants["keep_nominal"] = a.keep_nominal
 reserve = a.reserve_cus if a.reserve_cus is not None else (1 if (a.distributed and not a.data_parallel) else 0)   # (the exchange's collective and read-backs beside the rollout: 11.0 M with one unit per XCD set aside, 9.6 M without)
 if a.distributed:
     import torch, torch.distributed as dist
@@ -45,9 +59,11 @@ if a.distributed:
     sys.exit(0)
 st = train_loop.train(a.arg_file, a.data_root, a.envs, max_iters=a.iters, max_frames=a.frames, log_every=50, overlap=a.overlap, frames_per_drain=a.frames_per_drain,
                       extra_args=dict(({"reserve_cus": reserve} if reserve else {}), **({"trainer_num_init_samples": a.init_samples} if a.init_samples is not None else {})) or None,
-                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll)
+                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll, variants=variants)
 if a.out:
     np.save(a.out + ".npy", st["weights"])
+if variants:
+    print("[variants] %d models, %d draws; envs per variant at the end: %s" % (a.variants, int(st["variants"]["draws"].sum()), np.bincount(st["variants"]["variant"], minlength=a.variants).tolist()))
 print("[trainer=%s reserve_cus=%d side-stream start delay %.0f us] " % (a.trainer, reserve, st["side_stream_delay_us"]), end="")
 print("frames %d  trainer iters %d  tuples %d  %.1f s  ->  %.2f M env-steps/s while training, %.1f trainer iters/s" % (
     st["frames"], st["iters"], st["tuples"], st["seconds"], st["env_steps_per_s"] / 1e6, st["trainer_iters_per_s"]))
