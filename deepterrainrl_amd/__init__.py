@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "dtrl_snapshot_save", "dtrl_snapshot_restore", "dtrl_clone_envs", "dtrl_snapshot_export", "dtrl_snapshot_import", "dtrl_snapshot_info", "dtrl_snapshot_free",
     "dtrl_slots_create", "dtrl_slot_set_policy", "dtrl_slot_set_policy_device", "dtrl_slot_alias", "dtrl_slot_set_explore", "dtrl_assign_slots", "dtrl_get_slots", "dtrl_slot_stats",
     "dtrl_variants_create", "dtrl_variant_load_file", "dtrl_variant_load_json", "dtrl_assign_variants", "dtrl_get_variants", "dtrl_variant_stats", "dtrl_variant_redraw", "dtrl_variant_redraw_info",
+    "dtrl_push_schedule", "dtrl_push_scale", "dtrl_push_info",
     "dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats", "dtrl_terrain_ladder", "dtrl_ladder_info",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
@@ -162,6 +163,9 @@ def _bind(path):
     L.dtrl_variant_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dtrl_variant_redraw.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, vp]
     L.dtrl_variant_redraw_info.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    L.dtrl_push_schedule.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double]
+    L.dtrl_push_scale.argtypes = [vp, vp, C.c_int, vp]
+    L.dtrl_push_info.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
     L.dtrl_terrains_create.argtypes = [vp, C.c_int]
     L.dtrl_terrain_set_file.argtypes = [vp, C.c_int, C.c_char_p, C.c_double]
     L.dtrl_terrain_set_params.argtypes = [vp, C.c_int, C.c_char_p, vp]
@@ -572,6 +576,32 @@ class BatchScenario:
         """cScenarioSimChar::ApplyRandForce(): random body part / direction / magnitude / duration per env."""
         ids, n = self._ids(env_ids)
         self._chk(self._lib.dtrl_apply_rand_force(self._h, _p(ids), n, int(seed)))
+
+    # ---- push schedule: random pushes on the device at per-env random times (the reference calls ApplyRandForce by hand) ----
+    def PushSchedule(self, wait, seed=0, force=None, duration=None):
+        """dtrl_push_schedule: from now on every env of scale != 0 is pushed at random times -- wait = (lo, hi) frame boundaries between two pushes of an env
+        (1 <= lo <= hi), force = (lo, hi) magnitude range, duration = (lo, hi) seconds; None: the batch's -min_perturb= ... arguments. Link, direction, magnitude
+        and duration are drawn as ApplyRandForce draws them, from a stream of (seed, global env id, the env's own counter) alone, and written into the env's
+        perturbation slot at its frame boundary by one small launch per env group (no host wait). An episode start draws a new wait and never pushes.
+        PushSchedule((1, 0)) removes the schedule (records, counters and scales stay). Not with -policy_mode= external."""
+        nan = float("nan")
+        f = (nan, nan) if force is None else force
+        d = (nan, nan) if duration is None else duration
+        self._chk(self._lib.dtrl_push_schedule(self._h, int(wait[0]), int(wait[1]), int(seed) & 0xFFFFFFFFFFFFFFFF, float(f[0]), float(f[1]), float(d[0]), float(d[1])))
+
+    def PushScale(self, scales, env_ids=None):
+        """dtrl_push_scale: per-env factor on the scheduled force (finite, >= 0; 1.0 unless set). 0 takes the env out of the schedule."""
+        ids, n = self._ids(env_ids)
+        scales = np.ascontiguousarray(np.broadcast_to(np.asarray(scales, np.float64), (n,)))
+        self._chk(self._lib.dtrl_push_scale(self._h, _p(ids), n, _p(scales)))
+
+    def PushInfo(self, env_ids=None):
+        """dtrl_push_info: {"wait", "pushes", "last_link" (int32 per listed env, all by default; last_link -1: none yet), "last_force" [n, 2], "last_dur" [n]}."""
+        ids, n = self._ids(env_ids)
+        wait, pushes, link = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        force, dur = np.zeros((n, 2), np.float64), np.zeros(n, np.float64)
+        self._chk(self._lib.dtrl_push_info(self._h, _p(ids), n, _p(wait), _p(pushes), _p(link), _p(force), _p(dur)))
+        return {"wait": wait, "pushes": pushes, "last_link": link, "last_force": force, "last_dur": dur}
 
     def SetPoseVel(self, q, qd, env_ids=None):
         ids, n = self._ids(env_ids)

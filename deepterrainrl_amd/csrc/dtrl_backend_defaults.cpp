@@ -6,6 +6,7 @@
 #include "dtrl_engine.h"
 #include "dtrl_terrain_dev.h"
 #include <algorithm>
+#include <cstddef>
 
 namespace dtrl {
 
@@ -159,6 +160,51 @@ bool Backend::VariantRedraw(const EnvStatus* status, int e0, int n, const int32_
 		const int32_t next = var_redraw_step(r, key, true, cfg, cum.data(), e);
 		if (next != key && !H2D(env_model + e, &next, sizeof(next))) return false;
 		if (r.draws != draws0 && !H2D(recs + e, &r, sizeof(r))) return false;
+	}
+	return true;
+}
+// Push schedule: the rule (push_step) on the host, env by env; record and slot go back where they changed. The first D2H waits for the selected stream.
+// The slot's seven fields are two runs of EnvState: pert_link / pert_on, and pert_f .. pert_dur.
+static bool WriteSlotFields(Backend& be, EnvState* dst, const EnvState& src)
+{
+	static_assert(offsetof(EnvState, pert_on) == offsetof(EnvState, pert_link) + sizeof(int32_t), "pert_link / pert_on are one run");
+	static_assert(offsetof(EnvState, pert_dur) == offsetof(EnvState, pert_f) + 6 * sizeof(real), "pert_f .. pert_dur are one run");
+	char* d = reinterpret_cast<char*>(dst); const char* s = reinterpret_cast<const char*>(&src);
+	return be.H2D(d + offsetof(EnvState, pert_link), s + offsetof(EnvState, pert_link), 2 * sizeof(int32_t))
+		&& be.H2D(d + offsetof(EnvState, pert_f), s + offsetof(EnvState, pert_f), 7 * sizeof(real));
+}
+bool Backend::PushSchedule(const EnvStatus* status, int e0, int n, const int32_t* env_list, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg)
+{
+	if (n <= 0) return true;
+	std::vector<int32_t> list(static_cast<size_t>(n));
+	if (!env_list) { for (int k = 0; k < n; ++k) list[k] = e0 + k; }
+	else if (!D2H(list.data(), env_list, sizeof(int32_t) * list.size())) return false;
+	if (!SyncSelected()) return false;
+	EnvStatus es; PushRec r; double sc = 0; EnvState slot;
+	for (int32_t e : list) {
+		if (!D2H(&sc, scale + e, sizeof(sc))) return false;
+		if (sc == 0) continue;
+		bool start = true;
+		if (status) { if (!D2H(&es, status + e, sizeof(es))) return false; start = es.need_reset != 0; }
+		if (!D2H(&r, recs + e, sizeof(r))) return false;
+		PushOut out;
+		const bool fired = push_step(r, sc, start, cfg, e, out);
+		if (fired) { push_write_slot(slot, out); if (!WriteSlotFields(*this, st + e, slot)) return false; }
+		if (!H2D(recs + e, &r, sizeof(r))) return false;   // (an env in the schedule moves its record at every boundary: the wait, or the counter)
+	}
+	return true;
+}
+// dtrl_add_perturb's rows, env by env: the whole EnvState down, the seven fields, the whole EnvState up (what Engine::AddPerturb did before there was a launch for it)
+bool Backend::PerturbScatter(EnvState* st, const PerturbRow* rows, int n)
+{
+	if (n <= 0) return true;
+	std::vector<PerturbRow> host(static_cast<size_t>(n));
+	if (!D2H(host.data(), rows, sizeof(PerturbRow) * host.size())) return false;
+	EnvState es;
+	for (const PerturbRow& r : host) {
+		if (!D2H(&es, st + r.env, sizeof(EnvState))) return false;
+		perturb_write_slot(es, r);
+		if (!H2D(st + r.env, &es, sizeof(EnvState))) return false;
 	}
 	return true;
 }

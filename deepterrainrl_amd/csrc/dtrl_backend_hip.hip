@@ -196,6 +196,32 @@ __global__ void dtrl_variant_redraw(const EnvStatus* __restrict__ status, int e0
 	if (next != v) env_model[e] = next;
 	if (r.draws != draws0) recs[e] = r;
 }
+// Push schedule (include/dtrl.h dtrl_push_schedule): the envs of a group count their waits down behind the group's frame and boundary work, and the ones that reach
+// 0 get a random push into their perturbation slot (push_step, dtrl_terrain_dev.h). A kernel of its own: the frame and boundary kernels stay as they are. Thread
+// per env, every word per env: no atomics. An env of scale 0 is left after one load; record and slot are written back only where they changed. status == nullptr:
+// every listed env starts an episode (creation of the schedule, dtrl_reset, a terrain restart).
+__global__ void __launch_bounds__(64) dtrl_push_schedule(const EnvStatus* __restrict__ status, int e0, int n, const int32_t* __restrict__ env_list, EnvState* __restrict__ st, PushRec* __restrict__ recs,
+	const double* __restrict__ scale, PushCfg pc)
+{
+	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+	if (k >= n) return;
+	const int e = env_list ? env_list[k] : e0 + k;
+	const double sc = scale[e];
+	if (sc == 0) return;
+	const bool start = status ? status[e].need_reset != 0 : true;
+	PushRec r = recs[e];
+	PushOut out;
+	if (push_step(r, sc, start, pc, e, out)) push_write_slot(st[e], out);
+	recs[e] = r;   // (an env in the schedule moves its record at every boundary: the wait, or the counter)
+}
+// dtrl_add_perturb in one launch: a thread per row (the engine has reduced the rows to one per env), the seven slot fields each
+__global__ void __launch_bounds__(64) dtrl_perturb_scatter(EnvState* __restrict__ st, const PerturbRow* __restrict__ rows, int n)
+{
+	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+	if (k >= n) return;
+	const PerturbRow r = rows[k];
+	perturb_write_slot(st[r.env], r);
+}
 // launch order of a group's next frame: counting sort on cost / 16, costliest first (one workgroup; the order inside a bucket is whatever the
 // atomics produce -- it only decides which wavefront starts first)
 constexpr int kOrderBuckets = 1024;
@@ -616,6 +642,22 @@ public:
 		if (n <= 0) return true;
 		hipLaunchKernelGGL(dtrl_variant_redraw, dim3((n + 63) / 64), dim3(64), 0, stream_, status, e0, n, env_list, env_model, recs, cfg);
 		return Check(hipGetLastError(), "variant redraw launch");
+	}
+	// push schedule: ONE launch per group and frame, queued like the boundary work. DTRL_PUSH_FALLBACK=1 takes the host default
+	bool PushSchedule(const EnvStatus* status, int e0, int n, const int32_t* env_list, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg) override
+	{
+		if (EnvFlag("DTRL_PUSH_FALLBACK")) return Backend::PushSchedule(status, e0, n, env_list, st, recs, scale, cfg);
+		if (n <= 0) return true;
+		hipLaunchKernelGGL(dtrl_push_schedule, dim3((n + 63) / 64), dim3(64), 0, stream_, status, e0, n, env_list, st, recs, scale, cfg);
+		return Check(hipGetLastError(), "push schedule launch");
+	}
+	// dtrl_add_perturb: ONE launch for all rows. DTRL_PERTURB_FALLBACK=1 takes the host default
+	bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n) override
+	{
+		if (EnvFlag("DTRL_PERTURB_FALLBACK")) return Backend::PerturbScatter(st, rows, n);
+		if (n <= 0) return true;
+		hipLaunchKernelGGL(dtrl_perturb_scatter, dim3((n + 63) / 64), dim3(64), 0, stream_, st, rows, n);
+		return Check(hipGetLastError(), "perturb scatter launch");
 	}
 	bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) override
 	{

@@ -286,6 +286,10 @@ dtrl_status dtrl_get_variants(dtrl_batch* b, const int32_t* env_ids, int n, int3
 dtrl_status dtrl_variant_redraw(dtrl_batch* b, int lo, int hi, uint64_t seed, const double* weights) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantRedraw(lo, hi, seed, weights)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_variant_redraw_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* lo, int32_t* hi, int32_t* variant, int32_t* draws) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantRedrawInfo(env_ids, n, lo, hi, variant, draws)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_variant_stats(dtrl_batch* b, int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantStats(v, n_envs, avg_dist, episodes, cycles, resets)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+// push schedule
+dtrl_status dtrl_push_schedule(dtrl_batch* b, int min_wait, int max_wait, uint64_t seed, double min_force, double max_force, double min_dur, double max_dur) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.PushSchedule(min_wait, max_wait, seed, min_force, max_force, min_dur, max_dur)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_push_scale(dtrl_batch* b, const int32_t* env_ids, int n, const double* scales) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.PushScale(env_ids, n, scales)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_push_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* wait, int32_t* pushes, int32_t* last_link, double* last_force, double* last_dur) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.PushInfo(env_ids, n, wait, pushes, last_link, last_force, last_dur)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 // terrain sets
 dtrl_status dtrl_terrains_create(dtrl_batch* b, int n_terrains) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainsCreate(n_terrains)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_terrain_set_file(dtrl_batch* b, int t, const char* terrain_file, double lerp) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainSetFile(t, terrain_file, lerp)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }

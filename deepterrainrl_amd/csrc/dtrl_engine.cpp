@@ -398,6 +398,7 @@ int Engine::UploadTerrainCfg(const double* params)
 //   dtrl_terrain_boundary  fresh windows for the envs that fell, slid windows where the character got close to an edge, episode distances logged
 //   dtrl_order_by_cost     launch order of the next frame (costliest wavefronts first)
 //   dtrl_variant_redraw    (with a variant redraw) the envs that fell draw the model variant of their next episode
+//   dtrl_push_schedule     (with a push schedule) the envs whose wait ran out get a random push into their perturbation slot
 //   0-step frame launch    the device half of the reset, taken by the envs that fell, skipped by the others (reset_listed = 2)
 int Engine::DeviceFrameWork(int group)
 {
@@ -409,6 +410,9 @@ int Engine::DeviceFrameWork(int group)
 	if (!Boundary(grp.e0, grp.n, 0, nullptr) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	// variant redraw: the envs that fell draw their next variant behind their frame and in front of the reset launch, which then runs reset_env under the new model
 	if (redraw_on_) { redraw_stale_ = true; if (!be_->VariantRedraw(buf_.status, grp.e0, grp.n, nullptr, variant_keys_.d_env_key, d_redraw_, redraw_)) return Fail(DTRL_ERR_DEVICE, be_->error()); }
+	// push schedule: the group's envs count down, and the ones that are due get their push, behind the frame and in front of the reset launch (an env that fell
+	// draws a new wait and is not pushed: the reset launch clears nothing the rule wrote)
+	if (push_on_ && !be_->PushSchedule(buf_.status, grp.e0, grp.n, nullptr, buf_.st, d_push_, d_push_scale_, push_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	b.env_list = d_order_ + grp.e0;
 	if (!LaunchEnvs(b, grp.n, 0, 0.0, false, nullptr, grp.e0)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
@@ -502,6 +506,9 @@ int Engine::HostFrameWork(int group)
 	for (int k = 0; k < kBuckets; ++k) bucket_[k + 1] += bucket_[k];
 	for (int e = e0; e < e1; ++e) pin_order_[e0 + bucket_[key(e)]++] = e;
 	const double ht3 = g_ht.on ? now_s() : 0;
+	// push schedule: the same launch as in device terrain mode, on the group's stream (idle since the wait above) in front of the reset launch; status_ is the
+	// page-locked array the frame kernel wrote, which the device reads through the same pointer
+	if (push_on_ && !be_->PushSchedule(buf_.status, e0, grp.n, nullptr, buf_.st, d_push_, d_push_scale_, push_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	const int rc = ApplyResets(reset_ids_, group);
 	if (g_ht.on) { const double ht4 = now_s(); g_ht.t_sync += ht1 - ht0; g_ht.t_loop += ht2 - ht1; g_ht.t_sort += ht3 - ht2; g_ht.t_reset += ht4 - ht3; g_ht.regen += used; ++g_ht.n; }
 	return rc;
@@ -700,6 +707,7 @@ int Engine::Reset(const int32_t* env_ids, int n, const uint64_t* seeds)
 	if (int rc = RedrawListed(reset_ids_); rc != DTRL_OK) return rc;   // variant redraw: an episode starts, once per listed env, and the reset below runs under the new model
 	int rc = ApplyResets(reset_ids_, -1);
 	if (rc != DTRL_OK) return rc;
+	if (rc = PushStart(static_cast<int>(reset_ids_.size())); rc != DTRL_OK) return rc;   // push schedule: an episode starts, a new wait once per listed env
 	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
 }
@@ -1238,25 +1246,39 @@ int Engine::AddPerturb(const int32_t* env_ids, int n, const int32_t* link, const
 	if (env_ids && n < 0) return Fail(DTRL_ERR_ARG, "negative env count");
 	be_->Sync();
 	if (int rc = VariantRefresh(); rc != DTRL_OK) return rc;
-	EnvState st;
 	const int cnt = env_ids ? n : n_;
-	for (int i = 0; i < cnt; ++i) {
+	// The list becomes one row per env, the env's LAST row (applied in list order the last one won; a thread per row must not race), and goes into the slots in
+	// one launch (Backend::PerturbScatter). A bad row stops the list where the sequential loop stopped: the rows in front of it are applied, then the error returns.
+	std::vector<PerturbRow> rows;
+	std::vector<int32_t> row_of(static_cast<size_t>(n_), -1);
+	const char* bad = nullptr;
+	for (int i = 0; i < cnt && !bad; ++i) {
 		const int e = EnvIndex(env_ids, i);
-		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, "env id out of range");
+		if (e < 0 || e >= n_) { bad = "env id out of range"; break; }
 		const DevModel& m = ModelOf(e);   // (body_theta is the env's variant's)
 		const int l = link[i];
-		if (l < 0 || l >= m.L) return Fail(DTRL_ERR_ARG, "perturbation link out of range");
-		if (!(duration[i] >= 0)) return Fail(DTRL_ERR_ARG, "perturbation duration must be non-negative");
-		if (!be_->D2H(&st, &buf_.st[e], sizeof(EnvState))) return Fail(DTRL_ERR_DEVICE, be_->error());
+		if (l < 0 || l >= m.L) { bad = "perturbation link out of range"; break; }
+		if (!(duration[i] >= 0)) { bad = "perturbation duration must be non-negative"; break; }
 		// the body frame is the joint frame turned by the body's attach angle: store the offset in the joint frame (the kernel has cos/sin of that)
 		const double c = std::cos(m.body_theta[l]), sn = std::sin(m.body_theta[l]);
 		const double lx = local_pos ? local_pos[2 * i] : 0.0, ly = local_pos ? local_pos[2 * i + 1] : 0.0;
-		st.pert_link = l; st.pert_on = 0;
-		st.pert_lp[0] = c * lx - sn * ly; st.pert_lp[1] = sn * lx + c * ly;
-		st.pert_f[0] = force[2 * i]; st.pert_f[1] = force[2 * i + 1];
-		st.pert_torque = 0; st.pert_time = 0; st.pert_dur = duration[i];
-		if (!be_->H2D(&buf_.st[e], &st, sizeof(EnvState))) return Fail(DTRL_ERR_DEVICE, be_->error());
+		PerturbRow r;
+		r.env = e; r.link = l;
+		r.lp[0] = c * lx - sn * ly; r.lp[1] = sn * lx + c * ly;
+		r.f[0] = force[2 * i]; r.f[1] = force[2 * i + 1];
+		r.dur = duration[i];
+		if (row_of[e] < 0) { row_of[e] = static_cast<int32_t>(rows.size()); rows.push_back(r); } else rows[row_of[e]] = r;
 	}
+	if (!rows.empty()) {
+		if (!d_pert_rows_) {
+			d_pert_rows_ = static_cast<PerturbRow*>(be_->Alloc(sizeof(PerturbRow) * static_cast<size_t>(n_)));
+			if (!d_pert_rows_) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+			allocs_.push_back(d_pert_rows_);
+		}
+		if (!be_->H2D(d_pert_rows_, rows.data(), sizeof(PerturbRow) * rows.size()) || !be_->PerturbScatter(buf_.st, d_pert_rows_, static_cast<int>(rows.size())) || !be_->SyncSelected())
+			return Fail(DTRL_ERR_DEVICE, be_->error());
+	}
+	if (bad) return Fail(DTRL_ERR_ARG, bad);
 	return DTRL_OK;
 }
 
@@ -2116,6 +2138,89 @@ int Engine::VariantRedrawInfo(const int32_t* env_ids, int n, int32_t* lo, int32_
 	return DTRL_OK;
 }
 
+// ---- push schedule (include/dtrl.h: dtrl_push_schedule, dtrl_push_scale, dtrl_push_info) ----
+// The rule is push_step (dtrl_terrain_dev.h), run by Backend::PushSchedule on the group's stream at every frame boundary in front of the reset launch -- queued by
+// DeviceFrameWork (-terrain_gen= device) and by HostFrameWork (host terrain) alike -- and with `start` here, by PushStart under dtrl_reset and a terrain restart.
+// Records and scales live in device memory only.
+int Engine::PushAlloc()
+{
+	if (d_push_) return DTRL_OK;
+	PushRec* recs = static_cast<PushRec*>(be_->Alloc(sizeof(PushRec) * static_cast<size_t>(n_)));
+	double* scales = static_cast<double*>(be_->Alloc(sizeof(double) * static_cast<size_t>(n_)));
+	if (!recs || !scales) { if (recs) be_->Free(recs); if (scales) be_->Free(scales); return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error()); }
+	allocs_.push_back(recs); allocs_.push_back(scales);
+	std::vector<PushRec> r0(static_cast<size_t>(n_), PushRec{0, 0u, 0, -1, {0.0, 0.0}, 0.0});   // (last_link -1: no push yet)
+	std::vector<double> one(static_cast<size_t>(n_), 1.0);
+	if (!be_->H2D(recs, r0.data(), sizeof(PushRec) * r0.size()) || !be_->H2D(scales, one.data(), sizeof(double) * one.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	d_push_ = recs; d_push_scale_ = scales;
+	return DTRL_OK;
+}
+int Engine::PushStart(int n_listed)
+{
+	if (!push_on_ || n_listed <= 0) return DTRL_OK;
+	if (!be_->PushSchedule(nullptr, 0, n_listed, zero_copy_ ? pin_ids_ : d_env_list_, buf_.st, d_push_, d_push_scale_, push_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+int Engine::PushSchedule(int min_wait, int max_wait, uint64_t seed, double min_force, double max_force, double min_dur, double max_dur)
+{
+	const std::string w = "dtrl_push_schedule: ";
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, w + "not available with -policy_mode= external (a parked env's boundaries are not frames: a wait counted in ticks would depend on the caller's pace)");
+	if (int rc = RequireIdle("dtrl_push_schedule" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (min_wait > max_wait) { push_on_ = false; return DTRL_OK; }   // records, counters and scales stay; a push already in a slot runs out as it would have
+	if (min_wait < 1) return Fail(DTRL_ERR_ARG, w + "min_wait (" + std::to_string(min_wait) + ") must be at least 1 frame boundary");
+	if (std::isnan(min_force)) min_force = cfg_.min_perturb;
+	if (std::isnan(max_force)) max_force = cfg_.max_perturb;
+	if (std::isnan(min_dur)) min_dur = cfg_.min_perturb_duration;
+	if (std::isnan(max_dur)) max_dur = cfg_.max_perturb_duration;
+	const double v[4] = {min_force, max_force, min_dur, max_dur};
+	const char* const name[4] = {"min_force", "max_force", "min_dur", "max_dur"};
+	for (int i = 0; i < 4; ++i) if (!(v[i] >= 0) || !std::isfinite(v[i])) return Fail(DTRL_ERR_ARG, w + name[i] + " (" + std::to_string(v[i]) + ") must be a non-negative finite number");
+	if (min_force > max_force) return Fail(DTRL_ERR_ARG, w + "min_force exceeds max_force");
+	if (min_dur > max_dur) return Fail(DTRL_ERR_ARG, w + "min_dur exceeds max_dur");
+	if (int rc = PushAlloc(); rc != DTRL_OK) return rc;
+	push_ = PushCfg{min_wait, max_wait, min_force, max_force, min_dur, max_dur, seed, static_cast<int64_t>(cfg_.run.env_id_base), cfg_.model.L, 0};
+	push_on_ = true;
+	// every env of the schedule draws its first wait under the new settings (the counters go on where they were)
+	if (!be_->PushSchedule(nullptr, 0, n_, nullptr, buf_.st, d_push_, d_push_scale_, push_) || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+int Engine::PushScale(const int32_t* env_ids, int n, const double* scales)
+{
+	const std::string w = "dtrl_push_scale: ";
+	if (int rc = RequireIdle("dtrl_push_scale" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (n < 0 || n > n_ || (n > 0 && !scales)) return Fail(DTRL_ERR_ARG, w + "scales is required and the env count must be 0 .. num_envs");
+	for (int i = 0; i < n; ++i) {   // all or nothing
+		const int e = EnvIndex(env_ids, i);
+		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range; nothing changed");
+		if (!(scales[i] >= 0) || !std::isfinite(scales[i])) return Fail(DTRL_ERR_ARG, w + "scale " + std::to_string(scales[i]) + " of env " + std::to_string(e) + " must be a non-negative finite number; nothing changed");
+	}
+	if (int rc = PushAlloc(); rc != DTRL_OK) return rc;
+	std::vector<double> all(static_cast<size_t>(n_));
+	if (!be_->D2H(all.data(), d_push_scale_, sizeof(double) * all.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	for (int i = 0; i < n; ++i) all[EnvIndex(env_ids, i)] = scales[i];
+	if (!be_->H2D(d_push_scale_, all.data(), sizeof(double) * all.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+int Engine::PushInfo(const int32_t* env_ids, int n, int32_t* wait, int32_t* pushes, int32_t* last_link, double* last_force, double* last_dur)
+{
+	const std::string w = "dtrl_push_info: ";
+	if (int rc = RequireIdle("dtrl_push_info" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (!d_push_) return Fail(DTRL_ERR_ARG, w + "the batch has no push schedule (call dtrl_push_schedule first)");
+	if (n < 0 || n > n_) return Fail(DTRL_ERR_ARG, w + "the env count must be 0 .. num_envs");
+	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range"); }
+	std::vector<PushRec> recs(static_cast<size_t>(n_));
+	if (!be_->D2H(recs.data(), d_push_, sizeof(PushRec) * recs.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	for (int i = 0; i < n; ++i) {
+		const PushRec& r = recs[EnvIndex(env_ids, i)];
+		if (wait) wait[i] = r.wait;
+		if (pushes) pushes[i] = r.pushes;
+		if (last_link) last_link[i] = r.last_link;
+		if (last_force) { last_force[2 * i] = r.last_f[0]; last_force[2 * i + 1] = r.last_f[1]; }
+		if (last_dur) last_dur[i] = r.last_dur;
+	}
+	return DTRL_OK;
+}
+
 // ---- terrain sets (include/dtrl.h: dtrl_terrains_create ... dtrl_terrain_stats) ----
 // The third per-env key family, and the one no frame launch reads: a terrain decides what an env's NEXT segments look like, and segments are built at the frame
 // boundary -- by the env's GroundWindow on the host, or by the boundary kernel (-terrain_gen= device), which takes the table and the per-env array as two extra
@@ -2234,6 +2339,7 @@ int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrain
 			|| !Boundary(0, static_cast<int>(reset_ids_.size()), 2, d_env_list_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
 	if (int rc = ApplyResets(reset_ids_, -1); rc != DTRL_OK) return rc;
+	if (int rc = PushStart(static_cast<int>(reset_ids_.size())); rc != DTRL_OK) return rc;   // push schedule: the listed envs start over, a new wait each
 	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
 }

@@ -130,6 +130,17 @@ public:
 	// id) are written back where they changed. status / env_list / cfg.cum are device memory too. The default is a host loop with per-env D2H / H2D, synchronised
 	// (the lane-loop check build, DTRL_VARIANTS_FALLBACK=1 on HIP); the HIP backend overrides it with one launch of dtrl_variant_redraw on the selected stream.
 	virtual bool VariantRedraw(const EnvStatus* status, int e0, int n, const int32_t* env_list, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg);
+	// Push schedule (include/dtrl.h dtrl_push_schedule): the rule (push_step, dtrl_terrain_dev.h) for envs [e0, e0 + n) (or env_list[0 .. n) when given) at a frame
+	// boundary. status != nullptr: an env with status[e].need_reset != 0 starts an episode (its wait is drawn afresh), any other counts down and is pushed at 0;
+	// status == nullptr: every listed env starts (creation of the schedule, dtrl_reset, a terrain restart). recs[e], scale[e] and the seven slot fields of st[e] are
+	// device memory under the local env id; record and slot are written back only where they changed, an env of scale 0 is not touched. The default is a host loop
+	// with per-env D2H / H2D of the record and of the slot fields, behind a wait for the selected stream (the lane-loop check build, DTRL_PUSH_FALLBACK=1 on HIP);
+	// the HIP backend overrides it with one launch of dtrl_push_schedule on the selected stream.
+	virtual bool PushSchedule(const EnvStatus* status, int e0, int n, const int32_t* env_list, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg);
+	// dtrl_add_perturb: rows[0 .. n) (device memory, at most one row per env) into the perturbation slots of st[rows[i].env]. The default copies each env's whole
+	// EnvState down, edits the seven fields and copies it back (the lane-loop check build, DTRL_PERTURB_FALLBACK=1 on HIP); the HIP backend overrides it with one
+	// launch of dtrl_perturb_scatter on the selected stream.
+	virtual bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n);
 	// order[e0 .. e0 + n) = the envs e0 .. e0 + n - 1 sorted by status[].cost, costliest first (launch order of the group's next frame), on the selected stream
 	virtual bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) = 0;
 	// pending tuples -> block [block_rows + 1][W + 2] (header row + rows sorted by env id, flag word and global env id as the two extra columns); rows
@@ -272,6 +283,10 @@ public:
 	void ApplyPendingPolicy();
 	void* SideStream(int k, double* delay_us) { void* s = be_ ? be_->SideStream(k) : nullptr; if (delay_us) *delay_us = be_ ? be_->SideStreamDelayUs(k) : -1.0; return s; }
 	int AddPerturb(const int32_t* env_ids, int n, const int32_t* link, const double* local_pos, const double* force, const double* duration);
+	// push schedule (include/dtrl.h)
+	int PushSchedule(int min_wait, int max_wait, uint64_t seed, double min_force, double max_force, double min_dur, double max_dur);
+	int PushScale(const int32_t* env_ids, int n, const double* scales);
+	int PushInfo(const int32_t* env_ids, int n, int32_t* wait, int32_t* pushes, int32_t* last_link, double* last_force, double* last_dur);
 	int ApplyRandForce(const int32_t* env_ids, int n, uint64_t seed);
 	int GetPoliState(const int32_t* env_ids, int n, double* s);
 	int GetPolicyOutput(const int32_t* env_ids, int n, double* y);
@@ -451,6 +466,14 @@ private:
 	int VariantRefresh();                    // redraw on device terrain: host keys and counters <- device (call with the streams idle); else nothing
 	int VariantIdle(const char* what);       // redraw on device terrain: KeysIdle + VariantRefresh; else nothing
 	int RedrawListed(const std::vector<int32_t>& ids);   // dtrl_reset: the rule for the listed envs on the host, keys and counters uploaded (streams idle)
+	// push schedule: settings, per-env records and per-env scales are batch state. The DEVICE records and scales are the truth in both terrain modes (no host
+	// copies): the rule runs in Backend::PushSchedule on the group's stream at every frame boundary, and the calls that read the records wait for queued work
+	bool push_on_ = false;
+	PushCfg push_{};
+	PushRec* d_push_ = nullptr; double* d_push_scale_ = nullptr;   // device [n] each (allocated by the first dtrl_push_schedule / dtrl_push_scale; scales 1.0)
+	PerturbRow* d_pert_rows_ = nullptr;                            // device [n]: the rows of one dtrl_add_perturb (allocated by the first call)
+	int PushAlloc();                                               // the two push arrays, once
+	int PushStart(int n_listed);   // dtrl_reset / terrain restart: the rule with `start` for the n_listed envs ApplyResets(ids, -1) has just launched (same list, stream 0)
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

@@ -189,4 +189,77 @@ DTRL_TG_HD inline int32_t var_redraw_step(RedrawRec& r, int32_t k, bool start, c
 	return next > c.hi ? c.hi : next;
 }
 
+// ---- push schedule (include/dtrl.h dtrl_push_schedule): random external pushes at per-env random times, written into the env's perturbation slot ----
+// per-env record: frame boundaries left until the env's next push, the counter of its draw stream, how many pushes it got, and the last one as it was drawn
+// (force and duration in double, before the cast to `real` with which they are stored into EnvState)
+struct PushRec { int32_t wait; uint32_t ctr; int32_t pushes, last_link; double last_f[2]; double last_dur; };
+// the batch's schedule: the wait between two pushes of an env in frame boundaries (1 <= min_wait <= max_wait), the ranges of force magnitude and duration, the
+// stream's seed and env-id base, and the link count the link draw runs over. A kernel ARGUMENT: DevBuffers and RunParams keep their layout
+struct PushCfg {
+	int32_t min_wait, max_wait;
+	double min_force, max_force, min_dur, max_dur;
+	uint64_t seed; int64_t env_id_base;
+	int32_t L, pad_;
+};
+// what a push puts into the slot (Engine::AddPerturb's fields for a push at the link's COM: the rest of the slot is zero)
+struct PushOut { int32_t link; double f[2]; double dur; };
+// counter-based like ladder_draw and redraw_bits, under a constant of its own: a function of (seed, GLOBAL env id) -- shard-invariant
+DTRL_TG_HD inline uint64_t push_stream_key(uint64_t seed, int64_t global_env) { return tg_mix(tg_mix(seed) ^ (0x9054ED1ULL + static_cast<uint64_t>(global_env))); }
+DTRL_TG_HD inline double push_u01(uint64_t key, PushRec& r)
+{
+	const uint64_t z = tg_mix(key + static_cast<uint64_t>(r.ctr) * 0xD1342543DE82EF95ULL);
+	r.ctr += 1;
+	return static_cast<double>(z >> 11) * (1.0 / 9007199254740992.0);
+}
+DTRL_TG_HD inline int32_t push_draw_wait(uint64_t key, PushRec& r, const PushCfg& c)
+{
+	const int32_t w = c.min_wait + static_cast<int32_t>(push_u01(key, r) * static_cast<double>(c.max_wait - c.min_wait + 1));
+	return w > c.max_wait ? c.max_wait : w;
+}
+// The rule, the one body of host and device: env `env` (local id) at its frame boundary. `start`: an episode of the env starts in this boundary (it fell:
+// status.need_reset != 0; creation of the schedule; dtrl_reset naming it; a terrain restart) -- the wait is drawn afresh and no push happens, so the rule does not
+// depend on whether it runs in front of or behind the reset launch that clears the slot. Otherwise the wait counts down, and at 0 a push is drawn in the order
+// Engine::ApplyRandForce draws (link, three (sign, magnitude) pairs, force magnitude, duration), returned in `out` (true: the caller writes the slot), recorded,
+// and the next wait is drawn. scale == 0: the env is not in the schedule, nothing of it is touched. Doubles and integers only; every product, sum, divide and
+// square root below is a single correctly rounded operation (the sources are compiled without contraction), so host and device give the same bits.
+DTRL_TG_HD inline bool push_step(PushRec& r, double scale, bool start, const PushCfg& c, int env, PushOut& out)
+{
+	if (scale == 0) return false;
+	const uint64_t key = push_stream_key(c.seed, c.env_id_base + env);
+	if (start) { r.wait = push_draw_wait(key, r, c); return false; }
+	r.wait -= 1;
+	if (r.wait > 0) return false;
+	int32_t link = static_cast<int32_t>(push_u01(key, r) * static_cast<double>(c.L));
+	if (link >= c.L) link = c.L - 1;
+	double d[3];
+	for (int k = 0; k < 3; ++k) { const double sgn = push_u01(key, r) < 0.5 ? -1.0 : 1.0; d[k] = sgn * push_u01(key, r); }
+	double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+	if (nrm == 0) { d[0] = 1; nrm = 1; }
+	const double mag = scale * (c.min_force + push_u01(key, r) * (c.max_force - c.min_force));
+	out.link = link;
+	out.f[0] = mag * d[0] / nrm; out.f[1] = mag * d[1] / nrm;
+	out.dur = c.min_dur + push_u01(key, r) * (c.max_dur - c.min_dur);
+	r.last_link = link; r.last_f[0] = out.f[0]; r.last_f[1] = out.f[1]; r.last_dur = out.dur;
+	r.pushes += 1;
+	r.wait = push_draw_wait(key, r, c);
+	return true;
+}
+// the slot as Engine::AddPerturb writes it for a push at the link's COM (values cast to `real` here and nowhere else)
+DTRL_TG_HD inline void push_write_slot(EnvState& st, const PushOut& p)
+{
+	st.pert_link = p.link; st.pert_on = 0;
+	st.pert_lp[0] = 0; st.pert_lp[1] = 0;
+	st.pert_f[0] = static_cast<real>(p.f[0]); st.pert_f[1] = static_cast<real>(p.f[1]);
+	st.pert_torque = 0; st.pert_time = 0; st.pert_dur = static_cast<real>(p.dur);
+}
+// one row of dtrl_add_perturb as the engine uploads it (Backend::PerturbScatter): the rotated offset is the host's, bit for bit
+struct PerturbRow { int32_t env, link; real f[2], lp[2], dur; };
+DTRL_TG_HD inline void perturb_write_slot(EnvState& st, const PerturbRow& r)
+{
+	st.pert_link = r.link; st.pert_on = 0;
+	st.pert_lp[0] = r.lp[0]; st.pert_lp[1] = r.lp[1];
+	st.pert_f[0] = r.f[0]; st.pert_f[1] = r.f[1];
+	st.pert_torque = 0; st.pert_time = 0; st.pert_dur = r.dur;
+}
+
 }  // namespace dtrl

@@ -119,9 +119,25 @@ def setup_variants(b, spec):
     return {"scales": scales, "weights": weights}
 
 
+def setup_pushes(b, spec, greedy_envs=0):
+    """Pushes while training (BatchScenario.PushSchedule): spec["wait"] = (lo, hi) frame boundaries between two pushes of an env, spec["force"] / ["duration"] =
+    (lo, hi) ranges (missing: the batch's -min_perturb= ... arguments), spec["seed"], spec["hold_out"] = env ids that are never pushed (scale 0). The last
+    greedy_envs envs (train(greedy_envs=k): the evaluation envs) are held out as well. Returns {"hold_out": the ids with scale 0}."""
+    unknown = set(spec) - {"wait", "force", "duration", "seed", "hold_out"}
+    if unknown:
+        raise ValueError("pushes: unknown keys %s" % ", ".join(sorted(unknown)))
+    if "wait" not in spec:
+        raise ValueError("pushes: wait=(lo, hi) is required")
+    held = sorted(set(int(e) for e in spec.get("hold_out", ())) | set(range(b.num_envs - greedy_envs, b.num_envs)))
+    if held:
+        b.PushScale(0.0, env_ids=held)
+    b.PushSchedule(tuple(spec["wait"]), seed=int(spec.get("seed", 0)), force=spec.get("force"), duration=spec.get("duration"))
+    return {"hold_out": held}
+
+
 def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, device_id=-1, extra_args=None, seed=0, log_every=0, out_scale_file=None,
           trainer_device=None, overlap=False, frames_per_drain=1, scenario_cls=BatchScenario, trainer="torch", trainer_lib=None, poll=False,
-          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None):
+          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None, pushes=None):
     """extra_args override / extend the arg file (both for the engine and for the -trainer_* keys read here).
     overlap=True trains on frame f's tuples while the GPU already rolls out frame f+1 (dtrl_step_begin / dtrl_step_end): the policy
     each frame runs with is one frame staler, as with the reference's concurrent env threads; overlap=False is the strictly
@@ -137,7 +153,10 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     stats["greedy"]. k = 0 (default) creates no slots and runs exactly as before.
     variants=dict(count=, mass=(lo, hi), torque_lim=, kp=, kd=, seed=, keep_nominal=) trains under domain randomisation (setup_variants: a table of scaled
     character models, every episode of every env under a model drawn afresh); stats["variants"] then holds the scales, the weights and VariantRedrawInfo() at the
-    end. Not together with greedy_envs: the greedy envs use policy slots, and slots exclude model variants. None (default) runs exactly as before."""
+    end. Not together with greedy_envs: the greedy envs use policy slots, and slots exclude model variants. None (default) runs exactly as before.
+    pushes=dict(wait=(lo, hi), force=(lo, hi), duration=(lo, hi), seed=, hold_out=[env ids]) trains under random external pushes (setup_pushes: every env but the
+    held-out and the greedy ones is pushed at random times on the device, no host work per frame); stats["pushes"] then holds the held-out ids and PushInfo() at
+    the end. Combines with greedy_envs and with variants. None (default) runs exactly as before."""
     if variants is not None and greedy_envs:
         raise ValueError("greedy_envs > 0 together with variants: the greedy envs use policy slots, and policy slots exclude model variants")
     if overlap:
@@ -199,6 +218,7 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
 
     sync(0)
     var_info = setup_variants(b, variants) if variants is not None else None   # (behind the first SetPolicy / SetExplore: its Reset runs a launch)
+    push_info = setup_pushes(b, pushes, greedy_envs) if pushes is not None else None
     frames = tuples = 0
     next_eval = [0 if eval_fn else None]
     if eval_fn:
@@ -286,6 +306,8 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
         stats["greedy"] = dict(b.SlotStats(1), falls_k=greedy_falls())
     if var_info is not None:
         stats["variants"] = dict(var_info, **b.VariantRedrawInfo())
+    if push_info is not None:
+        stats["pushes"] = dict(push_info, **b.PushInfo())
     return stats
 
 

@@ -462,12 +462,52 @@ dtrl_status dtrl_ladder_info(dtrl_batch* b, const int32_t* env_ids, int n, doubl
 /* Replaces: cScenarioSimChar::AddPerturb -> cWorld::AddPerturb (scenarios/ScenarioSimChar.cpp:204-207, sim/World.cpp:256-259) with a
  * tPerturb of type ePerturbForce (sim/Perturb.cpp:52-79, sim/World.cpp:445-470): a world-frame force[n][2] on body part link[n] at the
  * body-local offset local_pos[n][2] (NULL = the COM) for duration[n] seconds of simulated time, advanced and applied at the start of
- * every env-step like cPerturbManager::UpdatePerturbs. One slot per env (a new perturbation replaces the old one); reset clears it. */
+ * every env-step like cPerturbManager::UpdatePerturbs. One slot per env (a new perturbation replaces the old one); reset clears it. An env listed
+ * several times keeps its last row. The rows reach the slots in one launch. */
 dtrl_status dtrl_add_perturb(dtrl_batch* b, const int32_t* env_ids, int n, const int32_t* link, const double* local_pos, const double* force, const double* duration);
 /* Replaces: cScenarioSimChar::ApplyRandForce() (scenarios/ScenarioSimChar.cpp:209-235; ranges -min_perturb= -max_perturb=
  * -min_pertrub_duration= -max_perturb_duration= as the reference spells them): a random body part, direction, magnitude and duration per
  * env. The reference draws from its time-seeded global RNG; here the draw is a function of (seed, global env id). */
 dtrl_status dtrl_apply_rand_force(dtrl_batch* b, const int32_t* env_ids, int n, uint64_t seed);
+
+/* ---- Push schedule: random external pushes on the device at per-env random times (robustness training and evaluation) ----
+ * No counterpart in the reference as a schedule: its scenarios call ApplyRandForce by hand (a key press). Replaces: cScenarioSimChar::ApplyRandForce
+ * (scenarios/ScenarioSimChar.cpp:209-235) called from a host loop. A schedule is a range of waits [min_wait, max_wait] counted in the env's frame boundaries, a
+ * range of force magnitudes and of durations, and a seed. Each env carries a record (wait, ctr, pushes, the last push) and a scale (1.0 unless set). The draws of
+ * env e are u(i) = (bits(i) >> 11) * 2^-53 with bits(i) = mix(mix(mix(seed) ^ (C + global env id)) + i * 0xD1342543DE82EF95), i = ctr++ for every draw: mix is
+ * the terrain streams' 64-bit finaliser, C a constant of the schedule's own, the global env id -env_id_base= + local id. The stream is shard-invariant and
+ * independent of exploration, reward and every other env. At env e's FRAME BOUNDARY (behind every dtrl_step / dtrl_step_end / frame of dtrl_run_frames /
+ * dtrl_step_updates), in this order:
+ *   scale[e] == 0           nothing: the env is not in the schedule, nothing of it is read, drawn or written (evaluation envs are held out this way)
+ *   an episode starts       (the env fell in this frame; dtrl_push_schedule itself; dtrl_reset naming it, once however often it is listed; dtrl_assign_terrains
+ *                           with restart != 0) wait = min_wait + floor(u * (max_wait - min_wait + 1)), clamped to max_wait. No push.
+ *   else                    wait -= 1; while it is still > 0 nothing more
+ *   wait reached 0          a push, drawn in ApplyRandForce's order: link floor(u * L) (clamped to L - 1); three (sign, magnitude) pairs d = +-u (sign: u < 0.5 is
+ *                           -1), normalised, (1, 0, 0) standing in for a zero vector, x and y kept; f = scale * (min_force + u * (max_force - min_force)) * d / |d|;
+ *                           dur = min_dur + u * (max_dur - min_dur). The env's perturbation slot is written as dtrl_add_perturb writes it for a push at the
+ *                           link's COM, the push is recorded, pushes += 1, and the next wait is drawn.
+ * Every value is computed in double in both libraries and cast to the library's arithmetic type only where it is stored into the slot. A push never happens at an
+ * episode start, so nothing depends on whether the rule runs in front of or behind the reset that clears the slot. A scheduled push and dtrl_add_perturb share
+ * the env's one slot: the later writer wins, as in the reference's manager. The rule is one small launch per env group and frame on the group's stream in both
+ * terrain modes (no host wait is added; dtrl_run_frames and the overlapped loops included); a batch without a schedule queues what it always queued. It combines
+ * with policy slots, model variants and their redraw, terrain sets and the ladder. NOT available with -policy_mode= external: a parked env's boundaries are not
+ * frames, a wait counted in ticks would depend on the caller's pace. Settings, records and scales are batch state: snapshots, restores, clones and blobs leave
+ * them alone (the slot itself is part of the env's state and travels as it always has). */
+/* No counterpart in the reference / Replaces: cScenarioSimChar::ApplyRandForce (scenarios/ScenarioSimChar.cpp:209-235). Turn the schedule on or replace its
+ * settings (1 <= min_wait <= max_wait; every env of scale != 0 draws a first wait under them), or remove it (min_wait > max_wait). Records, counters and scales
+ * are kept in all three cases. NaN for any of the four ranges means the batch's -min_perturb= -max_perturb= -min_pertrub_duration= -max_perturb_duration=.
+ * DTRL_ERR_ARG, nothing changed: min_wait < 1, a negative or infinite range, min > max, -policy_mode= external, a frame in flight. */
+dtrl_status dtrl_push_schedule(dtrl_batch* b, int min_wait, int max_wait, uint64_t seed, double min_force, double max_force, double min_dur, double max_dur);
+/* No counterpart in the reference / Replaces: cScenarioSimChar::ApplyRandForce (scenarios/ScenarioSimChar.cpp:209-235). scales[i] -> env_ids[i] (env_ids == NULL:
+ * the first n envs): finite and >= 0, all or nothing (DTRL_ERR_ARG, nothing changed). 0 takes the env out of the schedule, any other value multiplies its force
+ * (one batch can hold a magnitude sweep). May be called before dtrl_push_schedule. An env that comes in from 0 while a schedule runs has not drawn a wait: it
+ * is pushed at its next boundary and follows the schedule from there. Refused while a frame is in flight. */
+dtrl_status dtrl_push_scale(dtrl_batch* b, const int32_t* env_ids, int n, const double* scales);
+/* No counterpart in the reference / Replaces: cScenarioSimChar::ApplyRandForce (scenarios/ScenarioSimChar.cpp:209-235). Per listed env (env_ids == NULL: the
+ * first n): boundaries left until its next push, pushes so far, and the last push as drawn (link, -1 = none yet; force[n][2]; duration), as of the last completed
+ * boundary: refused between dtrl_step_begin and dtrl_step_end and before the first dtrl_push_schedule / dtrl_push_scale, otherwise waits for queued work. Any
+ * output may be NULL. */
+dtrl_status dtrl_push_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* wait, int32_t* pushes, int32_t* last_link, double* last_force, double* last_dur);
 /* Replaces: cNNController::RecordPoliState (sim/TerrainRLCharController.cpp:120-123). */
 dtrl_status dtrl_get_poli_state(dtrl_batch* b, const int32_t* env_ids, int n, double* s);
 /* Replaces: cNeuralNet::GetLayerState("output", y) (learning/NeuralNet.cpp:814-834) after the controller's last cNeuralNet::Eval

@@ -1,0 +1,196 @@
+"""Push schedule on the product library (libdtrl.so / libdtrl_f32.so on cuda:0): the twins of tests/test_push_schedule.py -- there the host defaults of
+Backend::PushSchedule and Backend::PerturbScatter, here ONE launch of dtrl_push_schedule per env group and frame in both terrain modes and ONE launch of
+dtrl_perturb_scatter per dtrl_add_perturb -- and what only exists on HIP: the kernels against their host fallbacks (DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1)
+at 70 envs / rows (two 64-thread blocks, the second partial) with one and two env groups in both libraries, frames queued without a host wait (RunFrames) against
+frame-by-frame Update, run-to-run determinism, the fast kernel against the reference kernel under a schedule, and the new symbols in both libraries."""
+import ctypes
+import os
+
+import pytest
+
+import test_external_policy as X
+import test_host_and_emul as H
+import test_model_variants as V
+import test_policy_slots as P
+import test_push_schedule as R
+import test_terrain_ladder as LD
+import test_terrain_sets as T
+from conftest import HIP_LIB
+
+pytestmark = pytest.mark.gpu
+
+KNOBS = ("DTRL_KERNEL", "DTRL_TERRAINS_FALLBACK", "DTRL_SLOTS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_GROUPS")
+
+
+@pytest.fixture(autouse=True)
+def hip_batch(monkeypatch):
+    import deepterrainrl_amd
+    for mod in (R, T, V, X, P, LD, H):
+        monkeypatch.setattr(mod, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+
+
+# ---- twins ----
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_records_equal_the_rule(da, om, mode, precision):
+    """(both libraries: the rule is doubles and integers in either, so the fp32 library's records equal the same Python rule, given its own falls)"""
+    R.test_records_equal_the_rule(da, om, mode, **(dict(physics_precision="f32") if precision == "f32" else {}))
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_replay_through_add_perturb(da, om, mode):
+    R.test_replay_through_add_perturb(da, om, mode)
+
+
+def test_scheduled_push_vs_oracle(da, om):
+    R.test_scheduled_push_vs_oracle(da, om)
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_held_out_envs_equal_a_batch_without_schedule(da, om, mode):
+    R.test_held_out_envs_equal_a_batch_without_schedule(da, om, mode)
+
+
+def test_scale_multiplies_the_force_and_nothing_else(da, om):
+    R.test_scale_multiplies_the_force_and_nothing_else(da, om)
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_batch_state_resets_and_removal(da, om, mode):
+    R.test_batch_state_resets_and_removal(da, om, mode)
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_shard_invariance(da, om, mode):
+    R.test_shard_invariance(da, om, mode)
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_with_policy_slots(da, om, mode):
+    R.test_with_policy_slots(da, om, mode)
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_with_model_variants_and_redraw(da, om, tmp_path, mode):
+    R.test_with_model_variants_and_redraw(da, om, tmp_path, mode)
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_with_terrain_ladder(da, om, mode):
+    R.test_with_terrain_ladder(da, om, mode)
+
+
+def test_refusals(da, om):
+    R.test_refusals(da, om)
+
+
+def test_add_perturb_equals_row_by_row(da, om, tmp_path):
+    R.test_add_perturb_equals_row_by_row(da, om, tmp_path)
+
+
+def test_apply_rand_force_goes_through_the_launch(da, om):
+    R.test_apply_rand_force_goes_through_the_launch(da, om)
+
+
+def test_push_robustness_tool(da, om):
+    R.test_push_robustness_tool(da, om)
+
+
+def test_train_loop_with_pushes(da, om):
+    """A few hundred iterations of the native trainer on the product libraries under a schedule."""
+    out, _ = R.run_train_loop_with_pushes(200, 4000, trainer_device="cuda")
+    assert out["iters"] >= 200, (out["frames"], out["iters"])
+
+
+# ---- GPU only: 70 envs (two blocks of 64 threads, the second partial), bit for bit ----
+N, FRAMES = 70, 30
+
+
+def end_state(b):
+    info = b.PushInfo()
+    return X.env_states(b), b.RecordPoliState(), [X.ground_key(b, e) for e in range(b.num_envs)], {k: v.tobytes() for k, v in info.items()}, info
+
+
+def push_run(om, monkeypatch, env, mode, extra, run_frames=False):
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    scale = [0.0 if e % 7 == 3 else 1.0 + 0.25 * (e % 3) for e in range(N)]     # held-out envs and a magnitude sweep in both blocks
+    b = R.push_batch(om, N, mode, scale=scale, **extra)
+    if run_frames:
+        b.RunFrames(FRAMES)
+    else:
+        for _ in range(FRAMES):
+            b.Update()
+    out = end_state(b)
+    pushes = out[4]["pushes"]
+    assert pushes[[e for e in range(N) if e % 7 != 3]].min() >= 3 and not pushes[3::7].any() and out[0]["num_resets"][64:].sum() >= 1, pushes
+    return out
+
+
+@pytest.mark.parametrize("groups", ["1", "2"], ids=["one_group", "two_groups"])
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_push_kernel_equals_host_fallback(da, om, monkeypatch, mode, precision, groups):
+    """One launch of dtrl_push_schedule per group and frame against the rule run on the host, env by env (DTRL_PUSH_FALLBACK=1); two groups: the second starts at a
+    non-zero e0."""
+    extra = dict(physics_precision="f32") if precision == "f32" else {}
+    base = push_run(om, monkeypatch, {"DTRL_GROUPS": groups}, mode, extra)
+    R.assert_same_end(base, push_run(om, monkeypatch, {"DTRL_GROUPS": groups, "DTRL_PUSH_FALLBACK": "1"}, mode, extra), "host fallback")
+
+
+@pytest.mark.parametrize("precision", ["f64", "f32"])
+def test_perturb_scatter_equals_host_fallback(da, om, tmp_path, monkeypatch, precision, n=70, rows=70):
+    """dtrl_perturb_scatter against the per-env copy loop the call ran before (DTRL_PERTURB_FALLBACK=1): 70 rows over 70 envs of four variants, offsets, an env
+    named three times."""
+    env, link, force, lp, dur = R.perturb_rows(n, rows)
+    paths = V.write_variants(tmp_path, R.DOG) + [V.write_doc(tmp_path, "geom.txt", V.geometry_doc())]
+    extra = dict(terrain_seed=11, **(dict(physics_precision="f32") if precision == "f32" else {}))
+
+    def run(fallback):
+        monkeypatch.delenv("DTRL_PERTURB_FALLBACK", raising=False)
+        if fallback:
+            monkeypatch.setenv("DTRL_PERTURB_FALLBACK", "1")
+        b = V.with_variants(om, R.DOG, n, paths, [e % 4 for e in range(n)], extra)
+        b.Update()
+        b.AddPerturb(link, force, dur, local_pos=lp, env_ids=env)
+        b.ApplyRandForce(5, env_ids=[1, 2, 66])
+        written = X.env_states(b)
+        for _ in range(3):
+            b.Update()
+        return written, X.env_states(b)
+    (wa, sa), (wb, sb) = run(False), run(True)
+    for what, x, y in (("after the calls", wa, wb), ("three frames on", sa, sb)):
+        for e in range(n):
+            bad = X.same_record(x[e], y[e])
+            assert bad is None, "%s: env %d: EnvState.%s differs from the host fallback" % (what, e, bad)
+    named = set(env.tolist()) | {1, 2, 66}
+    assert [e for e in range(n) if wa["pert_link"][e] >= 0] == sorted(named) and len(named) >= 40     # every named env's slot was written, no other
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_queued_frames_equal_frame_by_frame_and_repeat(da, om, monkeypatch, mode):
+    """RunFrames -- with device terrain every frame, boundary, push and reset launch queued, the host never waits between them -- equals frame-by-frame Update(); a
+    second run gives the same bits."""
+    base = push_run(om, monkeypatch, {}, mode, {})
+    R.assert_same_end(base, push_run(om, monkeypatch, {}, mode, {}, run_frames=True), "RunFrames")
+    R.assert_same_end(base, push_run(om, monkeypatch, {}, mode, {}), "run after run")
+
+
+def test_fast_kernel_equals_reference_kernel_under_a_schedule(da, om, monkeypatch):
+    mode = dict(terrain_gen="device")
+    base = push_run(om, monkeypatch, {}, mode, {})
+    R.assert_same_end(base, push_run(om, monkeypatch, {"DTRL_KERNEL": "ref"}, mode, {}), "DTRL_KERNEL=ref")
+
+
+SYMBOLS = ("dtrl_push_schedule", "dtrl_push_scale", "dtrl_push_info")
+
+
+@pytest.mark.parametrize("lib", ["libdtrl.so", "libdtrl_f32.so"])
+def test_new_symbols_resolve(lib):
+    lib_ = ctypes.CDLL(os.path.join(os.path.dirname(HIP_LIB), lib))
+    for name in SYMBOLS:
+        assert getattr(lib_, name) is not None, name

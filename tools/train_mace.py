@@ -29,7 +29,20 @@ ap.add_argument("--variant-kp", type=float, nargs=2, default=[1.0, 1.0], metavar
 ap.add_argument("--variant-kd", type=float, nargs=2, default=[1.0, 1.0], metavar=("LO", "HI"), help="with --variants: range of the PD controllers' Kd scale")
 ap.add_argument("--variant-seed", type=int, default=0, help="with --variants: seed of the scales, the initial deal and the redraw")
 ap.add_argument("--keep-nominal", type=float, default=None, help="with --variants: share of the draw's weight on the nominal model (default: 1 / variants)")
+ap.add_argument("--pushes", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="random pushes while training (train_loop.train(pushes=...)): every env is pushed on the device every LO .. HI frames (not with --distributed)")
+ap.add_argument("--push-force", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --pushes: range of the force magnitude in N (default: the arg file's -min_perturb= / -max_perturb=)")
+ap.add_argument("--push-duration", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --pushes: range of the duration in s (default: the arg file's)")
+ap.add_argument("--push-seed", type=int, default=0, help="with --pushes: seed of the push streams")
 a = ap.parse_args()
+if a.pushes and a.distributed:
+    ap.error("--pushes is not available with --distributed")
+pushes = None
+if a.pushes:
+    pushes = dict(wait=tuple(a.pushes), seed=a.push_seed)
+    if a.push_force:
+        pushes["force"] = tuple(a.push_force)
+    if a.push_duration:
+        pushes["duration"] = tuple(a.push_duration)
 if a.variants and a.distributed:
     ap.error("--variants is not available with --distributed")
 variants = None
@@ -59,11 +72,13 @@ if a.distributed:
     sys.exit(0)
 st = train_loop.train(a.arg_file, a.data_root, a.envs, max_iters=a.iters, max_frames=a.frames, log_every=50, overlap=a.overlap, frames_per_drain=a.frames_per_drain,
                       extra_args=dict(({"reserve_cus": reserve} if reserve else {}), **({"trainer_num_init_samples": a.init_samples} if a.init_samples is not None else {})) or None,
-                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll, variants=variants)
+                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll, variants=variants, pushes=pushes)
 if a.out:
     np.save(a.out + ".npy", st["weights"])
 if variants:
     print("[variants] %d models, %d draws; envs per variant at the end: %s" % (a.variants, int(st["variants"]["draws"].sum()), np.bincount(st["variants"]["variant"], minlength=a.variants).tolist()))
+if pushes:
+    print("[pushes] every %d .. %d frames; %d pushes, most on one env %d" % (a.pushes[0], a.pushes[1], int(st["pushes"]["pushes"].sum()), int(st["pushes"]["pushes"].max())))
 print("[trainer=%s reserve_cus=%d side-stream start delay %.0f us] " % (a.trainer, reserve, st["side_stream_delay_us"]), end="")
 print("frames %d  trainer iters %d  tuples %d  %.1f s  ->  %.2f M env-steps/s while training, %.1f trainer iters/s" % (
     st["frames"], st["iters"], st["tuples"], st["seconds"], st["env_steps_per_s"] / 1e6, st["trainer_iters_per_s"]))
