@@ -2,6 +2,7 @@
 // check build (tests/emul, TESTS ONLY) after `Backend` is defined.
 #include "../../include/dtrl_trainer.h"
 #include "dtrl_trainer_files.h"
+#include <cstdlib>
 #include <new>
 #include <random>
 
@@ -10,8 +11,32 @@ struct dtrl_trainer {
 	std::string err;
 	float* host_x = nullptr; float* host_y = nullptr;      // device staging of the host-pointer calls (dtrl_trainer_eval_host / _step_host), made on first use
 	std::vector<float> fx, fy;
+	int fused_mode = 1;                                     // DTRL_TRAINER_FUSED as read at creation (dtrl_trainer_fused_info)
 };
-namespace { std::string g_tr_create_error; }
+namespace {
+std::string g_tr_create_error;
+// a description the allocations and kernels below cannot take: every size that becomes a divisor, a loop bound or an allocation must be positive
+bool tr_bad_desc(const dtrl_trainer_desc& s, std::string& why)
+{
+	auto bad = [&](const char* field, int idx, long long v) { why = std::string("bad trainer description: ") + field + (idx >= 0 ? "[" + std::to_string(idx) + "]" : std::string()) + " = " + std::to_string(v); return true; };
+	if (s.n_heads < 1 || s.n_heads > dtrl_tr::kMaxHeads) return bad("n_heads", -1, s.n_heads);
+	if (s.batch < 1) return bad("batch", -1, s.batch);
+	if (s.max_eval < s.batch) return bad("max_eval", -1, s.max_eval);
+	if (s.n_terrain < 1) return bad("n_terrain", -1, s.n_terrain);
+	if (s.state_size <= s.n_terrain) return bad("state_size", -1, s.state_size);
+	for (int l = 0; l < 3; ++l) {
+		if (s.conv_ch[l] < 1) return bad("conv_ch", l, s.conv_ch[l]);
+		if (s.conv_k[l] < 1) return bad("conv_k", l, s.conv_k[l]);
+	}
+	if (s.fc_terr < 1) return bad("fc_terr", -1, s.fc_terr);
+	if (s.fc_trunk < 1) return bad("fc_trunk", -1, s.fc_trunk);
+	if (s.fc_head < 1) return bad("fc_head", -1, s.fc_head);
+	for (int f = 0; f < s.n_heads; ++f) if (s.head_out[f] < 1) return bad("head_out", f, s.head_out[f]);
+	if (s.n_frags < 0) return bad("n_frags", -1, s.n_frags);
+	if (s.frag_size < 0) return bad("frag_size", -1, s.frag_size);
+	return false;
+}
+}
 
 extern "C" {
 
@@ -19,7 +44,7 @@ int dtrl_trainer_create(const dtrl_trainer_desc* desc, int device_id, dtrl_train
 try {
 	if (!desc || !out) return 1;
 	*out = nullptr;
-	if (desc->n_heads < 1 || desc->n_heads > dtrl_tr::kMaxHeads || desc->batch < 1 || desc->max_eval < desc->batch || desc->state_size <= desc->n_terrain) { g_tr_create_error = "bad trainer description"; return 1; }
+	if (tr_bad_desc(*desc, g_tr_create_error)) return 1;
 	dtrl_tr::TrainerConfig c;
 	dtrl_tr::NetDims& d = c.dims;
 	std::memset(&d, 0, sizeof(d));
@@ -33,6 +58,7 @@ try {
 	c.base_lr = desc->base_lr; c.momentum = desc->momentum; c.weight_decay = desc->weight_decay; c.discount = desc->discount;
 	if (c.n_frags > 0 && (d.n_heads != 1 + c.n_frags || d.head_out[0] != c.n_frags)) { g_tr_create_error = "MACE layout: head 0 must hold n_frags values, heads 1.. the fragments"; return 1; }
 	dtrl_trainer* t = new dtrl_trainer();
+	{ const char* e = std::getenv("DTRL_TRAINER_FUSED"); t->fused_mode = e ? std::atoi(e) : 1; }   // (the HIP backend's setup_fused reads the same variable during Init)
 	t->core = new dtrl_tr::TrainerCore<Backend>(c);
 	t->core->cfg_target_frozen = desc->freeze_target != 0;
 	t->core->be.device_id = device_id;
@@ -44,6 +70,17 @@ try {
 void dtrl_trainer_destroy(dtrl_trainer* t) { if (t) { if (t->host_x) t->core->be.free_dev(t->host_x); if (t->host_y) t->core->be.free_dev(t->host_y); delete t->core; delete t; } }
 const char* dtrl_trainer_last_error(const dtrl_trainer* t) { return t ? t->err.c_str() : g_tr_create_error.c_str(); }
 #define TR_GUARD(expr) try { if (!t) return 1; if (!(expr)) { t->err = t->core->be.error().empty() ? "bad arguments" : t->core->be.error(); return t->core->be.error().empty() ? 1 : 4; } return 0; } catch (const std::exception& e) { t->err = e.what(); return 5; } catch (...) { t->err = "unknown exception"; return 5; }
+// which cut of the step this trainer runs: host-only, answered from fused_plan() of the net's dimensions and the mode read at creation (both builds; the check build
+// reports the plan although it always runs the layer-by-layer form)
+int dtrl_trainer_fused_info(const dtrl_trainer* t, int* plan_ok, int* lds_bytes, int* mode)
+{
+	if (!t) return 1;
+	const dtrl_tr::FusedPlan p = dtrl_tr::fused_plan(t->core->cfg.dims);
+	if (plan_ok) *plan_ok = p.ok ? 1 : 0;
+	if (lds_bytes) *lds_bytes = p.lds_bytes;
+	if (mode) *mode = t->fused_mode;
+	return 0;
+}
 int dtrl_trainer_set_stream(dtrl_trainer* t, void* s) { TR_GUARD((t->core->be.set_stream(s), true)) }
 int dtrl_trainer_sync(dtrl_trainer* t) { TR_GUARD((t->core->be.sync(), t->core->be.ok())) }
 int64_t dtrl_trainer_num_params(const dtrl_trainer* t) { return t ? t->core->cfg.dims.num_params : 0; }

@@ -30,7 +30,7 @@ TRAINER_ABI_SYMBOLS = [
     "dtrl_trainer_stage_rows", "dtrl_trainer_stage_flags", "dtrl_trainer_stage_capacity", "dtrl_trainer_add_staged",
     "dtrl_trainer_create_from_files", "dtrl_trainer_dims", "dtrl_trainer_init_xavier", "dtrl_trainer_eval_host", "dtrl_trainer_step_host", "dtrl_trainer_get_normalizers",
     "dtrl_trainer_copy_model", "dtrl_trainer_bind_grad", "dtrl_trainer_grad_device", "dtrl_trainer_grad_step", "dtrl_trainer_critic_grad", "dtrl_trainer_actor_grad", "dtrl_trainer_zero_grad", "dtrl_trainer_apply_grad",
-    "dtrl_trainer_value_step", "dtrl_trainer_td_filter", "dtrl_trainer_td", "dtrl_trainer_action_step",
+    "dtrl_trainer_value_step", "dtrl_trainer_td_filter", "dtrl_trainer_td", "dtrl_trainer_action_step", "dtrl_trainer_fused_info",
 ]
 
 
@@ -81,6 +81,11 @@ def _bind(path):
     L.dtrl_trainer_td_filter.argtypes = [vp, C.c_int]
     L.dtrl_trainer_td.restype = C.POINTER(C.c_float); L.dtrl_trainer_td.argtypes = [vp]
     L.dtrl_trainer_action_step.argtypes = [vp]
+    L.dtrl_trainer_fused_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.dtrl_trainer_dims.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.dtrl_trainer_init_xavier.argtypes = [vp, C.c_uint64]
+    L.dtrl_trainer_eval_host.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    L.dtrl_trainer_step_host.argtypes = [vp, vp, vp, C.POINTER(C.c_double)]
     return L
 
 
@@ -138,6 +143,35 @@ class NativeTrainer:
     def _chk(self, rc):
         if rc != 0:
             raise DtrlError("dtrl_trainer call failed (%d): %s" % (rc, self._lib.dtrl_trainer_last_error(self._h).decode()))
+
+    def fused_info(self):
+        """(plan_ok, lds_bytes, mode): whether the net is inside the fused kernels' plan, the LDS they need, DTRL_TRAINER_FUSED as read at creation"""
+        ok, lds, mode = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self._lib.dtrl_trainer_fused_info(self._h, C.byref(ok), C.byref(lds), C.byref(mode)))
+        return bool(ok.value), int(lds.value), int(mode.value)
+
+    def dims(self):
+        """(in_size, out_size, batch, max_eval)"""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self._lib.dtrl_trainer_dims(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def init_xavier(self, seed): self._chk(self._lib.dtrl_trainer_init_xavier(self._h, int(seed)))
+
+    def eval_host(self, which, X):
+        """un-normalised outputs of net `which` on host rows X [n][in_size] (any n: chunks of max_eval); float64 in and out, synchronous"""
+        X = np.ascontiguousarray(X, np.float64)
+        Y = np.zeros((X.shape[0], self.dims()[1]), np.float64)
+        self._chk(self._lib.dtrl_trainer_eval_host(self._h, int(which), X.ctypes.data_as(C.c_void_p), X.shape[0], Y.ctypes.data_as(C.c_void_p)))
+        return Y
+
+    def step_host(self, X, Y):
+        """one solver iteration on host rows X [batch][in_size], labels Y [batch][out_size]; returns the loss; synchronous"""
+        X = np.ascontiguousarray(X, np.float64); Y = np.ascontiguousarray(Y, np.float64)
+        assert X.shape[0] == self.batch and Y.shape[0] == self.batch
+        loss = C.c_double()
+        self._chk(self._lib.dtrl_trainer_step_host(self._h, X.ctypes.data_as(C.c_void_p), Y.ctypes.data_as(C.c_void_p), C.byref(loss)))
+        return float(loss.value)
 
     def set_stream(self, ptr): self._chk(self._lib.dtrl_trainer_set_stream(self._h, C.c_void_p(ptr)))
     def sync(self): self._chk(self._lib.dtrl_trainer_sync(self._h))

@@ -35,6 +35,11 @@ typedef struct dtrl_trainer_desc {
 int dtrl_trainer_create(const dtrl_trainer_desc* desc, int device_id, dtrl_trainer** out);
 void dtrl_trainer_destroy(dtrl_trainer* t);
 const char* dtrl_trainer_last_error(const dtrl_trainer* t);
+/* Which cut of the step this trainer runs (host-only, no device work): *plan_ok = 1 when the net's dimensions are inside what the per-sample fused kernels are
+ * written for (else every pass runs layer by layer, whatever the mode), *lds_bytes = the LDS a fused workgroup needs (0 when a dimension check refused the net
+ * before the sum), *mode = DTRL_TRAINER_FUSED as read when the trainer was created (0 layer by layer, 1 fused forward = default, 2 - 4 the measured alternatives).
+ * Any of the three pointers may be NULL. */
+int dtrl_trainer_fused_info(const dtrl_trainer* t, int* plan_ok, int* lds_bytes, int* mode);
 /* every later call is queued on this HIP stream (hipStream_t as a pointer; NULL = the legacy default stream), so it is ordered with the caller's own work */
 int dtrl_trainer_set_stream(dtrl_trainer* t, void* hip_stream);
 int dtrl_trainer_sync(dtrl_trainer* t);
