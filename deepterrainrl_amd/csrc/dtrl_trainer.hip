@@ -155,6 +155,55 @@ __global__ void tr_foreach_kernel(int64_t n, F f)
 	for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x) f(i);
 }
 
+// ---- the solver's apply (dtrl_trainer_ops.h: solver_rule): ONE launch per update. Thread v owns elements [4 v, 4 v + 4): one 128-bit load / store per array (w, g,
+// history, second history where the type keeps one, the two multiplier arrays); the n % 4 elements behind the last whole group go to the first threads of block 0.
+// VEC = false (a gradient buffer of the caller's that is not 16-byte aligned): element by element. The step record is read through its pointer.
+template <int TYPE, bool VEC>
+__global__ void __launch_bounds__(256) tr_solver_apply_kernel(SolverArgs a, int64_t n)
+{
+	const StepRec r = *a.rec;
+	if (!r.active) return;
+	constexpr bool kH2 = TYPE == kSolverAdaDelta || TYPE == kSolverAdam;
+	const int64_t tid = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x, stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+	const int64_t n4 = VEC ? n / 4 : 0;
+	if (VEC) {
+		float4* w4 = reinterpret_cast<float4*>(a.w); float4* h4 = reinterpret_cast<float4*>(a.h); float4* s4 = reinterpret_cast<float4*>(a.h2);
+		const float4* g4 = reinterpret_cast<const float4*>(a.g); const float4* rm4 = reinterpret_cast<const float4*>(a.rate_mult); const float4* dm4 = reinterpret_cast<const float4*>(a.decay_mult);
+		for (int64_t v = tid; v < n4; v += stride) {
+			float4 w = w4[v], h = h4[v], s = kH2 ? s4[v] : make_float4(0, 0, 0, 0);
+			const float4 g = g4[v], rm = rm4[v], dm = dm4[v];
+			solver_rule<TYPE>(w.x, h.x, s.x, g.x, rm.x, dm.x, r, a); solver_rule<TYPE>(w.y, h.y, s.y, g.y, rm.y, dm.y, r, a);
+			solver_rule<TYPE>(w.z, h.z, s.z, g.z, rm.z, dm.z, r, a); solver_rule<TYPE>(w.w, h.w, s.w, g.w, rm.w, dm.w, r, a);
+			w4[v] = w; h4[v] = h; if (kH2) s4[v] = s;
+		}
+	}
+	for (int64_t i = 4 * n4 + tid; i < n; i += stride) {      // scalar tail (VEC: at most three elements)
+		float h2 = kH2 ? a.h2[i] : 0.0f;
+		solver_rule<TYPE>(a.w[i], a.h[i], h2, a.g[i], a.rate_mult[i], a.decay_mult[i], r, a);
+		if (kH2) a.h2[i] = h2;
+	}
+}
+// the clip's sum of squares over the flat gradient, no atomics: block b sums elements [b chunk, (b + 1) chunk) -- per thread in stride order, per wavefront by
+// shuffles, the four wavefronts in index order -- into parts[b]; solver_prep folds parts[0 .. blocks) in index order. Same launch shape, same bits, every run.
+template <bool VEC>
+__global__ void __launch_bounds__(256) tr_sumsq_kernel(const float* __restrict__ g, int64_t n, int64_t chunk, float* __restrict__ parts)
+{
+	__shared__ float wsum[4];
+	const int t = static_cast<int>(threadIdx.x);
+	const int64_t lo = static_cast<int64_t>(blockIdx.x) * chunk, hi = lo + chunk < n ? lo + chunk : n;    // chunk is a multiple of 4
+	float s = 0;
+	if (VEC) {
+		const float4* g4 = reinterpret_cast<const float4*>(g);
+		const int64_t v_hi = hi / 4;
+		for (int64_t v = lo / 4 + t; v < v_hi; v += 256) { const float4 x = g4[v]; s += x.x * x.x; s += x.y * x.y; s += x.z * x.z; s += x.w * x.w; }
+		for (int64_t i = 4 * v_hi + t; i < hi; i += 256) s += g[i] * g[i];
+	} else for (int64_t i = lo + t; i < hi; i += 256) s += g[i] * g[i];
+	for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+	if ((t & 63) == 0) wsum[t >> 6] = s;
+	__syncthreads();
+	if (t == 0) parts[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
 struct HipTrainerBE {
 	int device_id = -1;
 	hipStream_t stream = nullptr;
@@ -345,6 +394,36 @@ struct HipTrainerBE {
 		hipLaunchKernelGGL(tr_fused_grad_kernel, dim3(conv_blocks + fc_blocks), dim3(256), 0, stream, d, wk, conv_blocks, a);
 		chk(hipGetLastError(), "fused backward launch");
 		return true;
+	}
+	// ---- the solver's dedicated kernels (TrainerCore::SolverApply takes these instead of the element-wise functors) ----
+	static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+	int solver_sumsq(const float* g, int64_t n, float* parts)
+	{
+		// at least 4096 elements per block, at most kClipParts blocks
+		int64_t chunk = (n + kClipParts - 1) / kClipParts; chunk = std::max<int64_t>(4096, (chunk + 3) / 4 * 4);
+		const int blocks = static_cast<int>((n + chunk - 1) / chunk);
+		if (aligned16(g)) hipLaunchKernelGGL(tr_sumsq_kernel<true>, dim3(blocks), dim3(256), 0, stream, g, n, chunk, parts);
+		else hipLaunchKernelGGL(tr_sumsq_kernel<false>, dim3(blocks), dim3(256), 0, stream, g, n, chunk, parts);
+		chk(hipGetLastError(), "sum of squares launch");
+		return blocks;
+	}
+	template <int TYPE> void launch_apply(const SolverArgs& a, int64_t n)
+	{
+		const bool vec = aligned16(a.w) && aligned16(a.h) && aligned16(a.h2) && aligned16(a.g) && aligned16(a.rate_mult) && aligned16(a.decay_mult);
+		const int64_t items = vec ? std::max<int64_t>(n / 4, 4) : n;
+		const int blocks = static_cast<int>(std::min<int64_t>((items + 255) / 256, 2048));
+		if (vec) hipLaunchKernelGGL((tr_solver_apply_kernel<TYPE, true>), dim3(blocks), dim3(256), 0, stream, a, n);
+		else hipLaunchKernelGGL((tr_solver_apply_kernel<TYPE, false>), dim3(blocks), dim3(256), 0, stream, a, n);
+	}
+	void solver_apply(int type, const SolverArgs& a, int64_t n)
+	{
+		if (n <= 0) return;
+		switch (type) {
+		case kSolverSgd: launch_apply<kSolverSgd>(a, n); break; case kSolverNesterov: launch_apply<kSolverNesterov>(a, n); break;
+		case kSolverAdaGrad: launch_apply<kSolverAdaGrad>(a, n); break; case kSolverRmsProp: launch_apply<kSolverRmsProp>(a, n); break;
+		case kSolverAdaDelta: launch_apply<kSolverAdaDelta>(a, n); break; default: launch_apply<kSolverAdam>(a, n); break;
+		}
+		chk(hipGetLastError(), "solver apply launch");
 	}
 	template <class F>
 	void for_each(int64_t n, const F& f)

@@ -86,7 +86,8 @@ int dtrl_trainer_sync(dtrl_trainer* t) { TR_GUARD((t->core->be.sync(), t->core->
 int64_t dtrl_trainer_num_params(const dtrl_trainer* t) { return t ? t->core->cfg.dims.num_params : 0; }
 static float* tr_param_ptr(dtrl_trainer* t, int which)
 {
-	switch (which) { case 0: return t->core->w_cur; case 1: return t->core->w_tgt; case 2: return t->core->hist; case 3: return t->core->rate_mult; case 4: return t->core->decay_mult; }
+	switch (which) { case 0: return t->core->w_cur; case 1: return t->core->w_tgt; case 2: return t->core->hist; case 3: return t->core->rate_mult; case 4: return t->core->decay_mult;
+		case 5: return dtrl_tr::solver_needs_h2(t->core->solver.type) ? t->core->hist2 : nullptr; }
 	return nullptr;
 }
 int dtrl_trainer_set_params(dtrl_trainer* t, int which, const float* host, int64_t n)
@@ -133,6 +134,33 @@ int dtrl_trainer_td_filter(dtrl_trainer* t, int n) { TR_GUARD(t->core->TdFilter(
 float* dtrl_trainer_td(dtrl_trainer* t) { return t ? t->core->td_host : nullptr; }
 int dtrl_trainer_action_step(dtrl_trainer* t) { TR_GUARD(t->core->ActionStep()) }
 // ---- entry points for a C++ host that has nothing but the reference's files and host arrays (include/BatchNeuralNet.h) ----
+// ---- the six solver types (cNNSolver::BuildSolver, learning/NNSolver.cpp:9-35) ----
+static dtrl_tr::SolverCfg tr_solver_cfg(const dtrl_solver_desc& s)
+{
+	dtrl_tr::SolverCfg c;
+	c.type = s.type; c.policy = s.lr_policy; c.base_lr = s.base_lr; c.momentum = s.momentum; c.momentum2 = s.momentum2; c.rms_decay = s.rms_decay; c.delta = s.delta;
+	c.weight_decay = s.weight_decay; c.gamma = s.gamma; c.power = s.power; c.clip = s.clip_gradients; c.stepsize = s.stepsize;
+	return c;
+}
+int dtrl_trainer_set_solver(dtrl_trainer* t, const dtrl_solver_desc* s)
+try {
+	if (!t || !s) return 1;
+	std::string why;
+	if (!t->core->SetSolver(tr_solver_cfg(*s), why)) { t->err = why; return t->core->be.ok() ? 1 : 4; }
+	return 0;
+} catch (const std::exception& e) { t->err = e.what(); return 5; } catch (...) { t->err = "unknown exception"; return 5; }
+int dtrl_trainer_get_solver(dtrl_trainer* t, dtrl_solver_desc* s, int64_t* iter)
+try {
+	if (!t) return 1;
+	const dtrl_tr::SolverCfg& c = t->core->solver;
+	if (s) { s->type = c.type; s->lr_policy = c.policy; s->base_lr = c.base_lr; s->momentum = c.momentum; s->momentum2 = c.momentum2; s->rms_decay = c.rms_decay; s->delta = c.delta;
+		s->weight_decay = c.weight_decay; s->gamma = c.gamma; s->power = c.power; s->clip_gradients = c.clip; s->stepsize = c.stepsize; }
+	const int64_t it = t->core->GetIter();
+	if (iter) *iter = it;
+	if (!t->core->be.ok()) { t->err = t->core->be.error(); return 4; }
+	return 0;
+} catch (...) { return 5; }
+int dtrl_trainer_set_solver_iter(dtrl_trainer* t, int64_t iter) { TR_GUARD(iter >= 0 && (t->core->SetIter(iter), t->core->be.ok())) }
 int dtrl_trainer_create_from_files(const char* net_file, const char* solver_file, const char* data_root, float discount, int freeze_target, int device_id, dtrl_trainer** out)
 try {
 	if (!net_file || !out) return 1;
@@ -147,6 +175,10 @@ try {
 	t->core->be.h2d(t->core->decay_mult, f.decay_mult.data(), sizeof(float) * f.decay_mult.size());
 	t->core->be.sync();
 	if (!t->core->be.ok()) { g_tr_create_error = t->core->be.error(); dtrl_trainer_destroy(t); *out = nullptr; return 4; }
+	if (f.has_solver) {       // the solver file's type and policy (a file that names none: SGD / "fixed", which is what the description alone gives)
+		const int rs = dtrl_trainer_set_solver(t, &f.solver);
+		if (rs != 0) { g_tr_create_error = f.solver_file + ": " + t->err; dtrl_trainer_destroy(t); *out = nullptr; return rs; }
+	}
 	return 0;
 } catch (const std::exception& e) { g_tr_create_error = e.what(); return 5; } catch (...) { g_tr_create_error = "unknown exception"; return 5; }
 int dtrl_trainer_dims(const dtrl_trainer* t, int* in_size, int* out_size, int* batch, int* max_eval)
@@ -170,9 +202,9 @@ try {
 	fill(d.wo_terr, static_cast<int64_t>(d.fc_terr) * d.n_flat, d.n_flat);
 	fill(d.wo_ip0, static_cast<int64_t>(d.fc_trunk) * (d.fc_terr + d.n_char), d.fc_terr + d.n_char);
 	for (int f = 0; f < d.n_heads; ++f) { fill(d.wo_h0[f], static_cast<int64_t>(d.fc_head) * d.fc_trunk, d.fc_trunk); fill(d.wo_h1[f], static_cast<int64_t>(d.head_out[f]) * d.fc_head, d.fc_head); }
-	std::vector<float> zero(w.size(), 0.0f);
 	t->core->be.sync();
-	t->core->be.h2d(t->core->w_cur, w.data(), sizeof(float) * w.size()); t->core->be.h2d(t->core->w_tgt, w.data(), sizeof(float) * w.size()); t->core->be.h2d(t->core->hist, zero.data(), sizeof(float) * w.size());
+	t->core->be.h2d(t->core->w_cur, w.data(), sizeof(float) * w.size()); t->core->be.h2d(t->core->w_tgt, w.data(), sizeof(float) * w.size());
+	t->core->ClearSolverState();      // both histories and the counter
 	t->core->be.sync();
 	if (!t->core->be.ok()) { t->err = t->core->be.error(); return 4; }
 	return 0;

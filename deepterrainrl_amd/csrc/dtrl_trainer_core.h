@@ -12,6 +12,8 @@
 #include "dtrl_trainer_fused.h"
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace dtrl_tr {
@@ -148,6 +150,17 @@ struct FSgdScaled { float* w; float* hist; const float* g; const float* rate_mul
 		hist[i] = hv; w[i] = w[i] - hv;
 	} };
 struct FZero { float* p; TR_HD void operator()(int64_t i) const { p[i] = 0.0f; } };
+// ---- the six solver types (dtrl_trainer_ops.h: solver_prep / solver_rule). These functors are what every backend can run; a backend with kernels of its own for the
+// sum of squares and the apply (solver_sumsq / solver_apply: the HIP backend) is used instead, detected at compile time (has_solver_kernels) ----
+// index space [0, 1): the sum of squares of the flat gradient in index order (one running sum over every parameter: kept in double, rounded once)
+struct FSumSq { const float* g; int64_t n; float* parts;
+	TR_HD void operator()(int64_t) const { double s = 0; for (int64_t i = 0; i < n; ++i) s += static_cast<double>(g[i]) * g[i]; parts[0] = static_cast<float>(s); } };
+// index space [0, 1): the step record of this update
+struct FSolverPrep { SolverCfg cfg; StepRec* rec; const float* g; int64_t num_params; float batch; const float* parts; int n_parts; float* count_out;
+	TR_HD void operator()(int64_t) const { solver_prep(cfg, *rec, g, num_params, batch, parts, n_parts, count_out); } };
+template <int TYPE> struct FSolverApply { SolverArgs a; TR_HD void operator()(int64_t i) const { solver_elem<TYPE>(a, i); } };
+template <class BE, class = void> struct has_solver_kernels : std::false_type {};
+template <class BE> struct has_solver_kernels<BE, std::void_t<decltype(std::declval<BE&>().solver_apply(0, std::declval<const SolverArgs&>(), int64_t(0)))>> : std::true_type {};
 
 // staged rows -> replay slots: element i = (row i / W, column i % W) of the page-locked staging area goes to slot (head + row) % mem_size; the flag word with column 0
 struct FAddStaged { const float* src; const int64_t* src_flags; float* mem; int64_t* flags; int W; int64_t head, mem_size;
@@ -170,7 +183,7 @@ struct TrainerConfig {
 template <class BE>
 class TrainerCore {
 public:
-	explicit TrainerCore(const TrainerConfig& c) : cfg(c) {}
+	explicit TrainerCore(const TrainerConfig& c) : cfg(c) { solver.base_lr = c.base_lr; solver.momentum = c.momentum; solver.weight_decay = c.weight_decay; }
 	~TrainerCore()
 	{
 		for (void* p : dev_) be.free_dev(p);
@@ -232,6 +245,7 @@ public:
 	void BackwardAndUpdate()
 	{
 		const NetDims& d = cfg.dims;
+		if (!LegacySgd()) { BackwardOnly(); SolverApply(nullptr); return; }    // every setting but SGD / "fixed" / no clip: the gradient alone, then the solver's apply
 		if (be.fused_backward(d_dims, d_train, d, cfg.batch, SgdArgs{w_cur, hist, grad, rate_mult, decay_mult, cfg.base_lr, cfg.momentum, cfg.weight_decay, 1, static_cast<float>(cfg.batch)})) return;
 		Backward();
 		be.for_each(d.num_params, FSgdConv{d_dims, d_train, d.wo_terr, w_cur, hist, grad, rate_mult, decay_mult, cfg.base_lr, cfg.momentum, cfg.weight_decay});
@@ -292,6 +306,7 @@ public:
 	{
 		const NetDims& d = cfg.dims;
 		const int n = cfg.batch;
+		CountStep();
 		be.for_each(static_cast<int64_t>(n) * d.S, FNormIn{d.S, norm(), X, train.xin});
 		Forward(d_train, n);
 		be.label_loss(n * d.out_size, FLabelDout{d.out_size, norm(), 0, Y, nullptr, 0, d.S, nullptr, nullptr, cfg.n_frags, cfg.frag_size, n, train.out, train.dout, sq}, sq, 0.5f / static_cast<float>(n), loss_host);
@@ -319,13 +334,14 @@ public:
 	}
 
 	// idx_host[0 .. batch) = the critic minibatch's slots. loss -> loss_host[0]
-	bool CriticStep() { if (!mem_ || cfg.n_frags <= 0) return false; be.run_graph(0, [this] { CriticStepBody(); }); return be.ok(); }
+	bool CriticStep() { if (!mem_ || cfg.n_frags <= 0) return false; CountStep(); be.run_graph(0, [this] { CriticStepBody(); }); return be.ok(); }
 	// frozen target only (cMACETrainer::EnableTargetNet()): the critic step and the actor candidates' test in ONE pass -- Q_target is needed on s' of the critic
 	// batch and on s, s' of the candidates, none of which depends on the critic update, so the target net runs once over [s'_critic | s_cand | s'_cand].
 	// idx_host[batch .. 2 batch) must hold `batch` valid slots (pad a shorter candidate list by repeating a slot; the caller ignores the padded answers).
 	bool CriticStepAndFilter()
 	{
 		if (!mem_ || cfg.n_frags <= 0 || !cfg_target_frozen || cfg.max_eval < 3 * cfg.batch) return false;
+		CountStep();
 		be.run_graph(3, [this] {
 			const NetDims& d = cfg.dims;
 			const int n = cfg.batch, S = d.S, A = 1 + cfg.frag_size;
@@ -373,7 +389,7 @@ public:
 		return be.ok();
 	}
 	// idx_host[max_eval .. max_eval + batch) = the actor batch's slots (a second window, so that a filter's candidates stay intact). loss -> loss_host[1]
-	bool ActorStep() { if (!mem_ || cfg.n_frags <= 0) return false; be.run_graph(2, [this] { ActorStepBody(); }); return be.ok(); }
+	bool ActorStep() { if (!mem_ || cfg.n_frags <= 0) return false; CountStep(); be.run_graph(2, [this] { ActorStepBody(); }); return be.ok(); }
 	void ActorStepBody()
 	{
 		const NetDims& d = cfg.dims;
@@ -393,6 +409,7 @@ public:
 	bool ValueStep(int kind)
 	{
 		if (!mem_ || cfg.n_frags != 0 || kind < 0 || kind > 1 || ActionWidth() < 1 || (kind == 0 && ActionWidth() != cfg.dims.out_size) || (kind == 1 && cfg.dims.out_size != 1)) return false;
+		CountStep();
 		be.run_graph(4 + kind, [this, kind] {
 			const NetDims& d = cfg.dims;
 			const int n = cfg.batch, S = d.S, A = ActionWidth();
@@ -426,6 +443,7 @@ public:
 	bool ActionStep()
 	{
 		if (!mem_ || cfg.n_frags != 0 || ActionWidth() != cfg.dims.out_size) return false;
+		CountStep();
 		be.run_graph(6, [this] {
 			const NetDims& d = cfg.dims;
 			const int n = cfg.batch, S = d.S;
@@ -491,9 +509,93 @@ public:
 	{
 		if (slot < 2 || slot > 3) return false;
 		const NetDims& d = cfg.dims;
+		if (!LegacySgd()) { SolverApply(loss_host + slot); return be.ok(); }
+		// (the launch below is the one the SGD default always queued; whether it counted -- rows behind the gradient -- is read from the page-locked slot afterwards)
+		if (pending_[slot - 2]) { be.sync(); ResolvePending(); }
+		pending_[slot - 2] = true;
 		be.for_each(d.num_params, FSgdScaled{w_cur, hist, grad, rate_mult, decay_mult, cfg.base_lr, cfg.momentum, cfg.weight_decay, d.num_params, static_cast<float>(cfg.batch), loss_host + slot});
 		return be.ok();
 	}
+
+	// ---- solver (cNNSolver::BuildSolver, learning/NNSolver.cpp:9-35) ----
+	// SGD at a fixed rate without a clip is the rule the step kernels carry themselves (sgd_elem behind FSgd / FSgdConv / FSgdScaled / tr_fused_grad_kernel): nothing
+	// of it depends on the iteration, and it queues what it always queued. Its counter is kept on the host.
+	void CountStep() { if (LegacySgd()) ++iter_host_; }      // (a recorded sequence is not re-entered on replay: counted where the step is queued)
+	bool LegacySgd() const { return solver.type == kSolverSgd && solver.policy == kLrFixed && solver.clip < 0; }
+	// all-or-nothing: `why` names the refused field
+	static bool CheckSolver(const SolverCfg& s, std::string& why)
+	{
+		auto unit = [](float v) { return v >= 0.0f && v < 1.0f; };
+		if (s.type < 0 || s.type >= kSolverTypes) { why = "solver: unknown type " + std::to_string(s.type); return false; }
+		if (s.policy < 0 || s.policy >= kLrPolicies) { why = "solver: unknown lr_policy " + std::to_string(s.policy); return false; }
+		if (!unit(s.momentum)) { why = "solver: momentum " + std::to_string(s.momentum) + " outside [0, 1)"; return false; }
+		if (!unit(s.momentum2)) { why = "solver: momentum2 " + std::to_string(s.momentum2) + " outside [0, 1)"; return false; }
+		if (!unit(s.rms_decay)) { why = "solver: rms_decay " + std::to_string(s.rms_decay) + " outside [0, 1)"; return false; }
+		if (s.type >= kSolverAdaGrad && !(s.delta > 0.0f)) { why = "solver: delta must be positive for this type"; return false; }
+		if ((s.type == kSolverAdaGrad || s.type == kSolverRmsProp) && s.momentum != 0.0f) { why = "solver: momentum must be 0 for AdaGrad / RMSProp"; return false; }
+		if (s.policy == kLrStep && s.stepsize < 1) { why = "solver: stepsize " + std::to_string(static_cast<long long>(s.stepsize)) + " < 1 under lr_policy \"step\""; return false; }
+		return true;
+	}
+	void ClearSolverState()
+	{
+		const size_t P = static_cast<size_t>(cfg.dims.num_params);
+		std::vector<float> zero(P, 0.0f);
+		be.h2d(hist, zero.data(), sizeof(float) * P);
+		if (hist2) be.h2d(hist2, zero.data(), sizeof(float) * P);
+		SetIter(0);
+	}
+	bool SetSolver(const SolverCfg& s, std::string& why)
+	{
+		if (!CheckSolver(s, why)) return false;
+		be.sync();
+		if (!rec_) { rec_ = static_cast<StepRec*>(Dev(sizeof(StepRec))); clip_parts_ = F(kClipParts); }
+		if (solver_needs_h2(s.type) && !hist2) hist2 = F(static_cast<size_t>(cfg.dims.num_params));
+		if (!be.ok()) { why = be.error(); return false; }
+		solver = s;
+		cfg.base_lr = s.base_lr; cfg.momentum = s.momentum; cfg.weight_decay = s.weight_decay;
+		ClearSolverState();
+		be.drop_graphs();       // the recorded launches carry the rule
+		be.sync();
+		return be.ok();
+	}
+	void ResolvePending() { for (int k = 0; k < 2; ++k) if (pending_[k]) { if (loss_host[2 + k] > 0) ++iter_host_; pending_[k] = false; } }
+	int64_t GetIter()
+	{
+		be.sync();
+		if (LegacySgd() || !rec_) { ResolvePending(); return iter_host_; }
+		StepRec r{}; be.d2h(&r, rec_, sizeof(r)); return r.iter;
+	}
+	void SetIter(int64_t it)
+	{
+		be.sync();
+		pending_[0] = pending_[1] = false; iter_host_ = it;
+		if (rec_) { StepRec r{}; r.iter = it; r.rate = solver.base_lr; r.corr = 1.0f; r.gscale = 1.0f; be.h2d(rec_, &r, sizeof(r)); }
+	}
+	// prep + apply on the gradient buffer (rows behind it in grad[num_params]); recorded with the step it belongs to
+	void SolverApply(float* count_out)
+	{
+		const NetDims& d = cfg.dims;
+		const SolverArgs a{w_cur, hist, hist2, grad, rate_mult, decay_mult, rec_, solver.momentum, solver.momentum2, solver.rms_decay, solver.delta, solver.weight_decay};
+		int n_parts = 0;        // (a function of the parameter count alone)
+		if (solver.clip >= 0) {
+			if constexpr (has_solver_kernels<BE>::value) n_parts = be.solver_sumsq(grad, d.num_params, clip_parts_);
+			else { be.for_each(1, FSumSq{grad, d.num_params, clip_parts_}); n_parts = 1; }
+		}
+		be.for_each(1, FSolverPrep{solver, rec_, grad, d.num_params, static_cast<float>(cfg.batch), clip_parts_, n_parts, count_out});
+		if constexpr (has_solver_kernels<BE>::value) be.solver_apply(solver.type, a, d.num_params);
+		else switch (solver.type) {
+			case kSolverSgd: be.for_each(d.num_params, FSolverApply<kSolverSgd>{a}); break;
+			case kSolverNesterov: be.for_each(d.num_params, FSolverApply<kSolverNesterov>{a}); break;
+			case kSolverAdaGrad: be.for_each(d.num_params, FSolverApply<kSolverAdaGrad>{a}); break;
+			case kSolverRmsProp: be.for_each(d.num_params, FSolverApply<kSolverRmsProp>{a}); break;
+			case kSolverAdaDelta: be.for_each(d.num_params, FSolverApply<kSolverAdaDelta>{a}); break;
+			default: be.for_each(d.num_params, FSolverApply<kSolverAdam>{a}); break;
+		}
+	}
+	SolverCfg solver;
+	float* hist2 = nullptr;               // second history: AdaDelta, Adam only
+	StepRec* rec_ = nullptr; float* clip_parts_ = nullptr;
+	int64_t iter_host_ = 0; bool pending_[2] = {false, false};
 
 	TrainerConfig cfg;
 	bool cfg_target_frozen = false;   // cMACETrainer::EnableTargetNet(): freeze_target_iters > 0, else the "target" is the current net

@@ -1,11 +1,14 @@
 // dtrl_trainer_files.h -- host side: a trainer description straight from the reference's own files, so that a C++ caller (include/BatchNeuralNet.h) needs
 // nothing but the two paths cNeuralNet::LoadNet / LoadSolver get (learning/NeuralNet.cpp:62-79, 110-136; learning/NNSolver.cpp): the net prototxt (deploy
 // or train form) gives the topology of the family (slice -> 3 x Convolution -> terr_ip0 -> trunk InnerProduct -> heads), the train prototxt the MemoryData
-// batch_size and the per-blob lr_mult / decay_mult (`param { }` blocks, Caffe defaults 1 / 1), the solver prototxt base_lr / momentum / weight_decay /
-// lr_policy and -- in the reference's own files -- the path of the train net (`net: "..."`).
+// batch_size and the per-blob lr_mult / decay_mult (`param { }` blocks, Caffe defaults 1 / 1), the solver prototxt base_lr / momentum / weight_decay, the solver
+// type (`solver_type: ADAM`, the enum of the reference's Caffe generation, or `type: "Adam"`, the later spelling; neither: SGD), lr_policy (fixed / step / exp / inv)
+// with gamma / power / stepsize, momentum2 / rms_decay / delta / clip_gradients, and -- in the reference's own files -- the path of the train net (`net: "..."`).
 // Plain text scanning (no protobuf here either): a layer's fields are looked up inside its `layer { ... }` block at any nesting depth, which covers both
 // the reference's files (convolution_param { num_output: .. kernel_w: .. }) and the flattened digests under tests/golden/refdata.
 #pragma once
+#include <algorithm>
+#include <cctype>
 #include <fstream>
 #include <map>
 #include <regex>
@@ -21,6 +24,9 @@ struct TrainerFiles {
 	dtrl_trainer_desc desc{};
 	std::vector<float> lr_mult, decay_mult;   // per parameter element, Caffe blob order
 	std::string train_net;                    // the file the multipliers and the batch size came from ("" = none found: Caffe defaults, batch 32)
+	dtrl_solver_desc solver{};                // cNNSolver::BuildSolver's input (learning/NNSolver.cpp:9-35): type, policy and their numbers, Caffe's defaults where the file is silent
+	bool has_solver = false;                  // a solver file was read
+	std::string solver_file;
 };
 
 namespace files_detail {
@@ -87,7 +93,28 @@ inline bool ParseTrainerFiles(const std::string& net_file, const std::string& so
 		std::smatch m;
 		auto getf = [&](const char* key, float& dst) { if (std::regex_search(s, m, std::regex(std::string("(^|\\n)\\s*") + key + ":\\s*([-0-9.eE]+)"))) dst = std::stof(m[2]); };
 		getf("base_lr", d.base_lr); getf("momentum", d.momentum); getf("weight_decay", d.weight_decay);
-		if (std::regex_search(s, m, std::regex("lr_policy:\\s*\"([^\"]+)\"")) && m[1] != "fixed") { err = solver_file + ": lr_policy \"" + std::string(m[1]) + "\" (the native step implements \"fixed\", what the shipped solvers use)"; return false; }
+		dtrl_solver_desc& sv = out.solver;
+		sv = dtrl_solver_desc{}; sv.momentum2 = 0.999f; sv.rms_decay = 0.99f; sv.delta = 1e-8f; sv.gamma = 0.1f; sv.power = 0.75f; sv.clip_gradients = -1.0f; sv.stepsize = 0;
+		getf("momentum2", sv.momentum2); getf("rms_decay", sv.rms_decay); getf("delta", sv.delta); getf("gamma", sv.gamma); getf("power", sv.power); getf("clip_gradients", sv.clip_gradients);
+		sv.base_lr = d.base_lr; sv.momentum = d.momentum; sv.weight_decay = d.weight_decay;
+		if (std::regex_search(s, m, std::regex("(^|\\n)\\s*stepsize:\\s*(-?\\d+)"))) sv.stepsize = std::stoll(m[2]);      // (absent: 0, which \"step\" refuses)
+		auto lower = [](std::string v) { std::transform(v.begin(), v.end(), v.begin(), [](unsigned char ch) { return static_cast<char>(std::tolower(ch)); }); return v; };
+		std::string type_name;
+		if (std::regex_search(s, m, std::regex("(^|\\n)\\s*solver_type:\\s*\"?([A-Za-z_]+)\"?"))) type_name = m[2];
+		else if (std::regex_search(s, m, std::regex("(^|\\n)\\s*type:\\s*\"([^\"]*)\""))) type_name = m[2];
+		if (!type_name.empty()) {
+			static const char* const names[] = {"sgd", "nesterov", "adagrad", "rmsprop", "adadelta", "adam"};
+			sv.type = -1;
+			for (int k = 0; k < 6; ++k) if (lower(type_name) == names[k]) sv.type = k;
+			if (sv.type < 0) { err = solver_file + ": solver type \"" + type_name + "\" (the native step implements SGD, Nesterov, AdaGrad, RMSProp, AdaDelta, Adam)"; return false; }
+		}
+		if (std::regex_search(s, m, std::regex("lr_policy:\\s*\"([^\"]+)\""))) {
+			static const char* const pols[] = {"fixed", "step", "exp", "inv"};
+			sv.lr_policy = -1;
+			for (int k = 0; k < 4; ++k) if (m[1] == pols[k]) sv.lr_policy = k;
+			if (sv.lr_policy < 0) { err = solver_file + ": lr_policy \"" + std::string(m[1]) + "\" (the native step implements \"fixed\", \"step\", \"exp\" and \"inv\")"; return false; }
+		}
+		out.has_solver = true; out.solver_file = solver_file;
 		// the train net: the solver's `net:` entry, else <x>_solver -> <x>_train, else <net>_deploy -> <net>_train
 		std::vector<std::string> cand;
 		if (std::regex_search(s, m, std::regex("(^|\\n)\\s*net:\\s*\"([^\"]+)\""))) { cand.push_back(data_root.empty() ? std::string(m[2]) : data_root + "/" + std::string(m[2])); cand.push_back(m[2]); }

@@ -11,6 +11,7 @@
 // whole iteration captured as one HIP graph) and, expanded into plain loops by g++, in the CPU-side check build (tests/emul/, TESTS ONLY), so the index
 // arithmetic is verified against an independent restatement on a box without a GPU.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -234,6 +235,85 @@ TR_HD inline void sgd_elem(float* w, float* hist, const float* g, const float* r
 	const float diff = g[i] + weight_decay * decay_mult[i] * w[i];
 	const float hv = momentum * hist[i] + rate * rate_mult[i] * diff;
 	hist[i] = hv; w[i] = w[i] - hv;
+}
+
+// ---- Caffe's six solver types and its learning-rate policies (cNNSolver::BuildSolver, learning/NNSolver.cpp:9-35; include/dtrl_trainer.h: dtrl_solver_desc) ----
+enum SolverType : int { kSolverSgd, kSolverNesterov, kSolverAdaGrad, kSolverRmsProp, kSolverAdaDelta, kSolverAdam, kSolverTypes };
+enum LrPolicy : int { kLrFixed, kLrStep, kLrExp, kLrInv, kLrPolicies };
+struct SolverCfg {
+	int type = kSolverSgd, policy = kLrFixed;
+	float base_lr = 0.01f, momentum = 0.0f, momentum2 = 0.999f, rms_decay = 0.99f, delta = 1e-8f, weight_decay = 0.0f, gamma = 0.1f, power = 0.75f, clip = -1.0f;
+	int64_t stepsize = 1;
+};
+inline bool solver_needs_h2(int type) { return type == kSolverAdaDelta || type == kSolverAdam; }
+// The step record: what depends on the iteration lives in DEVICE memory, written by solver_prep in front of every apply and read by the apply through a pointer, so
+// that a recorded launch sequence replays with the values of ITS step (a by-value launch argument would keep those of the step that was recorded).
+struct StepRec {
+	int64_t iter;        // applied updates of this trainer (Caffe's iter_), before the step that is being prepared
+	float rate;          // the lr policy's rate of this step
+	float corr;          // Adam: sqrt(1 - momentum2^(t + 1)) / (1 - momentum^(t + 1))
+	float gscale;        // what the gradient buffer is multiplied by: batch / rows behind it, times clip / norm where the clip bites
+	int32_t active;      // 0: no rows behind the gradient -- nothing moves, the counter stays
+};
+constexpr int kClipParts = 256;   // upper bound of the partial sums of squares the clip folds in index order
+// one thread in front of the apply. g[num_params] = rows behind the (summed) gradient; parts[0 .. n_parts) = partial sums of squares over g (clip only).
+// The record's scalars are formed in double and rounded once (pow of a float base to the power of the counter loses digits that 1 - x then exposes).
+TR_HD inline void solver_prep(const SolverCfg& c, StepRec& r, const float* g, int64_t num_params, float batch, const float* parts, int n_parts, float* count_out)
+{
+	const float count = g[num_params];
+	if (count_out) *count_out = count;
+	if (!(count > 0)) { r.active = 0; return; }
+	const int64_t t = r.iter;
+	const double td = static_cast<double>(t);
+	double rate = c.base_lr;
+	if (c.policy == kLrStep) rate *= pow(static_cast<double>(c.gamma), static_cast<double>(t / c.stepsize));
+	else if (c.policy == kLrExp) rate *= pow(static_cast<double>(c.gamma), td);
+	else if (c.policy == kLrInv) rate *= pow(1.0 + static_cast<double>(c.gamma) * td, -static_cast<double>(c.power));
+	r.rate = static_cast<float>(rate);
+	r.corr = c.type == kSolverAdam ? static_cast<float>(sqrt(1.0 - pow(static_cast<double>(c.momentum2), td + 1.0)) / (1.0 - pow(static_cast<double>(c.momentum), td + 1.0))) : 1.0f;
+	double gs = static_cast<double>(batch) / static_cast<double>(count);
+	if (c.clip >= 0) {
+		float ss = 0;
+		for (int k = 0; k < n_parts; ++k) ss += parts[k];   // index order: the same bits every run
+		const double n = sqrt(static_cast<double>(ss)) * gs;
+		if (n > static_cast<double>(c.clip)) gs *= static_cast<double>(c.clip) / n;
+	}
+	r.gscale = static_cast<float>(gs);
+	r.active = 1;
+	r.iter = t + 1;
+}
+struct SolverArgs { float* w; float* h; float* h2; const float* g; const float* rate_mult; const float* decay_mult; const StepRec* rec; float momentum, momentum2, rms_decay, delta, weight_decay; };
+// one parameter element under rule TYPE: Regularize (L2) -> the type's ComputeUpdateValue -> Net::Update. g = the element of the gradient buffer, rm / dm its multipliers
+template <int TYPE>
+TR_HD inline void solver_rule(float& w, float& h, float& h2, float g, float rm, float dm, const StepRec& r, const SolverArgs& a)
+{
+	const float local = r.rate * rm;
+	const float d = g * r.gscale + a.weight_decay * dm * w;
+	float u;
+	if (TYPE == kSolverSgd) { h = a.momentum * h + local * d; u = h; }
+	else if (TYPE == kSolverNesterov) { const float hp = h; h = a.momentum * h + local * d; u = (1.0f + a.momentum) * h - a.momentum * hp; }
+	else if (TYPE == kSolverAdaGrad) { h += d * d; u = local * d / (sqrtf(h) + a.delta); }
+	else if (TYPE == kSolverRmsProp) { h = a.rms_decay * h + (1.0f - a.rms_decay) * (d * d); u = local * d / (sqrtf(h) + a.delta); }
+	else if (TYPE == kSolverAdaDelta) {
+		h = a.momentum * h + (1.0f - a.momentum) * (d * d);
+		const float e = d * sqrtf((h2 + a.delta) / (h + a.delta));
+		h2 = a.momentum * h2 + (1.0f - a.momentum) * (e * e);
+		u = local * e;
+	} else {
+		h = a.momentum * h + (1.0f - a.momentum) * d;
+		h2 = a.momentum2 * h2 + (1.0f - a.momentum2) * (d * d);
+		u = local * r.corr * h / (sqrtf(h2) + a.delta);
+	}
+	w -= u;
+}
+template <int TYPE>
+TR_HD inline void solver_elem(const SolverArgs& a, int64_t i)
+{
+	const StepRec& r = *a.rec;
+	if (!r.active) return;
+	float h2 = (TYPE == kSolverAdaDelta || TYPE == kSolverAdam) ? a.h2[i] : 0.0f;
+	solver_rule<TYPE>(a.w[i], a.h[i], h2, a.g[i], a.rate_mult[i], a.decay_mult[i], r, a);
+	if (TYPE == kSolverAdaDelta || TYPE == kSolverAdam) a.h2[i] = h2;
 }
 
 // ---- the trainer's own arithmetic around the net (cMACETrainer), per row ----

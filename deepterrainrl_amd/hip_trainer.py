@@ -31,6 +31,7 @@ TRAINER_ABI_SYMBOLS = [
     "dtrl_trainer_create_from_files", "dtrl_trainer_dims", "dtrl_trainer_init_xavier", "dtrl_trainer_eval_host", "dtrl_trainer_step_host", "dtrl_trainer_get_normalizers",
     "dtrl_trainer_copy_model", "dtrl_trainer_bind_grad", "dtrl_trainer_grad_device", "dtrl_trainer_grad_step", "dtrl_trainer_critic_grad", "dtrl_trainer_actor_grad", "dtrl_trainer_zero_grad", "dtrl_trainer_apply_grad",
     "dtrl_trainer_value_step", "dtrl_trainer_td_filter", "dtrl_trainer_td", "dtrl_trainer_action_step", "dtrl_trainer_fused_info",
+    "dtrl_trainer_set_solver", "dtrl_trainer_get_solver", "dtrl_trainer_set_solver_iter",
 ]
 
 
@@ -39,6 +40,36 @@ class TrainerDesc(C.Structure):
                 ("fc_terr", C.c_int32), ("fc_trunk", C.c_int32), ("fc_head", C.c_int32), ("n_heads", C.c_int32), ("head_out", C.c_int32 * 8),
                 ("n_frags", C.c_int32), ("frag_size", C.c_int32), ("batch", C.c_int32), ("max_eval", C.c_int32),
                 ("base_lr", C.c_float), ("momentum", C.c_float), ("weight_decay", C.c_float), ("discount", C.c_float), ("freeze_target", C.c_int32)]
+
+
+class SolverDesc(C.Structure):
+    """dtrl_solver_desc (include/dtrl_trainer.h): cNNSolver::BuildSolver's input, learning/NNSolver.cpp:9-35"""
+    _fields_ = [("type", C.c_int32), ("lr_policy", C.c_int32)] + [(k, C.c_float) for k in (
+        "base_lr", "momentum", "momentum2", "rms_decay", "delta", "weight_decay", "gamma", "power", "clip_gradients")] + [("stepsize", C.c_int64)]
+
+
+SOLVER_FLOATS = ("base_lr", "momentum", "momentum2", "rms_decay", "delta", "weight_decay", "gamma", "power", "clip_gradients")
+
+
+def solver_desc(solver):
+    """dtrl_solver_desc from trainer.parse_solver's dict (or one of the same keys); type / lr_policy as names or numbers"""
+    from .trainer import SOLVER_TYPES, LR_POLICIES
+    s = SolverDesc()
+    ty, pol = solver.get("type", "sgd"), solver.get("lr_policy", "fixed")
+    if isinstance(ty, str):
+        if ty.lower() not in SOLVER_TYPES:
+            raise DtrlError('solver type "%s"' % ty)
+        ty = SOLVER_TYPES.index(ty.lower())
+    if isinstance(pol, str):
+        if pol not in LR_POLICIES:
+            raise DtrlError('lr_policy "%s" (the native step implements "fixed", "step", "exp" and "inv")' % pol)
+        pol = LR_POLICIES.index(pol)
+    s.type, s.lr_policy = int(ty), int(pol)
+    dflt = dict(base_lr=0.01, momentum=0.0, momentum2=0.999, rms_decay=0.99, delta=1e-8, weight_decay=0.0, gamma=0.1, power=0.75, clip_gradients=-1.0)
+    for k in SOLVER_FLOATS:
+        setattr(s, k, float(solver.get(k, dflt[k])))
+    s.stepsize = int(min(float(solver.get("stepsize", 0)), 2.0 ** 62))
+    return s
 
 
 def _bind(path):
@@ -86,6 +117,9 @@ def _bind(path):
     L.dtrl_trainer_init_xavier.argtypes = [vp, C.c_uint64]
     L.dtrl_trainer_eval_host.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     L.dtrl_trainer_step_host.argtypes = [vp, vp, vp, C.POINTER(C.c_double)]
+    L.dtrl_trainer_set_solver.argtypes = [vp, C.POINTER(SolverDesc)]
+    L.dtrl_trainer_get_solver.argtypes = [vp, C.POINTER(SolverDesc), C.POINTER(C.c_int64)]
+    L.dtrl_trainer_set_solver_iter.argtypes = [vp, C.c_int64]
     return L
 
 
@@ -222,6 +256,24 @@ class NativeTrainer:
     def td_filter(self, n): self._chk(self._lib.dtrl_trainer_td_filter(self._h, int(n)))
     def action_step(self): self._chk(self._lib.dtrl_trainer_action_step(self._h))
 
+    # Caffe's six solver types and lr policies (cNNSolver::BuildSolver, learning/NNSolver.cpp:9-35; include/dtrl_trainer.h: dtrl_solver_desc)
+    def set_solver(self, solver=None, **kw):
+        """solver: a SolverDesc, or a dict with trainer.parse_solver's keys (type / lr_policy as names or numbers; missing keys take Caffe's defaults), or keywords.
+        Clears both histories and the counter."""
+        s = solver if isinstance(solver, SolverDesc) else solver_desc(dict(solver or {}, **kw))
+        self._chk(self._lib.dtrl_trainer_set_solver(self._h, C.byref(s)))
+
+    def get_solver(self):
+        """(dict with parse_solver's keys -- type and lr_policy as names --, applied updates)"""
+        from .trainer import SOLVER_TYPES, LR_POLICIES
+        s, it = SolverDesc(), C.c_int64()
+        self._chk(self._lib.dtrl_trainer_get_solver(self._h, C.byref(s), C.byref(it)))
+        d = {k: float(getattr(s, k)) for k in SOLVER_FLOATS}
+        d.update(type=SOLVER_TYPES[s.type], lr_policy=LR_POLICIES[s.lr_policy], stepsize=int(s.stepsize))
+        return d, int(it.value)
+
+    def set_solver_iter(self, it): self._chk(self._lib.dtrl_trainer_set_solver_iter(self._h, int(it)))
+
 
 class _HipNetSide:
     """The network side of a trainer.py trainer on the native step (mixin in front of MACETrainer / QNetTrainer / CaclaTrainer): weights, solver history and
@@ -233,12 +285,12 @@ class _HipNetSide:
         kw["dtype"] = torch.float32
         self._trainer_lib = lib_path               # (CaclaTrainer.Reset, called by the base constructor, builds the actor's trainer with it)
         super().__init__(*a, **kw)
-        if self.solver["lr_policy"] != "fixed":
-            raise DtrlError("the native trainer step implements lr_policy \"fixed\" (what the shipped solver prototxts use)")
         cdesc = desc_from_net(self.desc, self.S, self.batch, 3 * self.batch, self.solver, self.discount, self.freeze_target_iters > 0)
         dev_id = self.device.index if self.device.type == "cuda" and self.device.index is not None else -1
         self.nt = NativeTrainer(cdesc, dev_id, lib_path)
         assert self.nt.num_params == self.net.num_params()
+        if not (self.solver["type"] == "sgd" and self.solver["lr_policy"] == "fixed" and self.solver["clip_gradients"] < 0):
+            self.nt.set_solver(self.solver)        # (SGD / "fixed" / no clip is what the description alone gives: nothing to hand over)
         # a stream of the trainer's own (its fixed launch sequences are recorded as HIP graphs, which the legacy default stream does not allow); ordered
         # against the framework's stream where the two meet: replay rows written by AddTuples, tensors handed to / taken from _eval and _solver_step
         self._stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None   # (a high-priority stream was measured: no gain beside the rollout)

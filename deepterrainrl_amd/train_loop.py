@@ -137,7 +137,7 @@ def setup_pushes(b, spec, greedy_envs=0):
 
 def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, device_id=-1, extra_args=None, seed=0, log_every=0, out_scale_file=None,
           trainer_device=None, overlap=False, frames_per_drain=1, scenario_cls=BatchScenario, trainer="torch", trainer_lib=None, poll=False,
-          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None, pushes=None):
+          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None, pushes=None, solver=None):
     """extra_args override / extend the arg file (both for the engine and for the -trainer_* keys read here).
     overlap=True trains on frame f's tuples while the GPU already rolls out frame f+1 (dtrl_step_begin / dtrl_step_end): the policy
     each frame runs with is one frame staler, as with the reference's concurrent env threads; overlap=False is the strictly
@@ -156,7 +156,9 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     end. Not together with greedy_envs: the greedy envs use policy slots, and slots exclude model variants. None (default) runs exactly as before.
     pushes=dict(wait=(lo, hi), force=(lo, hi), duration=(lo, hi), seed=, hold_out=[env ids]) trains under random external pushes (setup_pushes: every env but the
     held-out and the greedy ones is pushed at random times on the device, no host work per frame); stats["pushes"] then holds the held-out ids and PushInfo() at
-    the end. Combines with greedy_envs and with variants. None (default) runs exactly as before."""
+    the end. Combines with greedy_envs and with variants. None (default) runs exactly as before.
+    solver=dict(type="adam", base_lr=1e-4, clip_gradients=10, ...): overrides laid over the parsed solver prototxt (trainer.parse_solver's keys), for both trainers
+    (CACLA: over both nets' files). None (default) runs exactly as before."""
     if variants is not None and greedy_envs:
         raise ValueError("greedy_envs > 0 together with variants: the greedy envs use policy slots, and policy slots exclude model variants")
     if overlap:
@@ -173,13 +175,15 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
         b.SlotAlias(1, 0)
         b.SlotSetExplore(1, 0, 0.0, 1.0, 0.0)
         b.AssignSlots(np.arange(n_train, num_envs, dtype=np.int32), np.ones(greedy_envs, np.int32))
-    solver = os.path.join(data_root, args["policy_solver"])
-    train_net = os.path.join(data_root, re.search(r'net:\s*"([^"]+)"', open(solver).read()).group(1)) if re.search(r'net:\s*"', open(solver).read()) \
+    solver_file = os.path.join(data_root, args["policy_solver"])
+    train_net = os.path.join(data_root, re.search(r'net:\s*"([^"]+)"', open(solver_file).read()).group(1)) if re.search(r'net:\s*"', open(solver_file).read()) \
         else os.path.join(data_root, args["policy_net"].replace("_deploy", "_train"))
     tkw = dict(mem_size=geti("trainer_replay_mem_size", 500000), num_init_samples=geti("trainer_num_init_samples", 200),
                steps_per_iter=geti("trainer_num_steps_per_iters", 1), freeze_target_iters=geti("trainer_freeze_target_iters", 0),
                init_input_offset_scale=args.get("trainer_init_input_offset_scale", "false").lower() == "true", seed=seed, device=trainer_device)
-    t = _make_trainer(args, data_root, train_net, solver, b, tkw, trainer, trainer_lib)
+    if solver:
+        tkw["solver"] = dict(solver)
+    t = _make_trainer(args, data_root, train_net, solver_file, b, tkw, trainer, trainer_lib)
     t.SetOutputOffsetScale(*b.BuildNNOutputOffsetScale())
     side = b.SideStream(0) if hasattr(b, "SideStream") else (None, -1.0)
     if side[0] is not None and hasattr(t, "UseStream"):

@@ -66,12 +66,41 @@ def parse_net(path):
     return d
 
 
+SOLVER_TYPES = ("sgd", "nesterov", "adagrad", "rmsprop", "adadelta", "adam")      # cNNSolver::BuildSolver's six (learning/NNSolver.cpp:9-35), in dtrl_solver_desc's numbering
+LR_POLICIES = ("fixed", "step", "exp", "inv")
+
+
 def parse_solver(path):
-    txt = open(path).read()
+    """the solver prototxt's numbers; "type": one of SOLVER_TYPES, from `solver_type: ADAM` (the enum of the reference's Caffe generation) or `type: "Adam"` (the
+    later spelling), case-insensitively; neither: "sgd". Caffe's defaults where the file is silent."""
+    txt = re.sub(r"#[^\n]*", "", open(path).read())
     g = lambda key, dflt: (lambda m: float(m.group(1)) if m else dflt)(re.search(r"^\s*" + key + r":\s*([-\d.eE]+)", txt, re.M))
     pol = re.search(r'lr_policy:\s*"([^"]+)"', txt)
+    ty = re.search(r'^\s*solver_type:\s*"?([A-Za-z_]+)"?', txt, re.M) or re.search(r'^\s*type:\s*"([^"]*)"', txt, re.M)
+    ty = ty.group(1).lower() if ty else "sgd"
+    if ty not in SOLVER_TYPES:
+        raise ValueError('%s: solver type "%s" (implemented: SGD, Nesterov, AdaGrad, RMSProp, AdaDelta, Adam)' % (path, ty))
     return {"base_lr": g("base_lr", 0.01), "momentum": g("momentum", 0.0), "weight_decay": g("weight_decay", 0.0),
-            "lr_policy": pol.group(1) if pol else "fixed", "gamma": g("gamma", 0.1), "stepsize": g("stepsize", 1e18), "power": g("power", 0.75)}
+            "lr_policy": pol.group(1) if pol else "fixed", "gamma": g("gamma", 0.1), "stepsize": g("stepsize", 1e18), "power": g("power", 0.75),
+            "type": ty, "momentum2": g("momentum2", 0.999), "rms_decay": g("rms_decay", 0.99), "delta": g("delta", 1e-8), "clip_gradients": g("clip_gradients", -1.0)}
+
+
+def check_solver(s, where="solver"):
+    """the refusals of dtrl_trainer_set_solver, for the torch peer and for overrides laid over a parsed file"""
+    if s["type"] not in SOLVER_TYPES:
+        raise ValueError('%s: solver type "%s"' % (where, s["type"]))
+    if s["lr_policy"] not in LR_POLICIES:
+        raise ValueError('%s: lr_policy "%s" (implemented: "fixed", "step", "exp", "inv")' % (where, s["lr_policy"]))
+    for key in ("momentum", "momentum2", "rms_decay"):
+        if not 0.0 <= s[key] < 1.0:
+            raise ValueError("%s: %s %g outside [0, 1)" % (where, key, s[key]))
+    if SOLVER_TYPES.index(s["type"]) >= 2 and not s["delta"] > 0:
+        raise ValueError("%s: delta must be positive for this type" % where)
+    if s["type"] in ("adagrad", "rmsprop") and s["momentum"] != 0:
+        raise ValueError("%s: momentum must be 0 for AdaGrad / RMSProp" % where)
+    if s["lr_policy"] == "step" and s["stepsize"] < 1:
+        raise ValueError('%s: stepsize %g < 1 under lr_policy "step"' % (where, s["stepsize"]))
+    return s
 
 
 class MaceNet(torch.nn.Module):
@@ -234,9 +263,15 @@ class MACETrainer:
     """cMACETrainer (pool size 1, synchronous mode)."""
 
     def __init__(self, net_file, solver_file, state_size, action_size, mem_size=500000, num_init_samples=200, steps_per_iter=1,
-                 freeze_target_iters=0, discount=0.9, init_input_offset_scale=True, device=None, dtype=torch.float32, seed=0, use_graphs=None):
+                 freeze_target_iters=0, discount=0.9, init_input_offset_scale=True, device=None, dtype=torch.float32, seed=0, use_graphs=None, solver=None):
         self.desc = parse_net(net_file)
         self.solver = parse_solver(solver_file)
+        if solver:                                                  # overrides laid over the parsed file, e.g. dict(type="adam", base_lr=1e-4)
+            unknown = set(solver) - set(self.solver)
+            if unknown:
+                raise ValueError("solver overrides: unknown keys %s" % sorted(unknown))
+            self.solver.update({k: (str(v).lower() if k in ("type", "lr_policy") else float(v)) for k, v in solver.items()})
+        check_solver(self.solver, solver_file)
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         self.dtype = dtype
         self.S, self.A = state_size, action_size
@@ -251,6 +286,7 @@ class MACETrainer:
         for p_ in self.target.parameters():
             p_.requires_grad_(False)
         self.hflat = torch.zeros_like(self.net.flat)
+        self.h2flat = None                                          # second history (AdaDelta, Adam): made on first use
         self.history, self.rate_mult, self.decay_mult = [], torch.empty_like(self.hflat), torch.empty_like(self.hflat)   # per-element lr_mult / decay_mult
         off = 0
         for b, (lm, dm) in zip(self.net.blobs(), self.net.blob_mults):
@@ -552,6 +588,8 @@ class MACETrainer:
         s = self.solver
         if s["lr_policy"] == "step":
             return s["base_lr"] * s["gamma"] ** int(self.solver_iter // s["stepsize"])
+        if s["lr_policy"] == "exp":
+            return s["base_lr"] * s["gamma"] ** self.solver_iter
         if s["lr_policy"] == "inv":
             return s["base_lr"] * (1 + s["gamma"] * self.solver_iter) ** (-s["power"])
         return s["base_lr"]
@@ -567,13 +605,51 @@ class MACETrainer:
         loss.backward()
         rate, mom, wd = self._lr(), self.solver["momentum"], self.solver["weight_decay"]
         with torch.no_grad():
+            if self.solver.get("type", "sgd") != "sgd" or self.solver.get("clip_gradients", -1.0) >= 0:
+                self._solver_rule(rate)
+                return loss.detach()
             diff = torch.addcmul(self.net.gflat, self.decay_mult, self.net.flat, value=wd)   # Regularize (L2): diff + wd * decay_mult * w
             self.hflat.mul_(mom).addcmul_(self.rate_mult, diff, value=rate)                    # ComputeUpdateValue
             self.net.flat.sub_(self.hflat)                                                     # Net::Update
         return loss.detach()
 
+    def _solver_rule(self, rate):
+        """Caffe's other five solver types and ClipGradients (cNNSolver::BuildSolver, learning/NNSolver.cpp:9-35), as include/dtrl_trainer.h states them; in the
+        trainer's dtype. t = self.solver_iter, the applied updates before this one."""
+        s, g, w, h = self.solver, self.net.gflat, self.net.flat, self.hflat
+        mom, delta, t = s["momentum"], s["delta"], self.solver_iter
+        if s["clip_gradients"] >= 0:
+            n = float(g.pow(2).sum().sqrt())
+            if n > s["clip_gradients"]:
+                g = g * (s["clip_gradients"] / n)
+        d = torch.addcmul(g, self.decay_mult, w, value=s["weight_decay"])
+        local = rate * self.rate_mult
+        ty = s["type"]
+        if ty in ("adadelta", "adam") and getattr(self, "h2flat", None) is None:
+            self.h2flat = torch.zeros_like(h)
+        if ty == "sgd":
+            h.mul_(mom).add_(local * d); u = h
+        elif ty == "nesterov":
+            hp = h.clone(); h.mul_(mom).add_(local * d); u = (1 + mom) * h - mom * hp
+        elif ty == "adagrad":
+            h.add_(d * d); u = local * d / (h.sqrt() + delta)
+        elif ty == "rmsprop":
+            h.mul_(s["rms_decay"]).add_((1 - s["rms_decay"]) * d * d); u = local * d / (h.sqrt() + delta)
+        elif ty == "adadelta":
+            h2 = self.h2flat
+            h.mul_(mom).add_((1 - mom) * d * d)
+            e = d * ((h2 + delta) / (h + delta)).sqrt()
+            h2.mul_(mom).add_((1 - mom) * e * e)
+            u = local * e
+        else:
+            h2, m2 = self.h2flat, s["momentum2"]
+            h.mul_(mom).add_((1 - mom) * d)
+            h2.mul_(m2).add_((1 - m2) * d * d)
+            u = local * ((1 - m2 ** (t + 1)) ** 0.5 / (1 - mom ** (t + 1))) * h / (h2.sqrt() + delta)
+        w.sub_(u)
+
     def _solver_step(self, X, Y):
-        if self.use_graphs and self.solver["lr_policy"] == "fixed" and X.shape[0] == self.batch:
+        if self.use_graphs and self.solver["lr_policy"] == "fixed" and self.solver.get("type", "sgd") == "sgd" and self.solver.get("clip_gradients", -1.0) < 0 and X.shape[0] == self.batch:
             try:
                 if self._g_step is None:
                     xs = torch.zeros((self.batch, self.S), device=self.device, dtype=torch.float32)

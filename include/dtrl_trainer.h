@@ -46,7 +46,8 @@ int dtrl_trainer_sync(dtrl_trainer* t);
 
 int64_t dtrl_trainer_num_params(const dtrl_trainer* t);
 /* Replaces: cNeuralNet::CopyModel / LoadModel / GetParams (learning/NeuralNet.cpp:636-658): which = 0 current net, 1 target net, 2 solver history,
- * 3 lr_mult per element, 4 decay_mult per element (the per-blob multipliers of the train prototxt, expanded). Host arrays of num_params floats; synchronous. */
+ * 3 lr_mult per element, 4 decay_mult per element (the per-blob multipliers of the train prototxt, expanded), 5 the second solver history (AdaDelta and Adam only,
+ * see dtrl_solver_desc). Host arrays of num_params floats; synchronous. */
 int dtrl_trainer_set_params(dtrl_trainer* t, int which, const float* host, int64_t n);
 int dtrl_trainer_get_params(dtrl_trainer* t, int which, float* host, int64_t n);
 /* test / diagnosis: the first n floats of an internal device buffer (10 eval input, 11 eval output, 12 new_q, 13 train input, 14 train output,
@@ -148,6 +149,38 @@ float* dtrl_trainer_td(dtrl_trainer* t);
 /* cCaclaTrainer's actor iteration (BuildTupleActorY): one solver step of THIS net towards the action parameters of the tuples in slots dtrl_trainer_idx()[max_eval ..
  * max_eval + batch) of the replay memory it is bound to (bind the actor's trainer to the critic's memory); A == out_size; loss -> dtrl_trainer_loss()[0] */
 int dtrl_trainer_action_step(dtrl_trainer* t);
+
+/* ---- Caffe's six solver types and learning-rate policies ----
+ * Replaces: cNNSolver::BuildSolver (learning/NNSolver.cpp:9-35), the factory over SGD / Nesterov / AdaGrad / RMSProp / AdaDelta / Adam, and the lr_policy of the
+ * solver prototxt (Caffe's GetLearningRate). Per parameter element, with g = the mean gradient over the batch, t = applied updates before this one:
+ *   clip (clip_gradients >= 0): n = sqrt(sum g^2) over all parameters; n > clip -> g *= clip / n
+ *   d = g + weight_decay decay_mult w;  local = rate lr_mult;  w -= u  with
+ *   0 SGD       h = momentum h + local d;  u = h                                   (the rule of dtrl_trainer_step as it always was)
+ *   1 Nesterov  hp = h;  h = momentum h + local d;  u = (1 + momentum) h - momentum hp
+ *   2 AdaGrad   h += d^2;  u = local d / (sqrt(h) + delta)
+ *   3 RMSProp   h = rms_decay h + (1 - rms_decay) d^2;  u = local d / (sqrt(h) + delta)
+ *   4 AdaDelta  h = momentum h + (1 - momentum) d^2;  e = d sqrt((h2 + delta) / (h + delta));  h2 = momentum h2 + (1 - momentum) e^2;  u = local e
+ *   5 Adam      h = momentum h + (1 - momentum) d;  h2 = momentum2 h2 + (1 - momentum2) d^2;  u = local sqrt(1 - momentum2^(t+1)) / (1 - momentum^(t+1)) h / (sqrt(h2) + delta)
+ *   rate: 0 fixed  base_lr;  1 step  base_lr gamma^floor(t / stepsize);  2 exp  base_lr gamma^t;  3 inv  base_lr (1 + gamma t)^-power
+ * t counts the applied updates of this trainer (critic and actor steps of a MACE net share it, as they share Caffe's iter_); a dtrl_trainer_apply_grad without
+ * rows behind the gradient applies nothing and does not count. Counter, rate and Adam's correction live in device memory and are advanced by a one-thread launch
+ * in front of the apply, so a recorded step replays with the values of its own iteration. A trainer made from a dtrl_trainer_desc alone runs type 0 / policy 0
+ * with the description's base_lr, momentum and weight_decay. */
+typedef struct dtrl_solver_desc {
+	int32_t type, lr_policy;
+	float base_lr, momentum, momentum2, rms_decay, delta, weight_decay, gamma, power, clip_gradients;   /* Caffe's defaults: momentum2 0.999, rms_decay 0.99, delta 1e-8, gamma 0.1, power 0.75, clip_gradients -1 (off) */
+	int64_t stepsize;
+} dtrl_solver_desc;
+/* cNNSolver::BuildSolver (learning/NNSolver.cpp:9-35). Synchronises; validates all-or-nothing (an unknown type or policy; momentum, momentum2 or rms_decay outside
+ * [0, 1); delta <= 0 for types 2-5; AdaGrad / RMSProp with momentum != 0; stepsize < 1 under "step": status 1, dtrl_trainer_last_error names the field, nothing
+ * changes); clears both histories and the counter; drops the recorded launch sequences. */
+int dtrl_trainer_set_solver(dtrl_trainer* t, const dtrl_solver_desc* solver);
+/* the solver in force (cNNSolver::BuildSolver, learning/NNSolver.cpp:9-35) and the number of applied updates (Caffe's Solver::iter()); either pointer may be NULL. Synchronises. */
+int dtrl_trainer_get_solver(dtrl_trainer* t, dtrl_solver_desc* solver, int64_t* iter);
+/* the counter of a resumed run (Caffe's Solver::Restore for iter_; the solver is cNNSolver::BuildSolver's, learning/NNSolver.cpp:9-35): the schedule continues from `iter`. Synchronises. */
+int dtrl_trainer_set_solver_iter(dtrl_trainer* t, int64_t iter);
+/* dtrl_trainer_set_params / _get_params take which = 5 for the second history (types 4 and 5; refused for types 0-3, which keep none).
+ * dtrl_trainer_init_xavier clears both histories and the counter. */
 
 #ifdef __cplusplus
 }

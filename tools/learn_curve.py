@@ -98,7 +98,13 @@ def main():
     ap.add_argument("--lib", default="", help="(CPU smoke runs only) bind the scenario to this build of the engine, e.g. tests/emul/libdtrl_emul.so")
     ap.add_argument("--eval-batched", action="store_true", help="collect the intermediate weights and evaluate them in one slotted batch at the end instead of one fresh batch per evaluation")
     ap.add_argument("--sequential", action="store_true", help="no overlap: train on frame f's tuples before frame f+1 is launched")
+    ap.add_argument("--solver", default=None, choices=["sgd", "nesterov", "adagrad", "rmsprop", "adadelta", "adam"], help="Caffe solver type laid over the solver prototxt (train_loop.train(solver=...))")
+    ap.add_argument("--base-lr", type=float, default=None, help="base_lr laid over the solver prototxt's")
+    ap.add_argument("--clip", type=float, default=None, help="clip_gradients")
     a = ap.parse_args()
+    solver = {k: v for k, v in (("type", a.solver), ("base_lr", a.base_lr), ("clip_gradients", a.clip)) if v is not None} or None
+    if solver and a.solver in ("adagrad", "rmsprop"):
+        solver["momentum"] = 0.0
     c = CHARS[a.char]; envs = a.envs or c["envs"]
     global SCENARIO
     if a.lib:
@@ -106,8 +112,8 @@ def main():
             def _library(self):
                 return da._bind(os.path.abspath(a.lib))
         SCENARIO = LibScenario
-    lines = ["# tools/learn_curve.py --char %s --iters %d: %s with -terrain_file= %s, %d envs, native trainer, %s; greedy evaluation of the current net every %d iterations on %d envs x %d frames of %s (fixed terrain seeds)"
-             % (a.char, a.iters, c["train"], c["terrain"], envs, "sequential" if a.sequential else "overlapped", a.eval_every, a.eval_envs, a.eval_frames, c["evalf"]),
+    lines = ["# tools/learn_curve.py --char %s --iters %d: %s with -terrain_file= %s, %d envs, native trainer%s, %s; greedy evaluation of the current net every %d iterations on %d envs x %d frames of %s (fixed terrain seeds)"
+             % (a.char, a.iters, c["train"], c["terrain"], envs, (" under solver overrides %s" % solver) if solver else "", "sequential" if a.sequential else "overlapped", a.eval_every, a.eval_envs, a.eval_frames, c["evalf"]),
              "# %8s %9s %9s %8s %8s %9s %7s %9s %9s %8s" % ("iter", "tuples", "wall_s", "speed", "falls_k", "avg_dist", "alive", "episodes", "critic", "exp_rate")]
     t0 = time.time()
     curve = []
@@ -134,7 +140,7 @@ def main():
         stem = os.path.join(a.save, "%s_mace3_%s_model" % (a.char, os.path.splitext(os.path.basename(c["terrain"]))[0].replace("cliffs_rugged", "cliffs")))
     st = train_loop.train(c["train"], a.data_root, envs, max_iters=a.iters, overlap=not a.sequential, trainer=a.trainer, scenario_cls=SCENARIO,
                           extra_args=dict({"terrain_file": c["terrain"]}, **({"trainer_num_init_samples": a.init_samples} if a.init_samples is not None else {})),
-                          eval_every=a.eval_every, eval_fn=eval_fn, out_model_file=(stem + ".h5") if stem else None, out_scale_file=(stem + "_scale.txt") if stem else None)
+                          eval_every=a.eval_every, eval_fn=eval_fn, out_model_file=(stem + ".h5") if stem else None, out_scale_file=(stem + "_scale.txt") if stem else None, solver=solver)
     for k in range(0, len(pending), MAX_SLOTS):
         part = pending[k:k + MAX_SLOTS]
         for r, (_, _, meta) in zip(evaluate_many(c["evalf"], a.data_root, [(w, norm) for w, norm, _ in part], a.eval_envs, a.eval_frames), part):

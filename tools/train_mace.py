@@ -33,7 +33,15 @@ ap.add_argument("--pushes", type=int, nargs=2, default=None, metavar=("LO", "HI"
 ap.add_argument("--push-force", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --pushes: range of the force magnitude in N (default: the arg file's -min_perturb= / -max_perturb=)")
 ap.add_argument("--push-duration", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --pushes: range of the duration in s (default: the arg file's)")
 ap.add_argument("--push-seed", type=int, default=0, help="with --pushes: seed of the push streams")
+ap.add_argument("--solver", default=None, choices=["sgd", "nesterov", "adagrad", "rmsprop", "adadelta", "adam"], help="Caffe solver type laid over the solver prototxt (train_loop.train(solver=...); default: what the file names, SGD where it names none; not with --distributed)")
+ap.add_argument("--base-lr", type=float, default=None, help="with or without --solver: base_lr laid over the solver prototxt's")
+ap.add_argument("--clip", type=float, default=None, help="clip_gradients: the gradient's L2 norm is scaled down to this where it exceeds it")
 a = ap.parse_args()
+solver = {k: v for k, v in (("type", a.solver), ("base_lr", a.base_lr), ("clip_gradients", a.clip)) if v is not None} or None
+if solver and a.solver in ("adagrad", "rmsprop"):
+    solver["momentum"] = 0.0       # (these two take none; the shipped files set 0.9 for SGD)
+if solver and a.distributed:
+    ap.error("--solver / --base-lr / --clip are not available with --distributed")
 if a.pushes and a.distributed:
     ap.error("--pushes is not available with --distributed")
 pushes = None
@@ -72,7 +80,7 @@ if a.distributed:
     sys.exit(0)
 st = train_loop.train(a.arg_file, a.data_root, a.envs, max_iters=a.iters, max_frames=a.frames, log_every=50, overlap=a.overlap, frames_per_drain=a.frames_per_drain,
                       extra_args=dict(({"reserve_cus": reserve} if reserve else {}), **({"trainer_num_init_samples": a.init_samples} if a.init_samples is not None else {})) or None,
-                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll, variants=variants, pushes=pushes)
+                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll, variants=variants, pushes=pushes, solver=solver)
 if a.out:
     np.save(a.out + ".npy", st["weights"])
 if variants:
