@@ -1,6 +1,8 @@
 // dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, launches over
-// envs of several slots or variants and the per-slot sums, the variant redraw, the frame-boundary terrain work of envs under several terrains, each built from the interface's own copies and Launch. What the lane-loop check build runs; the HIP backend overrides every one
-// of them with kernels and keeps these as its cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1).
+// envs of several slots or variants and the per-slot sums, and the per-env rules of the frame boundary (terrain work under the batch's terrain, a terrain set
+// or a ladder; variant redraw; push schedule; perturbation rows), each built from the interface's own copies and Launch. The rules all run over an EnvSpan that
+// SpanList turns into a host vector. What the lane-loop check build runs; the HIP backend overrides every one of them with kernels and keeps these as its
+// cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1, DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1).
 // Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
 // lane-loop check build of any tests/ tree, the sanitizer scripts -- has the defaults, and no source list can lack them.
 #include "dtrl_engine.h"
@@ -142,13 +144,19 @@ bool Backend::SlotReduce(const EnvState* st, const int32_t* env_slot, int n_envs
 	}
 	return true;
 }
-// Variant redraw: the rule (var_redraw_step) on the host, env by env; key and counter go back where they changed. The first D2H waits for the selected stream.
-bool Backend::VariantRedraw(const EnvStatus* status, int e0, int n, const int32_t* env_list, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg)
+bool Backend::SpanList(const EnvSpan& span, std::vector<int32_t>& list)
 {
-	if (n <= 0) return true;
-	std::vector<int32_t> list(static_cast<size_t>(n));
-	if (!env_list) { for (int k = 0; k < n; ++k) list[k] = e0 + k; }
-	else if (!D2H(list.data(), env_list, sizeof(int32_t) * list.size())) return false;
+	list.resize(static_cast<size_t>(span.n > 0 ? span.n : 0));
+	if (span.list) return list.empty() || D2H(list.data(), span.list, sizeof(int32_t) * list.size());
+	for (int k = 0; k < span.n; ++k) span_env(k, span.e0, span.n, nullptr, list[k]);
+	return true;
+}
+// Variant redraw: the rule (var_redraw_step) on the host, env by env; key and counter go back where they changed. The first D2H waits for the selected stream.
+bool Backend::VariantRedraw(const EnvStatus* status, const EnvSpan& span, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg)
+{
+	std::vector<int32_t> list;
+	if (!SpanList(span, list)) return false;
+	if (list.empty()) return true;
 	std::vector<double> cum(static_cast<size_t>(cfg.hi - cfg.lo + 1));
 	if (!D2H(cum.data(), cfg.cum, sizeof(double) * cum.size())) return false;
 	EnvStatus st; RedrawRec r; int32_t key = 0;
@@ -173,12 +181,11 @@ static bool WriteSlotFields(Backend& be, EnvState* dst, const EnvState& src)
 	return be.H2D(d + offsetof(EnvState, pert_link), s + offsetof(EnvState, pert_link), 2 * sizeof(int32_t))
 		&& be.H2D(d + offsetof(EnvState, pert_f), s + offsetof(EnvState, pert_f), 7 * sizeof(real));
 }
-bool Backend::PushSchedule(const EnvStatus* status, int e0, int n, const int32_t* env_list, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg)
+bool Backend::PushSchedule(const EnvStatus* status, const EnvSpan& span, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg)
 {
-	if (n <= 0) return true;
-	std::vector<int32_t> list(static_cast<size_t>(n));
-	if (!env_list) { for (int k = 0; k < n; ++k) list[k] = e0 + k; }
-	else if (!D2H(list.data(), env_list, sizeof(int32_t) * list.size())) return false;
+	std::vector<int32_t> list;
+	if (!SpanList(span, list)) return false;
+	if (list.empty()) return true;
 	if (!SyncSelected()) return false;
 	EnvStatus es; PushRec r; double sc = 0; EnvState slot;
 	for (int32_t e : list) {
@@ -208,37 +215,36 @@ bool Backend::PerturbScatter(EnvState* st, const PerturbRow* rows, int n)
 	}
 	return true;
 }
-// Terrain sets: tg_env_boundary on the host, env by env, under the env's own table entry. A finished episode goes to the device distance ring as the kernel
-// would have put it there (one cursor read at the start, one write at the end: nothing else runs on this stream meanwhile -- D2H waits for it).
-bool Backend::TerrainBoundaryKeyed(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, const int32_t* env_terrain)
+// The terrain work: tg_env_boundary on the host, env by env, under the TerrainCfg the rule names -- the batch's own, the env's table entry, or the entry of the
+// level the ladder's rule (tg_ladder_step) has just moved the env to; key and ladder record go back where they changed. A finished episode goes to the device
+// distance ring as the kernel would have put it there (one cursor read at the start, one write at the end: nothing else runs on this stream meanwhile -- D2H
+// waits for it).
+bool Backend::TerrainBoundary(const DevBuffers& buf, const EnvSpan& span, int mode, const TerrainRule& rule)
 {
-	// (this class's loop, not a backend's override of it; without ladder records it writes nothing to the key array)
-	return Backend::TerrainBoundaryLadder(buf, e0, n, mode, env_list, table, const_cast<int32_t*>(env_terrain), nullptr, LadderCfg{});
+	return rule.table ? TerrainBoundaryLoop(buf, span, mode, rule) : TerrainBoundary(buf, span.e0, span.n, mode, span.list);
 }
-// Terrain ladder: the same loop with the rule (tg_ladder_step) in front of each env's terrain work; key and ladder record go back where they changed.
-// ladder == nullptr: no rule, the keyed form.
-bool Backend::TerrainBoundaryLadder(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, int32_t* env_terrain, LadderRec* ladder, const LadderCfg& lc)
+bool Backend::TerrainBoundary(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list) { return TerrainBoundaryLoop(buf, EnvSpan{e0, n, env_list}, mode, TerrainRule{}); }
+bool Backend::TerrainBoundaryLoop(const DevBuffers& buf, const EnvSpan& span, int mode, const TerrainRule& rule)
 {
-	if (n <= 0) return true;
-	std::vector<int32_t> list(static_cast<size_t>(n));
-	if (!env_list) { for (int k = 0; k < n; ++k) list[k] = e0 + k; }
-	else if (!D2H(list.data(), env_list, sizeof(int32_t) * list.size())) return false;
+	std::vector<int32_t> list;
+	if (!SpanList(span, list)) return false;
+	if (list.empty()) return true;
 	int32_t cursor = 0;
 	if (buf.dist_ring && !D2H(&cursor, buf.dist_count, sizeof(cursor))) return false;
 	const int32_t cursor0 = cursor;
 	GroundRec rec; GroundGen gen; EnvStatus st; TerrainCfg cfg; int32_t key = 0;
 	for (int32_t e : list) {
-		if (!D2H(&key, env_terrain + e, sizeof(key)) || !D2H(&st, buf.status + e, sizeof(st))) return false;
-		if (ladder) {
+		if ((rule.table && !D2H(&key, rule.env_terrain + e, sizeof(key))) || !D2H(&st, buf.status + e, sizeof(st))) return false;
+		if (rule.ladder) {
 			LadderRec lr;
-			if (!D2H(&lr, ladder + e, sizeof(lr))) return false;
+			if (!D2H(&lr, rule.ladder + e, sizeof(lr))) return false;
 			const LadderRec lr0 = lr;
-			const int32_t next = tg_ladder_step(lr, key, st, lc, mode, e);
-			if (next != key && !H2D(env_terrain + e, &next, sizeof(next))) return false;
-			if ((lr.mark_x != lr0.mark_x || lr.ups != lr0.ups || lr.downs != lr0.downs) && !H2D(ladder + e, &lr, sizeof(lr))) return false;
+			const int32_t next = tg_ladder_step(lr, key, st, rule.lc, mode, e);
+			if (next != key && !H2D(rule.env_terrain + e, &next, sizeof(next))) return false;
+			if ((lr.mark_x != lr0.mark_x || lr.ups != lr0.ups || lr.downs != lr0.downs) && !H2D(rule.ladder + e, &lr, sizeof(lr))) return false;
 			key = next;
 		}
-		if (!D2H(&cfg, table + key, sizeof(cfg)) || !D2H(&gen, buf.gen + e, sizeof(gen)) || !D2H(&rec, buf.gr + e, sizeof(rec))) return false;
+		if (!D2H(&cfg, rule.table ? rule.table + key : buf.tcfg, sizeof(cfg)) || !D2H(&gen, buf.gen + e, sizeof(gen)) || !D2H(&rec, buf.gr + e, sizeof(rec))) return false;
 		const GroundGen gen0 = gen;
 		DistRec one; int32_t got = 0;
 		tg_env_boundary(rec, gen, st, cfg, mode, e, buf.dist_ring ? &one : nullptr, &got, 1);

@@ -147,9 +147,8 @@ __global__ void __launch_bounds__(kGroup) dtrl_snap_move(SnapPlan p, char* paylo
 // -terrain_gen= device: one thread per env; only the few envs whose window must move (or that fell) do any work
 __global__ void dtrl_terrain_boundary(DevBuffers buf, int e0, int n, int mode, const int32_t* __restrict__ env_list)
 {
-	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
-	if (k >= n) return;
-	const int e = env_list ? env_list[k] : e0 + k;
+	int e;
+	if (!span_env(static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x), e0, n, env_list, e)) return;
 	tg_env_boundary(buf.gr[e], buf.gen[e], buf.status[e], *buf.tcfg, mode, e, buf.dist_ring, buf.dist_count, buf.dist_cap);
 }
 // Terrain sets (include/dtrl.h dtrl_terrains_create ...): the same thread-per-env boundary with one TerrainCfg per env. The table and the per-env terrain array
@@ -158,9 +157,8 @@ __global__ void dtrl_terrain_boundary(DevBuffers buf, int e0, int n, int mode, c
 // part ways in tgen::build_terrain's type dispatch and run their generators one type after the other (docs/EXPERIMENTS.md, terrain sets).
 __global__ void dtrl_terrain_boundary_keyed(DevBuffers buf, int e0, int n, int mode, const int32_t* __restrict__ env_list, const TerrainCfg* __restrict__ table, const int32_t* __restrict__ env_terrain)
 {
-	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
-	if (k >= n) return;
-	const int e = env_list ? env_list[k] : e0 + k;
+	int e;
+	if (!span_env(static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x), e0, n, env_list, e)) return;
 	tg_env_boundary(buf.gr[e], buf.gen[e], buf.status[e], table[env_terrain[e]], mode, e, buf.dist_ring, buf.dist_count, buf.dist_cap);
 }
 // Terrain ladder (include/dtrl.h dtrl_terrain_ladder): the keyed boundary with the rule in front of it, in the same launch -- the env's level moves by its own
@@ -169,9 +167,8 @@ __global__ void dtrl_terrain_boundary_keyed(DevBuffers buf, int e0, int n, int m
 __global__ void dtrl_terrain_boundary_ladder(DevBuffers buf, int e0, int n, int mode, const int32_t* __restrict__ env_list, const TerrainCfg* __restrict__ table, int32_t* __restrict__ env_terrain,
 	LadderRec* __restrict__ ladder, LadderCfg lc)
 {
-	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
-	if (k >= n) return;
-	const int e = env_list ? env_list[k] : e0 + k;
+	int e;
+	if (!span_env(static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x), e0, n, env_list, e)) return;
 	const int32_t level = env_terrain[e];
 	LadderRec lr = ladder[e];
 	const LadderRec lr0 = lr;
@@ -185,9 +182,8 @@ __global__ void dtrl_terrain_boundary_ladder(DevBuffers buf, int e0, int n, int 
 // per env, every word per env, key and counter written back only where they changed: no atomics. The settings and the cumulative table are arguments.
 __global__ void dtrl_variant_redraw(const EnvStatus* __restrict__ status, int e0, int n, const int32_t* __restrict__ env_list, int32_t* __restrict__ env_model, RedrawRec* __restrict__ recs, RedrawCfg rc)
 {
-	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
-	if (k >= n) return;
-	const int e = env_list ? env_list[k] : e0 + k;
+	int e;
+	if (!span_env(static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x), e0, n, env_list, e)) return;
 	if (!(status[e].need_reset & 1)) return;
 	const int32_t v = env_model[e];
 	RedrawRec r = recs[e];
@@ -203,9 +199,8 @@ __global__ void dtrl_variant_redraw(const EnvStatus* __restrict__ status, int e0
 __global__ void __launch_bounds__(64) dtrl_push_schedule(const EnvStatus* __restrict__ status, int e0, int n, const int32_t* __restrict__ env_list, EnvState* __restrict__ st, PushRec* __restrict__ recs,
 	const double* __restrict__ scale, PushCfg pc)
 {
-	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
-	if (k >= n) return;
-	const int e = env_list ? env_list[k] : e0 + k;
+	int e;
+	if (!span_env(static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x), e0, n, env_list, e)) return;
 	const double sc = scale[e];
 	if (sc == 0) return;
 	const bool start = status ? status[e].need_reset != 0 : true;
@@ -217,8 +212,8 @@ __global__ void __launch_bounds__(64) dtrl_push_schedule(const EnvStatus* __rest
 // dtrl_add_perturb in one launch: a thread per row (the engine has reduced the rows to one per env), the seven slot fields each
 __global__ void __launch_bounds__(64) dtrl_perturb_scatter(EnvState* __restrict__ st, const PerturbRow* __restrict__ rows, int n)
 {
-	const int k = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
-	if (k >= n) return;
+	int k;
+	if (!span_env(static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x), 0, n, nullptr, k)) return;
 	const PerturbRow r = rows[k];
 	perturb_write_slot(st[r.env], r);
 }
@@ -613,51 +608,39 @@ public:
 	bool SyncPolicyReady() override { return !policy_ready_ || Check(hipEventSynchronize(policy_ready_), "hipEventSynchronize"); }
 	bool MarkWeightReader(int group, int wbuf) override { return Mark(group, kWeightReader + wbuf); }
 	bool WaitWeightReaders(void* stream, int wbuf, int n_groups) override { return WaitMarks(stream ? static_cast<hipStream_t>(stream) : stream_, kWeightReader + wbuf, n_groups); }
-	bool TerrainBoundary(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list) override
+	// The per-env launches of the frame boundary: one thread per env or row, 64 per workgroup, on the selected stream; `what` names the launch in the error text
+	template <class... P, class... A>
+	bool LaunchPerEnv(void (*kernel)(P...), int n, const char* what, const A&... args)
 	{
 		if (n <= 0) return true;
-		hipLaunchKernelGGL(dtrl_terrain_boundary, dim3((n + 63) / 64), dim3(64), 0, stream_, buf, e0, n, mode, env_list);
-		return Check(hipGetLastError(), "terrain boundary launch");
+		hipLaunchKernelGGL(kernel, dim3((n + 63) / 64), dim3(64), 0, stream_, args...);
+		return Check(hipGetLastError(), what);
 	}
-	// terrain sets: ONE launch over the listed envs, each under its own table entry. DTRL_TERRAINS_FALLBACK=1 takes the host default instead (A/B and cross-check)
-	bool TerrainBoundaryKeyed(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, const int32_t* env_terrain) override
+	// ONE launch per group and frame, whatever the rule: the batch's own terrain, one table entry per env (terrain sets), or the ladder's rule in front of that, in
+	// the same launch. DTRL_TERRAINS_FALLBACK=1 takes the host default for the two forms with a table (A/B and cross-check)
+	bool TerrainBoundary(const DevBuffers& buf, const EnvSpan& s, int mode, const TerrainRule& r) override
 	{
-		if (EnvFlag("DTRL_TERRAINS_FALLBACK")) return Backend::TerrainBoundaryKeyed(buf, e0, n, mode, env_list, table, env_terrain);
-		if (n <= 0) return true;
-		hipLaunchKernelGGL(dtrl_terrain_boundary_keyed, dim3((n + 63) / 64), dim3(64), 0, stream_, buf, e0, n, mode, env_list, table, env_terrain);
-		return Check(hipGetLastError(), "keyed terrain boundary launch");
+		if (!r.table) return LaunchPerEnv(dtrl_terrain_boundary, s.n, "terrain boundary launch", buf, s.e0, s.n, mode, s.list);
+		if (EnvFlag("DTRL_TERRAINS_FALLBACK")) return TerrainBoundaryLoop(buf, s, mode, r);
+		if (!r.ladder) return LaunchPerEnv(dtrl_terrain_boundary_keyed, s.n, "keyed terrain boundary launch", buf, s.e0, s.n, mode, s.list, r.table, r.env_terrain);
+		return LaunchPerEnv(dtrl_terrain_boundary_ladder, s.n, "ladder terrain boundary launch", buf, s.e0, s.n, mode, s.list, r.table, r.env_terrain, r.ladder, r.lc);
 	}
-	// terrain ladder: still ONE launch per group and frame -- the rule runs inside it. DTRL_TERRAINS_FALLBACK=1 takes the host default
-	bool TerrainBoundaryLadder(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, int32_t* env_terrain, LadderRec* ladder, const LadderCfg& lc) override
+	// variant redraw, push schedule, dtrl_add_perturb: ONE launch each, queued like the boundary work. DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 /
+	// DTRL_PERTURB_FALLBACK=1 takes the host default
+	bool VariantRedraw(const EnvStatus* status, const EnvSpan& s, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg) override
 	{
-		if (EnvFlag("DTRL_TERRAINS_FALLBACK")) return Backend::TerrainBoundaryLadder(buf, e0, n, mode, env_list, table, env_terrain, ladder, lc);
-		if (n <= 0) return true;
-		hipLaunchKernelGGL(dtrl_terrain_boundary_ladder, dim3((n + 63) / 64), dim3(64), 0, stream_, buf, e0, n, mode, env_list, table, env_terrain, ladder, lc);
-		return Check(hipGetLastError(), "ladder terrain boundary launch");
+		if (EnvFlag("DTRL_VARIANTS_FALLBACK")) return Backend::VariantRedraw(status, s, env_model, recs, cfg);
+		return LaunchPerEnv(dtrl_variant_redraw, s.n, "variant redraw launch", status, s.e0, s.n, s.list, env_model, recs, cfg);
 	}
-	// variant redraw: ONE launch per group and frame, queued like the boundary work. DTRL_VARIANTS_FALLBACK=1 takes the host default
-	bool VariantRedraw(const EnvStatus* status, int e0, int n, const int32_t* env_list, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg) override
+	bool PushSchedule(const EnvStatus* status, const EnvSpan& s, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg) override
 	{
-		if (EnvFlag("DTRL_VARIANTS_FALLBACK")) return Backend::VariantRedraw(status, e0, n, env_list, env_model, recs, cfg);
-		if (n <= 0) return true;
-		hipLaunchKernelGGL(dtrl_variant_redraw, dim3((n + 63) / 64), dim3(64), 0, stream_, status, e0, n, env_list, env_model, recs, cfg);
-		return Check(hipGetLastError(), "variant redraw launch");
+		if (EnvFlag("DTRL_PUSH_FALLBACK")) return Backend::PushSchedule(status, s, st, recs, scale, cfg);
+		return LaunchPerEnv(dtrl_push_schedule, s.n, "push schedule launch", status, s.e0, s.n, s.list, st, recs, scale, cfg);
 	}
-	// push schedule: ONE launch per group and frame, queued like the boundary work. DTRL_PUSH_FALLBACK=1 takes the host default
-	bool PushSchedule(const EnvStatus* status, int e0, int n, const int32_t* env_list, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg) override
-	{
-		if (EnvFlag("DTRL_PUSH_FALLBACK")) return Backend::PushSchedule(status, e0, n, env_list, st, recs, scale, cfg);
-		if (n <= 0) return true;
-		hipLaunchKernelGGL(dtrl_push_schedule, dim3((n + 63) / 64), dim3(64), 0, stream_, status, e0, n, env_list, st, recs, scale, cfg);
-		return Check(hipGetLastError(), "push schedule launch");
-	}
-	// dtrl_add_perturb: ONE launch for all rows. DTRL_PERTURB_FALLBACK=1 takes the host default
 	bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n) override
 	{
 		if (EnvFlag("DTRL_PERTURB_FALLBACK")) return Backend::PerturbScatter(st, rows, n);
-		if (n <= 0) return true;
-		hipLaunchKernelGGL(dtrl_perturb_scatter, dim3((n + 63) / 64), dim3(64), 0, stream_, st, rows, n);
-		return Check(hipGetLastError(), "perturb scatter launch");
+		return LaunchPerEnv(dtrl_perturb_scatter, n, "perturb scatter launch", st, rows, n);
 	}
 	bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) override
 	{

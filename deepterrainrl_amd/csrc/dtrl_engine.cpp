@@ -278,7 +278,7 @@ int Engine::Create(const char* const* argv, int argc, int num_envs, int device_i
 		std::vector<GroundGen> gen(n_);
 		for (int e = 0; e < n_; ++e) { gen[e].key = terrain_stream_key(cfg_.terrain_seed, cfg_.run.env_id_base + e); gen[e].ctr = 0; gen[e].builds = 0; gen[e].overflow = 0; }
 		if (!be_->H2D(buf_.gen, gen.data(), sizeof(GroundGen) * n_)) return Fail(DTRL_ERR_DEVICE, be_->error());
-		if (!Boundary(0, n_, 1, nullptr) || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+		if (!Boundary(EnvSpan{0, n_, nullptr}, 1) || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	} else {
 	std::vector<GroundRec> recs(n_);
 	for (int e = 0; e < n_; ++e) {
@@ -369,7 +369,7 @@ bool Engine::LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, b
 	const bool variants = !var_models_.empty();   // (variants and slots exclude each other: dtrl_variants_create / dtrl_slots_create)
 	if (!variants && slots_.empty()) return be_->Launch(d_model_, cfg_.run, b, n_envs, n_steps, dt, frame_end);
 	EnvKeyView v = (variants ? variant_keys_ : slot_keys_).View(list_host, part_off);
-	if (variants) { v.models_dev = d_var_models_; v.keys_on_device = RedrawOnDevice(); }
+	if (variants) v.models_dev = d_var_models_;
 	else { v.slots_dev = d_slot_table_; v.slots_host = slot_table_.data(); }
 	return be_->LaunchKeyed(variants ? d_var_models_ : d_model_, cfg_.run, b, v, n_envs, n_steps, dt, frame_end);
 }
@@ -407,12 +407,13 @@ int Engine::DeviceFrameWork(int group)
 	struct Restore { Backend* b; ~Restore() { b->SelectStream(0); } } restore{be_};
 	DevBuffers b = buf_;
 	b.env_list = nullptr; b.reset_listed = 2;
-	if (!Boundary(grp.e0, grp.n, 0, nullptr) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	const EnvSpan span{grp.e0, grp.n, nullptr};
+	if (!Boundary(span, 0) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	// variant redraw: the envs that fell draw their next variant behind their frame and in front of the reset launch, which then runs reset_env under the new model
-	if (redraw_on_) { redraw_stale_ = true; if (!be_->VariantRedraw(buf_.status, grp.e0, grp.n, nullptr, variant_keys_.d_env_key, d_redraw_, redraw_)) return Fail(DTRL_ERR_DEVICE, be_->error()); }
+	if (redraw_on_) { variant_keys_.stale = true; if (!be_->VariantRedraw(buf_.status, span, variant_keys_.d_env_key, redraw_.dev, redraw_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error()); }
 	// push schedule: the group's envs count down, and the ones that are due get their push, behind the frame and in front of the reset launch (an env that fell
 	// draws a new wait and is not pushed: the reset launch clears nothing the rule wrote)
-	if (push_on_ && !be_->PushSchedule(buf_.status, grp.e0, grp.n, nullptr, buf_.st, d_push_, d_push_scale_, push_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (push_on_ && !be_->PushSchedule(buf_.status, span, buf_.st, push_.dev, push_scale_.dev, push_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	b.env_list = d_order_ + grp.e0;
 	if (!LaunchEnvs(b, grp.n, 0, 0.0, false, nullptr, grp.e0)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
@@ -454,17 +455,17 @@ int Engine::HostFrameWork(int group)
 	reset_ids_.clear();
 	work_.clear();
 	bool level_moved = false, variant_moved = false;
-	RedrawCfg rd = redraw_; rd.cum = redraw_cum_.data();
+	RedrawCfg rd = redraw_cfg_; rd.cum = redraw_cum_.host.data();
 	for (int e = e0; e < e1; ++e) {
 		const EnvStatus& s = status_[e];
 		if (redraw_on_) {   // the redraw's rule: an env that fell draws the variant its next episode runs under (the reset launch below reads the key)
 			int32_t& k = variant_keys_.env_key[e];
-			const int32_t next = var_redraw_step(redraw_rec_[e], k, (s.need_reset & 1) != 0, rd, rd.cum, e);
+			const int32_t next = var_redraw_step(redraw_.host[e], k, (s.need_reset & 1) != 0, rd, rd.cum, e);
 			if (next != k) { k = next; variant_moved = true; }
 		}
 		if (ladder_on_) {   // the ladder's rule, in front of the env's terrain work: the window built or slid below is already the new level's
 			int32_t& k = terrain_keys_.env_key[e];
-			const int32_t next = tg_ladder_step(ladder_rec_[e], k, s, ladder_, 0, e);
+			const int32_t next = tg_ladder_step(ladder_.host[e], k, s, ladder_cfg_, 0, e);
 			if (next != k) { k = next; const TerrainCfg& c = terrain_table_[k]; grounds_[e].SetTerrain(c.type, c.params); level_moved = true; }
 		}
 		if (s.need_reset & 2) dist_log_.emplace_back(e, s.episode_dist);   // cScenarioPoliEval::RecordDistTraveled -> mDistLog
@@ -508,7 +509,7 @@ int Engine::HostFrameWork(int group)
 	const double ht3 = g_ht.on ? now_s() : 0;
 	// push schedule: the same launch as in device terrain mode, on the group's stream (idle since the wait above) in front of the reset launch; status_ is the
 	// page-locked array the frame kernel wrote, which the device reads through the same pointer
-	if (push_on_ && !be_->PushSchedule(buf_.status, e0, grp.n, nullptr, buf_.st, d_push_, d_push_scale_, push_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (push_on_ && !be_->PushSchedule(buf_.status, EnvSpan{e0, grp.n, nullptr}, buf_.st, push_.dev, push_scale_.dev, push_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	const int rc = ApplyResets(reset_ids_, group);
 	if (g_ht.on) { const double ht4 = now_s(); g_ht.t_sync += ht1 - ht0; g_ht.t_loop += ht2 - ht1; g_ht.t_sort += ht3 - ht2; g_ht.t_reset += ht4 - ht3; g_ht.regen += used; ++g_ht.n; }
 	return rc;
@@ -693,7 +694,7 @@ int Engine::Reset(const int32_t* env_ids, int n, const uint64_t* seeds)
 			continue;
 		}
 		GroundWindow& g = grounds_[e];
-		if (ladder_on_) tg_ladder_step(ladder_rec_[e], terrain_keys_.env_key[e], status_[e], ladder_, 1, e);   // (device terrain: the boundary launch below does it)
+		if (ladder_on_) tg_ladder_step(ladder_.host[e], terrain_keys_.env_key[e], status_[e], ladder_cfg_, 1, e);   // (device terrain: the boundary launch below does it)
 		if (seeds) g.SeedRand(static_cast<unsigned long>(seeds[i]));
 		g.Clear();
 		g.Update(-kViewDist + kGroundSpawnOffset, kViewDist + kGroundSpawnOffset);
@@ -702,7 +703,7 @@ int Engine::Reset(const int32_t* env_ids, int n, const uint64_t* seeds)
 	}
 	if (cfg_.device_terrain && !reset_ids_.empty()) {
 		std::memcpy(pin_ids_, reset_ids_.data(), sizeof(int32_t) * reset_ids_.size());
-		if (!be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size()) || !Boundary(0, static_cast<int>(reset_ids_.size()), 1, d_env_list_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+		if (!be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size()) || !Boundary(EnvSpan{0, static_cast<int>(reset_ids_.size()), d_env_list_}, 1)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
 	if (int rc = RedrawListed(reset_ids_); rc != DTRL_OK) return rc;   // variant redraw: an episode starts, once per listed env, and the reset below runs under the new model
 	int rc = ApplyResets(reset_ids_, -1);
@@ -1245,11 +1246,12 @@ int Engine::AddPerturb(const int32_t* env_ids, int n, const int32_t* link, const
 {
 	if (env_ids && n < 0) return Fail(DTRL_ERR_ARG, "negative env count");
 	be_->Sync();
-	if (int rc = VariantRefresh(); rc != DTRL_OK) return rc;
+	if (int rc = KeysRefresh(variant_keys_); rc != DTRL_OK) return rc;
 	const int cnt = env_ids ? n : n_;
 	// The list becomes one row per env, the env's LAST row (applied in list order the last one won; a thread per row must not race), and goes into the slots in
 	// one launch (Backend::PerturbScatter). A bad row stops the list where the sequential loop stopped: the rows in front of it are applied, then the error returns.
-	std::vector<PerturbRow> rows;
+	std::vector<PerturbRow>& rows = pert_rows_.host;
+	rows.clear();
 	std::vector<int32_t> row_of(static_cast<size_t>(n_), -1);
 	const char* bad = nullptr;
 	for (int i = 0; i < cnt && !bad; ++i) {
@@ -1270,12 +1272,8 @@ int Engine::AddPerturb(const int32_t* env_ids, int n, const int32_t* link, const
 		if (row_of[e] < 0) { row_of[e] = static_cast<int32_t>(rows.size()); rows.push_back(r); } else rows[row_of[e]] = r;
 	}
 	if (!rows.empty()) {
-		if (!d_pert_rows_) {
-			d_pert_rows_ = static_cast<PerturbRow*>(be_->Alloc(sizeof(PerturbRow) * static_cast<size_t>(n_)));
-			if (!d_pert_rows_) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
-			allocs_.push_back(d_pert_rows_);
-		}
-		if (!be_->H2D(d_pert_rows_, rows.data(), sizeof(PerturbRow) * rows.size()) || !be_->PerturbScatter(buf_.st, d_pert_rows_, static_cast<int>(rows.size())) || !be_->SyncSelected())
+		if (int rc = RecsAlloc(pert_rows_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
+		if (!pert_rows_.Push(*be_) || !be_->PerturbScatter(buf_.st, pert_rows_.dev, static_cast<int>(rows.size())) || !be_->SyncSelected())
 			return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
 	if (bad) return Fail(DTRL_ERR_ARG, bad);
@@ -1821,6 +1819,29 @@ int Engine::KeysIdle(const EnvAssignment& a, const char* what, int key, bool wai
 	return be_->Sync() ? DTRL_OK : Fail(DTRL_ERR_DEVICE, be_->error());
 }
 
+int Engine::DevOk(bool ok) { return ok ? DTRL_OK : Fail(DTRL_ERR_DEVICE, be_->error()); }
+template <class Rec> int Engine::RecsAlloc(RuleRecs<Rec>& r, size_t n) { return r.Alloc(*be_, n, allocs_) ? DTRL_OK : Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error()); }
+int Engine::KeysRefresh(EnvAssignment& a)
+{
+	if (!a.on_device || !a.stale) return DTRL_OK;
+	if (!be_->D2H(a.env_key.data(), a.d_env_key, sizeof(int32_t) * a.env_key.size()) || !a.recs->Pull(*be_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	a.stale = false;
+	return DTRL_OK;
+}
+int Engine::KeysCurrent(EnvAssignment& a, const char* what, bool always)
+{
+	if (!a.on_device && !always) return DTRL_OK;
+	if (int rc = KeysIdle(a, what, 0); rc != DTRL_OK) return rc;
+	return KeysRefresh(a);
+}
+
+int Engine::CheckEnvList(const std::string& w, const int32_t* env_ids, int n, const char* tail, const char* name, const void* required)
+{
+	if (n < 0 || n > n_ || (name && n > 0 && !required)) return Fail(DTRL_ERR_ARG, w + (name ? std::string(name) + " is required and the env count" : std::string("the env count")) + " must be 0 .. num_envs");
+	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range" + tail); }
+	return DTRL_OK;
+}
+
 int Engine::KeysAssign(EnvAssignment& a, const char* what, const int32_t* env_ids, int n, const int32_t* keys)
 {
 	int rc = KeysIdle(a, what, 0);
@@ -1842,8 +1863,7 @@ int Engine::KeysGet(const EnvAssignment& a, const char* what, const int32_t* env
 {
 	const std::string w = std::string(what) + ": ";
 	if (a.filled.empty()) return Fail(DTRL_ERR_ARG, w + a.none_text);
-	if (n < 0 || n > n_ || (n > 0 && !keys_out)) return Fail(DTRL_ERR_ARG, w + a.noun + "s_out is required and the env count must be 0 .. num_envs");
-	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range"); }
+	if (int rc = CheckEnvList(w, env_ids, n, "", (std::string(a.noun) + "s_out").c_str(), keys_out); rc != DTRL_OK) return rc;
 	for (int i = 0; i < n; ++i) keys_out[i] = a.env_key[EnvIndex(env_ids, i)];
 	return DTRL_OK;
 }
@@ -2048,48 +2068,32 @@ int Engine::VariantLoad(int v, const char* character_file, const char* text, siz
 // The rule is var_redraw_step (dtrl_terrain_dev.h), run at an env's episode start in front of the reset launch: by HostFrameWork's status loop (host terrain), by
 // Backend::VariantRedraw queued between the boundary work and the reset launch (-terrain_gen= device), by RedrawListed under dtrl_reset. dtrl_engine.h says who
 // owns the key array when.
-int Engine::VariantRefresh()
-{
-	if (!RedrawOnDevice() || !redraw_stale_) return DTRL_OK;
-	if (!be_->D2H(variant_keys_.env_key.data(), variant_keys_.d_env_key, sizeof(int32_t) * variant_keys_.env_key.size())
-		|| !be_->D2H(redraw_rec_.data(), d_redraw_, sizeof(RedrawRec) * redraw_rec_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	redraw_stale_ = false;
-	return DTRL_OK;
-}
-int Engine::VariantIdle(const char* what)
-{
-	if (!RedrawOnDevice()) return DTRL_OK;
-	if (int rc = KeysIdle(variant_keys_, what, 0); rc != DTRL_OK) return rc;
-	return VariantRefresh();
-}
 int Engine::AssignVariants(const int32_t* env_ids, int n, const int32_t* variants)
 {
-	if (int rc = VariantIdle("dtrl_assign_variants"); rc != DTRL_OK) return rc;   // (the whole-array upload below would otherwise undo every draw the kernel made)
+	if (int rc = KeysCurrent(variant_keys_, "dtrl_assign_variants"); rc != DTRL_OK) return rc;   // (the whole-array upload below would otherwise undo every draw the kernel made)
 	return KeysAssign(variant_keys_, "dtrl_assign_variants", env_ids, n, variants);
 }
 int Engine::GetVariants(const int32_t* env_ids, int n, int32_t* variants_out)
 {
-	if (int rc = VariantIdle("dtrl_get_variants"); rc != DTRL_OK) return rc;   // with a redraw on device terrain: the variants as of the last completed boundary
+	if (int rc = KeysCurrent(variant_keys_, "dtrl_get_variants"); rc != DTRL_OK) return rc;   // with a redraw on device terrain: the variants as of the last completed boundary
 	return KeysGet(variant_keys_, "dtrl_get_variants", env_ids, n, variants_out);
 }
 // (dtrl_reset only, never per frame: the streams are idle, and both arrays go up whole with synchronous copies -- O(num_envs) per call, whatever the list's length)
 int Engine::RedrawListed(const std::vector<int32_t>& ids)
 {
 	if (!redraw_on_ || ids.empty()) return DTRL_OK;
-	if (int rc = VariantRefresh(); rc != DTRL_OK) return rc;
-	RedrawCfg rd = redraw_; rd.cum = redraw_cum_.data();
-	for (int32_t e : ids) variant_keys_.env_key[e] = var_redraw_step(redraw_rec_[e], variant_keys_.env_key[e], true, rd, rd.cum, e);
-	if (!be_->H2D(variant_keys_.d_env_key, variant_keys_.env_key.data(), sizeof(int32_t) * variant_keys_.env_key.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	if (cfg_.device_terrain && !be_->H2D(d_redraw_, redraw_rec_.data(), sizeof(RedrawRec) * redraw_rec_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
+	if (int rc = KeysRefresh(variant_keys_); rc != DTRL_OK) return rc;
+	RedrawCfg rd = redraw_cfg_; rd.cum = redraw_cum_.host.data();
+	for (int32_t e : ids) variant_keys_.env_key[e] = var_redraw_step(redraw_.host[e], variant_keys_.env_key[e], true, rd, rd.cum, e);
+	return DevOk(be_->H2D(variant_keys_.d_env_key, variant_keys_.env_key.data(), sizeof(int32_t) * variant_keys_.env_key.size()) && redraw_.Push(*be_));
 }
 
 int Engine::VariantRedraw(int lo, int hi, uint64_t seed, const double* weights)
 {
 	const std::string w = "dtrl_variant_redraw: ";
 	if (int rc = KeysIdle(variant_keys_, "dtrl_variant_redraw", 0); rc != DTRL_OK) return rc;
-	if (int rc = VariantRefresh(); rc != DTRL_OK) return rc;   // (a redraw in place: the host keys and counters are current again before it goes or is replaced)
-	if (lo > hi) { redraw_on_ = false; return DTRL_OK; }        // the envs keep the variants they have, the counters stay
+	if (int rc = KeysRefresh(variant_keys_); rc != DTRL_OK) return rc;   // (a redraw in place: the host keys and counters are current again before it goes or is replaced)
+	if (lo > hi) { redraw_on_ = variant_keys_.on_device = false; return DTRL_OK; }   // the envs keep the variants they have, the counters stay
 	const int V = variant_keys_.n_keys();
 	if (lo < 0 || hi >= V) return Fail(DTRL_ERR_ARG, w + "variants " + std::to_string(lo) + " .. " + std::to_string(hi) + " out of range (variants 0 .. " + std::to_string(V - 1) + ")");
 	for (int v = lo; v <= hi; ++v) if (!variant_keys_.filled[v]) return Fail(DTRL_ERR_ARG, w + "variant " + std::to_string(v) + " " + variant_keys_.empty_text + ": every variant of the redraw must be filled");
@@ -2105,18 +2109,16 @@ int Engine::VariantRedraw(int lo, int hi, uint64_t seed, const double* weights)
 	if (!std::isfinite(sum)) return Fail(DTRL_ERR_ARG, w + "the sum of the weights is not a finite number");
 	for (int j = 0; j < m; ++j) cum[j] /= sum;
 	cum[m - 1] = 1.0;
-	if (cfg_.device_terrain && !d_redraw_) {
-		RedrawRec* recs = static_cast<RedrawRec*>(be_->Alloc(sizeof(RedrawRec) * static_cast<size_t>(n_)));
-		double* table = static_cast<double*>(be_->Alloc(sizeof(double) * static_cast<size_t>(V)));
-		if (!recs || !table) { if (recs) be_->Free(recs); if (table) be_->Free(table); return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error()); }
-		allocs_.push_back(recs); allocs_.push_back(table);
-		d_redraw_ = recs; d_redraw_cum_ = table;
+	if (cfg_.device_terrain) {
+		if (int rc = RecsAlloc(redraw_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
+		if (int rc = RecsAlloc(redraw_cum_, static_cast<size_t>(V)); rc != DTRL_OK) return rc;
 	}
-	if (redraw_rec_.empty()) redraw_rec_.assign(static_cast<size_t>(n_), RedrawRec{0});
-	if (cfg_.device_terrain && (!be_->H2D(d_redraw_cum_, cum.data(), sizeof(double) * cum.size()) || !be_->H2D(d_redraw_, redraw_rec_.data(), sizeof(RedrawRec) * redraw_rec_.size()))) return Fail(DTRL_ERR_DEVICE, be_->error());
-	redraw_cum_.swap(cum);
-	redraw_ = RedrawCfg{lo, hi, seed, static_cast<int64_t>(cfg_.run.env_id_base), d_redraw_cum_};
-	redraw_on_ = true; redraw_stale_ = false;
+	if (redraw_.host.empty()) redraw_.host.assign(static_cast<size_t>(n_), RedrawRec{0});
+	redraw_cum_.host.swap(cum);
+	if (int rc = DevOk(redraw_cum_.Push(*be_) && redraw_.Push(*be_)); rc != DTRL_OK) return rc;
+	redraw_cfg_ = RedrawCfg{lo, hi, seed, static_cast<int64_t>(cfg_.run.env_id_base), redraw_cum_.dev};
+	redraw_on_ = true;
+	variant_keys_.recs = &redraw_; variant_keys_.on_device = cfg_.device_terrain; variant_keys_.stale = false;
 	return DTRL_OK;
 }
 
@@ -2125,15 +2127,14 @@ int Engine::VariantRedrawInfo(const int32_t* env_ids, int n, int32_t* lo, int32_
 	const std::string w = "dtrl_variant_redraw_info: ";
 	if (int rc = KeysIdle(variant_keys_, "dtrl_variant_redraw_info", 0); rc != DTRL_OK) return rc;
 	if (!redraw_on_) return Fail(DTRL_ERR_ARG, w + "the batch has no variant redraw (call dtrl_variant_redraw first)");
-	if (int rc = VariantRefresh(); rc != DTRL_OK) return rc;
-	if (n < 0 || n > n_) return Fail(DTRL_ERR_ARG, w + "the env count must be 0 .. num_envs");
-	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range"); }
-	if (lo) *lo = redraw_.lo;
-	if (hi) *hi = redraw_.hi;
+	if (int rc = KeysRefresh(variant_keys_); rc != DTRL_OK) return rc;
+	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
+	if (lo) *lo = redraw_cfg_.lo;
+	if (hi) *hi = redraw_cfg_.hi;
 	for (int i = 0; i < n; ++i) {
 		const int e = EnvIndex(env_ids, i);
 		if (variant) variant[i] = variant_keys_.env_key[e];
-		if (draws) draws[i] = redraw_rec_[e].draws;
+		if (draws) draws[i] = redraw_.host[e].draws;
 	}
 	return DTRL_OK;
 }
@@ -2144,22 +2145,17 @@ int Engine::VariantRedrawInfo(const int32_t* env_ids, int n, int32_t* lo, int32_
 // Records and scales live in device memory only.
 int Engine::PushAlloc()
 {
-	if (d_push_) return DTRL_OK;
-	PushRec* recs = static_cast<PushRec*>(be_->Alloc(sizeof(PushRec) * static_cast<size_t>(n_)));
-	double* scales = static_cast<double*>(be_->Alloc(sizeof(double) * static_cast<size_t>(n_)));
-	if (!recs || !scales) { if (recs) be_->Free(recs); if (scales) be_->Free(scales); return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error()); }
-	allocs_.push_back(recs); allocs_.push_back(scales);
-	std::vector<PushRec> r0(static_cast<size_t>(n_), PushRec{0, 0u, 0, -1, {0.0, 0.0}, 0.0});   // (last_link -1: no push yet)
-	std::vector<double> one(static_cast<size_t>(n_), 1.0);
-	if (!be_->H2D(recs, r0.data(), sizeof(PushRec) * r0.size()) || !be_->H2D(scales, one.data(), sizeof(double) * one.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	d_push_ = recs; d_push_scale_ = scales;
-	return DTRL_OK;
+	if (push_.dev && push_scale_.dev) return DTRL_OK;
+	if (int rc = RecsAlloc(push_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
+	if (int rc = RecsAlloc(push_scale_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
+	push_.host.assign(static_cast<size_t>(n_), PushRec{0, 0u, 0, -1, {0.0, 0.0}, 0.0});   // (last_link -1: no push yet)
+	push_scale_.host.assign(static_cast<size_t>(n_), 1.0);
+	return DevOk(push_.Push(*be_) && push_scale_.Push(*be_));
 }
 int Engine::PushStart(int n_listed)
 {
 	if (!push_on_ || n_listed <= 0) return DTRL_OK;
-	if (!be_->PushSchedule(nullptr, 0, n_listed, zero_copy_ ? pin_ids_ : d_env_list_, buf_.st, d_push_, d_push_scale_, push_)) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
+	return DevOk(be_->PushSchedule(nullptr, EnvSpan{0, n_listed, zero_copy_ ? pin_ids_ : d_env_list_}, buf_.st, push_.dev, push_scale_.dev, push_cfg_));
 }
 int Engine::PushSchedule(int min_wait, int max_wait, uint64_t seed, double min_force, double max_force, double min_dur, double max_dur)
 {
@@ -2178,40 +2174,34 @@ int Engine::PushSchedule(int min_wait, int max_wait, uint64_t seed, double min_f
 	if (min_force > max_force) return Fail(DTRL_ERR_ARG, w + "min_force exceeds max_force");
 	if (min_dur > max_dur) return Fail(DTRL_ERR_ARG, w + "min_dur exceeds max_dur");
 	if (int rc = PushAlloc(); rc != DTRL_OK) return rc;
-	push_ = PushCfg{min_wait, max_wait, min_force, max_force, min_dur, max_dur, seed, static_cast<int64_t>(cfg_.run.env_id_base), cfg_.model.L, 0};
+	push_cfg_ = PushCfg{min_wait, max_wait, min_force, max_force, min_dur, max_dur, seed, static_cast<int64_t>(cfg_.run.env_id_base), cfg_.model.L, 0};
 	push_on_ = true;
 	// every env of the schedule draws its first wait under the new settings (the counters go on where they were)
-	if (!be_->PushSchedule(nullptr, 0, n_, nullptr, buf_.st, d_push_, d_push_scale_, push_) || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
+	return DevOk(be_->PushSchedule(nullptr, EnvSpan{0, n_, nullptr}, buf_.st, push_.dev, push_scale_.dev, push_cfg_) && be_->Sync());
 }
 int Engine::PushScale(const int32_t* env_ids, int n, const double* scales)
 {
 	const std::string w = "dtrl_push_scale: ";
 	if (int rc = RequireIdle("dtrl_push_scale" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
-	if (n < 0 || n > n_ || (n > 0 && !scales)) return Fail(DTRL_ERR_ARG, w + "scales is required and the env count must be 0 .. num_envs");
+	if (int rc = CheckEnvList(w, env_ids, n, "; nothing changed", "scales", scales); rc != DTRL_OK) return rc;
 	for (int i = 0; i < n; ++i) {   // all or nothing
 		const int e = EnvIndex(env_ids, i);
-		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range; nothing changed");
 		if (!(scales[i] >= 0) || !std::isfinite(scales[i])) return Fail(DTRL_ERR_ARG, w + "scale " + std::to_string(scales[i]) + " of env " + std::to_string(e) + " must be a non-negative finite number; nothing changed");
 	}
 	if (int rc = PushAlloc(); rc != DTRL_OK) return rc;
-	std::vector<double> all(static_cast<size_t>(n_));
-	if (!be_->D2H(all.data(), d_push_scale_, sizeof(double) * all.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	for (int i = 0; i < n; ++i) all[EnvIndex(env_ids, i)] = scales[i];
-	if (!be_->H2D(d_push_scale_, all.data(), sizeof(double) * all.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
+	if (int rc = DevOk(push_scale_.Pull(*be_)); rc != DTRL_OK) return rc;
+	for (int i = 0; i < n; ++i) push_scale_.host[EnvIndex(env_ids, i)] = scales[i];
+	return DevOk(push_scale_.Push(*be_));
 }
 int Engine::PushInfo(const int32_t* env_ids, int n, int32_t* wait, int32_t* pushes, int32_t* last_link, double* last_force, double* last_dur)
 {
 	const std::string w = "dtrl_push_info: ";
 	if (int rc = RequireIdle("dtrl_push_info" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
-	if (!d_push_) return Fail(DTRL_ERR_ARG, w + "the batch has no push schedule (call dtrl_push_schedule first)");
-	if (n < 0 || n > n_) return Fail(DTRL_ERR_ARG, w + "the env count must be 0 .. num_envs");
-	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range"); }
-	std::vector<PushRec> recs(static_cast<size_t>(n_));
-	if (!be_->D2H(recs.data(), d_push_, sizeof(PushRec) * recs.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (!push_.dev) return Fail(DTRL_ERR_ARG, w + "the batch has no push schedule (call dtrl_push_schedule first)");
+	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
+	if (int rc = DevOk(push_.Pull(*be_)); rc != DTRL_OK) return rc;
 	for (int i = 0; i < n; ++i) {
-		const PushRec& r = recs[EnvIndex(env_ids, i)];
+		const PushRec& r = push_.host[EnvIndex(env_ids, i)];
 		if (wait) wait[i] = r.wait;
 		if (pushes) pushes[i] = r.pushes;
 		if (last_link) last_link[i] = r.last_link;
@@ -2225,7 +2215,7 @@ int Engine::PushInfo(const int32_t* env_ids, int n, int32_t* wait, int32_t* push
 // The third per-env key family, and the one no frame launch reads: a terrain decides what an env's NEXT segments look like, and segments are built at the frame
 // boundary -- by the env's GroundWindow on the host, or by the boundary kernel (-terrain_gen= device), which takes the table and the per-env array as two extra
 // pointers. So terrains neither touch LaunchEnvs nor exclude slots, variants or external policy mode. The timing rules are those of the other families (KeysIdle).
-// With a terrain ladder on device terrain the DEVICE key array is the truth while frames run: the calls that read or upload it refresh the host copy first (LadderIdle).
+// With a terrain ladder on device terrain the DEVICE key array is the truth while frames run: the calls that read or upload it refresh the host copy first (KeysCurrent).
 int Engine::TerrainsCreate(int n_terrains)
 {
 	if (n_terrains < 1 || n_terrains > n_) return Fail(DTRL_ERR_ARG, "dtrl_terrains_create: n_terrains must be 1 .. num_envs (" + std::to_string(n_) + "), not " + std::to_string(n_terrains));
@@ -2304,7 +2294,7 @@ int Engine::TerrainInfo(int t, char* type_out, int type_cap, double* params40_ou
 int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrains, bool restart)
 {
 	const char* what = "dtrl_assign_terrains";
-	if (int rc = LadderIdle(what); rc != DTRL_OK) return rc;   // (with a ladder on device terrain the upload below would otherwise overwrite every move the kernel made)
+	if (int rc = KeysCurrent(terrain_keys_, what, ladder_on_); rc != DTRL_OK) return rc;   // (with a ladder on device terrain the upload below would otherwise overwrite every move the kernel made)
 	if (int rc = KeysAssign(terrain_keys_, what, env_ids, n, terrains); rc != DTRL_OK) return rc;
 	reset_ids_.clear();
 	std::vector<char> seen(static_cast<size_t>(n_), 0);
@@ -2312,10 +2302,10 @@ int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrain
 	if (ladder_on_) {
 		// the listed envs' marks: the env's current root x, or -- restart -- the spawn point (host terrain here; device terrain: the mode-2 boundary launch below)
 		for (int32_t e : reset_ids_) {
-			if (restart) { if (!cfg_.device_terrain) tg_ladder_step(ladder_rec_[e], terrain_keys_.env_key[e], status_[e], ladder_, 2, e); }
-			else if (int rc = RootX(e, &ladder_rec_[e].mark_x); rc != DTRL_OK) return rc;
+			if (restart) { if (!cfg_.device_terrain) tg_ladder_step(ladder_.host[e], terrain_keys_.env_key[e], status_[e], ladder_cfg_, 2, e); }
+			else if (int rc = RootX(e, &ladder_.host[e].mark_x); rc != DTRL_OK) return rc;
 		}
-		if (int rc = LadderUpload(); rc != DTRL_OK) return rc;
+		if (int rc = DevOk(ladder_.Push(*be_)); rc != DTRL_OK) return rc;
 	}
 	if (!cfg_.device_terrain) {
 		for (int32_t e : reset_ids_) {
@@ -2336,7 +2326,7 @@ int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrain
 		for (int32_t e : reset_ids_) gen[e].key = terrain_stream_key(cfg_.terrain_seed, cfg_.run.env_id_base + e);
 		std::memcpy(pin_ids_, reset_ids_.data(), sizeof(int32_t) * reset_ids_.size());
 		if (!be_->H2D(buf_.gen, gen.data(), sizeof(GroundGen) * gen.size()) || !be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size())
-			|| !Boundary(0, static_cast<int>(reset_ids_.size()), 2, d_env_list_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+			|| !Boundary(EnvSpan{0, static_cast<int>(reset_ids_.size()), d_env_list_}, 2)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
 	if (int rc = ApplyResets(reset_ids_, -1); rc != DTRL_OK) return rc;
 	if (int rc = PushStart(static_cast<int>(reset_ids_.size())); rc != DTRL_OK) return rc;   // push schedule: the listed envs start over, a new wait each
@@ -2346,13 +2336,13 @@ int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrain
 
 int Engine::GetTerrains(const int32_t* env_ids, int n, int32_t* terrains_out)
 {
-	if (int rc = LadderIdle("dtrl_get_terrains"); rc != DTRL_OK) return rc;   // with a ladder: the levels as of the last completed boundary
+	if (int rc = KeysCurrent(terrain_keys_, "dtrl_get_terrains", ladder_on_); rc != DTRL_OK) return rc;   // with a ladder: the levels as of the last completed boundary
 	return KeysGet(terrain_keys_, "dtrl_get_terrains", env_ids, n, terrains_out);
 }
 
 // ---- terrain ladder (include/dtrl.h: dtrl_terrain_ladder, dtrl_ladder_info) ----
 // The rule is tg_ladder_step (dtrl_terrain_dev.h), run at every frame boundary in front of the env's terrain work: by HostFrameWork / Reset / AssignTerrains on
-// the host (host terrain), inside the boundary launch (-terrain_gen= device, Backend::TerrainBoundaryLadder). dtrl_engine.h says who owns the key array when.
+// the host (host terrain), inside the boundary launch (-terrain_gen= device, Backend::TerrainBoundary). dtrl_engine.h says who owns the key array when.
 int Engine::RootX(int e, double* x)
 {
 	real q0 = 0;
@@ -2360,32 +2350,12 @@ int Engine::RootX(int e, double* x)
 	*x = static_cast<double>(q0);
 	return DTRL_OK;
 }
-int Engine::LadderRefresh()
-{
-	if (!ladder_on_ || !cfg_.device_terrain) return DTRL_OK;
-	if (!be_->D2H(terrain_keys_.env_key.data(), terrain_keys_.d_env_key, sizeof(int32_t) * terrain_keys_.env_key.size())
-		|| !be_->D2H(ladder_rec_.data(), d_ladder_, sizeof(LadderRec) * ladder_rec_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
-}
-int Engine::LadderUpload()
-{
-	if (!ladder_on_ || !cfg_.device_terrain) return DTRL_OK;
-	if (!be_->H2D(d_ladder_, ladder_rec_.data(), sizeof(LadderRec) * ladder_rec_.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
-}
-int Engine::LadderIdle(const char* what)
-{
-	if (!ladder_on_) return DTRL_OK;
-	if (int rc = KeysIdle(terrain_keys_, what, 0); rc != DTRL_OK) return rc;
-	return LadderRefresh();
-}
-
 int Engine::TerrainLadder(int lo, int hi, double up_dist, double down_dist, int at_top)
 {
 	const std::string w = "dtrl_terrain_ladder: ";
 	if (int rc = KeysIdle(terrain_keys_, "dtrl_terrain_ladder", 0); rc != DTRL_OK) return rc;
-	if (int rc = LadderRefresh(); rc != DTRL_OK) return rc;   // (a ladder in place: the host keys are current again before it goes or is replaced)
-	if (lo > hi) { ladder_on_ = false; return DTRL_OK; }       // the levels stay where they are
+	if (int rc = KeysRefresh(terrain_keys_); rc != DTRL_OK) return rc;   // (a ladder in place: the host keys are current again before it goes or is replaced)
+	if (lo > hi) { ladder_on_ = terrain_keys_.on_device = false; return DTRL_OK; }   // the levels stay where they are
 	const int T = terrain_keys_.n_keys();
 	if (lo < 0 || hi >= T) return Fail(DTRL_ERR_ARG, w + "levels " + std::to_string(lo) + " .. " + std::to_string(hi) + " out of range (terrains 0 .. " + std::to_string(T - 1) + ")");
 	for (int t = lo; t <= hi; ++t) if (!terrain_keys_.filled[t]) return Fail(DTRL_ERR_ARG, w + "terrain " + std::to_string(t) + " " + terrain_keys_.empty_text + ": every level of the ladder must be filled");
@@ -2397,17 +2367,14 @@ int Engine::TerrainLadder(int lo, int hi, double up_dist, double down_dist, int 
 	const double spawn_x = spawn_of(cfg_.model);
 	for (size_t v = 0; v < var_models_.size(); ++v)
 		if (spawn_of(var_models_[v]) != spawn_x) return Fail(DTRL_ERR_ARG, w + "model variant " + std::to_string(v) + " spawns at another root x (" + std::to_string(spawn_of(var_models_[v])) + ") than the batch's model (" + std::to_string(spawn_x) + "): the ladder keeps one spawn x per batch");
-	if (cfg_.device_terrain && !d_ladder_) {
-		d_ladder_ = static_cast<LadderRec*>(be_->Alloc(sizeof(LadderRec) * static_cast<size_t>(n_)));
-		if (!d_ladder_) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
-		allocs_.push_back(d_ladder_);
-	}
+	if (cfg_.device_terrain) if (int rc = RecsAlloc(ladder_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
 	std::vector<LadderRec> rec(static_cast<size_t>(n_));
 	for (int e = 0; e < n_; ++e) { rec[e].ups = 0; rec[e].downs = 0; if (int rc = RootX(e, &rec[e].mark_x); rc != DTRL_OK) return rc; }
-	ladder_rec_.swap(rec);
-	ladder_ = LadderCfg{lo, hi, at_top, 0, up_dist, down_dist, spawn_x, cfg_.terrain_seed, static_cast<int64_t>(cfg_.run.env_id_base)};
+	ladder_.host.swap(rec);
+	ladder_cfg_ = LadderCfg{lo, hi, at_top, 0, up_dist, down_dist, spawn_x, cfg_.terrain_seed, static_cast<int64_t>(cfg_.run.env_id_base)};
 	ladder_on_ = true;
-	return LadderUpload();
+	terrain_keys_.recs = &ladder_; terrain_keys_.on_device = cfg_.device_terrain; terrain_keys_.stale = false;
+	return DevOk(ladder_.Push(*be_));
 }
 
 int Engine::LadderInfo(const int32_t* env_ids, int n, double* mark_x_out, int32_t* ups_out, int32_t* downs_out)
@@ -2415,11 +2382,10 @@ int Engine::LadderInfo(const int32_t* env_ids, int n, double* mark_x_out, int32_
 	const std::string w = "dtrl_ladder_info: ";
 	if (terrain_keys_.filled.empty()) return Fail(DTRL_ERR_ARG, w + terrain_keys_.none_text);
 	if (!ladder_on_) return Fail(DTRL_ERR_ARG, w + "the batch has no terrain ladder (call dtrl_terrain_ladder first)");
-	if (int rc = LadderIdle("dtrl_ladder_info"); rc != DTRL_OK) return rc;
-	if (n < 0 || n > n_) return Fail(DTRL_ERR_ARG, w + "the env count must be 0 .. num_envs");
-	for (int i = 0; i < n; ++i) { const int e = EnvIndex(env_ids, i); if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range"); }
+	if (int rc = KeysCurrent(terrain_keys_, "dtrl_ladder_info", true); rc != DTRL_OK) return rc;
+	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
 	for (int i = 0; i < n; ++i) {
-		const LadderRec& r = ladder_rec_[EnvIndex(env_ids, i)];
+		const LadderRec& r = ladder_.host[EnvIndex(env_ids, i)];
 		if (mark_x_out) mark_x_out[i] = r.mark_x;
 		if (ups_out) ups_out[i] = r.ups;
 		if (downs_out) downs_out[i] = r.downs;

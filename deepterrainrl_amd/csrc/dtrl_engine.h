@@ -58,6 +58,9 @@ struct EnvKeyView {
 // per-slot totals of dtrl_slot_stats (Backend::SlotReduce): envs in the slot, and over them the sums dtrl_eval_stats takes over the batch
 struct SlotSums { int64_t n_envs, episodes, cycles, resets; double dist_sum; };   // dist_sum = sum of avg_dist * num_episodes
 
+// which TerrainCfg the terrain work of an env runs under, and the ladder's rule in front of it (Backend::TerrainBoundary). All null: the batch's own *buf.tcfg
+struct TerrainRule { const TerrainCfg* table = nullptr; int32_t* env_terrain = nullptr; LadderRec* ladder = nullptr; LadderCfg lc{}; };
+
 class Backend {
 public:
 	virtual ~Backend() {}
@@ -112,34 +115,29 @@ public:
 	virtual bool GatherF32(float* dst, const float* src, const int32_t* idx, size_t n) = 0;
 	// the same on a stream of the caller's (a hipStream_t; nullptr = the selected stream), synchronised: work the caller has queued there comes first
 	virtual bool GatherF32On(void* stream, float* dst, const float* src, const int32_t* idx, size_t n) { (void)stream; return GatherF32(dst, src, idx, n); }
-	// -terrain_gen= device: the frame-boundary terrain work of envs [e0, e0 + n) (or of env_list[0 .. n) when given), queued on the selected stream
-	// (tg_env_boundary, dtrl_terrain_dev.h); mode 0 = after a frame, 1 = (re)initialise
-	virtual bool TerrainBoundary(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list) = 0;
-	// Terrain sets (include/dtrl.h dtrl_terrains_create ...): the same work with one TerrainCfg per env -- env e is built under table[env_terrain[e]] instead of
-	// *buf.tcfg (table / env_terrain / env_list: device memory, env_terrain indexed by local env id); mode 2 = re-seed + initialise (tg_env_boundary). The default
-	// fetches each listed env's GroundRec / GroundGen / EnvStatus, runs tg_env_boundary on the host and writes the records back, synchronised (what the lane-loop
-	// check build runs, and DTRL_TERRAINS_FALLBACK=1 on HIP); the HIP backend overrides it with one launch of dtrl_terrain_boundary_keyed on the selected stream.
-	virtual bool TerrainBoundaryKeyed(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, const int32_t* env_terrain);
-	// Terrain ladder (include/dtrl.h dtrl_terrain_ladder): the keyed work with the rule in front of it -- env e's level moves by its status record (tg_ladder_step,
-	// dtrl_terrain_dev.h), env_terrain[e] and ladder[e] (device memory, local env id) are written back, and the env is built under table[its new level]. The
-	// default is the keyed default's host loop with the rule in it (the lane-loop check build, DTRL_TERRAINS_FALLBACK=1 on HIP); the HIP backend overrides it with
-	// one launch of dtrl_terrain_boundary_ladder on the selected stream.
-	virtual bool TerrainBoundaryLadder(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list, const TerrainCfg* table, int32_t* env_terrain, LadderRec* ladder, const LadderCfg& lc);
-	// Variant redraw (include/dtrl.h dtrl_variant_redraw): the rule (var_redraw_step, dtrl_terrain_dev.h) for envs [e0, e0 + n) (or env_list[0 .. n) when given) at
-	// a frame boundary -- an env with status[e].need_reset & 1 whose variant is inside [cfg.lo, cfg.hi] draws; env_model[e] and recs[e] (device memory, local env
-	// id) are written back where they changed. status / env_list / cfg.cum are device memory too. The default is a host loop with per-env D2H / H2D, synchronised
-	// (the lane-loop check build, DTRL_VARIANTS_FALLBACK=1 on HIP); the HIP backend overrides it with one launch of dtrl_variant_redraw on the selected stream.
-	virtual bool VariantRedraw(const EnvStatus* status, int e0, int n, const int32_t* env_list, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg);
-	// Push schedule (include/dtrl.h dtrl_push_schedule): the rule (push_step, dtrl_terrain_dev.h) for envs [e0, e0 + n) (or env_list[0 .. n) when given) at a frame
-	// boundary. status != nullptr: an env with status[e].need_reset != 0 starts an episode (its wait is drawn afresh), any other counts down and is pushed at 0;
-	// status == nullptr: every listed env starts (creation of the schedule, dtrl_reset, a terrain restart). recs[e], scale[e] and the seven slot fields of st[e] are
-	// device memory under the local env id; record and slot are written back only where they changed, an env of scale 0 is not touched. The default is a host loop
-	// with per-env D2H / H2D of the record and of the slot fields, behind a wait for the selected stream (the lane-loop check build, DTRL_PUSH_FALLBACK=1 on HIP);
-	// the HIP backend overrides it with one launch of dtrl_push_schedule on the selected stream.
-	virtual bool PushSchedule(const EnvStatus* status, int e0, int n, const int32_t* env_list, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg);
-	// dtrl_add_perturb: rows[0 .. n) (device memory, at most one row per env) into the perturbation slots of st[rows[i].env]. The default copies each env's whole
-	// EnvState down, edits the seven fields and copies it back (the lane-loop check build, DTRL_PERTURB_FALLBACK=1 on HIP); the HIP backend overrides it with one
-	// launch of dtrl_perturb_scatter on the selected stream.
+	// ---- the per-env rules of the frame boundary (dtrl_terrain_dev.h), each over an EnvSpan and queued on the selected stream ----
+	// Every default is a host loop over the span's envs with per-env D2H / H2D of what the rule reads and writes, synchronised -- what the lane-loop check build
+	// runs, and DTRL_TERRAINS_FALLBACK=1 / DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 / DTRL_PERTURB_FALLBACK=1 on HIP; the HIP backend overrides each with ONE
+	// launch of its kernel. All per-env arrays are device memory under the local env id, and are written back only where the rule changed them.
+	// the span as a host vector (a list is read back: the copy waits for the selected stream)
+	bool SpanList(const EnvSpan& span, std::vector<int32_t>& list);
+	// -terrain_gen= device: the terrain work (tg_env_boundary); mode 0 = after a frame, 1 = (re)initialise, 2 = re-seed + initialise. `rule` says under which
+	// TerrainCfg env e is built: *buf.tcfg (no table), table[env_terrain[e]] (terrain sets, include/dtrl.h dtrl_terrains_create ...), or -- with ladder records
+	// (dtrl_terrain_ladder) -- table[its new level] after tg_ladder_step has moved env_terrain[e] and ladder[e] in front of the terrain work, in the same launch
+	virtual bool TerrainBoundary(const DevBuffers& buf, const EnvSpan& span, int mode, const TerrainRule& rule);
+	// where the default above sends the rule-less case (the batch's own terrain): a backend whose host addresses device memory runs tg_env_boundary in place (the
+	// lane-loop check build); else the same host loop (TerrainBoundaryLoop: the body of both defaults). The engine calls the entry above only.
+	virtual bool TerrainBoundary(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list);
+	bool TerrainBoundaryLoop(const DevBuffers& buf, const EnvSpan& span, int mode, const TerrainRule& rule);
+	// Variant redraw (include/dtrl.h dtrl_variant_redraw; var_redraw_step): an env with status[e].need_reset & 1 whose variant is inside [cfg.lo, cfg.hi] draws;
+	// env_model[e] and recs[e] move. cfg.cum is device memory too.
+	virtual bool VariantRedraw(const EnvStatus* status, const EnvSpan& span, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg);
+	// Push schedule (include/dtrl.h dtrl_push_schedule; push_step). status != nullptr: an env with status[e].need_reset != 0 starts an episode (its wait is drawn
+	// afresh), any other counts down and is pushed at 0; status == nullptr: every env of the span starts (creation of the schedule, dtrl_reset, a terrain
+	// restart). recs[e] and the seven slot fields of st[e] move; an env of scale[e] == 0 is not touched. The default waits for the selected stream first.
+	virtual bool PushSchedule(const EnvStatus* status, const EnvSpan& span, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg);
+	// dtrl_add_perturb: rows[0 .. n) (device memory, at most one row per env: the row names its env, so there is no span) into the perturbation slots of
+	// st[rows[i].env] (perturb_write_slot). The default copies each env's whole EnvState down, edits the seven fields and copies it back.
 	virtual bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n);
 	// order[e0 .. e0 + n) = the envs e0 .. e0 + n - 1 sorted by status[].cost, costliest first (launch order of the group's next frame), on the selected stream
 	virtual bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) = 0;
@@ -254,7 +252,7 @@ public:
 	int num_terrains() const { return terrain_keys_.n_keys(); }
 	// the model env e (local id, in range) runs under: what host-side readers of per-env geometry use (dtrl_get_link_states, AddPerturb). With a redraw on device
 	// terrain the caller brings the host keys up to date first (VariantKeysCurrent, once per call, behind a wait for the streams)
-	int VariantKeysCurrent() { return VariantRefresh(); }
+	int VariantKeysCurrent() { return KeysRefresh(variant_keys_); }
 	const DevModel& ModelOf(int e) const { return var_models_.empty() ? cfg_.model : var_models_[variant_keys_.env_key[e]]; }
 	~Engine();
 	int Create(const char* const* argv, int argc, int num_envs, int device_id);
@@ -316,12 +314,14 @@ private:
 	int DrainDeviceDistLog();
 	int UploadTerrainCfg(const double* params);
 	TerrainCfg MakeTerrainCfg(int type, const double* params) const;   // the scene constants of a TerrainCfg are the batch's
-	// -terrain_gen= device: the boundary work of every caller -- Backend::TerrainBoundary as it always was, once terrains exist the keyed form, with a ladder the ladder form
-	bool Boundary(int e0, int n, int mode, const int32_t* env_list)
+	// -terrain_gen= device: the boundary work of every caller, under the rule in force -- the batch's own terrain, once terrains exist the env's table entry, with a
+	// ladder its rule in front of that (which moves the device keys and records: the host copies go stale)
+	bool Boundary(const EnvSpan& span, int mode)
 	{
-		if (terrain_keys_.filled.empty()) return be_->TerrainBoundary(buf_, e0, n, mode, env_list);
-		if (!ladder_on_) return be_->TerrainBoundaryKeyed(buf_, e0, n, mode, env_list, d_terrain_table_, terrain_keys_.d_env_key);
-		return be_->TerrainBoundaryLadder(buf_, e0, n, mode, env_list, d_terrain_table_, terrain_keys_.d_env_key, d_ladder_, ladder_);
+		TerrainRule r;
+		if (!terrain_keys_.filled.empty()) { r.table = d_terrain_table_; r.env_terrain = terrain_keys_.d_env_key; }
+		if (ladder_on_) { r.ladder = ladder_.dev; r.lc = ladder_cfg_; terrain_keys_.stale = true; }
+		return be_->TerrainBoundary(buf_, span, mode, r);
 	}
 	int ApplyResets(const std::vector<int32_t>& ids, int group);
 	int LaunchGroup(int group, int n_steps, double dt_step, bool frame_end);
@@ -335,6 +335,10 @@ private:
 	bool UploadGround(int env);
 	bool FetchGroundRec(int env);
 	int EnvIndex(const int32_t* env_ids, int i) const { return env_ids ? env_ids[i] : i; }
+	// the env list of a per-env getter or setter: DTRL_ERR_ARG unless n is 0 .. num_envs (and `required`, the call's array `name`, is there when n > 0) and every id
+	// is in range. w: the call's prefix "dtrl_xxx: "; tail: what a refused setter adds ("; nothing changed")
+	int CheckEnvList(const std::string& w, const int32_t* env_ids, int n, const char* tail = "", const char* name = nullptr, const void* required = nullptr);
+	int DevOk(bool ok);   // DTRL_OK, or DTRL_ERR_DEVICE with the backend's error text
 
 	ScenarioConfig cfg_;
 	Backend* be_ = nullptr;
@@ -404,14 +408,39 @@ private:
 	// Per-env keys: what policy slots, model variants and terrain sets share (slots and variants exclude each other; terrains combine with either). A key is a slot, a variant or a terrain number; every env starts under
 	// key 0. The family's table and the per-env array are read by launches in flight and are therefore rewritten only by calls that have refused a frame in flight and
 	// waited for every stream (KeysIdle). The three texts are the family's own words in the refusals (they differ in more than the noun).
+	// WHO OWNS THE KEYS. The host array is the truth and the device array its copy (KeysAssign uploads it) -- also under a frame-boundary rule that moves keys
+	// (terrain ladder, variant redraw) in host terrain mode, where HostFrameWork runs the rule and uploads the group's slice. With such a rule and -terrain_gen=
+	// device the rule's kernel moves the DEVICE keys and the rule's device records (`recs`) while frames run (on_device): whoever queues such a launch sets `stale`,
+	// and every call that reads or uploads the keys or the records first waits for every stream and brings both host copies up to date (KeysCurrent, or KeysRefresh
+	// behind a wait of the caller's own), which clears it.
+	struct RecsBase { virtual ~RecsBase() {} virtual bool Pull(Backend& be) = 0; };
 	struct EnvAssignment {
 		const char* noun; const char* none_text; const char* empty_text;
 		std::vector<char> filled;                // per key: it may be assigned. Empty: the family was not created, every launch is Backend::Launch as it always was
 		std::vector<int32_t> env_key;            // host form of the per-env array
 		int32_t* d_env_key = nullptr; int32_t* part = nullptr;   // device array [n], page-locked [2 n] (the scratch of the per-key default's list split)
+		bool on_device = false, stale = false; RecsBase* recs = nullptr;   // a rule moves the keys on the device / has been queued since the last refresh / its records
 		int n_keys() const { return static_cast<int>(filled.size()); }
-		EnvKeyView View(const int32_t* list_host, int part_off) const { EnvKeyView v; v.n_keys = n_keys(); v.env_key_dev = d_env_key; v.env_key_host = env_key.data(); v.env_list_host = list_host; v.part = part + part_off; return v; }
+		EnvKeyView View(const int32_t* list_host, int part_off) const { EnvKeyView v; v.n_keys = n_keys(); v.env_key_dev = d_env_key; v.env_key_host = env_key.data(); v.keys_on_device = on_device; v.env_list_host = list_host; v.part = part + part_off; return v; }
 	};
+	// The per-env records of a frame-boundary rule: a device array [count] and a host form, which is the truth without a device array (a rule the host runs),
+	// its copy with one, or only the staging of Pull / Push (records that live on the device alone)
+	template <class Rec> struct RuleRecs : RecsBase {
+		std::vector<Rec> host; Rec* dev = nullptr; size_t count = 0;
+		bool Alloc(Backend& be, size_t n, std::vector<void*>& owner)   // once; zero-filled
+		{
+			if (dev) return true;
+			dev = static_cast<Rec*>(be.Alloc(sizeof(Rec) * n));
+			if (dev) { owner.push_back(dev); count = n; }
+			return dev != nullptr;
+		}
+		bool Pull(Backend& be) override { if (!dev) return true; host.resize(count); return be.D2H(host.data(), dev, sizeof(Rec) * count); }   // host <- device, all of it
+		bool Push(Backend& be) { return !dev || be.H2D(dev, host.data(), sizeof(Rec) * host.size()); }                                         // device <- host, as far as the host form goes
+	};
+	template <class Rec> int RecsAlloc(RuleRecs<Rec>& r, size_t n);   // (dtrl_engine.cpp)
+	int KeysRefresh(EnvAssignment& a);       // on_device and stale: host keys and the rule's records <- device (call with the streams idle); else nothing
+	// KeysIdle + KeysRefresh for an assignment whose keys move on the device; else nothing (`always`: KeysIdle even so -- the ladder's calls, in either terrain mode)
+	int KeysCurrent(EnvAssignment& a, const char* what, bool always = false);
 	void* KeysAllocate(EnvAssignment& a, size_t table_bytes);   // the family's device table (returned; nullptr: failed, error set), the per-env array and the scratch
 	// DTRL_ERR_ARG without keys / key out of range / frame in flight, else every stream idle. wait_in_flight (dtrl_slot_stats alone): a frame in flight is waited for
 	int KeysIdle(const EnvAssignment& a, const char* what, int key, bool wait_in_flight = false);
@@ -434,44 +463,30 @@ private:
 	std::vector<DevModel> var_models_; DevModel* d_var_models_ = nullptr;   // the table: host form (empty: no variants), device memory [n_variants]
 	// terrain sets. Terrain 0 is the batch's terrain (cfg_.terrain_type / terrain_param_sets at terrain_lerp_: what dtrl_set_terrain_lerp moves); a terrain >= 1 is
 	// empty until dtrl_terrain_set_* fills it. No frame launch reads the table: the consumers are the frame-boundary paths (host: each env's GroundWindow carries its
-	// terrain's type and parameters; device: Backend::TerrainBoundaryKeyed), so terrains combine with slots, variants and external policy mode
+	// terrain's type and parameters; device: Backend::TerrainBoundary), so terrains combine with slots, variants and external policy mode
 	struct TerrainSource { std::vector<std::vector<double>> sets; double lerp = 0; };   // where a terrain's parameters came from (a file's sets; empty: given directly)
 	EnvAssignment terrain_keys_{"terrain", "the batch has no terrain sets (call dtrl_terrains_create first)", "is empty (no dtrl_terrain_set_file / dtrl_terrain_set_params has filled it)"};
 	std::vector<TerrainCfg> terrain_table_; TerrainCfg* d_terrain_table_ = nullptr;   // the table: host form (empty: no terrains), device memory [n_terrains]
 	std::vector<TerrainSource> terrain_src_;
 	double terrain_lerp_ = 0;                // terrain 0's lerp in force
 	int TerrainFill(const char* what, int t, int type, const double* params);   // table entry t (>= 1) in both forms, and the windows of the envs under it
-	// terrain ladder: settings and per-env records are batch state, like the assignment. WHO OWNS THE TERRAIN KEYS: without a ladder the host array is the truth and
-	// the device array its copy (KeysAssign uploads it). With a ladder, host terrain mode keeps it so (HostFrameWork runs the rule and brings the device copy up to
-	// date), but with -terrain_gen= device the boundary kernel moves the DEVICE array and the device ladder records while frames run: every terrain call that reads
-	// or uploads the key array first waits for every stream (KeysIdle) and then refreshes both host copies from the device (LadderRefresh)
+	// terrain ladder and variant redraw: settings and per-env records are batch state, like the assignment whose keys the rule moves (see EnvAssignment for who owns
+	// keys and records when). The records' host form is kept when the rule is replaced or removed.
 	bool ladder_on_ = false;
-	LadderCfg ladder_{};
-	std::vector<LadderRec> ladder_rec_;      // host form [n]
-	LadderRec* d_ladder_ = nullptr;          // device [n] (-terrain_gen= device; allocated by the first ladder)
-	int LadderRefresh();                     // device terrain + ladder: host keys and ladder records <- device (call behind KeysIdle); else nothing
-	int LadderUpload();                      // device terrain + ladder: device ladder records <- host
+	LadderCfg ladder_cfg_{};
+	RuleRecs<LadderRec> ladder_;             // device array with -terrain_gen= device (allocated by the first ladder)
 	int RootX(int e, double* x);             // env e's current root x (q[0] of its state record; call with the streams idle)
-	int LadderIdle(const char* what);        // with a ladder: KeysIdle + LadderRefresh; without: nothing
-	// variant redraw: settings and per-env counters are batch state, like the assignment. WHO OWNS THE VARIANT KEYS: the ladder's protocol. Without a redraw, and
-	// with one in host terrain mode (HostFrameWork runs the rule and uploads the group's slice in front of the reset launch, which reads it), the host array is
-	// the truth. With a redraw and -terrain_gen= device the redraw kernel moves the DEVICE array and the device counters while frames run: every call that reads
-	// or uploads the variant keys first waits for every stream and then refreshes both host copies from the device (VariantRefresh)
-	bool redraw_on_ = false, redraw_stale_ = false;   // stale: a redraw launch was queued since the last refresh
-	RedrawCfg redraw_{};                     // (cum: the DEVICE table)
-	std::vector<double> redraw_cum_;         // host form of the cumulative table
-	std::vector<RedrawRec> redraw_rec_;      // host form [n]; kept when the redraw is replaced or removed
-	RedrawRec* d_redraw_ = nullptr; double* d_redraw_cum_ = nullptr;   // device [n], [n_variants] (allocated by the first redraw)
-	bool RedrawOnDevice() const { return redraw_on_ && cfg_.device_terrain; }
-	int VariantRefresh();                    // redraw on device terrain: host keys and counters <- device (call with the streams idle); else nothing
-	int VariantIdle(const char* what);       // redraw on device terrain: KeysIdle + VariantRefresh; else nothing
+	bool redraw_on_ = false;
+	RedrawCfg redraw_cfg_{};                 // (cum: the DEVICE table)
+	RuleRecs<RedrawRec> redraw_;             // device array with -terrain_gen= device (allocated by the first redraw)
+	RuleRecs<double> redraw_cum_;            // the cumulative table: host form [hi - lo + 1], device [n_variants]
 	int RedrawListed(const std::vector<int32_t>& ids);   // dtrl_reset: the rule for the listed envs on the host, keys and counters uploaded (streams idle)
-	// push schedule: settings, per-env records and per-env scales are batch state. The DEVICE records and scales are the truth in both terrain modes (no host
-	// copies): the rule runs in Backend::PushSchedule on the group's stream at every frame boundary, and the calls that read the records wait for queued work
+	// push schedule: settings, per-env records and per-env scales are batch state. The DEVICE records and scales are the truth in both terrain modes (the host form
+	// is staging): the rule runs in Backend::PushSchedule on the group's stream at every frame boundary, and the calls that read the records wait for queued work
 	bool push_on_ = false;
-	PushCfg push_{};
-	PushRec* d_push_ = nullptr; double* d_push_scale_ = nullptr;   // device [n] each (allocated by the first dtrl_push_schedule / dtrl_push_scale; scales 1.0)
-	PerturbRow* d_pert_rows_ = nullptr;                            // device [n]: the rows of one dtrl_add_perturb (allocated by the first call)
+	PushCfg push_cfg_{};
+	RuleRecs<PushRec> push_; RuleRecs<double> push_scale_;   // device [n] each (allocated by the first dtrl_push_schedule / dtrl_push_scale; scales 1.0)
+	RuleRecs<PerturbRow> pert_rows_;                         // device [n]: the rows of one dtrl_add_perturb (allocated by the first call)
 	int PushAlloc();                                               // the two push arrays, once
 	int PushStart(int n_listed);   // dtrl_reset / terrain restart: the rule with `start` for the n_listed envs ApplyResets(ids, -1) has just launched (same list, stream 0)
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create

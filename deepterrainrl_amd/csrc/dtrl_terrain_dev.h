@@ -122,6 +122,21 @@ DTRL_TG_HD inline void tg_env_boundary(GroundRec& rec, GroundGen& gen, const Env
 	else tg_window_update(rec, st.root_x + c.view_min, st.root_x + c.view_max, c, rnd, &gen);
 }
 
+// ---- env span: which envs a per-env rule runs over at a frame boundary ----
+// envs [e0, e0 + n), or list[0 .. n) when a list is given (device memory for a kernel and for Backend's entries; local env ids)
+struct EnvSpan { int e0, n; const int32_t* list; };
+// the env of thread or iteration k of a span: false (env untouched) when k is beyond it. Takes the span as the three scalars the kernels have as arguments and is
+// always inlined on the device, so a kernel that opens with it is compiled as when it spelled the three lines out
+#if defined(__HIPCC__)
+__attribute__((always_inline))
+#endif
+DTRL_TG_HD inline bool span_env(int k, int e0, int n, const int32_t* env_list, int& env)
+{
+	if (k >= n) return false;
+	env = env_list ? env_list[k] : e0 + k;
+	return true;
+}
+
 // ---- terrain ladder (include/dtrl.h dtrl_terrain_ladder): envs climb and descend a range of the terrain set by their episodes ----
 // per-env record: the root x at which the env last spawned or last changed level, and how often it went up / down
 struct LadderRec { double mark_x; int32_t ups, downs; };

@@ -27,9 +27,10 @@ public:
 	bool D2H(void* dst, const void* src, size_t n) override { std::memcpy(dst, src, n); return true; }
 	bool D2D(void* dst, const void* src, size_t n) override { std::memcpy(dst, src, n); return true; }
 	bool GatherF32(float* dst, const float* src, const int32_t* idx, size_t n) override { for (size_t i = 0; i < n; ++i) dst[i] = idx[i] >= 0 ? src[idx[i]] : 0.0f; return true; }
+	// (the rule-less terrain work in place; every other per-env rule of the frame boundary is Backend's host default: dtrl_backend_defaults.cpp)
 	bool TerrainBoundary(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list) override
 	{
-		for (int k = 0; k < n; ++k) { const int e = env_list ? env_list[k] : e0 + k; tg_env_boundary(buf.gr[e], buf.gen[e], buf.status[e], *buf.tcfg, mode, e, buf.dist_ring, buf.dist_count, buf.dist_cap); }
+		for (int k = 0, e; span_env(k, e0, n, env_list, e); ++k) tg_env_boundary(buf.gr[e], buf.gen[e], buf.status[e], *buf.tcfg, mode, e, buf.dist_ring, buf.dist_count, buf.dist_cap);
 		return true;
 	}
 	bool OrderByCost(const EnvStatus* status, int e0, int n, int32_t* order) override

@@ -2,7 +2,8 @@
 Backend::PushSchedule and Backend::PerturbScatter, here ONE launch of dtrl_push_schedule per env group and frame in both terrain modes and ONE launch of
 dtrl_perturb_scatter per dtrl_add_perturb -- and what only exists on HIP: the kernels against their host fallbacks (DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1)
 at 70 envs / rows (two 64-thread blocks, the second partial) with one and two env groups in both libraries, frames queued without a host wait (RunFrames) against
-frame-by-frame Update, run-to-run determinism, the fast kernel against the reference kernel under a schedule, and the new symbols in both libraries."""
+frame-by-frame Update, run-to-run determinism, the fast kernel against the reference kernel under a schedule, every frame-boundary rule (ladder, redraw, schedule) in ONE batch
+against all the host fallbacks at once, and the new symbols in both libraries."""
 import ctypes
 import os
 
@@ -184,6 +185,53 @@ def test_fast_kernel_equals_reference_kernel_under_a_schedule(da, om, monkeypatc
     mode = dict(terrain_gen="device")
     base = push_run(om, monkeypatch, {}, mode, {})
     R.assert_same_end(base, push_run(om, monkeypatch, {"DTRL_KERNEL": "ref"}, mode, {}), "DTRL_KERNEL=ref")
+
+
+# ---- GPU only: every frame-boundary rule in one batch ----
+RESET_IDS = [69, 3, 64, 17, 66, 0, 40, 65]     # out of order, in both 64-thread blocks: the env-list form of every rule
+
+
+def all_rules_run(om, tmp_path, monkeypatch, env, n=N, frames=FRAMES):
+    """Terrain sets under a ladder, model variants under a redraw and a push schedule on device terrain; a reset of RESET_IDS halfway."""
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    paths = V.write_variants(tmp_path, R.DOG)
+    b = V.with_variants(om, R.DOG, n, paths, [e % 3 for e in range(n)], dict(terrain_seed=31, rand_seed=3, terrain_gen="device"))
+    T.fill(b, T.four_walkable_files(T.DOG))
+    b.AssignTerrains(None, [(e // 3) % 3 for e in range(n)], restart=True)
+    b.TerrainLadder(0, 2, up_dist=2.0, down_dist=1.5)
+    b.VariantRedraw(0, 2, seed=5)
+    b.PushSchedule(R.WAIT, seed=R.SEED, force=R.FORCE, duration=R.DUR)
+    for f in range(frames):
+        if f == frames // 2:
+            b.Reset(RESET_IDS)
+        b.Update()
+    terrains, again = list(b.GetTerrains()), list(b.GetTerrains())      # no frame between: the second call finds the host keys current and copies nothing
+    assert terrains == again
+    ladder, redraw = b.LadderInfo(), b.VariantRedrawInfo()
+    keys = {"terrain": terrains, "variant": list(b.GetVariants())}
+    keys.update(("ladder " + k, v.tobytes()) for k, v in ladder.items())
+    keys.update(("redraw " + k, v.tobytes() if hasattr(v, "tobytes") else v) for k, v in redraw.items())
+    assert keys["variant"] == list(redraw["variant"])
+    moved = int(ladder["ups"].sum() + ladder["downs"].sum())
+    return end_state(b), keys, (moved, int(redraw["draws"].sum()), int(redraw["draws"][64:].sum()))
+
+
+@pytest.mark.parametrize("groups", ["1", "2"], ids=["one_group", "two_groups"])
+def test_all_rules_in_one_batch_equal_the_host_fallbacks(da, om, tmp_path, monkeypatch, groups):
+    """70 envs (two 64-thread blocks, the second partial) under a terrain ladder, a variant redraw and a push schedule at once, 30 frames with a dtrl_reset of a
+    listed subset halfway: the boundary, redraw and push kernels against the host defaults of all three (DTRL_TERRAINS_FALLBACK, DTRL_VARIANTS_FALLBACK,
+    DTRL_PUSH_FALLBACK) -- env states, windows, terrain and variant keys, ladder records, redraw counters and push records bit for bit. Two calls of
+    dtrl_get_terrains with no frame between return the same levels (the second refreshes nothing)."""
+    base, keys, (moved, draws, draws_hi) = all_rules_run(om, tmp_path, monkeypatch, {"DTRL_GROUPS": groups})
+    assert moved >= 1 and draws >= len(RESET_IDS) + 1 and draws_hi >= 1 and base[4]["pushes"].min() >= 1, (moved, draws, draws_hi, base[4]["pushes"])
+    fb = {"DTRL_GROUPS": groups, "DTRL_TERRAINS_FALLBACK": "1", "DTRL_VARIANTS_FALLBACK": "1", "DTRL_PUSH_FALLBACK": "1"}
+    other, other_keys, _ = all_rules_run(om, tmp_path, monkeypatch, fb)
+    R.assert_same_end(base, other, "host fallbacks")
+    for k in keys:
+        assert keys[k] == other_keys[k], "%s differs from the host fallbacks" % k
 
 
 SYMBOLS = ("dtrl_push_schedule", "dtrl_push_scale", "dtrl_push_info")

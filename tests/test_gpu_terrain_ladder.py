@@ -1,5 +1,5 @@
 """Terrain ladder on the product library (libdtrl.so / libdtrl_f32.so on cuda:0): the twins of tests/test_terrain_ladder.py -- there the host default of
-Backend::TerrainBoundaryLadder, here ONE launch of dtrl_terrain_boundary_ladder per env group and frame -- and what only exists on HIP: the kernel against the host
+Backend::TerrainBoundary, here ONE launch of dtrl_terrain_boundary_ladder per env group and frame -- and what only exists on HIP: the kernel against the host
 fallback (DTRL_TERRAINS_FALLBACK=1) at 70 envs (two 64-thread blocks, the second partial) with one and two env groups in both libraries, frames queued without a
 host wait (RunFrames) against frame-by-frame Update, run-to-run determinism, and the new symbols in both libraries."""
 import ctypes

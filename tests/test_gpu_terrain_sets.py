@@ -1,5 +1,5 @@
 """Terrain sets on the product library (libdtrl.so / libdtrl_f32.so on cuda:0): the twins of tests/test_terrain_sets.py -- there the host default of
-Backend::TerrainBoundaryKeyed, here ONE launch of dtrl_terrain_boundary_keyed per env group and frame -- and what only exists on HIP: the keyed kernel against the
+Backend::TerrainBoundary, here ONE launch of dtrl_terrain_boundary_keyed per env group and frame -- and what only exists on HIP: the keyed kernel against the
 host fallback (DTRL_TERRAINS_FALLBACK=1) with one and two env groups, in both libraries and under the reference frame kernel, determinism and shard invariance of
 mixed device terrain, and the new symbols in both libraries."""
 import ctypes

@@ -2,7 +2,7 @@
 front of the env's terrain work. The yardstick uses only calls that existed before: a second batch WITHOUT a ladder whose caller finds out per frame what every
 env's frame will end like (SaveState / Update / RestoreState / StepUpdates), runs a pure-Python copy of the rule and moves the envs with AssignTerrains.
 Every comparison is bit for bit: every field of the EnvState record, the policy state, the ground window and its build count.
-Runs on the lane-loop check build (the host default of Backend::TerrainBoundaryLadder with -terrain_gen= device); tests/test_gpu_terrain_ladder.py points `Scenario`
+Runs on the lane-loop check build (the host default of Backend::TerrainBoundary with -terrain_gen= device); tests/test_gpu_terrain_ladder.py points `Scenario`
 at the product library (one launch of dtrl_terrain_boundary_ladder per env group and frame)."""
 import numpy as np
 import pytest

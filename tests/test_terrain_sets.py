@@ -1,7 +1,7 @@
 """Terrain sets (include/dtrl.h dtrl_terrains_create ...): several terrains in one batch, one per env. The yardsticks are the paths that existed before: a batch
 CREATED with a terrain file (restart), the curriculum call dtrl_set_terrain_lerp (no restart), and the batch that puts all its envs into one terrain (independence).
 Every comparison is bit for bit: every field of the EnvState record, the policy state, the ground window and its build count.
-Runs on the lane-loop check build of the kernel source (tests/emul: the host default of Backend::TerrainBoundaryKeyed with -terrain_gen= device);
+Runs on the lane-loop check build of the kernel source (tests/emul: the host default of Backend::TerrainBoundary with -terrain_gen= device);
 tests/test_gpu_terrain_sets.py points `Scenario` at the product library (one launch of dtrl_terrain_boundary_keyed)."""
 import json
 import os

@@ -8,7 +8,7 @@ rounds (>= 3), every round times --steps frames of every configuration in turn, 
   parent commit's library     the same batch on the parent commit's libdtrl.so (--parent-lib DIR: a directory that holds it): what the no-terrain rate is held against
   terrains, all in terrain 0  CreateTerrains(4), every env left in terrain 0 (device terrain: dtrl_terrain_boundary_keyed, one type in every wavefront)
   four terrains mixed         slopes_mixed / narrow_gaps / cliffs_rugged / flat dealt e % 4 with restart (device terrain: the lanes of a wavefront part ways by type)
-  ... DTRL_TERRAINS_FALLBACK=1  the same through the host default of Backend::TerrainBoundaryKeyed (device terrain only; --fallback-steps frames per round: it is slow)
+  ... DTRL_TERRAINS_FALLBACK=1  the same through the host default of Backend::TerrainBoundary (device terrain only; --fallback-steps frames per round: it is slow)
 --mode trace --variant none|zero|mixed runs 60 frames of one device-terrain variant and nothing else: the workload of a kernel trace of its own
   rocprofv3 --kernel-trace --stats -d DIR -o t -- python tools/terrain_sets_bench.py --mode trace --variant mixed"""
 import argparse, os, sys, time
