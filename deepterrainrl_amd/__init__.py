@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "dtrl_snapshot_save", "dtrl_snapshot_restore", "dtrl_clone_envs", "dtrl_snapshot_export", "dtrl_snapshot_import", "dtrl_snapshot_info", "dtrl_snapshot_free",
     "dtrl_slots_create", "dtrl_slot_set_policy", "dtrl_slot_set_policy_device", "dtrl_slot_alias", "dtrl_slot_set_explore", "dtrl_assign_slots", "dtrl_get_slots", "dtrl_slot_stats",
     "dtrl_variants_create", "dtrl_variant_load_file", "dtrl_variant_load_json", "dtrl_assign_variants", "dtrl_get_variants", "dtrl_variant_stats", "dtrl_variant_redraw", "dtrl_variant_redraw_info",
+    "dtrl_variant_rescale", "dtrl_variant_rescale_info", "dtrl_variant_scalars",
     "dtrl_push_schedule", "dtrl_push_scale", "dtrl_push_info",
     "dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats", "dtrl_terrain_ladder", "dtrl_ladder_info",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
@@ -72,6 +73,15 @@ ABI_SYMBOLS = [
 
 class DtrlError(RuntimeError):
     pass
+
+
+class RescaleDesc(C.Structure):
+    """include/dtrl.h dtrl_rescale_desc: the four ranges {lo, hi} of the variant rescale and its per_link mask"""
+    _fields_ = [("mass", C.c_double * 2), ("kp", C.c_double * 2), ("kd", C.c_double * 2), ("torque_lim", C.c_double * 2), ("per_link", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RESCALE_QUANTITIES = ("mass", "kp", "kd", "torque_lim")   # the order of the per_link bits and of the factor rows
+RESCALE_SCALARS = ("mass", "inertia", "sub_mass", "kp", "kd", "torque_lim")   # the rows of dtrl_variant_scalars
 
 
 def _bind(path):
@@ -163,6 +173,9 @@ def _bind(path):
     L.dtrl_variant_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.dtrl_variant_redraw.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, vp]
     L.dtrl_variant_redraw_info.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    L.dtrl_variant_rescale.argtypes = [vp, C.c_int, vp, C.c_int, C.c_uint64, C.POINTER(RescaleDesc)]
+    L.dtrl_variant_rescale_info.argtypes = [vp, vp, C.c_int, i32p, u64p, C.POINTER(RescaleDesc), vp, vp, vp]
+    L.dtrl_variant_scalars.argtypes = [vp, C.c_int, vp, dp]
     L.dtrl_push_schedule.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double]
     L.dtrl_push_scale.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_push_info.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
@@ -863,6 +876,48 @@ class BatchScenario:
         variant, draws = np.zeros(n, np.int32), np.zeros(n, np.int32)
         self._chk(self._lib.dtrl_variant_redraw_info(self._h, _p(ids), n, C.byref(lo), C.byref(hi), _p(variant), _p(draws)))
         return {"lo": int(lo.value), "hi": int(hi.value), "variant": variant, "draws": draws}
+
+    # ---- variant rescale: per-episode continuous mass and motor scales, drawn on the device (no counterpart in the reference) ----
+    def VariantRescale(self, base=0, env_ids=None, seed=0, mass=None, kp=None, kd=None, torque_lim=None, per_link=()):
+        """dtrl_variant_rescale: from now on the listed envs (all by default; [] = the settings only) run under a private model record -- key num_variants + env
+        id, at first a copy of variant `base` -- whose mass and motor scalars are redrawn at each of the env's episode starts: one factor per quantity from its
+        range (lo, hi) (None = (1, 1): not scaled), for every link alike or, for the quantities named in per_link ("mass", "kp", "kd", "torque_lim"), one per
+        link. The record then holds the bits ScaledVariant under the same factors would load. The draw depends on (seed, global env id, the env's episode
+        number) alone. One small launch per env group and frame, no host wait. Costs sizeof(DevModel) more device memory per env. AssignVariants of an ordinary
+        variant takes an env out; VariantRescale(None) removes the rescale (its envs go back to `base`, the counters stay)."""
+        if base is None:
+            self._chk(self._lib.dtrl_variant_rescale(self._h, 0, None, 0, 0, None))
+            return
+        unknown = set(per_link) - set(RESCALE_QUANTITIES)
+        if unknown:
+            raise DtrlError("VariantRescale: per_link names no quantity of the rescale: %s" % ", ".join(sorted(map(str, unknown))))
+        d = RescaleDesc()
+        for q, (name, r) in enumerate(zip(RESCALE_QUANTITIES, (mass, kp, kd, torque_lim))):
+            lo, hi = (1.0, 1.0) if r is None else r
+            getattr(d, name)[0], getattr(d, name)[1] = float(lo), float(hi)
+            if name in per_link:
+                d.per_link |= 1 << q
+        ids, n = self._ids(env_ids)
+        self._chk(self._lib.dtrl_variant_rescale(self._h, int(base), _p(ids), n, int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(d)))
+
+    def VariantRescaleInfo(self, env_ids=None):
+        """dtrl_variant_rescale_info: {"base", "seed", "ranges" {quantity: (lo, hi)}, "per_link" (tuple of names), "key", "episodes" (int32 per listed env, all by
+        default), "factors" [n, 4, L]: the factors of each env's CURRENT episode in RESCALE_QUANTITIES order, recomputed on the host by the library's rule from
+        episodes - 1 (all 1 outside the rescale or before the first episode start)}."""
+        ids, n = self._ids(env_ids)
+        base, seed, d = C.c_int32(), C.c_uint64(), RescaleDesc()
+        key, episodes = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        factors = np.zeros((n, 4, self.L), np.float64)
+        self._chk(self._lib.dtrl_variant_rescale_info(self._h, _p(ids), n, C.byref(base), C.byref(seed), C.byref(d), _p(key), _p(episodes), _p(factors)))
+        return {"base": int(base.value), "seed": int(seed.value), "ranges": {q: (getattr(d, q)[0], getattr(d, q)[1]) for q in RESCALE_QUANTITIES},
+                "per_link": tuple(q for k, q in enumerate(RESCALE_QUANTITIES) if d.per_link >> k & 1), "key": key, "episodes": episodes, "factors": factors}
+
+    def VariantScalars(self, env):
+        """dtrl_variant_scalars: the mass and motor scalars of the model record env `env` runs under, read from the device table: ({"mass", "inertia", "sub_mass",
+        "kp", "kd", "torque_lim"}: float64 [L], exact casts of the record's values; total_mass)."""
+        out = np.zeros((6, self.L), np.float64); tm = C.c_double()
+        self._chk(self._lib.dtrl_variant_scalars(self._h, int(env), _p(out), C.byref(tm)))
+        return {k: out[r].copy() for r, k in enumerate(RESCALE_SCALARS)}, float(tm.value)
 
     # ---- terrain sets: several terrains in one batch, one per env (no counterpart in the reference, which keeps one terrain per scene object) ----
     num_terrains = 0

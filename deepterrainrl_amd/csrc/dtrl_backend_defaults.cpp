@@ -1,6 +1,6 @@
 // dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, launches over
 // envs of several slots or variants and the per-slot sums, and the per-env rules of the frame boundary (terrain work under the batch's terrain, a terrain set
-// or a ladder; variant redraw; push schedule; perturbation rows), each built from the interface's own copies and Launch. The rules all run over an EnvSpan that
+// or a ladder; variant redraw; variant rescale; push schedule; perturbation rows), each built from the interface's own copies and Launch. The rules all run over an EnvSpan that
 // SpanList turns into a host vector. What the lane-loop check build runs; the HIP backend overrides every one of them with kernels and keeps these as its
 // cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1, DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1).
 // Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
@@ -168,6 +168,30 @@ bool Backend::VariantRedraw(const EnvStatus* status, const EnvSpan& span, int32_
 		const int32_t next = var_redraw_step(r, key, true, cfg, cum.data(), e);
 		if (next != key && !H2D(env_model + e, &next, sizeof(next))) return false;
 		if (r.draws != draws0 && !H2D(recs + e, &r, sizeof(r))) return false;
+	}
+	return true;
+}
+// Variant rescale: the rule (rescale_step) on the host, env by env, on a copy of the env's private record; the seven fields the rule writes -- and only those --
+// and the counter go back. Waits for the selected stream first.
+bool Backend::VariantRescale(const EnvStatus* status, const EnvSpan& span, const int32_t* env_model, DevModel* models, int key_base, RescaleRec* recs, const ModelScalarsD* base, const RescaleCfg& cfg)
+{
+	std::vector<int32_t> list;
+	if (!SpanList(span, list)) return false;
+	if (list.empty()) return true;
+	if (!SyncSelected()) return false;
+	ModelScalarsD b;
+	if (!D2H(&b, base, sizeof(b))) return false;
+	EnvStatus st; RescaleRec r; int32_t key = 0; DevModel m;
+	for (int32_t e : list) {
+		if (status) { if (!D2H(&st, status + e, sizeof(st))) return false; if (!(st.need_reset & 1)) continue; }
+		if (!D2H(&key, env_model + e, sizeof(key))) return false;
+		if (key != key_base + e) continue;
+		DevModel* dst = models + key;
+		if (!D2H(&r, recs + e, sizeof(r)) || !D2H(&m, dst, sizeof(m))) return false;
+		if (!rescale_step(r, true, true, cfg, b, e, m)) continue;
+		const size_t row = sizeof(real) * static_cast<size_t>(cfg.L);
+		if (!H2D(dst->mass, m.mass, row) || !H2D(dst->sub_mass, m.sub_mass, row) || !H2D(dst->inertia, m.inertia, row) || !H2D(dst->kp, m.kp, row) || !H2D(dst->kd, m.kd, row)
+			|| !H2D(dst->torque_lim, m.torque_lim, row) || !H2D(&dst->total_mass, &m.total_mass, sizeof(real)) || !H2D(recs + e, &r, sizeof(r))) return false;
 	}
 	return true;
 }

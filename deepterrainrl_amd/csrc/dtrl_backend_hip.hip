@@ -192,6 +192,36 @@ __global__ void dtrl_variant_redraw(const EnvStatus* __restrict__ status, int e0
 	if (next != v) env_model[e] = next;
 	if (r.draws != draws0) recs[e] = r;
 }
+// Variant rescale (include/dtrl.h dtrl_variant_rescale): the envs of a group that start an episode under their private model record get its mass and motor
+// scalars redrawn, behind the group's frame and boundary work and in front of its reset launch (rescale_link, dtrl_terrain_dev.h). One wavefront per env of the
+// span, lanes are links. An env that is not at an episode start, or not under its private key key_base + e, is left after two loads (wave-uniform). Every lane
+// draws its own link's factors; the total (in `real`, link order) and the subtree masses (in double, ascending over the bits of sub_mask) are taken by
+// broadcasting the lanes' masses one after the other, as the loader's loops add them. The six arrays are stored one element per lane, total_mass and the counter by
+// lane 0: no atomics, no scratch. status == nullptr: every listed env starts (dtrl_reset). A kernel of its own: every other kernel of this unit stays as it is.
+__global__ void __launch_bounds__(kGroup) dtrl_variant_rescale(const EnvStatus* __restrict__ status, int e0, int n, const int32_t* __restrict__ env_list, const int32_t* __restrict__ env_model,
+	DevModel* __restrict__ models, int key_base, RescaleRec* __restrict__ recs, const ModelScalarsD* __restrict__ base, RescaleCfg rc)
+{
+	int e;
+	if (!span_env(static_cast<int>(blockIdx.x), e0, n, env_list, e)) return;
+	if (status && !(status[e].need_reset & 1)) return;
+	if (env_model[e] != key_base + e) return;
+	const int lane = static_cast<int>(threadIdx.x);
+	const int32_t episode = recs[e].episodes;
+	DevModel& m = models[key_base + e];
+	const uint64_t key = rescale_stream_key(rc.seed, rc.env_id_base + e);
+	const bool link = lane < rc.L;
+	RescaleLink o{0, 0, 0, 0, 0};
+	uint32_t sub = 0;
+	if (link) { o = rescale_link(rc, key, episode, *base, lane); sub = m.sub_mask[lane]; }
+	real total = 0; double sm = 0;
+	for (int k = 0; k < rc.L; ++k) {
+		const real mk = __shfl(o.mass, k, kGroup);
+		total += mk;
+		if ((sub >> k) & 1u) sm += mk;
+	}
+	if (link) { m.mass[lane] = o.mass; m.sub_mass[lane] = static_cast<real>(sm); m.inertia[lane] = o.inertia; m.kp[lane] = o.kp; m.kd[lane] = o.kd; m.torque_lim[lane] = o.torque_lim; }
+	if (lane == 0) { m.total_mass = total; recs[e].episodes = episode + 1; }
+}
 // Push schedule (include/dtrl.h dtrl_push_schedule): the envs of a group count their waits down behind the group's frame and boundary work, and the ones that reach
 // 0 get a random push into their perturbation slot (push_step, dtrl_terrain_dev.h). A kernel of its own: the frame and boundary kernels stay as they are. Thread
 // per env, every word per env: no atomics. An env of scale 0 is left after one load; record and slot are written back only where they changed. status == nullptr:
@@ -625,12 +655,20 @@ public:
 		if (!r.ladder) return LaunchPerEnv(dtrl_terrain_boundary_keyed, s.n, "keyed terrain boundary launch", buf, s.e0, s.n, mode, s.list, r.table, r.env_terrain);
 		return LaunchPerEnv(dtrl_terrain_boundary_ladder, s.n, "ladder terrain boundary launch", buf, s.e0, s.n, mode, s.list, r.table, r.env_terrain, r.ladder, r.lc);
 	}
-	// variant redraw, push schedule, dtrl_add_perturb: ONE launch each, queued like the boundary work. DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 /
+	// variant redraw, variant rescale, push schedule, dtrl_add_perturb: ONE launch each, queued like the boundary work. DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 /
 	// DTRL_PERTURB_FALLBACK=1 takes the host default
 	bool VariantRedraw(const EnvStatus* status, const EnvSpan& s, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg) override
 	{
 		if (EnvFlag("DTRL_VARIANTS_FALLBACK")) return Backend::VariantRedraw(status, s, env_model, recs, cfg);
 		return LaunchPerEnv(dtrl_variant_redraw, s.n, "variant redraw launch", status, s.e0, s.n, s.list, env_model, recs, cfg);
+	}
+	// (one wavefront per env of the span)
+	bool VariantRescale(const EnvStatus* status, const EnvSpan& s, const int32_t* env_model, DevModel* models, int key_base, RescaleRec* recs, const ModelScalarsD* base, const RescaleCfg& cfg) override
+	{
+		if (EnvFlag("DTRL_VARIANTS_FALLBACK")) return Backend::VariantRescale(status, s, env_model, models, key_base, recs, base, cfg);
+		if (s.n <= 0) return true;
+		hipLaunchKernelGGL(dtrl_variant_rescale, dim3(s.n), dim3(kGroup), 0, stream_, status, s.e0, s.n, s.list, env_model, models, key_base, recs, base, cfg);
+		return Check(hipGetLastError(), "variant rescale launch");
 	}
 	bool PushSchedule(const EnvStatus* status, const EnvSpan& s, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg) override
 	{

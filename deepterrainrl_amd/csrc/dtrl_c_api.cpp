@@ -285,6 +285,20 @@ dtrl_status dtrl_assign_variants(dtrl_batch* b, const int32_t* env_ids, int n, c
 dtrl_status dtrl_get_variants(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* variants_out) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.GetVariants(env_ids, n, variants_out)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_variant_redraw(dtrl_batch* b, int lo, int hi, uint64_t seed, const double* weights) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantRedraw(lo, hi, seed, weights)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_variant_redraw_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* lo, int32_t* hi, int32_t* variant, int32_t* draws) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantRedrawInfo(env_ids, n, lo, hi, variant, draws)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_variant_rescale(dtrl_batch* b, int base, const int32_t* env_ids, int n, uint64_t seed, const dtrl_rescale_desc* d) try {
+	CHECK_B();
+	if (!d) return static_cast<dtrl_status>(b->eng.VariantRescale(base, env_ids, n, seed, nullptr, nullptr, 0, true));
+	const double lo[4] = {d->mass[0], d->kp[0], d->kd[0], d->torque_lim[0]}, hi[4] = {d->mass[1], d->kp[1], d->kd[1], d->torque_lim[1]};
+	return static_cast<dtrl_status>(b->eng.VariantRescale(base, env_ids, n, seed, lo, hi, d->per_link, false));
+} catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_variant_rescale_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* base, uint64_t* seed, dtrl_rescale_desc* d, int32_t* key, int32_t* episodes, double* factors) try {
+	CHECK_B();
+	double lo[4], hi[4]; uint32_t per_link = 0;
+	const int rc = b->eng.VariantRescaleInfo(env_ids, n, base, seed, lo, hi, &per_link, key, episodes, factors);
+	if (rc == DTRL_OK && d) { double* const r[4] = {d->mass, d->kp, d->kd, d->torque_lim}; for (int q = 0; q < 4; ++q) { r[q][0] = lo[q]; r[q][1] = hi[q]; } d->per_link = per_link; d->reserved = 0; }
+	return static_cast<dtrl_status>(rc);
+} catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_variant_scalars(dtrl_batch* b, int env, double* out, double* total_mass) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantScalars(env, out, total_mass)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_variant_stats(dtrl_batch* b, int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.VariantStats(v, n_envs, avg_dist, episodes, cycles, resets)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 // push schedule
 dtrl_status dtrl_push_schedule(dtrl_batch* b, int min_wait, int max_wait, uint64_t seed, double min_force, double max_force, double min_dur, double max_dur) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.PushSchedule(min_wait, max_wait, seed, min_force, max_force, min_dur, max_dur)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }

@@ -369,7 +369,7 @@ bool Engine::LaunchEnvs(const DevBuffers& b, int n_envs, int n_steps, real dt, b
 	const bool variants = !var_models_.empty();   // (variants and slots exclude each other: dtrl_variants_create / dtrl_slots_create)
 	if (!variants && slots_.empty()) return be_->Launch(d_model_, cfg_.run, b, n_envs, n_steps, dt, frame_end);
 	EnvKeyView v = (variants ? variant_keys_ : slot_keys_).View(list_host, part_off);
-	if (variants) v.models_dev = d_var_models_;
+	if (variants) { v.models_dev = d_var_models_; if (rescale_table_) v.n_keys += n_; }   // (the private records of a variant rescale: keys V .. V + num_envs - 1)
 	else { v.slots_dev = d_slot_table_; v.slots_host = slot_table_.data(); }
 	return be_->LaunchKeyed(variants ? d_var_models_ : d_model_, cfg_.run, b, v, n_envs, n_steps, dt, frame_end);
 }
@@ -398,6 +398,7 @@ int Engine::UploadTerrainCfg(const double* params)
 //   dtrl_terrain_boundary  fresh windows for the envs that fell, slid windows where the character got close to an edge, episode distances logged
 //   dtrl_order_by_cost     launch order of the next frame (costliest wavefronts first)
 //   dtrl_variant_redraw    (with a variant redraw) the envs that fell draw the model variant of their next episode
+//   dtrl_variant_rescale   (with a variant rescale) the envs that fell under a private record get its mass and motor scalars redrawn
 //   dtrl_push_schedule     (with a push schedule) the envs whose wait ran out get a random push into their perturbation slot
 //   0-step frame launch    the device half of the reset, taken by the envs that fell, skipped by the others (reset_listed = 2)
 int Engine::DeviceFrameWork(int group)
@@ -411,6 +412,8 @@ int Engine::DeviceFrameWork(int group)
 	if (!Boundary(span, 0) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	// variant redraw: the envs that fell draw their next variant behind their frame and in front of the reset launch, which then runs reset_env under the new model
 	if (redraw_on_) { variant_keys_.stale = true; if (!be_->VariantRedraw(buf_.status, span, variant_keys_.d_env_key, redraw_.dev, redraw_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error()); }
+	// variant rescale: behind the redraw (which acts on keys below V only), the envs that fell under their private record get it rewritten for their next episode
+	if (rescale_on_ && !RescaleQueue(buf_.status, span)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	// push schedule: the group's envs count down, and the ones that are due get their push, behind the frame and in front of the reset launch (an env that fell
 	// draws a new wait and is not pushed: the reset launch clears nothing the rule wrote)
 	if (push_on_ && !be_->PushSchedule(buf_.status, span, buf_.st, push_.dev, push_scale_.dev, push_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error());
@@ -507,8 +510,10 @@ int Engine::HostFrameWork(int group)
 	for (int k = 0; k < kBuckets; ++k) bucket_[k + 1] += bucket_[k];
 	for (int e = e0; e < e1; ++e) pin_order_[e0 + bucket_[key(e)]++] = e;
 	const double ht3 = g_ht.on ? now_s() : 0;
-	// push schedule: the same launch as in device terrain mode, on the group's stream (idle since the wait above) in front of the reset launch; status_ is the
+	// variant rescale, then push schedule: the same launches as in device terrain mode, on the group's stream (idle since the wait above; the redraw's key upload is
+	// queued on it) in front of the reset launch; status_ is the
 	// page-locked array the frame kernel wrote, which the device reads through the same pointer
+	if (rescale_on_ && !RescaleQueue(buf_.status, EnvSpan{e0, grp.n, nullptr})) return Fail(DTRL_ERR_DEVICE, be_->error());
 	if (push_on_ && !be_->PushSchedule(buf_.status, EnvSpan{e0, grp.n, nullptr}, buf_.st, push_.dev, push_scale_.dev, push_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	const int rc = ApplyResets(reset_ids_, group);
 	if (g_ht.on) { const double ht4 = now_s(); g_ht.t_sync += ht1 - ht0; g_ht.t_loop += ht2 - ht1; g_ht.t_sort += ht3 - ht2; g_ht.t_reset += ht4 - ht3; g_ht.regen += used; ++g_ht.n; }
@@ -706,6 +711,7 @@ int Engine::Reset(const int32_t* env_ids, int n, const uint64_t* seeds)
 		if (!be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size()) || !Boundary(EnvSpan{0, static_cast<int>(reset_ids_.size()), d_env_list_}, 1)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
 	if (int rc = RedrawListed(reset_ids_); rc != DTRL_OK) return rc;   // variant redraw: an episode starts, once per listed env, and the reset below runs under the new model
+	if (int rc = RescaleListed(reset_ids_); rc != DTRL_OK) return rc;  // variant rescale: the same for the listed envs under a private record, behind the redraw
 	int rc = ApplyResets(reset_ids_, -1);
 	if (rc != DTRL_OK) return rc;
 	if (rc = PushStart(static_cast<int>(reset_ids_.size())); rc != DTRL_OK) return rc;   // push schedule: an episode starts, a new wait once per listed env
@@ -2011,6 +2017,7 @@ int Engine::VariantsCreate(int n_variants)
 	if (!d_var_models_) return DTRL_ERR_DEVICE;
 	if (!be_->H2D(d_var_models_, &cfg_.model, sizeof(DevModel))) return Fail(DTRL_ERR_DEVICE, be_->error());
 	var_models_.assign(static_cast<size_t>(n_variants), cfg_.model);   // (an empty variant holds the batch's model until it is loaded; it cannot be assigned)
+	var_scalars_.assign(static_cast<size_t>(n_variants), cfg_.scalars);
 	variant_keys_.filled.assign(static_cast<size_t>(n_variants), 0); variant_keys_.filled[0] = 1;
 	return DTRL_OK;
 }
@@ -2034,6 +2041,7 @@ int Engine::VariantLoad(int v, const char* character_file, const char* text, siz
 	int rc = KeysIdle(variant_keys_, what, v);
 	if (rc != DTRL_OK) return rc;
 	if (v == 0) return Fail(DTRL_ERR_ARG, std::string(what) + ": variant 0 is the batch's own model and cannot be replaced");
+	if (rescale_on_ && v == rescale_base_) return Fail(DTRL_ERR_ARG, std::string(what) + ": variant " + std::to_string(v) + " is the base of the variant rescale (dtrl_variant_rescale): the private records are scaled copies of it; remove the rescale first");
 	std::string doc; CharSource src;
 	if (text) { doc.assign(text, bytes); src.name = "variant " + std::to_string(v) + " (JSON text)"; }
 	else {
@@ -2060,7 +2068,7 @@ int Engine::VariantLoad(int v, const char* character_file, const char* text, siz
 	if (const char* f = VariantMisfit(vc.model, cfg_.model))
 		return Fail(DTRL_ERR_ARG, std::string(what) + ": variant " + std::to_string(v) + " does not fit the batch: " + f + " differs from the batch's model (the skeleton, the scene and the controller part -- parameters, actions, default action -- are one per batch)");
 	if (!be_->H2D(d_var_models_ + v, &vc.model, sizeof(DevModel))) return Fail(DTRL_ERR_DEVICE, be_->error());
-	var_models_[v] = vc.model; variant_keys_.filled[v] = 1;
+	var_models_[v] = vc.model; var_scalars_[v] = vc.scalars; variant_keys_.filled[v] = 1;
 	return DTRL_OK;
 }
 
@@ -2136,6 +2144,120 @@ int Engine::VariantRedrawInfo(const int32_t* env_ids, int n, int32_t* lo, int32_
 		if (variant) variant[i] = variant_keys_.env_key[e];
 		if (draws) draws[i] = redraw_.host[e].draws;
 	}
+	return DTRL_OK;
+}
+
+// ---- variant rescale (include/dtrl.h: dtrl_variant_rescale, dtrl_variant_rescale_info, dtrl_variant_scalars) ----
+// The rule is rescale_step (dtrl_terrain_dev.h), run by Backend::VariantRescale on the group's stream at every frame boundary, behind the redraw and in front of the
+// push schedule and the reset launch -- queued by DeviceFrameWork and by HostFrameWork alike -- and in its listed form by RescaleListed under dtrl_reset. dtrl_engine.h
+// says where the private records live and who writes them when.
+int Engine::RescaleListed(const std::vector<int32_t>& ids)
+{
+	if (!rescale_on_ || ids.empty()) return DTRL_OK;
+	// (the list as ApplyResets is about to lay it out again, on the same stream 0)
+	std::memcpy(pin_ids_, ids.data(), sizeof(int32_t) * ids.size());
+	if (!zero_copy_ && !be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * ids.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DevOk(RescaleQueue(nullptr, EnvSpan{0, static_cast<int>(ids.size()), zero_copy_ ? pin_ids_ : d_env_list_}));
+}
+
+int Engine::VariantRescale(int base, const int32_t* env_ids, int n, uint64_t seed, const double* lo4, const double* hi4, uint32_t per_link, bool remove)
+{
+	const std::string w = "dtrl_variant_rescale: ";
+	if (int rc = KeysIdle(variant_keys_, "dtrl_variant_rescale", 0); rc != DTRL_OK) return rc;
+	if (int rc = KeysRefresh(variant_keys_); rc != DTRL_OK) return rc;   // (a redraw on device terrain: the whole-array uploads below must not undo its draws)
+	const int V = variant_keys_.n_keys();
+	if (remove) {   // the envs under a private record go back to the base; counters and records stay
+		if (!rescale_on_) return DTRL_OK;
+		for (int32_t& k : variant_keys_.env_key) if (k >= V) k = rescale_base_;
+		rescale_on_ = false;
+		return DevOk(be_->H2D(variant_keys_.d_env_key, variant_keys_.env_key.data(), sizeof(int32_t) * variant_keys_.env_key.size()));
+	}
+	if (base < 0 || base >= V) return Fail(DTRL_ERR_ARG, w + "base " + std::to_string(base) + " out of range (variants 0 .. " + std::to_string(V - 1) + ")");
+	if (!variant_keys_.filled[base]) return Fail(DTRL_ERR_ARG, w + "base: variant " + std::to_string(base) + " " + variant_keys_.empty_text);
+	static const char* const name[kRescaleQuantities] = {"mass", "kp", "kd", "torque_lim"};
+	for (int q = 0; q < kRescaleQuantities; ++q) {
+		const double lo = lo4[q], hi = hi4[q];
+		if (!std::isfinite(lo) || !std::isfinite(hi)) return Fail(DTRL_ERR_ARG, w + "range " + name[q] + " (" + std::to_string(lo) + ", " + std::to_string(hi) + ") must be two finite numbers");
+		if (!(lo > 0)) return Fail(DTRL_ERR_ARG, w + "range " + name[q] + ": lo (" + std::to_string(lo) + ") must be greater than 0");
+		if (lo > hi) return Fail(DTRL_ERR_ARG, w + "range " + name[q] + ": lo (" + std::to_string(lo) + ") exceeds hi (" + std::to_string(hi) + ")");
+	}
+	if (per_link >> kRescaleQuantities) return Fail(DTRL_ERR_ARG, w + "per_link (" + std::to_string(per_link) + ") has bits beyond the four quantities (mass 1, kp 2, kd 4, torque_lim 8)");
+	if (int rc = CheckEnvList(w, env_ids, n, "; nothing changed"); rc != DTRL_OK) return rc;
+	if (rescale_on_ && base != rescale_base_)
+		for (int32_t k : variant_keys_.env_key) if (k >= V) return Fail(DTRL_ERR_ARG, w + "base " + std::to_string(base) + " differs from the rescale's base (" + std::to_string(rescale_base_) + ") while envs run under private records of that one: remove the rescale first");
+	if (!rescale_table_) {   // once: the device table grows to V + num_envs records (the streams are idle), the old records copied from their host form
+		DevModel* grown = static_cast<DevModel*>(be_->Alloc(sizeof(DevModel) * (static_cast<size_t>(V) + static_cast<size_t>(n_))));
+		if (!grown) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+		allocs_.push_back(grown);
+		if (!be_->H2D(grown, var_models_.data(), sizeof(DevModel) * static_cast<size_t>(V))) return Fail(DTRL_ERR_DEVICE, be_->error());
+		auto old = std::find(allocs_.begin(), allocs_.end(), static_cast<void*>(d_var_models_));
+		if (old != allocs_.end()) { be_->Free(*old); allocs_.erase(old); }
+		d_var_models_ = grown;
+		d_rescale_base_ = static_cast<ModelScalarsD*>(be_->Alloc(sizeof(ModelScalarsD)));
+		if (!d_rescale_base_) return Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error());
+		allocs_.push_back(d_rescale_base_);
+		if (int rc = RecsAlloc(rescale_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
+		rescale_table_ = true;
+	}
+	if (!be_->H2D(d_rescale_base_, &var_scalars_[base], sizeof(ModelScalarsD))) return Fail(DTRL_ERR_DEVICE, be_->error());
+	rescale_cfg_ = RescaleCfg{};
+	for (int q = 0; q < kRescaleQuantities; ++q) { rescale_cfg_.lo[q] = lo4[q]; rescale_cfg_.hi[q] = hi4[q]; }
+	rescale_cfg_.per_link = per_link; rescale_cfg_.L = cfg_.model.L; rescale_cfg_.seed = seed; rescale_cfg_.env_id_base = static_cast<int64_t>(cfg_.run.env_id_base);
+	rescale_base_ = base; rescale_on_ = true;
+	// the listed envs: key V + e, the private record a copy of the base (all factors 1) until the env's next episode start
+	for (int i = 0; i < n; ++i) {
+		const int e = EnvIndex(env_ids, i);
+		if (!be_->H2D(d_var_models_ + V + e, &var_models_[base], sizeof(DevModel))) return Fail(DTRL_ERR_DEVICE, be_->error());
+		variant_keys_.env_key[e] = V + e;
+	}
+	if (n > 0 && !be_->H2D(variant_keys_.d_env_key, variant_keys_.env_key.data(), sizeof(int32_t) * variant_keys_.env_key.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return DTRL_OK;
+}
+
+int Engine::VariantRescaleInfo(const int32_t* env_ids, int n, int32_t* base, uint64_t* seed, double* lo4, double* hi4, uint32_t* per_link, int32_t* key, int32_t* episodes, double* factors)
+{
+	const std::string w = "dtrl_variant_rescale_info: ";
+	if (int rc = KeysIdle(variant_keys_, "dtrl_variant_rescale_info", 0); rc != DTRL_OK) return rc;
+	if (!rescale_on_) return Fail(DTRL_ERR_ARG, w + "the batch has no variant rescale (call dtrl_variant_rescale first)");
+	if (int rc = KeysRefresh(variant_keys_); rc != DTRL_OK) return rc;
+	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
+	if (int rc = DevOk(rescale_.Pull(*be_)); rc != DTRL_OK) return rc;
+	if (base) *base = rescale_base_;
+	if (seed) *seed = rescale_cfg_.seed;
+	for (int q = 0; q < kRescaleQuantities; ++q) { if (lo4) lo4[q] = rescale_cfg_.lo[q]; if (hi4) hi4[q] = rescale_cfg_.hi[q]; }
+	if (per_link) *per_link = rescale_cfg_.per_link;
+	const int L = cfg_.model.L, V = variant_keys_.n_keys();
+	for (int i = 0; i < n; ++i) {
+		const int e = EnvIndex(env_ids, i);
+		const int32_t k = variant_keys_.env_key[e], ep = rescale_.host[e].episodes;
+		if (key) key[i] = k;
+		if (episodes) episodes[i] = ep;
+		if (!factors) continue;
+		// the factors of the env's CURRENT episode, by the rule from episode number episodes - 1; an env that is not under its private record, or has not started
+		// an episode under the rescale yet, runs under factors 1
+		const uint64_t sk = rescale_stream_key(rescale_cfg_.seed, rescale_cfg_.env_id_base + e);
+		for (int q = 0; q < kRescaleQuantities; ++q) for (int j = 0; j < L; ++j)
+			factors[(static_cast<size_t>(i) * kRescaleQuantities + q) * L + j] = (k == V + e && ep > 0) ? rescale_factor(rescale_cfg_, sk, ep - 1, q, j) : 1.0;
+	}
+	return DTRL_OK;
+}
+
+int Engine::VariantScalars(int env, double* out6L, double* total_mass)
+{
+	const std::string w = "dtrl_variant_scalars: ";
+	if (int rc = RequireIdle("dtrl_variant_scalars" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (env < 0 || env >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(env) + " out of range");
+	const DevModel* src = d_model_;
+	if (!var_models_.empty()) {
+		if (int rc = KeysRefresh(variant_keys_); rc != DTRL_OK) return rc;
+		src = d_var_models_ + variant_keys_.env_key[env];
+	}
+	DevModel m;
+	if (!be_->D2H(&m, src, sizeof(m))) return Fail(DTRL_ERR_DEVICE, be_->error());
+	const int L = m.L;
+	const real* const rows[6] = {m.mass, m.inertia, m.sub_mass, m.kp, m.kd, m.torque_lim};
+	if (out6L) for (int r = 0; r < 6; ++r) for (int j = 0; j < L; ++j) out6L[r * L + j] = static_cast<double>(rows[r][j]);
+	if (total_mass) *total_mass = static_cast<double>(m.total_mass);
 	return DTRL_OK;
 }
 

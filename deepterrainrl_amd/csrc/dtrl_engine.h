@@ -132,6 +132,11 @@ public:
 	// Variant redraw (include/dtrl.h dtrl_variant_redraw; var_redraw_step): an env with status[e].need_reset & 1 whose variant is inside [cfg.lo, cfg.hi] draws;
 	// env_model[e] and recs[e] move. cfg.cum is device memory too.
 	virtual bool VariantRedraw(const EnvStatus* status, const EnvSpan& span, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg);
+	// Variant rescale (include/dtrl.h dtrl_variant_rescale; rescale_step): an env at an episode start -- status[e].need_reset & 1, or every env of the span with
+	// status == nullptr (the listed form, dtrl_reset) -- whose key env_model[e] is its private one, key_base + e, has the mass and motor scalars of its private
+	// record models[key_base + e] rewritten from the base scalars (device memory, one record) and its own draws; recs[e].episodes counts. Nothing else of the
+	// record, and no other env's record, is touched. The default waits for the selected stream first.
+	virtual bool VariantRescale(const EnvStatus* status, const EnvSpan& span, const int32_t* env_model, DevModel* models, int key_base, RescaleRec* recs, const ModelScalarsD* base, const RescaleCfg& cfg);
 	// Push schedule (include/dtrl.h dtrl_push_schedule; push_step). status != nullptr: an env with status[e].need_reset != 0 starts an episode (its wait is drawn
 	// afresh), any other counts down and is pushed at 0; status == nullptr: every env of the span starts (creation of the schedule, dtrl_reset, a terrain
 	// restart). recs[e] and the seven slot fields of st[e] move; an env of scale[e] == 0 is not touched. The default waits for the selected stream first.
@@ -236,6 +241,10 @@ public:
 	// variant redraw (include/dtrl.h)
 	int VariantRedraw(int lo, int hi, uint64_t seed, const double* weights);
 	int VariantRedrawInfo(const int32_t* env_ids, int n, int32_t* lo, int32_t* hi, int32_t* variant, int32_t* draws);
+	// variant rescale (include/dtrl.h)
+	int VariantRescale(int base, const int32_t* env_ids, int n, uint64_t seed, const double* lo4, const double* hi4, uint32_t per_link, bool remove);
+	int VariantRescaleInfo(const int32_t* env_ids, int n, int32_t* base, uint64_t* seed, double* lo4, double* hi4, uint32_t* per_link, int32_t* key, int32_t* episodes, double* factors);
+	int VariantScalars(int env, double* out6L, double* total_mass);
 	int VariantStats(int v, int64_t* n_envs, double* avg_dist, int64_t* episodes, int64_t* cycles, int64_t* resets) { return KeysStats(variant_keys_, "dtrl_variant_stats", false, v, n_envs, avg_dist, episodes, cycles, resets); }
 	int num_variants() const { return static_cast<int>(var_models_.size()); }
 	// terrain sets (include/dtrl.h)
@@ -253,7 +262,8 @@ public:
 	// the model env e (local id, in range) runs under: what host-side readers of per-env geometry use (dtrl_get_link_states, AddPerturb). With a redraw on device
 	// terrain the caller brings the host keys up to date first (VariantKeysCurrent, once per call, behind a wait for the streams)
 	int VariantKeysCurrent() { return KeysRefresh(variant_keys_); }
-	const DevModel& ModelOf(int e) const { return var_models_.empty() ? cfg_.model : var_models_[variant_keys_.env_key[e]]; }
+	// (an env under its private record of the variant rescale: the rescale's base -- geometry is not scaled)
+	const DevModel& ModelOf(int e) const { return var_models_.empty() ? cfg_.model : var_models_[PublicKey(variant_keys_.env_key[e])]; }
 	~Engine();
 	int Create(const char* const* argv, int argc, int num_envs, int device_id);
 	int Reset(const int32_t* env_ids, int n, const uint64_t* seeds);
@@ -480,7 +490,21 @@ private:
 	RedrawCfg redraw_cfg_{};                 // (cum: the DEVICE table)
 	RuleRecs<RedrawRec> redraw_;             // device array with -terrain_gen= device (allocated by the first redraw)
 	RuleRecs<double> redraw_cum_;            // the cumulative table: host form [hi - lo + 1], device [n_variants]
-	int RedrawListed(const std::vector<int32_t>& ids);   // dtrl_reset: the rule for the listed envs on the host, keys and counters uploaded (streams idle)
+	int RedrawListed(const std::vector<int32_t>& ids);
+	// variant rescale: settings, counters and the per-env private records are batch state. The private records are records V .. V + num_envs - 1 of the device
+	// table (V = n_variants; the table is grown once, by the first dtrl_variant_rescale, with the streams idle); env e's private key is V + e. The host table
+	// var_models_ keeps its V records: a private key stands for the rescale's base wherever the host reads a model (PublicKey). The DEVICE counters and records are
+	// the truth in both terrain modes: the rule runs in Backend::VariantRescale on the group's stream at every frame boundary, between the group's frame launch and
+	// its reset launch, and nothing else writes a record while launches run -- stream order is the whole timing rule.
+	bool rescale_on_ = false, rescale_table_ = false;   // (rescale_table_: the device table holds the private records)
+	int rescale_base_ = 0;
+	RescaleCfg rescale_cfg_{};
+	RuleRecs<RescaleRec> rescale_;           // device [n] (allocated by the first dtrl_variant_rescale)
+	std::vector<ModelScalarsD> var_scalars_; // per variant: the character file's doubles (empty: no variants)
+	ModelScalarsD* d_rescale_base_ = nullptr;   // device: the base's copy
+	int32_t PublicKey(int32_t k) const { return k >= static_cast<int32_t>(var_models_.size()) ? rescale_base_ : k; }
+	bool RescaleQueue(const EnvStatus* status, const EnvSpan& span) { return be_->VariantRescale(status, span, variant_keys_.d_env_key, d_var_models_, static_cast<int>(var_models_.size()), rescale_.dev, d_rescale_base_, rescale_cfg_); }
+	int RescaleListed(const std::vector<int32_t>& ids);  // dtrl_reset: the rule for the listed envs, in front of the reset launch (stream 0)   // dtrl_reset: the rule for the listed envs on the host, keys and counters uploaded (streams idle)
 	// push schedule: settings, per-env records and per-env scales are batch state. The DEVICE records and scales are the truth in both terrain modes (the host form
 	// is staging): the rule runs in Backend::PushSchedule on the group's stream at every frame boundary, and the calls that read the records wait for queued work
 	bool push_on_ = false;

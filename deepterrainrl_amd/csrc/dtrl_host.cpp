@@ -493,9 +493,11 @@ bool LoadScenario(const ArgParser& args, ScenarioConfig& cfg, std::string& err, 
 		double sx = bd.get_num("Param0", 0), sy = bd.get_num("Param1", 0);
 		m.body_half[j][0] = 0.5 * sx; m.body_half[j][1] = 0.5 * sy;
 		m.inertia[j] = m.mass[j] / 12.0 * (sx * sx + sy * sy);                                     // sim/RBDUtil.cpp:562-583 (zz term)
+		cfg.scalars.m0[j] = bd.get_num("Mass", 0); cfg.scalars.s2[j] = sx * sx + sy * sy;           // (the file's doubles, kept beside the model: ModelScalarsD)
 		m.col[j] = (m.char_type == 0) ? kDogCol[j] : kRaptorCol[j];
 		const Json& pd = pds->arr[j];
 		m.kp[j] = pd.get_num("Kp", 0); m.kd[j] = pd.get_num("Kd", 0); m.torque_lim[j] = pd.get_num("TorqueLim", 0);
+		cfg.scalars.kp[j] = pd.get_num("Kp", 0); cfg.scalars.kd[j] = pd.get_num("Kd", 0); cfg.scalars.torque_lim[j] = pd.get_num("TorqueLim", 0);
 		m.target_theta[j] = pd.get_num("TargetTheta", 0); m.use_world[j] = pd.get_num("UseWorldCoord", 0) != 0;
 	}
 	// hinge limits act on theta + ref_theta (sim/World.cpp:543-553: theta = -getHingeAngle() - ref_theta; :624-626 setLimit(-LimHigh, -LimLow)) with

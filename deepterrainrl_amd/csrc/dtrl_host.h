@@ -119,6 +119,7 @@ private:
 // ---- scenario configuration flattened from the arg file + data files ----
 struct ScenarioConfig {
 	DevModel model{};
+	ModelScalarsD scalars{};       // the character file's doubles behind model.mass / inertia / kp / kd / torque_lim (dtrl_types.h): the base values of the variant rescale
 	RunParams run{};
 	NetDesc net{};
 	bool has_policy_net = false;

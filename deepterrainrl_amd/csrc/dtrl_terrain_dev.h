@@ -204,6 +204,61 @@ DTRL_TG_HD inline int32_t var_redraw_step(RedrawRec& r, int32_t k, bool start, c
 	return next > c.hi ? c.hi : next;
 }
 
+// ---- variant rescale (include/dtrl.h dtrl_variant_rescale): envs under a private model record draw continuous mass and motor scales at each episode start ----
+// per-env record: how many episodes the env has started under the rescale (the episode number of its draw stream)
+struct RescaleRec { int32_t episodes; };
+// the batch's rescale: the four ranges [lo[q], hi[q]] (0 < lo <= hi, finite) of q = 0 mass, 1 kp, 2 kd, 3 torque_lim, the per_link mask (bit q: quantity q draws
+// one factor per link, else one for all links), the link count, the stream's seed and env-id base. A kernel ARGUMENT: DevBuffers and RunParams keep their layout
+enum RescaleQuantity { kRescaleMass = 0, kRescaleKp = 1, kRescaleKd = 2, kRescaleTorqueLim = 3, kRescaleQuantities = 4 };
+struct RescaleCfg {
+	double lo[kRescaleQuantities], hi[kRescaleQuantities];
+	uint32_t per_link; int32_t L;
+	uint64_t seed; int64_t env_id_base;
+};
+// counter-based like the other rules, under a constant of its own: a function of (seed, GLOBAL env id) -- shard-invariant
+DTRL_TG_HD inline uint64_t rescale_stream_key(uint64_t seed, int64_t global_env) { return tg_mix(tg_mix(seed) ^ (0x5CA1EDULL + static_cast<uint64_t>(global_env))); }
+// factor of quantity q for link j in the env's episode n. The index layout n * 4 L + q L + j is fixed, and a quantity that is not per link reads index j = 0 for
+// every link: switching one quantity between the two forms moves no other quantity's draws
+DTRL_TG_HD inline double rescale_factor(const RescaleCfg& c, uint64_t key, int32_t n, int q, int j)
+{
+	const uint64_t L = static_cast<uint64_t>(c.L);
+	const uint64_t idx = static_cast<uint64_t>(n) * 4u * L + static_cast<uint64_t>(q) * L + (((c.per_link >> q) & 1u) ? static_cast<uint64_t>(j) : 0u);
+	const double u = static_cast<double>(tg_mix(key + idx * 0xD1342543DE82EF95ULL) >> 11) * (1.0 / 9007199254740992.0);
+	return c.lo[q] + u * (c.hi[q] - c.lo[q]);
+}
+// what the rule writes for one link from its own draws: the loader's formulas (dtrl_host.cpp LoadScenario), operation by operation, on the character file's
+// doubles times the factor -- doubles until the one cast to `real`
+struct RescaleLink { real mass, inertia, kp, kd, torque_lim; };
+DTRL_TG_HD inline RescaleLink rescale_link(const RescaleCfg& c, uint64_t key, int32_t n, const ModelScalarsD& b, int j)
+{
+	RescaleLink o;
+	o.mass = static_cast<real>(b.m0[j] * rescale_factor(c, key, n, kRescaleMass, j));
+	o.inertia = static_cast<real>(o.mass / 12.0 * b.s2[j]);
+	o.kp = static_cast<real>(b.kp[j] * rescale_factor(c, key, n, kRescaleKp, j));
+	o.kd = static_cast<real>(b.kd[j] * rescale_factor(c, key, n, kRescaleKd, j));
+	o.torque_lim = static_cast<real>(b.torque_lim[j] * rescale_factor(c, key, n, kRescaleTorqueLim, j));
+	return o;
+}
+// The rule, the one body of host and device (the kernel runs rescale_link on its lanes and takes the two sums below by lane broadcasts in the same order): env
+// `env` (local id) at a frame boundary or under dtrl_reset. `start`: the env is at an episode start; `is_private`: its key is its private record's. Otherwise
+// nothing is touched. Rewrites mass, total_mass (running sum in link order, in `real`), inertia, sub_mass (double sum over the bits of sub_mask in ascending
+// order, cast once), kp, kd and torque_lim of the env's private record `m` -- geometry, margins, contact points and limits do not move -- and counts the episode.
+// Runs IN FRONT OF the reset launch, so reset_env runs under the new scales. true: the record was rewritten.
+DTRL_TG_HD inline bool rescale_step(RescaleRec& r, bool start, bool is_private, const RescaleCfg& c, const ModelScalarsD& b, int env, DevModel& m)
+{
+	if (!start || !is_private) return false;
+	const uint64_t key = rescale_stream_key(c.seed, c.env_id_base + env);
+	m.total_mass = 0;
+	for (int j = 0; j < c.L; ++j) {
+		const RescaleLink o = rescale_link(c, key, r.episodes, b, j);
+		m.mass[j] = o.mass; m.total_mass += m.mass[j];
+		m.inertia[j] = o.inertia; m.kp[j] = o.kp; m.kd[j] = o.kd; m.torque_lim[j] = o.torque_lim;
+	}
+	for (int j = 0; j < c.L; ++j) { double sm = 0; for (int k = 0; k < c.L; ++k) if ((m.sub_mask[j] >> k) & 1u) sm += m.mass[k]; m.sub_mass[j] = static_cast<real>(sm); }
+	r.episodes += 1;
+	return true;
+}
+
 // ---- push schedule (include/dtrl.h dtrl_push_schedule): random external pushes at per-env random times, written into the env's perturbation slot ----
 // per-env record: frame boundaries left until the env's next push, the counter of its draw stream, how many pushes it got, and the last one as it was drawn
 // (force and duration in double, before the cast to `real` with which they are stored into EnvState)

@@ -119,6 +119,11 @@ struct DevModel {
 	real bt_cs[kMaxL], bt_sn[kMaxL];        // cos / sin of body_theta (box frame against the joint frame)
 };
 
+// The character file's own DOUBLES behind the model's mass and motor scalars, per link: body mass, sx^2 + sy^2 of its box, and the PD controller's Kp, Kd and
+// TorqueLim. The loader fills one next to the DevModel (which holds their casts to `real` and what is derived from them); the variant rescale (dtrl_terrain_dev.h
+// rescale_step) scales these and casts once, so that it writes the bits the loader would have loaded from a character file with the scaled numbers.
+struct ModelScalarsD { double m0[kMaxL], s2[kMaxL], kp[kMaxL], kd[kMaxL], torque_lim[kMaxL]; };
+
 // exploration knobs + seeds: may change between launches (dtrl_set_explore)
 struct RunParams {
 	int32_t enable_exp;

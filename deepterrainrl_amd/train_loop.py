@@ -119,6 +119,24 @@ def setup_variants(b, spec):
     return {"scales": scales, "weights": weights}
 
 
+def setup_rescale(b, spec):
+    """Continuous domain randomisation while training (BatchScenario.VariantRescale): every env runs under a private model record whose mass and motor scalars are
+    drawn afresh from the ranges spec["mass"] / ["kp"] / ["kd"] / ["torque_lim"] ((lo, hi) each; a missing key: not scaled) at every episode start, on the device
+    -- no table of fixed models. spec["per_link"]: the quantities that draw one factor per link instead of one for all links; spec["seed"]; spec["hold_out"]: env
+    ids that stay on the nominal model. A batch that has no variants yet gets a table of one (the batch's own model, the rescale's base). The Reset makes the
+    first episodes start drawn. Returns {"hold_out"}."""
+    unknown = set(spec) - {"mass", "kp", "kd", "torque_lim", "per_link", "seed", "hold_out"}
+    if unknown:
+        raise ValueError("rescale: unknown keys %s" % ", ".join(sorted(unknown)))
+    held = sorted(set(int(e) for e in spec.get("hold_out", ())))
+    if not b.num_variants:
+        b.CreateVariants(1)
+    b.VariantRescale(0, env_ids=[e for e in range(b.num_envs) if e not in set(held)] if held else None, seed=int(spec.get("seed", 0)),
+                     mass=spec.get("mass"), kp=spec.get("kp"), kd=spec.get("kd"), torque_lim=spec.get("torque_lim"), per_link=tuple(spec.get("per_link", ())))
+    b.Reset()
+    return {"hold_out": held}
+
+
 def setup_pushes(b, spec, greedy_envs=0):
     """Pushes while training (BatchScenario.PushSchedule): spec["wait"] = (lo, hi) frame boundaries between two pushes of an env, spec["force"] / ["duration"] =
     (lo, hi) ranges (missing: the batch's -min_perturb= ... arguments), spec["seed"], spec["hold_out"] = env ids that are never pushed (scale 0). The last
@@ -137,7 +155,7 @@ def setup_pushes(b, spec, greedy_envs=0):
 
 def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, device_id=-1, extra_args=None, seed=0, log_every=0, out_scale_file=None,
           trainer_device=None, overlap=False, frames_per_drain=1, scenario_cls=BatchScenario, trainer="torch", trainer_lib=None, poll=False,
-          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None, pushes=None, solver=None):
+          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None, pushes=None, solver=None, rescale=None):
     """extra_args override / extend the arg file (both for the engine and for the -trainer_* keys read here).
     overlap=True trains on frame f's tuples while the GPU already rolls out frame f+1 (dtrl_step_begin / dtrl_step_end): the policy
     each frame runs with is one frame staler, as with the reference's concurrent env threads; overlap=False is the strictly
@@ -157,10 +175,16 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     pushes=dict(wait=(lo, hi), force=(lo, hi), duration=(lo, hi), seed=, hold_out=[env ids]) trains under random external pushes (setup_pushes: every env but the
     held-out and the greedy ones is pushed at random times on the device, no host work per frame); stats["pushes"] then holds the held-out ids and PushInfo() at
     the end. Combines with greedy_envs and with variants. None (default) runs exactly as before.
+    rescale=dict(mass=(lo, hi), kp=, kd=, torque_lim=, per_link=("mass", ...), seed=, hold_out=[env ids]) trains under CONTINUOUS domain randomisation
+    (setup_rescale: every episode of every env under mass and motor scales drawn afresh from the ranges, on the device, without a table); stats["rescale"] then
+    holds the held-out ids and VariantRescaleInfo() at the end. Combines with variants (whose redraw then acts on the held-out envs alone) and with pushes; not
+    together with greedy_envs, as for variants. None (default) runs exactly as before.
     solver=dict(type="adam", base_lr=1e-4, clip_gradients=10, ...): overrides laid over the parsed solver prototxt (trainer.parse_solver's keys), for both trainers
     (CACLA: over both nets' files). None (default) runs exactly as before."""
     if variants is not None and greedy_envs:
         raise ValueError("greedy_envs > 0 together with variants: the greedy envs use policy slots, and policy slots exclude model variants")
+    if rescale is not None and greedy_envs:
+        raise ValueError("greedy_envs > 0 together with rescale: the greedy envs use policy slots, and policy slots exclude model variants")
     if overlap:
         extra_args = dict({"tuple_ring": "host"}, **(extra_args or {}))    # drains beside a running frame must not queue copies behind it (include/dtrl.h: dtrl_drain_tuples)
     args = parse_arg_file(os.path.join(data_root, arg_file))
@@ -222,6 +246,7 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
 
     sync(0)
     var_info = setup_variants(b, variants) if variants is not None else None   # (behind the first SetPolicy / SetExplore: its Reset runs a launch)
+    rescale_info = setup_rescale(b, rescale) if rescale is not None else None
     push_info = setup_pushes(b, pushes, greedy_envs) if pushes is not None else None
     frames = tuples = 0
     next_eval = [0 if eval_fn else None]
@@ -310,6 +335,8 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
         stats["greedy"] = dict(b.SlotStats(1), falls_k=greedy_falls())
     if var_info is not None:
         stats["variants"] = dict(var_info, **b.VariantRedrawInfo())
+    if rescale_info is not None:
+        stats["rescale"] = dict(rescale_info, **b.VariantRescaleInfo())
     if push_info is not None:
         stats["pushes"] = dict(push_info, **b.PushInfo())
     return stats

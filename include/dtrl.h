@@ -393,6 +393,46 @@ dtrl_status dtrl_variant_redraw(dtrl_batch* b, int lo, int hi, uint64_t seed, co
  * a redraw, otherwise waits for queued work. */
 dtrl_status dtrl_variant_redraw_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* lo, int32_t* hi, int32_t* variant, int32_t* draws);
 
+/* ---- Variant rescale: per-episode continuous mass and motor scales, drawn on the device ----
+ * No counterpart in the reference, which keeps one character per scene object. Where the redraw picks among the table's models, the rescale gives an env a PRIVATE
+ * model record and rewrites its mass and motor scalars from ranges at every episode start. With V = n_variants, the first call grows the device table once to
+ * V + num_envs records (with the streams idle, the old records copied): sizeof(DevModel) more per env -- 14 352 bytes in the fp64 library, 8 276 in the fp32
+ * library; 59 MB at 4096 envs in fp64. An env e that joins gets key V + e; its private record starts as a copy of variant `base` (all factors 1). At env e's
+ * EPISODE START -- a frame boundary at which it fell (need_reset bit 0), or dtrl_reset naming it -- while its key is V + e, with n = the env's `episodes`:
+ *   key    = mix(mix(seed) ^ (C + global env id))                                   (mix: the terrain streams' 64-bit finaliser, C a constant of the rescale's own)
+ *   u(q,j) = (mix(key + (n * 4 * L + q * L + j) * 0xD1342543DE82EF95) >> 11) * 2^-53   q = 0 mass, 1 kp, 2 kd, 3 torque_lim
+ *   f_q[j] = lo_q + u(q, j') * (hi_q - lo_q),  j' = j when bit q of per_link is set (one factor per link), else 0 (one factor for all links)
+ *   mass[j] = m0[j] * f_0[j]; total_mass, inertia[j] = mass[j] / 12 * (sx^2 + sy^2) and the subtree masses follow; kp, kd, torque_lim[j] = base value * f[j]
+ *   episodes += 1
+ * The base values are the character file's doubles, every product is taken in double and cast once, and every derived field is computed by the loader's
+ * formulas in the loader's order: the record holds the bits dtrl_variant_load_json would load from the base's character file with Mass, Kp, Kd and TorqueLim
+ * multiplied by the same factors -- in the fp32 library too. The index layout is fixed, so switching a quantity between uniform and per-link moves no other
+ * quantity's draws. The draw is a function of the seed, the GLOBAL env id and the env's episode number alone: shard-invariant, independent of exploration and
+ * of every other env. Only these scalars move: geometry, margins, contact points and limits are the base's (size scaling would move them and stays a matter of
+ * the table: ScaledVariant). The rule is one small launch per env group and frame in BOTH terrain modes, queued on the group's stream behind the variant redraw
+ * and in front of the push schedule and the reset launch, which therefore runs under the new scales; no host wait is added. Nothing else writes a record while
+ * launches run. Keys >= V appear in dtrl_get_variants; dtrl_assign_variants does not accept them (its range check stays), and assigning an ordinary variant to
+ * an env takes it out of the rescale. The redraw acts on keys below V only, so both rules can be on. dtrl_variant_stats keeps its range 0 .. V - 1.
+ * dtrl_get_link_states and dtrl_add_perturb read the base's geometry for an env under a private key. Settings, counters and private records are batch state
+ * like the assignment: snapshots, restores, clones and blobs leave them alone. */
+/* The four ranges {lo, hi} (0 < lo <= hi, finite; {1, 1} = not scaled) and the per_link mask (bit 0 mass, 1 kp, 2 kd, 3 torque_lim). */
+typedef struct dtrl_rescale_desc { double mass[2], kp[2], kd[2], torque_lim[2]; uint32_t per_link; uint32_t reserved; } dtrl_rescale_desc;
+/* No counterpart in the reference, which keeps one character per scene object. Turn the rescale on or replace its settings (desc != NULL), and put the listed
+ * envs under their private records (env_ids == NULL: the first n envs, n = num_envs: all; n = 0: the settings only). desc == NULL removes the rescale: its envs
+ * go back to key `base` of the rescale, the counters are kept. DTRL_ERR_ARG, nothing changed: no variants, base out of range or empty, a range with lo <= 0,
+ * lo > hi or a NaN or infinite bound, per_link bits beyond the four, an env id out of range, another base than the rescale's while envs run under private
+ * records, a frame in flight. While the rescale is on, dtrl_variant_load_* into its base is refused. */
+dtrl_status dtrl_variant_rescale(dtrl_batch* b, int base, const int32_t* env_ids, int n, uint64_t seed, const dtrl_rescale_desc* desc);
+/* No counterpart in the reference, which keeps one character per scene object. Any output may be NULL. The rescale's base, seed and settings, and per listed env
+ * (env_ids == NULL: the first n) its key, its episode count and the factors [n][4][L] of its CURRENT episode (recomputed on the host by the same rule from
+ * episodes - 1; all 1 for an env that is not under its private key or has started no episode yet), as of the last completed boundary: refused between
+ * dtrl_step_begin and dtrl_step_end and without a rescale, otherwise waits for queued work. */
+dtrl_status dtrl_variant_rescale_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* base, uint64_t* seed, dtrl_rescale_desc* desc, int32_t* key, int32_t* episodes, double* factors);
+/* No counterpart in the reference, which keeps one character per scene object. The mass and motor scalars of the model record env `env` runs under, read from the
+ * DEVICE table (private key or not; a batch without variants: its own model): out[6][L] = mass, inertia, sub_mass, kp, kd, torque_lim as doubles (exact casts of
+ * the record's `real`), and total_mass. Either output may be NULL. Refuses a frame in flight and waits for queued work. */
+dtrl_status dtrl_variant_scalars(dtrl_batch* b, int env, double* out, double* total_mass);
+
 /* ---- Terrain sets: several terrains in one batch, one per env ----
  * No counterpart in the reference, which keeps one terrain per scene object (cScenarioSimChar::ParseTerrainParams reads ONE -terrain_file= into the scene's
  * cGroundVar2D, scenarios/ScenarioSimChar.cpp:670-706): measuring a policy on flat / slopes_mixed / narrow_gaps / cliffs there means one scenario per terrain, and

@@ -5,7 +5,9 @@ Runs the dog's schedule of tools/learn_curve.py (args/opt_args_train_mace.txt on
 with the same seeds: once on the nominal model, once with train_loop.train(variants=...) -- a table of --variants models under seeded torso-mass and torque-limit
 scales, every episode of every env under a model drawn afresh (BatchScenario.VariantRedraw). Both final nets are then evaluated greedily over the torso mass x
 torque-limit grid of tools/robustness_sweep.py (one batch per net, one variant per cell, the same terrains in every cell and for both nets). Printed per cell:
-falls per 1000 env-steps of both nets. A result to report, not a bar to pass."""
+falls per 1000 env-steps of both nets. --continuous adds a third run: train_loop.train(rescale=...), the torso mass and the torque limits drawn afresh from the
+same two ranges at every episode of every env on the device (BatchScenario.VariantRescale, no table), evaluated over the same grid. A result to report, not a bar
+to pass."""
 import argparse, gc, os, sys, time
 import numpy as np
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
@@ -27,23 +29,30 @@ def run(a):
              % (a.variants, a.mass_range[0], a.mass_range[1], a.torque_range[0], a.torque_range[1], a.variant_seed, a.keep_nominal)]
     masses = [float(x) for x in a.mass.split(",")]; limits = [float(x) for x in a.torque.split(",")]
     grids = {}
-    for name, variants in (("nominal", None), ("redraw", spec)):
+    # (the rescale scales every body's mass by the one factor of the episode: per-link factors would scale each body on its own, and the grid varies the torso alone)
+    cont = dict(mass=tuple(a.mass_range), torque_lim=tuple(a.torque_range), seed=a.variant_seed)
+    if a.continuous:
+        lines.append("# continuous: mass scale (every body) uniform in [%g, %g], torque-limit scale uniform in [%g, %g], drawn per episode, seed %d" % (*a.mass_range, *a.torque_range, a.variant_seed))
+    runs = [("nominal", None, None), ("redraw", spec, None)] + ([("continuous", None, cont)] if a.continuous else [])
+    for name, variants, rescale in runs:
         t0 = time.time()
-        st = train_loop.train(c["train"], a.data_root, a.envs, max_iters=a.iters, overlap=True, trainer=a.trainer, seed=a.seed, extra_args=extra, variants=variants)
+        st = train_loop.train(c["train"], a.data_root, a.envs, max_iters=a.iters, overlap=True, trainer=a.trainer, seed=a.seed, extra_args=extra, variants=variants, rescale=rescale)
         line = "# %-8s training: %d frames, %d iterations, %d tuples, %.1f s, %.2f M env-steps/s" % (name, st["frames"], st["iters"], st["tuples"], time.time() - t0, st["env_steps_per_s"] / 1e6)
         if variants:
             line += "; %d draws, envs per variant at the end min %d max %d" % (int(st["variants"]["draws"].sum()), *(lambda h: (int(h.min()), int(h.max())))(np.bincount(st["variants"]["variant"], minlength=a.variants)))
+        if rescale:
+            line += "; %d episode starts under drawn scales" % int(st["rescale"]["episodes"].sum())
         lines.append(line); print(line, flush=True)
         gc.collect()   # (the training batch hangs in train()'s closures: give its device memory back before the next batches are built)
         grids[name] = robustness_sweep.sweep("dog", masses, limits, a.cell_envs, a.eval_frames, a.eval_seed, a.data_root, None, policy=(st["weights"], st["offset_scale"]))
-    for name in ("nominal", "redraw"):
+    for name, _, _ in runs:
         lines.append("## %s-trained net: falls per 1000 env-steps (rows: torso mass scale; columns: torque-limit scale)" % name)
         lines.append("   %8s " % "" + " ".join("%8.2f" % t for t in limits))
         for m in masses:
             lines.append("   %8.2f " % m + " ".join("%8.3f" % r["falls_k"] for mm, tt, r in grids[name] if mm == m))
     mean = {k: float(np.mean([r["falls_k"] for _, _, r in g])) for k, g in grids.items()}
     nom = {k: [r["falls_k"] for m, t, r in g if m == 1.0 and t == 1.0] for k, g in grids.items()}
-    lines.append("# mean over the grid: nominal-trained %.3f, redraw-trained %.3f; nominal cell (1, 1): %s" % (mean["nominal"], mean["redraw"],
+    lines.append("# mean over the grid: %s; nominal cell (1, 1): %s" % (", ".join("%s-trained %.3f" % (k, v) for k, v in mean.items()),
                  ", ".join("%s-trained %.3f" % (k, v[0]) for k, v in nom.items() if v) or "not in the grid"))
     return lines
 
@@ -58,6 +67,7 @@ def main():
     ap.add_argument("--keep-nominal", type=float, default=0.25)
     ap.add_argument("--mass-range", type=float, nargs=2, default=[0.7, 1.5])
     ap.add_argument("--torque-range", type=float, nargs=2, default=[0.6, 1.2])
+    ap.add_argument("--continuous", action="store_true", help="a third run trained under the variant rescale: scales drawn per episode from the two ranges, no table")
     ap.add_argument("--mass", default="0.7,0.85,1,1.15,1.3,1.5", help="evaluation grid: torso mass scales")
     ap.add_argument("--torque", default="0.6,0.8,1,1.2", help="evaluation grid: torque-limit scales")
     ap.add_argument("--cell-envs", type=int, default=128)

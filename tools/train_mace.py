@@ -29,6 +29,11 @@ ap.add_argument("--variant-kp", type=float, nargs=2, default=[1.0, 1.0], metavar
 ap.add_argument("--variant-kd", type=float, nargs=2, default=[1.0, 1.0], metavar=("LO", "HI"), help="with --variants: range of the PD controllers' Kd scale")
 ap.add_argument("--variant-seed", type=int, default=0, help="with --variants: seed of the scales, the initial deal and the redraw")
 ap.add_argument("--keep-nominal", type=float, default=None, help="with --variants: share of the draw's weight on the nominal model (default: 1 / variants)")
+ap.add_argument("--rescale", action="store_true", help="continuous domain randomisation while training (train_loop.train(rescale=...)): every episode of every env under mass and motor scales drawn afresh on the device from --rescale-mass / -kp / -kd / -torque-lim (not with --distributed)")
+for _q in ("mass", "kp", "kd", "torque-lim"):
+    ap.add_argument("--rescale-" + _q, type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --rescale: range of the %s scale (default: not scaled)" % _q)
+ap.add_argument("--rescale-per-link", nargs="*", default=[], choices=["mass", "kp", "kd", "torque_lim"], help="with --rescale: the quantities that draw one factor per link instead of one for all links")
+ap.add_argument("--rescale-seed", type=int, default=0, help="with --rescale: seed of the draws")
 ap.add_argument("--pushes", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="random pushes while training (train_loop.train(pushes=...)): every env is pushed on the device every LO .. HI frames (not with --distributed)")
 ap.add_argument("--push-force", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --pushes: range of the force magnitude in N (default: the arg file's -min_perturb= / -max_perturb=)")
 ap.add_argument("--push-duration", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --pushes: range of the duration in s (default: the arg file's)")
@@ -53,6 +58,14 @@ if a.pushes:
         pushes["duration"] = tuple(a.push_duration)
 if a.variants and a.distributed:
     ap.error("--variants is not available with --distributed")
+if a.rescale and a.distributed:
+    ap.error("--rescale is not available with --distributed")
+rescale = None
+if a.rescale:
+    rescale = dict(seed=a.rescale_seed, per_link=tuple(a.rescale_per_link))
+    for _q in ("mass", "kp", "kd", "torque_lim"):
+        if getattr(a, "rescale_" + _q) is not None:
+            rescale[_q] = tuple(getattr(a, "rescale_" + _q))
 variants = None
 if a.variants:
     variants = dict(count=a.variants, mass=tuple(a.variant_mass), torque_lim=tuple(a.variant_torque_lim), kp=tuple(a.variant_kp), kd=tuple(a.variant_kd), seed=a.variant_seed)
@@ -80,11 +93,13 @@ if a.distributed:
     sys.exit(0)
 st = train_loop.train(a.arg_file, a.data_root, a.envs, max_iters=a.iters, max_frames=a.frames, log_every=50, overlap=a.overlap, frames_per_drain=a.frames_per_drain,
                       extra_args=dict(({"reserve_cus": reserve} if reserve else {}), **({"trainer_num_init_samples": a.init_samples} if a.init_samples is not None else {})) or None,
-                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll, variants=variants, pushes=pushes, solver=solver)
+                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll, variants=variants, pushes=pushes, solver=solver, rescale=rescale)
 if a.out:
     np.save(a.out + ".npy", st["weights"])
 if variants:
     print("[variants] %d models, %d draws; envs per variant at the end: %s" % (a.variants, int(st["variants"]["draws"].sum()), np.bincount(st["variants"]["variant"], minlength=a.variants).tolist()))
+if rescale:
+    print("[rescale] %d episode starts under drawn scales, most on one env %d" % (int(st["rescale"]["episodes"].sum()), int(st["rescale"]["episodes"].max())))
 if pushes:
     print("[pushes] every %d .. %d frames; %d pushes, most on one env %d" % (a.pushes[0], a.pushes[1], int(st["pushes"]["pushes"].sum()), int(st["pushes"]["pushes"].max())))
 print("[trainer=%s reserve_cus=%d side-stream start delay %.0f us] " % (a.trainer, reserve, st["side_stream_delay_us"]), end="")
