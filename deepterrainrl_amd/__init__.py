@@ -66,6 +66,7 @@ ABI_SYMBOLS = [
     "dtrl_variants_create", "dtrl_variant_load_file", "dtrl_variant_load_json", "dtrl_assign_variants", "dtrl_get_variants", "dtrl_variant_stats", "dtrl_variant_redraw", "dtrl_variant_redraw_info",
     "dtrl_variant_rescale", "dtrl_variant_rescale_info", "dtrl_variant_scalars",
     "dtrl_push_schedule", "dtrl_push_scale", "dtrl_push_info",
+    "dtrl_episode_limit", "dtrl_episode_limit_envs", "dtrl_episode_info",
     "dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats", "dtrl_terrain_ladder", "dtrl_ladder_info",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
@@ -179,6 +180,9 @@ def _bind(path):
     L.dtrl_push_schedule.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double]
     L.dtrl_push_scale.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_push_info.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.dtrl_episode_limit.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint64]
+    L.dtrl_episode_limit_envs.argtypes = [vp, vp, C.c_int, vp]
+    L.dtrl_episode_info.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.dtrl_terrains_create.argtypes = [vp, C.c_int]
     L.dtrl_terrain_set_file.argtypes = [vp, C.c_int, C.c_char_p, C.c_double]
     L.dtrl_terrain_set_params.argtypes = [vp, C.c_int, C.c_char_p, vp]
@@ -615,6 +619,30 @@ class BatchScenario:
         force, dur = np.zeros((n, 2), np.float64), np.zeros(n, np.float64)
         self._chk(self._lib.dtrl_push_info(self._h, _p(ids), n, _p(wait), _p(pushes), _p(link), _p(force), _p(dur)))
         return {"wait": wait, "pushes": pushes, "last_link": link, "last_force": force, "last_dur": dur}
+
+    # ---- episode limits: episodes end by time or distance on the device (the reference's end by a fall alone) ----
+    def EpisodeLimit(self, frames=None, dist=None, seed=0):
+        """dtrl_episode_limit: from now on an env's episode ends -- as if the env had fallen, without a FAIL tuple -- after a number of frame boundaries drawn per
+        episode from frames = (lo, hi) (1 <= lo <= hi; None: no frame limit), or once its root is dist past the spawn x (None: no distance limit). The draw is a
+        function of (seed, global env id, the env's draws so far). One small launch per env group and frame, no host wait. EpisodeLimit() removes the limit
+        (records, counters and flags stay). Not with -policy_mode= external."""
+        lo, hi = (0, 0) if frames is None else frames
+        self._chk(self._lib.dtrl_episode_limit(self._h, int(lo), int(hi), float("inf") if dist is None else float(dist), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def EpisodeLimitEnvs(self, on, env_ids=None):
+        """dtrl_episode_limit_envs: per-env flag (1 unless set); 0 holds the env out of the limit: its episodes end by a fall alone and its record stays as it is."""
+        ids, n = self._ids(env_ids)
+        on = np.ascontiguousarray(np.broadcast_to(np.asarray(on).astype(bool).astype(np.uint8), (n,)))
+        self._chk(self._lib.dtrl_episode_limit_envs(self._h, _p(ids), n, _p(on)))
+
+    def EpisodeInfo(self, env_ids=None):
+        """dtrl_episode_info: {"frames", "limit", "last_frames", "last_cause" (int32 per listed env, all by default; cause 1 fall, 2 frame limit, 3 distance, 0 none
+        yet), "by_fall", "by_limit" (int64), "last_dist" (float64)} as of the last completed boundary."""
+        ids, n = self._ids(env_ids)
+        out = {k: np.zeros(n, t) for k, t in (("frames", np.int32), ("limit", np.int32), ("by_fall", np.int64), ("by_limit", np.int64), ("last_frames", np.int32),
+                                              ("last_dist", np.float64), ("last_cause", np.int32))}
+        self._chk(self._lib.dtrl_episode_info(self._h, _p(ids), n, *[_p(v) for v in out.values()]))
+        return out
 
     def SetPoseVel(self, q, qd, env_ids=None):
         ids, n = self._ids(env_ids)

@@ -1,8 +1,8 @@
 // dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, launches over
 // envs of several slots or variants and the per-slot sums, and the per-env rules of the frame boundary (terrain work under the batch's terrain, a terrain set
-// or a ladder; variant redraw; variant rescale; push schedule; perturbation rows), each built from the interface's own copies and Launch. The rules all run over an EnvSpan that
+// or a ladder; variant redraw; variant rescale; push schedule; perturbation rows; episode limit), each built from the interface's own copies and Launch. The rules all run over an EnvSpan that
 // SpanList turns into a host vector. What the lane-loop check build runs; the HIP backend overrides every one of them with kernels and keeps these as its
-// cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1, DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1).
+// cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1, DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1, DTRL_EPISODE_FALLBACK=1).
 // Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
 // lane-loop check build of any tests/ tree, the sanitizer scripts -- has the defaults, and no source list can lack them.
 #include "dtrl_engine.h"
@@ -222,6 +222,30 @@ bool Backend::PushSchedule(const EnvStatus* status, const EnvSpan& span, EnvStat
 		const bool fired = push_step(r, sc, start, cfg, e, out);
 		if (fired) { push_write_slot(slot, out); if (!WriteSlotFields(*this, st + e, slot)) return false; }
 		if (!H2D(recs + e, &r, sizeof(r))) return false;   // (an env in the schedule moves its record at every boundary: the wait, or the counter)
+	}
+	return true;
+}
+// Episode limit: the rule (episode_limit_step) on the host, env by env, behind a wait for the selected stream; the record goes back where it moved, and for an env
+// the rule ends, episode_end's three state fields and the status record. A held-out env costs one flag read.
+bool Backend::EpisodeLimit(EnvStatus* status, const EnvSpan& span, EnvState* st, EpisodeRec* recs, const uint8_t* on, const EpisodeCfg& cfg)
+{
+	std::vector<int32_t> list;
+	if (!SpanList(span, list)) return false;
+	if (list.empty()) return true;
+	if (!SyncSelected()) return false;
+	EnvStatus es; EpisodeRec r; uint8_t flag = 0; EnvState s;
+	for (int32_t e : list) {
+		if (!D2H(&flag, on + e, sizeof(flag))) return false;
+		if (!flag) continue;
+		if (status && !D2H(&es, status + e, sizeof(es))) return false;
+		if (!D2H(&r, recs + e, sizeof(r))) return false;
+		if (episode_limit_step(r, status ? &es : nullptr, cfg, e) != kEpisodeRuns) {
+			if (!D2H(&s, st + e, sizeof(s))) return false;
+			episode_end(s, es, cfg);
+			if (!H2D(&st[e].avg_dist, &s.avg_dist, sizeof(s.avg_dist)) || !H2D(&st[e].num_episodes, &s.num_episodes, sizeof(s.num_episodes)) || !H2D(&st[e].need_reset, &s.need_reset, sizeof(s.need_reset))
+				|| !H2D(&status[e].need_reset, &es.need_reset, sizeof(es.need_reset)) || !H2D(&status[e].episode_dist, &es.episode_dist, sizeof(es.episode_dist))) return false;
+		}
+		if (!H2D(recs + e, &r, sizeof(r))) return false;   // (an env under the limit moves its record at every boundary: the frame count)
 	}
 	return true;
 }

@@ -239,6 +239,23 @@ __global__ void __launch_bounds__(64) dtrl_push_schedule(const EnvStatus* __rest
 	if (push_step(r, sc, start, pc, e, out)) push_write_slot(st[e], out);
 	recs[e] = r;   // (an env in the schedule moves its record at every boundary: the wait, or the counter)
 }
+// Episode limit (include/dtrl.h dtrl_episode_limit): the envs of a group count the boundaries of their episodes behind the group's frame and IN FRONT OF every
+// other boundary rule, and an env that reached its drawn frame limit or the distance has its episode ended as a fall ends it (episode_limit_step / episode_end,
+// dtrl_terrain_dev.h): need_reset goes into its status record and its state, and everything queued behind -- boundary work, redraw, rescale, push schedule, the
+// reset launch -- sees an env whose episode ended. A kernel of its own: the frame and boundary kernels stay as they are. Thread per env, every word per env: no
+// atomics, no scratch. A held-out env is left after one byte load. The record is 48 bytes on a 16-byte boundary and is read as three 16-byte words; a boundary
+// that ends nothing stores the frame count alone, an episode start or end the whole record. status == nullptr: every listed env starts an episode.
+__global__ void __launch_bounds__(64) dtrl_episode_limit(EnvStatus* __restrict__ status, int e0, int n, const int32_t* __restrict__ env_list, EnvState* __restrict__ st, EpisodeRec* __restrict__ recs,
+	const uint8_t* __restrict__ on, EpisodeCfg ec)
+{
+	int e;
+	if (!span_env(static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x), e0, n, env_list, e)) return;
+	if (!on[e]) return;
+	EpisodeRec r = recs[e];
+	const int32_t cause = episode_limit_step(r, status ? status + e : nullptr, ec, e);
+	if (cause != kEpisodeRuns) episode_end(st[e], status[e], ec);
+	if (r.frames != 0) recs[e].frames = r.frames; else recs[e] = r;   // (frames == 0: an episode started or ended in this call)
+}
 // dtrl_add_perturb in one launch: a thread per row (the engine has reduced the rows to one per env), the seven slot fields each
 __global__ void __launch_bounds__(64) dtrl_perturb_scatter(EnvState* __restrict__ st, const PerturbRow* __restrict__ rows, int n)
 {
@@ -674,6 +691,12 @@ public:
 	{
 		if (EnvFlag("DTRL_PUSH_FALLBACK")) return Backend::PushSchedule(status, s, st, recs, scale, cfg);
 		return LaunchPerEnv(dtrl_push_schedule, s.n, "push schedule launch", status, s.e0, s.n, s.list, st, recs, scale, cfg);
+	}
+	// episode limit: ONE launch, queued in front of the boundary work. DTRL_EPISODE_FALLBACK=1 takes the host default
+	bool EpisodeLimit(EnvStatus* status, const EnvSpan& s, EnvState* st, EpisodeRec* recs, const uint8_t* on, const EpisodeCfg& cfg) override
+	{
+		if (EnvFlag("DTRL_EPISODE_FALLBACK")) return Backend::EpisodeLimit(status, s, st, recs, on, cfg);
+		return LaunchPerEnv(dtrl_episode_limit, s.n, "episode limit launch", status, s.e0, s.n, s.list, st, recs, on, cfg);
 	}
 	bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n) override
 	{

@@ -304,6 +304,10 @@ dtrl_status dtrl_variant_stats(dtrl_batch* b, int v, int64_t* n_envs, double* av
 dtrl_status dtrl_push_schedule(dtrl_batch* b, int min_wait, int max_wait, uint64_t seed, double min_force, double max_force, double min_dur, double max_dur) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.PushSchedule(min_wait, max_wait, seed, min_force, max_force, min_dur, max_dur)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_push_scale(dtrl_batch* b, const int32_t* env_ids, int n, const double* scales) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.PushScale(env_ids, n, scales)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_push_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* wait, int32_t* pushes, int32_t* last_link, double* last_force, double* last_dur) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.PushInfo(env_ids, n, wait, pushes, last_link, last_force, last_dur)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+// episode limit
+dtrl_status dtrl_episode_limit(dtrl_batch* b, int min_frames, int max_frames, double max_dist, uint64_t seed) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.EpisodeLimit(min_frames, max_frames, max_dist, seed)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_episode_limit_envs(dtrl_batch* b, const int32_t* env_ids, int n, const uint8_t* on) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.EpisodeLimitEnvs(env_ids, n, on)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
+dtrl_status dtrl_episode_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* frames, int32_t* limit, int64_t* by_fall, int64_t* by_limit, int32_t* last_frames, double* last_dist, int32_t* last_cause) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.EpisodeInfo(env_ids, n, frames, limit, by_fall, by_limit, last_frames, last_dist, last_cause)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 // terrain sets
 dtrl_status dtrl_terrains_create(dtrl_batch* b, int n_terrains) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainsCreate(n_terrains)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }
 dtrl_status dtrl_terrain_set_file(dtrl_batch* b, int t, const char* terrain_file, double lerp) try { CHECK_B(); return static_cast<dtrl_status>(b->eng.TerrainSetFile(t, terrain_file, lerp)); } catch (...) { return static_cast<dtrl_status>(dtrl_on_exception(b)); }

@@ -23,6 +23,7 @@
 #include <cstddef>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -358,6 +359,9 @@ int Engine::LaunchGroup(int group, int n_steps, double dt_step, bool frame_end)
 	if (ok && tuple_pipelining_ && n_steps > 0) ok = be_->MarkFrame(group, wr_ring_);
 	// the policy hand-over is double-buffered: remember which weight buffer this launch reads, so that a later gather INTO it can wait for the launch on the device
 	if (ok && weights_alt_ && n_steps > 0) ok = be_->MarkWeightReader(group, b.weights == weights_buf0_ ? 0 : 1);
+	// episode limit, host terrain: the rule is queued behind the group's frame so that it has amended the status records when HostFrameWork's wait for this stream
+	// returns and its loop reads them (device terrain: DeviceFrameWork queues it in front of the boundary launch)
+	if (ok && episode_on_ && !cfg_.device_terrain && n_steps > 0) ok = EpisodeQueue(buf_.status, EnvSpan{g.e0, g.n, nullptr});
 	if (g_ht.on) g_ht.t_launch += now_s() - lt0;
 	be_->SelectStream(0);
 	return ok ? DTRL_OK : Fail(DTRL_ERR_DEVICE, be_->error());
@@ -395,6 +399,7 @@ int Engine::UploadTerrainCfg(const double* params)
 
 // -terrain_gen= device: the frame boundary of one env group as three launches on the group's stream, behind its frame kernel and in front of its next
 // one -- the host neither waits nor loops over envs:
+//   dtrl_episode_limit     (with an episode limit) the envs whose episode reached its frame limit or the distance get need_reset, as if they had fallen
 //   dtrl_terrain_boundary  fresh windows for the envs that fell, slid windows where the character got close to an edge, episode distances logged
 //   dtrl_order_by_cost     launch order of the next frame (costliest wavefronts first)
 //   dtrl_variant_redraw    (with a variant redraw) the envs that fell draw the model variant of their next episode
@@ -409,6 +414,8 @@ int Engine::DeviceFrameWork(int group)
 	DevBuffers b = buf_;
 	b.env_list = nullptr; b.reset_listed = 2;
 	const EnvSpan span{grp.e0, grp.n, nullptr};
+	// episode limit: in front of every other rule -- for all of them an env the limit ended is an env whose episode ended
+	if (episode_on_ && !EpisodeQueue(buf_.status, span)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	if (!Boundary(span, 0) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	// variant redraw: the envs that fell draw their next variant behind their frame and in front of the reset launch, which then runs reset_env under the new model
 	if (redraw_on_) { variant_keys_.stale = true; if (!be_->VariantRedraw(buf_.status, span, variant_keys_.d_env_key, redraw_.dev, redraw_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error()); }
@@ -624,6 +631,8 @@ int Engine::RequireIdle(const std::string& refusal, bool drain)
 	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
 }
+// the x a reset leaves in q[0] (dtrl_kernel.h reset_env, cScenarioSimChar::InitCharacterPos)
+static double SpawnX(const DevModel& m) { return static_cast<double>(m.valid_init_pos_x ? m.init_pos_x : m.pose0[0]); }
 static const char* const kFrameInFlight = " between dtrl_step_begin and dtrl_step_end (or after dtrl_step_poll relaunched a group): a frame is in flight; call dtrl_step_end first";
 
 int Engine::StepUpdates(int n)
@@ -715,6 +724,7 @@ int Engine::Reset(const int32_t* env_ids, int n, const uint64_t* seeds)
 	int rc = ApplyResets(reset_ids_, -1);
 	if (rc != DTRL_OK) return rc;
 	if (rc = PushStart(static_cast<int>(reset_ids_.size())); rc != DTRL_OK) return rc;   // push schedule: an episode starts, a new wait once per listed env
+	if (rc = EpisodeStart(reset_ids_, true); rc != DTRL_OK) return rc;                   // episode limit: the same, frames 0 and a new limit once per listed env
 	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
 }
@@ -2333,6 +2343,79 @@ int Engine::PushInfo(const int32_t* env_ids, int n, int32_t* wait, int32_t* push
 	return DTRL_OK;
 }
 
+// ---- episode limit (include/dtrl.h: dtrl_episode_limit, dtrl_episode_limit_envs, dtrl_episode_info) ----
+// The rule is episode_limit_step (dtrl_terrain_dev.h), run by Backend::EpisodeLimit on the group's stream at every frame boundary in front of every other rule --
+// queued first by DeviceFrameWork (-terrain_gen= device), behind the frame launch by LaunchGroup (host terrain) -- and in its listed form here, by EpisodeStart
+// under dtrl_reset, a terrain restart and an env coming in. Records and flags live in device memory only.
+int Engine::EpisodeAlloc()
+{
+	if (episode_.dev && episode_flag_.dev) return DTRL_OK;
+	if (int rc = RecsAlloc(episode_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;   // (zero-filled: no episode yet)
+	if (int rc = RecsAlloc(episode_flag_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
+	episode_flag_.host.assign(static_cast<size_t>(n_), uint8_t(1));
+	return DevOk(episode_flag_.Push(*be_));
+}
+int Engine::EpisodeStart(const std::vector<int32_t>& ids, bool staged)
+{
+	if (!episode_on_ || ids.empty()) return DTRL_OK;
+	if (!staged) {
+		std::memcpy(pin_ids_, ids.data(), sizeof(int32_t) * ids.size());
+		if (!zero_copy_ && !be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * ids.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
+	}
+	return DevOk(EpisodeQueue(nullptr, EnvSpan{0, static_cast<int>(ids.size()), zero_copy_ ? pin_ids_ : d_env_list_}));
+}
+int Engine::EpisodeLimit(int min_frames, int max_frames, double max_dist, uint64_t seed)
+{
+	const std::string w = "dtrl_episode_limit: ";
+	if (cfg_.external_policy) return Fail(DTRL_ERR_ARG, w + "not available with -policy_mode= external (a parked env's boundaries are ticks, not frames: an episode counted in them would depend on the caller's pace)");
+	if (int rc = RequireIdle("dtrl_episode_limit" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (std::isnan(max_dist)) return Fail(DTRL_ERR_ARG, w + "max_dist is NaN (+inf or a value <= 0 means no distance limit); nothing changed");
+	if (min_frames < 0) return Fail(DTRL_ERR_ARG, w + "min_frames (" + std::to_string(min_frames) + ") must not be negative; nothing changed");
+	if (min_frames > max_frames) return Fail(DTRL_ERR_ARG, w + "min_frames (" + std::to_string(min_frames) + ") exceeds max_frames (" + std::to_string(max_frames) + "); nothing changed");
+	if (min_frames == 0 && max_frames != 0) return Fail(DTRL_ERR_ARG, w + "exactly one of min_frames / max_frames is 0 (both 0 mean no frame limit, else 1 <= min_frames <= max_frames); nothing changed");
+	if (!(max_dist > 0)) max_dist = std::numeric_limits<double>::infinity();
+	if (max_frames == 0 && std::isinf(max_dist)) { episode_on_ = false; return DTRL_OK; }   // removed: records, counters and flags stay
+	if (int rc = EpisodeAlloc(); rc != DTRL_OK) return rc;
+	episode_cfg_ = EpisodeCfg{min_frames, max_frames, max_dist, SpawnX(cfg_.model), seed, static_cast<int64_t>(cfg_.run.env_id_base), cfg_.model.scenario == kScnPoliEval ? 1 : 0, 0};
+	episode_on_ = true;
+	// every env under the limit starts an episode under the new settings: frames 0, a new limit (the counters and the draw streams go on where they were)
+	return DevOk(EpisodeQueue(nullptr, EnvSpan{0, n_, nullptr}) && be_->Sync());
+}
+int Engine::EpisodeLimitEnvs(const int32_t* env_ids, int n, const uint8_t* on)
+{
+	const std::string w = "dtrl_episode_limit_envs: ";
+	if (int rc = RequireIdle("dtrl_episode_limit_envs" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (int rc = CheckEnvList(w, env_ids, n, "; nothing changed", "on", on); rc != DTRL_OK) return rc;
+	if (int rc = EpisodeAlloc(); rc != DTRL_OK) return rc;
+	if (int rc = DevOk(episode_flag_.Pull(*be_)); rc != DTRL_OK) return rc;
+	const std::vector<uint8_t> before = episode_flag_.host;
+	for (int i = 0; i < n; ++i) episode_flag_.host[EnvIndex(env_ids, i)] = on[i] ? 1 : 0;   // (an env listed twice: its last flag holds)
+	std::vector<int32_t> came_in;
+	for (int e = 0; e < n_; ++e) if (episode_flag_.host[e] && !before[e]) came_in.push_back(e);
+	if (int rc = DevOk(episode_flag_.Push(*be_)); rc != DTRL_OK) return rc;
+	if (int rc = EpisodeStart(came_in, false); rc != DTRL_OK) return rc;   // an env that comes in while a limit runs starts an episode record now
+	return DevOk(be_->Sync());
+}
+int Engine::EpisodeInfo(const int32_t* env_ids, int n, int32_t* frames, int32_t* limit, int64_t* by_fall, int64_t* by_limit, int32_t* last_frames, double* last_dist, int32_t* last_cause)
+{
+	const std::string w = "dtrl_episode_info: ";
+	if (int rc = RequireIdle("dtrl_episode_info" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (!episode_.dev) return Fail(DTRL_ERR_ARG, w + "the batch has no episode limit (call dtrl_episode_limit or dtrl_episode_limit_envs first)");
+	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
+	if (int rc = DevOk(episode_.Pull(*be_)); rc != DTRL_OK) return rc;
+	for (int i = 0; i < n; ++i) {
+		const EpisodeRec& r = episode_.host[EnvIndex(env_ids, i)];
+		if (frames) frames[i] = r.frames;
+		if (limit) limit[i] = r.limit;
+		if (by_fall) by_fall[i] = r.by_fall;
+		if (by_limit) by_limit[i] = r.by_limit;
+		if (last_frames) last_frames[i] = r.last_frames;
+		if (last_dist) last_dist[i] = r.last_dist;
+		if (last_cause) last_cause[i] = r.last_cause;
+	}
+	return DTRL_OK;
+}
+
 // ---- terrain sets (include/dtrl.h: dtrl_terrains_create ... dtrl_terrain_stats) ----
 // The third per-env key family, and the one no frame launch reads: a terrain decides what an env's NEXT segments look like, and segments are built at the frame
 // boundary -- by the env's GroundWindow on the host, or by the boundary kernel (-terrain_gen= device), which takes the table and the per-env array as two extra
@@ -2452,6 +2535,7 @@ int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrain
 	}
 	if (int rc = ApplyResets(reset_ids_, -1); rc != DTRL_OK) return rc;
 	if (int rc = PushStart(static_cast<int>(reset_ids_.size())); rc != DTRL_OK) return rc;   // push schedule: the listed envs start over, a new wait each
+	if (int rc = EpisodeStart(reset_ids_, true); rc != DTRL_OK) return rc;                   // episode limit: and a new episode record each
 	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
 }
@@ -2484,8 +2568,8 @@ int Engine::TerrainLadder(int lo, int hi, double up_dist, double down_dist, int 
 	if (!(up_dist > 0)) return Fail(DTRL_ERR_ARG, w + "up_dist must be > 0, not " + std::to_string(up_dist));
 	if (!(down_dist >= 0)) return Fail(DTRL_ERR_ARG, w + "down_dist must be >= 0, not " + std::to_string(down_dist));
 	if (at_top != 0 && at_top != 1) return Fail(DTRL_ERR_ARG, w + "at_top must be 0 or 1, not " + std::to_string(at_top));
-	// the x a reset leaves in q[0] (dtrl_kernel.h reset_env, cScenarioSimChar::InitCharacterPos): one value for the batch
-	auto spawn_of = [](const DevModel& m) { return static_cast<double>(m.valid_init_pos_x ? m.init_pos_x : m.pose0[0]); };
+	// one spawn x for the batch
+	auto spawn_of = SpawnX;
 	const double spawn_x = spawn_of(cfg_.model);
 	for (size_t v = 0; v < var_models_.size(); ++v)
 		if (spawn_of(var_models_[v]) != spawn_x) return Fail(DTRL_ERR_ARG, w + "model variant " + std::to_string(v) + " spawns at another root x (" + std::to_string(spawn_of(var_models_[v])) + ") than the batch's model (" + std::to_string(spawn_x) + "): the ladder keeps one spawn x per batch");

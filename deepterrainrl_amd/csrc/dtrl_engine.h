@@ -117,7 +117,7 @@ public:
 	virtual bool GatherF32On(void* stream, float* dst, const float* src, const int32_t* idx, size_t n) { (void)stream; return GatherF32(dst, src, idx, n); }
 	// ---- the per-env rules of the frame boundary (dtrl_terrain_dev.h), each over an EnvSpan and queued on the selected stream ----
 	// Every default is a host loop over the span's envs with per-env D2H / H2D of what the rule reads and writes, synchronised -- what the lane-loop check build
-	// runs, and DTRL_TERRAINS_FALLBACK=1 / DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 / DTRL_PERTURB_FALLBACK=1 on HIP; the HIP backend overrides each with ONE
+	// runs, and DTRL_TERRAINS_FALLBACK=1 / DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 / DTRL_PERTURB_FALLBACK=1 / DTRL_EPISODE_FALLBACK=1 on HIP; the HIP backend overrides each with ONE
 	// launch of its kernel. All per-env arrays are device memory under the local env id, and are written back only where the rule changed them.
 	// the span as a host vector (a list is read back: the copy waits for the selected stream)
 	bool SpanList(const EnvSpan& span, std::vector<int32_t>& list);
@@ -141,6 +141,12 @@ public:
 	// afresh), any other counts down and is pushed at 0; status == nullptr: every env of the span starts (creation of the schedule, dtrl_reset, a terrain
 	// restart). recs[e] and the seven slot fields of st[e] move; an env of scale[e] == 0 is not touched. The default waits for the selected stream first.
 	virtual bool PushSchedule(const EnvStatus* status, const EnvSpan& span, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg);
+	// Episode limit (include/dtrl.h dtrl_episode_limit; episode_limit_step, episode_end). status != nullptr: every env of the span with on[e] != 0 counts the
+	// boundary; one that fell has its episode recorded, one that reached its frame limit or the distance has need_reset written into status[e] and st[e] (with the
+	// poli_eval episode bookkeeping frame_end() does for a fall), so that everything queued behind sees an env whose episode ended. status == nullptr: every env of
+	// the span starts an episode (the limit is set, dtrl_reset, a terrain restart). recs[e] moves; an env with on[e] == 0 is not touched. The default waits for the
+	// selected stream first (the lane-loop check build, DTRL_EPISODE_FALLBACK=1 on HIP); the HIP backend overrides it with one launch of dtrl_episode_limit.
+	virtual bool EpisodeLimit(EnvStatus* status, const EnvSpan& span, EnvState* st, EpisodeRec* recs, const uint8_t* on, const EpisodeCfg& cfg);
 	// dtrl_add_perturb: rows[0 .. n) (device memory, at most one row per env: the row names its env, so there is no span) into the perturbation slots of
 	// st[rows[i].env] (perturb_write_slot). The default copies each env's whole EnvState down, edits the seven fields and copies it back.
 	virtual bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n);
@@ -295,6 +301,10 @@ public:
 	int PushSchedule(int min_wait, int max_wait, uint64_t seed, double min_force, double max_force, double min_dur, double max_dur);
 	int PushScale(const int32_t* env_ids, int n, const double* scales);
 	int PushInfo(const int32_t* env_ids, int n, int32_t* wait, int32_t* pushes, int32_t* last_link, double* last_force, double* last_dur);
+	// episode limit (include/dtrl.h)
+	int EpisodeLimit(int min_frames, int max_frames, double max_dist, uint64_t seed);
+	int EpisodeLimitEnvs(const int32_t* env_ids, int n, const uint8_t* on);
+	int EpisodeInfo(const int32_t* env_ids, int n, int32_t* frames, int32_t* limit, int64_t* by_fall, int64_t* by_limit, int32_t* last_frames, double* last_dist, int32_t* last_cause);
 	int ApplyRandForce(const int32_t* env_ids, int n, uint64_t seed);
 	int GetPoliState(const int32_t* env_ids, int n, double* s);
 	int GetPolicyOutput(const int32_t* env_ids, int n, double* y);
@@ -513,6 +523,15 @@ private:
 	RuleRecs<PerturbRow> pert_rows_;                         // device [n]: the rows of one dtrl_add_perturb (allocated by the first call)
 	int PushAlloc();                                               // the two push arrays, once
 	int PushStart(int n_listed);   // dtrl_reset / terrain restart: the rule with `start` for the n_listed envs ApplyResets(ids, -1) has just launched (same list, stream 0)
+	// episode limit: settings, per-env records and per-env flags are batch state. The DEVICE records and flags are the only copy in both terrain modes (the host
+	// form is staging): the rule runs in Backend::EpisodeLimit on the group's stream in front of every other boundary rule -- first in DeviceFrameWork (-terrain_gen=
+	// device), behind the group's frame launch in LaunchGroup (host terrain: the wait HostFrameWork makes anyway covers it, and its loop reads the amended status)
+	bool episode_on_ = false;
+	EpisodeCfg episode_cfg_{};
+	RuleRecs<EpisodeRec> episode_; RuleRecs<uint8_t> episode_flag_;   // device [n] each (allocated by the first dtrl_episode_limit / dtrl_episode_limit_envs; flags 1)
+	int EpisodeAlloc();                                              // the two arrays, once
+	bool EpisodeQueue(EnvStatus* status, const EnvSpan& span) { return be_->EpisodeLimit(status, span, buf_.st, episode_.dev, episode_flag_.dev, episode_cfg_); }
+	int EpisodeStart(const std::vector<int32_t>& ids, bool staged);  // the rule's listed form for `ids` on stream 0 (staged: ApplyResets(ids, -1) has put this list into the id staging)
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

@@ -322,6 +322,68 @@ DTRL_TG_HD inline void push_write_slot(EnvState& st, const PushOut& p)
 	st.pert_f[0] = static_cast<real>(p.f[0]); st.pert_f[1] = static_cast<real>(p.f[1]);
 	st.pert_torque = 0; st.pert_time = 0; st.pert_dur = static_cast<real>(p.dur);
 }
+// ---- episode limit (include/dtrl.h dtrl_episode_limit): an env's episode ends after a per-episode drawn number of frame boundaries, or at a distance ----
+// per-env record: boundaries the running episode has seen, the limit drawn for it (0: none), the counter of the env's draw stream, the last episode that ended
+// (its length in boundaries, root_x - spawn_x at its end, cause 1 = fall, 2 = frame limit, 3 = distance; 0 = none yet) and how many ended by a fall / by a limit.
+// 48 bytes on a 16-byte boundary: a thread moves its record as three 16-byte words; what moves at a boundary that ends nothing is the first word alone
+struct alignas(16) EpisodeRec { int32_t frames, limit, draws, last_frames, last_cause, pad_; int64_t by_fall, by_limit; double last_dist; };
+static_assert(sizeof(EpisodeRec) == 48, "EpisodeRec is three 16-byte words");
+enum EpisodeCause { kEpisodeRuns = 0, kEpisodeFall = 1, kEpisodeFrames = 2, kEpisodeDist = 3 };
+// the batch's limit: the range the per-episode frame limit is drawn from (both 0: no frame limit), the distance (+inf: none), the x a reset leaves in q[0], the
+// stream's seed and env-id base, and whether the scenario is poli_eval (episode_end). A kernel ARGUMENT: DevBuffers and RunParams keep their layout
+struct EpisodeCfg {
+	int32_t min_frames, max_frames;
+	double max_dist, spawn_x;
+	uint64_t seed; int64_t env_id_base;
+	int32_t poli_eval, pad_;
+};
+// counter-based like the other rules, under a constant of its own: a function of (seed, GLOBAL env id, the env's draws so far) -- shard-invariant
+DTRL_TG_HD inline uint64_t episode_stream_key(uint64_t seed, int64_t global_env) { return tg_mix(tg_mix(seed) ^ (0xE9150DEULL + static_cast<uint64_t>(global_env))); }
+DTRL_TG_HD inline void episode_draw_limit(EpisodeRec& r, const EpisodeCfg& c, int env)
+{
+	if (c.max_frames == 0) { r.limit = 0; return; }   // no frame limit: nothing is drawn
+	const uint64_t key = episode_stream_key(c.seed, c.env_id_base + env);
+	const uint64_t z = tg_mix(key + static_cast<uint64_t>(r.draws) * 0xD1342543DE82EF95ULL);
+	r.draws += 1;
+	const double u = static_cast<double>(z >> 11) * (1.0 / 9007199254740992.0);
+	const int32_t l = c.min_frames + static_cast<int32_t>(u * static_cast<double>(c.max_frames - c.min_frames + 1));
+	r.limit = l > c.max_frames ? c.max_frames : l;
+}
+// The rule, the one body of host and device: env `env` (local id, not held out) at its frame boundary, given its status record as the frame kernel left it;
+// status == nullptr: an episode of the env starts without a boundary (the limit is set; dtrl_reset names the env; a terrain restart). Runs IN FRONT OF every other
+// boundary rule. Returns the cause for which the CALLER ends the env's episode (kEpisodeFrames, kEpisodeDist: episode_end below), else kEpisodeRuns -- also for an
+// env that fell, whose episode the frame kernel has ended already; a fall wins over a limit reached in the same frame. Doubles and integers only.
+DTRL_TG_HD inline int32_t episode_limit_step(EpisodeRec& r, const EnvStatus* status, const EpisodeCfg& c, int env)
+{
+	if (!status) { r.frames = 0; episode_draw_limit(r, c, env); return kEpisodeRuns; }
+	r.frames += 1;
+	const double dist = status->root_x - c.spawn_x;
+	int32_t cause = kEpisodeRuns;
+	if (status->need_reset != 0) cause = kEpisodeFall;
+	else if (r.limit > 0 && r.frames >= r.limit) cause = kEpisodeFrames;
+	else if (dist >= c.max_dist) cause = kEpisodeDist;
+	if (cause == kEpisodeRuns) return cause;
+	if (cause == kEpisodeFall) r.by_fall += 1; else r.by_limit += 1;
+	r.last_frames = r.frames; r.last_dist = dist; r.last_cause = cause;
+	r.frames = 0;
+	episode_draw_limit(r, c, env);
+	return cause == kEpisodeFall ? static_cast<int32_t>(kEpisodeRuns) : cause;
+}
+// What the caller of the rule does for an env whose episode the rule ended: frame_end()'s writes for a fall (dtrl_kernel.h), operation by operation in `real`,
+// without scenario_new_cycle -- no tuple is recorded, the one in progress is dropped by the reset. Reads q[0], pos_start_x, avg_dist, num_episodes and
+// num_cycles of the env's state; writes its avg_dist, num_episodes and need_reset, and need_reset / episode_dist of its status record.
+DTRL_TG_HD inline void episode_end(EnvState& st, EnvStatus& es, const EpisodeCfg& c)
+{
+	int32_t need = 1;
+	if (c.poli_eval && st.num_cycles >= 1) {
+		real dist = st.q[0] - st.pos_start_x;
+		st.avg_dist = (st.num_episodes * st.avg_dist + dist) / (st.num_episodes + 1.0);
+		st.num_episodes += 1;
+		es.episode_dist = dist; need = 3;
+	}
+	st.need_reset = need; es.need_reset = need;
+}
+
 // one row of dtrl_add_perturb as the engine uploads it (Backend::PerturbScatter): the rotated offset is the host's, bit for bit
 struct PerturbRow { int32_t env, link; real f[2], lp[2], dur; };
 DTRL_TG_HD inline void perturb_write_slot(EnvState& st, const PerturbRow& r)

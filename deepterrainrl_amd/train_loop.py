@@ -153,9 +153,26 @@ def setup_pushes(b, spec, greedy_envs=0):
     return {"hold_out": held}
 
 
+def setup_episode_limit(b, spec, greedy_envs=0):
+    """Episode limits while training (BatchScenario.EpisodeLimit): spec["frames"] = (lo, hi) frame boundaries an episode lasts at most, drawn per episode, and / or
+    spec["dist"] = the distance from the spawn x at which it ends; spec["seed"]; spec["hold_out"] = env ids whose episodes end by a fall alone. The last greedy_envs
+    envs (train(greedy_envs=k): the evaluation envs) are held out as well, as setup_pushes holds them out. Returns {"hold_out": the held-out ids}."""
+    unknown = set(spec) - {"frames", "dist", "seed", "hold_out"}
+    if unknown:
+        raise ValueError("episode_limit: unknown keys %s" % ", ".join(sorted(unknown)))
+    if spec.get("frames") is None and spec.get("dist") is None:
+        raise ValueError("episode_limit: frames=(lo, hi) or dist= is required")
+    held = sorted(set(int(e) for e in spec.get("hold_out", ())) | set(range(b.num_envs - greedy_envs, b.num_envs)))
+    if held:
+        b.EpisodeLimitEnvs(0, env_ids=held)
+    frames = spec.get("frames")
+    b.EpisodeLimit(None if frames is None else tuple(frames), dist=spec.get("dist"), seed=int(spec.get("seed", 0)))
+    return {"hold_out": held}
+
+
 def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, device_id=-1, extra_args=None, seed=0, log_every=0, out_scale_file=None,
           trainer_device=None, overlap=False, frames_per_drain=1, scenario_cls=BatchScenario, trainer="torch", trainer_lib=None, poll=False,
-          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None, pushes=None, solver=None, rescale=None):
+          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None, pushes=None, solver=None, rescale=None, episode_limit=None):
     """extra_args override / extend the arg file (both for the engine and for the -trainer_* keys read here).
     overlap=True trains on frame f's tuples while the GPU already rolls out frame f+1 (dtrl_step_begin / dtrl_step_end): the policy
     each frame runs with is one frame staler, as with the reference's concurrent env threads; overlap=False is the strictly
@@ -179,6 +196,10 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     (setup_rescale: every episode of every env under mass and motor scales drawn afresh from the ranges, on the device, without a table); stats["rescale"] then
     holds the held-out ids and VariantRescaleInfo() at the end. Combines with variants (whose redraw then acts on the held-out envs alone) and with pushes; not
     together with greedy_envs, as for variants. None (default) runs exactly as before.
+    episode_limit=dict(frames=(lo, hi), dist=, seed=, hold_out=[env ids]) ends every episode after a per-episode drawn number of frames or at a distance
+    (setup_episode_limit: on the device, no host work per frame), so that the per-episode draws of variants, rescale and pushes and the terrain ladder's mark keep
+    moving under a policy that no longer falls; the greedy evaluation envs are held out as setup_pushes holds them out. stats["episode_limit"] then holds the
+    held-out ids and EpisodeInfo() at the end. Combines with all of the above. None (default) runs exactly as before.
     solver=dict(type="adam", base_lr=1e-4, clip_gradients=10, ...): overrides laid over the parsed solver prototxt (trainer.parse_solver's keys), for both trainers
     (CACLA: over both nets' files). None (default) runs exactly as before."""
     if variants is not None and greedy_envs:
@@ -248,6 +269,7 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     var_info = setup_variants(b, variants) if variants is not None else None   # (behind the first SetPolicy / SetExplore: its Reset runs a launch)
     rescale_info = setup_rescale(b, rescale) if rescale is not None else None
     push_info = setup_pushes(b, pushes, greedy_envs) if pushes is not None else None
+    limit_info = setup_episode_limit(b, episode_limit, greedy_envs) if episode_limit is not None else None
     frames = tuples = 0
     next_eval = [0 if eval_fn else None]
     if eval_fn:
@@ -339,6 +361,8 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
         stats["rescale"] = dict(rescale_info, **b.VariantRescaleInfo())
     if push_info is not None:
         stats["pushes"] = dict(push_info, **b.PushInfo())
+    if limit_info is not None:
+        stats["episode_limit"] = dict(limit_info, **b.EpisodeInfo())
     return stats
 
 

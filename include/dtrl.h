@@ -548,6 +548,43 @@ dtrl_status dtrl_push_scale(dtrl_batch* b, const int32_t* env_ids, int n, const 
  * boundary: refused between dtrl_step_begin and dtrl_step_end and before the first dtrl_push_schedule / dtrl_push_scale, otherwise waits for queued work. Any
  * output may be NULL. */
 dtrl_status dtrl_push_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* wait, int32_t* pushes, int32_t* last_link, double* last_force, double* last_dur);
+/* ---- Episode limits: end episodes by time or distance, on the device ----
+ * No counterpart in the reference: its episodes end by a fall alone (`scenarios/ScenarioExp.cpp:83-98`, `scenarios/ScenarioPoliEval.cpp:110-125`). With a limit, an
+ * env whose episode has lasted a per-episode drawn number of frame boundaries, or has travelled max_dist from the spawn x, ends its episode at that boundary as if
+ * it had fallen -- without a DTRL_TUPLE_FAIL tuple and without the host. Each env carries a record (frames, limit, draws, the last episode, by_fall, by_limit) and a
+ * flag (1 unless set; 0 holds the env out: nothing of it is read, drawn or written). The limit of an episode is limit = min_frames + floor(u * (max_frames -
+ * min_frames + 1)), clamped to max_frames, with u = (bits >> 11) * 2^-53, bits = mix(mix(mix(seed) ^ (C + global env id)) + draws++ * 0xD1342543DE82EF95): mix is
+ * the terrain streams' 64-bit finaliser, C a constant of the limit's own, the global env id -env_id_base= + local id. A range rather than one number, so that
+ * lock-stepped envs do not all reset in the same frame. min_frames == max_frames == 0: no frame limit, nothing is drawn, limit is 0. At env e's FRAME BOUNDARY (the
+ * boundaries the push schedule counts), in front of every other boundary rule:
+ *   flag[e] == 0              nothing
+ *   the env fell              frames += 1, by_fall += 1, the episode is recorded (last_frames, last_dist = root_x - spawn_x, last_cause 1); frames = 0, a new limit.
+ *                             A fall wins over a limit reached in the same frame.
+ *   else                      frames += 1; limit > 0 and frames >= limit: cause 2; else root_x - spawn_x >= max_dist: cause 3. Either: by_limit += 1, the episode is
+ *                             recorded, frames = 0, a new limit, and the env's episode ENDS: need_reset is written into its status record and its state, in the
+ *                             poli_eval scenario with num_cycles >= 1 together with what a fall does there (dist = q[0] - pos_start_x, the avg_dist / num_episodes
+ *                             update, the distance log entry), computed in the library's arithmetic type.
+ * An episode also starts, without a boundary (frames = 0, a new limit), when the limit is set, when dtrl_reset names the env (once however often it is listed), on
+ * dtrl_assign_terrains with restart != 0, and when the env's flag goes from 0 to 1 while a limit runs. For every rule behind it the env is one whose episode ended:
+ * the terrain ladder puts its mark back to the spawn x (and moves the env down only if it is less than down_dist past its mark), redraw and rescale draw, the push
+ * schedule draws a wait, the terrain work builds a fresh window, and the reset launch resets it under the new model. The tuple in progress is dropped, as dtrl_reset
+ * on a running env drops it. The rule is one small launch per env group and frame on the group's stream in both terrain modes: no host wait is added
+ * (dtrl_run_frames and the overlapped loops included), and a batch without a limit queues what it always queued. dtrl_eval_stats' resets goes on counting every
+ * reset; by_fall / by_limit split them by cause. Settings, records and flags are batch state: snapshots, restores, clones and blobs leave them alone. */
+/* No counterpart in the reference: its episodes end by a fall alone (`scenarios/ScenarioExp.cpp:83-98`, `scenarios/ScenarioPoliEval.cpp:110-125`). Sets the limit,
+ * replaces it (every env under it starts an episode: frames 0, a new limit) or removes it (min_frames == max_frames == 0 and max_dist +inf or <= 0). max_dist +inf
+ * or <= 0: no distance limit. Records, counters and flags are kept in all three cases. spawn_x is the x a reset leaves in q[0]. DTRL_ERR_ARG, nothing changed:
+ * min_frames < 0, min_frames > max_frames, exactly one of the two is 0, NaN, -policy_mode= external (a parked env's boundaries are ticks), a frame in flight. */
+dtrl_status dtrl_episode_limit(dtrl_batch* b, int min_frames, int max_frames, double max_dist, uint64_t seed);
+/* No counterpart in the reference: its episodes end by a fall alone (`scenarios/ScenarioExp.cpp:83-98`, `scenarios/ScenarioPoliEval.cpp:110-125`). on[i] -> the flag
+ * of env_ids[i] (env_ids == NULL: the first n envs), all or nothing (DTRL_ERR_ARG, nothing changed); an env listed twice keeps its last flag. May be called before
+ * dtrl_episode_limit. An env that comes in (0 -> 1) while a limit runs starts an episode record at this call. Refused while a frame is in flight. */
+dtrl_status dtrl_episode_limit_envs(dtrl_batch* b, const int32_t* env_ids, int n, const uint8_t* on);
+/* No counterpart in the reference: its episodes end by a fall alone (`scenarios/ScenarioExp.cpp:83-98`, `scenarios/ScenarioPoliEval.cpp:110-125`). Per listed env
+ * (env_ids == NULL: the first n): the record as of the last completed boundary -- boundaries of the running episode, its limit (0: none), episodes ended by a fall
+ * and by a limit, and the last ended episode's length, root_x - spawn_x and cause (1 fall, 2 frame limit, 3 distance; 0 none yet). Refused between dtrl_step_begin
+ * and dtrl_step_end and before the first dtrl_episode_limit / dtrl_episode_limit_envs, otherwise waits for queued work. Any output may be NULL. */
+dtrl_status dtrl_episode_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* frames, int32_t* limit, int64_t* by_fall, int64_t* by_limit, int32_t* last_frames, double* last_dist, int32_t* last_cause);
 /* Replaces: cNNController::RecordPoliState (sim/TerrainRLCharController.cpp:120-123). */
 dtrl_status dtrl_get_poli_state(dtrl_batch* b, const int32_t* env_ids, int n, double* s);
 /* Replaces: cNeuralNet::GetLayerState("output", y) (learning/NeuralNet.cpp:814-834) after the controller's last cNeuralNet::Eval

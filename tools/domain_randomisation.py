@@ -33,15 +33,21 @@ def run(a):
     cont = dict(mass=tuple(a.mass_range), torque_lim=tuple(a.torque_range), seed=a.variant_seed)
     if a.continuous:
         lines.append("# continuous: mass scale (every body) uniform in [%g, %g], torque-limit scale uniform in [%g, %g], drawn per episode, seed %d" % (*a.mass_range, *a.torque_range, a.variant_seed))
+    # (--episode-limit: all runs alike, so that the redraw and the rescale keep drawing once the policy has stopped falling)
+    limit = dict(frames=tuple(a.episode_limit), seed=a.variant_seed) if a.episode_limit else None
+    if limit:
+        lines.append("# episode limit: every episode ends after %d .. %d frames at the latest, drawn per episode, seed %d" % (*a.episode_limit, a.variant_seed))
     runs = [("nominal", None, None), ("redraw", spec, None)] + ([("continuous", None, cont)] if a.continuous else [])
     for name, variants, rescale in runs:
         t0 = time.time()
-        st = train_loop.train(c["train"], a.data_root, a.envs, max_iters=a.iters, overlap=True, trainer=a.trainer, seed=a.seed, extra_args=extra, variants=variants, rescale=rescale)
+        st = train_loop.train(c["train"], a.data_root, a.envs, max_iters=a.iters, overlap=True, trainer=a.trainer, seed=a.seed, extra_args=extra, variants=variants, rescale=rescale, episode_limit=limit)
         line = "# %-8s training: %d frames, %d iterations, %d tuples, %.1f s, %.2f M env-steps/s" % (name, st["frames"], st["iters"], st["tuples"], time.time() - t0, st["env_steps_per_s"] / 1e6)
         if variants:
             line += "; %d draws, envs per variant at the end min %d max %d" % (int(st["variants"]["draws"].sum()), *(lambda h: (int(h.min()), int(h.max())))(np.bincount(st["variants"]["variant"], minlength=a.variants)))
         if rescale:
             line += "; %d episode starts under drawn scales" % int(st["rescale"]["episodes"].sum())
+        if limit:
+            line += "; %d episodes ended by the limit, %d by a fall" % (int(st["episode_limit"]["by_limit"].sum()), int(st["episode_limit"]["by_fall"].sum()))
         lines.append(line); print(line, flush=True)
         gc.collect()   # (the training batch hangs in train()'s closures: give its device memory back before the next batches are built)
         grids[name] = robustness_sweep.sweep("dog", masses, limits, a.cell_envs, a.eval_frames, a.eval_seed, a.data_root, None, policy=(st["weights"], st["offset_scale"]))
@@ -68,6 +74,7 @@ def main():
     ap.add_argument("--mass-range", type=float, nargs=2, default=[0.7, 1.5])
     ap.add_argument("--torque-range", type=float, nargs=2, default=[0.6, 1.2])
     ap.add_argument("--continuous", action="store_true", help="a third run trained under the variant rescale: scales drawn per episode from the two ranges, no table")
+    ap.add_argument("--episode-limit", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="every training run under an episode limit of LO .. HI frames (train_loop.train(episode_limit=...)): episodes, and with them the draws, keep coming under a policy that no longer falls")
     ap.add_argument("--mass", default="0.7,0.85,1,1.15,1.3,1.5", help="evaluation grid: torso mass scales")
     ap.add_argument("--torque", default="0.6,0.8,1,1.2", help="evaluation grid: torque-limit scales")
     ap.add_argument("--cell-envs", type=int, default=128)
