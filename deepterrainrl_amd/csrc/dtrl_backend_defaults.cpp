@@ -151,12 +151,18 @@ bool Backend::SpanList(const EnvSpan& span, std::vector<int32_t>& list)
 	for (int k = 0; k < span.n; ++k) span_env(k, span.e0, span.n, nullptr, list[k]);
 	return true;
 }
+// The opening of every rule default below: the span as a host vector and, with `wait`, the wait for the selected stream. False: the default is over, and *done
+// is what it returns -- true for an empty span, false where a copy or the wait failed
+static bool SpanOpen(Backend& be, const EnvSpan& span, bool wait, std::vector<int32_t>& list, bool* done)
+{
+	*done = be.SpanList(span, list) && (list.empty() || !wait || be.SyncSelected());
+	return *done && !list.empty();
+}
 // Variant redraw: the rule (var_redraw_step) on the host, env by env; key and counter go back where they changed. The first D2H waits for the selected stream.
 bool Backend::VariantRedraw(const EnvStatus* status, const EnvSpan& span, int32_t* env_model, RedrawRec* recs, const RedrawCfg& cfg)
 {
-	std::vector<int32_t> list;
-	if (!SpanList(span, list)) return false;
-	if (list.empty()) return true;
+	std::vector<int32_t> list; bool done;
+	if (!SpanOpen(*this, span, false, list, &done)) return done;
 	std::vector<double> cum(static_cast<size_t>(cfg.hi - cfg.lo + 1));
 	if (!D2H(cum.data(), cfg.cum, sizeof(double) * cum.size())) return false;
 	EnvStatus st; RedrawRec r; int32_t key = 0;
@@ -175,10 +181,8 @@ bool Backend::VariantRedraw(const EnvStatus* status, const EnvSpan& span, int32_
 // and the counter go back. Waits for the selected stream first.
 bool Backend::VariantRescale(const EnvStatus* status, const EnvSpan& span, const int32_t* env_model, DevModel* models, int key_base, RescaleRec* recs, const ModelScalarsD* base, const RescaleCfg& cfg)
 {
-	std::vector<int32_t> list;
-	if (!SpanList(span, list)) return false;
-	if (list.empty()) return true;
-	if (!SyncSelected()) return false;
+	std::vector<int32_t> list; bool done;
+	if (!SpanOpen(*this, span, true, list, &done)) return done;
 	ModelScalarsD b;
 	if (!D2H(&b, base, sizeof(b))) return false;
 	EnvStatus st; RescaleRec r; int32_t key = 0; DevModel m;
@@ -207,10 +211,8 @@ static bool WriteSlotFields(Backend& be, EnvState* dst, const EnvState& src)
 }
 bool Backend::PushSchedule(const EnvStatus* status, const EnvSpan& span, EnvState* st, PushRec* recs, const double* scale, const PushCfg& cfg)
 {
-	std::vector<int32_t> list;
-	if (!SpanList(span, list)) return false;
-	if (list.empty()) return true;
-	if (!SyncSelected()) return false;
+	std::vector<int32_t> list; bool done;
+	if (!SpanOpen(*this, span, true, list, &done)) return done;
 	EnvStatus es; PushRec r; double sc = 0; EnvState slot;
 	for (int32_t e : list) {
 		if (!D2H(&sc, scale + e, sizeof(sc))) return false;
@@ -229,10 +231,8 @@ bool Backend::PushSchedule(const EnvStatus* status, const EnvSpan& span, EnvStat
 // the rule ends, episode_end's three state fields and the status record. A held-out env costs one flag read.
 bool Backend::EpisodeLimit(EnvStatus* status, const EnvSpan& span, EnvState* st, EpisodeRec* recs, const uint8_t* on, const EpisodeCfg& cfg)
 {
-	std::vector<int32_t> list;
-	if (!SpanList(span, list)) return false;
-	if (list.empty()) return true;
-	if (!SyncSelected()) return false;
+	std::vector<int32_t> list; bool done;
+	if (!SpanOpen(*this, span, true, list, &done)) return done;
 	EnvStatus es; EpisodeRec r; uint8_t flag = 0; EnvState s;
 	for (int32_t e : list) {
 		if (!D2H(&flag, on + e, sizeof(flag))) return false;
@@ -274,9 +274,8 @@ bool Backend::TerrainBoundary(const DevBuffers& buf, const EnvSpan& span, int mo
 bool Backend::TerrainBoundary(const DevBuffers& buf, int e0, int n, int mode, const int32_t* env_list) { return TerrainBoundaryLoop(buf, EnvSpan{e0, n, env_list}, mode, TerrainRule{}); }
 bool Backend::TerrainBoundaryLoop(const DevBuffers& buf, const EnvSpan& span, int mode, const TerrainRule& rule)
 {
-	std::vector<int32_t> list;
-	if (!SpanList(span, list)) return false;
-	if (list.empty()) return true;
+	std::vector<int32_t> list; bool done;
+	if (!SpanOpen(*this, span, false, list, &done)) return done;
 	int32_t cursor = 0;
 	if (buf.dist_ring && !D2H(&cursor, buf.dist_count, sizeof(cursor))) return false;
 	const int32_t cursor0 = cursor;

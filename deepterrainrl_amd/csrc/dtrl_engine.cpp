@@ -317,17 +317,23 @@ bool Engine::UploadGround(int env)
 	if (!be_->H2D(&buf_.gr[env], &tmp_rec_, sizeof(GroundRec))) { err_ = be_->error(); return false; }
 	return true;
 }
+const int32_t* Engine::StageIds(const std::vector<int32_t>& ids, int off)
+{
+	std::memcpy(pin_ids_ + off, ids.data(), sizeof(int32_t) * ids.size());
+	if (zero_copy_) return pin_ids_ + off;
+	if (!be_->H2DAsync(d_env_list_ + off, pin_ids_ + off, sizeof(int32_t) * ids.size())) { err_ = be_->error(); return nullptr; }
+	return d_env_list_ + off;
+}
 // device-side half of a reset (cSimCharacter::Reset + controller reset + InitCharacterPos), on the listed envs only:
 // a compact 0-step launch, so getters observe the reset state right after Update() as with the reference.
 // group >= 0: the group's stream and its slices of the staging / list buffers; group < 0: whole batch on stream 0 (user resets).
-int Engine::ApplyResets(const std::vector<int32_t>& ids, int group)
+int Engine::ApplyResets(const std::vector<int32_t>& ids, int group, const int32_t* staged)
 {
 	if (ids.empty()) return DTRL_OK;
 	const int off = group >= 0 ? groups_[group].e0 : 0;
-	std::memcpy(pin_ids_ + off, ids.data(), sizeof(int32_t) * ids.size());
-	if (!zero_copy_ && !be_->H2DAsync(d_env_list_ + off, pin_ids_ + off, sizeof(int32_t) * ids.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
 	DevBuffers b = buf_;
-	b.env_list = (zero_copy_ ? pin_ids_ : d_env_list_) + off;
+	b.env_list = staged ? staged : StageIds(ids, off);
+	if (!b.env_list) return DTRL_ERR_DEVICE;
 	b.reset_listed = 1;
 	if (!LaunchEnvs(b, static_cast<int>(ids.size()), 0, 0.0, false, pin_ids_ + off, group >= 0 ? off : n_)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
@@ -361,7 +367,7 @@ int Engine::LaunchGroup(int group, int n_steps, double dt_step, bool frame_end)
 	if (ok && weights_alt_ && n_steps > 0) ok = be_->MarkWeightReader(group, b.weights == weights_buf0_ ? 0 : 1);
 	// episode limit, host terrain: the rule is queued behind the group's frame so that it has amended the status records when HostFrameWork's wait for this stream
 	// returns and its loop reads them (device terrain: DeviceFrameWork queues it in front of the boundary launch)
-	if (ok && episode_on_ && !cfg_.device_terrain && n_steps > 0) ok = EpisodeQueue(buf_.status, EnvSpan{g.e0, g.n, nullptr});
+	if (ok && !cfg_.device_terrain && n_steps > 0) ok = RulesBehindFrame(EnvSpan{g.e0, g.n, nullptr});
 	if (g_ht.on) g_ht.t_launch += now_s() - lt0;
 	be_->SelectStream(0);
 	return ok ? DTRL_OK : Fail(DTRL_ERR_DEVICE, be_->error());
@@ -414,16 +420,8 @@ int Engine::DeviceFrameWork(int group)
 	DevBuffers b = buf_;
 	b.env_list = nullptr; b.reset_listed = 2;
 	const EnvSpan span{grp.e0, grp.n, nullptr};
-	// episode limit: in front of every other rule -- for all of them an env the limit ended is an env whose episode ended
-	if (episode_on_ && !EpisodeQueue(buf_.status, span)) return Fail(DTRL_ERR_DEVICE, be_->error());
-	if (!Boundary(span, 0) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_)) return Fail(DTRL_ERR_DEVICE, be_->error());
-	// variant redraw: the envs that fell draw their next variant behind their frame and in front of the reset launch, which then runs reset_env under the new model
-	if (redraw_on_) { variant_keys_.stale = true; if (!be_->VariantRedraw(buf_.status, span, variant_keys_.d_env_key, redraw_.dev, redraw_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error()); }
-	// variant rescale: behind the redraw (which acts on keys below V only), the envs that fell under their private record get it rewritten for their next episode
-	if (rescale_on_ && !RescaleQueue(buf_.status, span)) return Fail(DTRL_ERR_DEVICE, be_->error());
-	// push schedule: the group's envs count down, and the ones that are due get their push, behind the frame and in front of the reset launch (an env that fell
-	// draws a new wait and is not pushed: the reset launch clears nothing the rule wrote)
-	if (push_on_ && !be_->PushSchedule(buf_.status, span, buf_.st, push_.dev, push_scale_.dev, push_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	// (the order of the rules: dtrl_engine.h)
+	if (!RulesBehindFrame(span) || !Boundary(span, 0) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_) || !RulesBeforeResets(span)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	b.env_list = d_order_ + grp.e0;
 	if (!LaunchEnvs(b, grp.n, 0, 0.0, false, nullptr, grp.e0)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
@@ -518,10 +516,8 @@ int Engine::HostFrameWork(int group)
 	for (int e = e0; e < e1; ++e) pin_order_[e0 + bucket_[key(e)]++] = e;
 	const double ht3 = g_ht.on ? now_s() : 0;
 	// variant rescale, then push schedule: the same launches as in device terrain mode, on the group's stream (idle since the wait above; the redraw's key upload is
-	// queued on it) in front of the reset launch; status_ is the
-	// page-locked array the frame kernel wrote, which the device reads through the same pointer
-	if (rescale_on_ && !RescaleQueue(buf_.status, EnvSpan{e0, grp.n, nullptr})) return Fail(DTRL_ERR_DEVICE, be_->error());
-	if (push_on_ && !be_->PushSchedule(buf_.status, EnvSpan{e0, grp.n, nullptr}, buf_.st, push_.dev, push_scale_.dev, push_cfg_)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	// queued on it) in front of the reset launch; status_ is the page-locked array the frame kernel wrote, which the device reads through the same pointer
+	if (!RulesBeforeResets(EnvSpan{e0, grp.n, nullptr})) return Fail(DTRL_ERR_DEVICE, be_->error());
 	const int rc = ApplyResets(reset_ids_, group);
 	if (g_ht.on) { const double ht4 = now_s(); g_ht.t_sync += ht1 - ht0; g_ht.t_loop += ht2 - ht1; g_ht.t_sort += ht3 - ht2; g_ht.t_reset += ht4 - ht3; g_ht.regen += used; ++g_ht.n; }
 	return rc;
@@ -715,18 +711,24 @@ int Engine::Reset(const int32_t* env_ids, int n, const uint64_t* seeds)
 		if (!UploadGround(e)) return DTRL_ERR_CAPACITY;
 		reset_ids_.push_back(e);
 	}
-	if (cfg_.device_terrain && !reset_ids_.empty()) {
-		std::memcpy(pin_ids_, reset_ids_.data(), sizeof(int32_t) * reset_ids_.size());
-		if (!be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size()) || !Boundary(EnvSpan{0, static_cast<int>(reset_ids_.size()), d_env_list_}, 1)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	return StartEpisodes(reset_ids_, true, 1);   // every rule once per listed env, the draws included: the reset runs under the new model
+}
+
+int Engine::StartEpisodes(const std::vector<int32_t>& ids, bool draw_models, int terrain_mode)
+{
+	if (!ids.empty()) {
+		const int32_t* list = StageIds(ids);
+		if (!list) return DTRL_ERR_DEVICE;
+		const EnvSpan span{0, static_cast<int>(ids.size()), list};
+		if (cfg_.device_terrain && !Boundary(span, terrain_mode)) return Fail(DTRL_ERR_DEVICE, be_->error());
+		if (draw_models) {
+			if (int rc = RedrawListed(ids); rc != DTRL_OK) return rc;
+			if (!RescaleQueue(nullptr, span)) return Fail(DTRL_ERR_DEVICE, be_->error());
+		}
+		if (int rc = ApplyResets(ids, -1, list); rc != DTRL_OK) return rc;
+		if (!PushQueue(nullptr, span) || !EpisodeQueue(nullptr, span)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
-	if (int rc = RedrawListed(reset_ids_); rc != DTRL_OK) return rc;   // variant redraw: an episode starts, once per listed env, and the reset below runs under the new model
-	if (int rc = RescaleListed(reset_ids_); rc != DTRL_OK) return rc;  // variant rescale: the same for the listed envs under a private record, behind the redraw
-	int rc = ApplyResets(reset_ids_, -1);
-	if (rc != DTRL_OK) return rc;
-	if (rc = PushStart(static_cast<int>(reset_ids_.size())); rc != DTRL_OK) return rc;   // push schedule: an episode starts, a new wait once per listed env
-	if (rc = EpisodeStart(reset_ids_, true); rc != DTRL_OK) return rc;                   // episode limit: the same, frames 0 and a new limit once per listed env
-	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
+	return DevOk(be_->Sync());
 }
 
 // device weight layout (dtrl_kernel.h conv_tile / fc_partial / fc_layer) as an index map into the caller's blob (Caffe blob order of the deploy net, W then b
@@ -1837,6 +1839,22 @@ int Engine::KeysIdle(const EnvAssignment& a, const char* what, int key, bool wai
 
 int Engine::DevOk(bool ok) { return ok ? DTRL_OK : Fail(DTRL_ERR_DEVICE, be_->error()); }
 template <class Rec> int Engine::RecsAlloc(RuleRecs<Rec>& r, size_t n) { return r.Alloc(*be_, n, allocs_) ? DTRL_OK : Fail(DTRL_ERR_DEVICE, "device allocation failed: " + be_->error()); }
+template <class Rec> int Engine::RecsAlloc(RuleRecs<Rec>& r, size_t n, const Rec& fill)
+{
+	if (r.dev) return DTRL_OK;
+	if (int rc = RecsAlloc(r, n); rc != DTRL_OK) return rc;
+	r.host.assign(n, fill);
+	return DevOk(r.Push(*be_));
+}
+int Engine::RuleCallBegin(const char* what, EnvAssignment* keys, const char* no_rule, const EnvListArg& list, RecsBase* recs)
+{
+	const std::string w = std::string(what) + ": ";
+	if (int rc = keys ? KeysIdle(*keys, what, 0) : RequireIdle(what + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (no_rule) return Fail(DTRL_ERR_ARG, w + no_rule);
+	if (keys) if (int rc = KeysRefresh(*keys); rc != DTRL_OK) return rc;
+	if (int rc = CheckEnvList(w, list.ids, list.n, list.tail, list.name, list.required); rc != DTRL_OK) return rc;
+	return recs ? DevOk(recs->Pull(*be_)) : DTRL_OK;
+}
 int Engine::KeysRefresh(EnvAssignment& a)
 {
 	if (!a.on_device || !a.stale) return DTRL_OK;
@@ -2142,11 +2160,7 @@ int Engine::VariantRedraw(int lo, int hi, uint64_t seed, const double* weights)
 
 int Engine::VariantRedrawInfo(const int32_t* env_ids, int n, int32_t* lo, int32_t* hi, int32_t* variant, int32_t* draws)
 {
-	const std::string w = "dtrl_variant_redraw_info: ";
-	if (int rc = KeysIdle(variant_keys_, "dtrl_variant_redraw_info", 0); rc != DTRL_OK) return rc;
-	if (!redraw_on_) return Fail(DTRL_ERR_ARG, w + "the batch has no variant redraw (call dtrl_variant_redraw first)");
-	if (int rc = KeysRefresh(variant_keys_); rc != DTRL_OK) return rc;
-	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
+	if (int rc = RuleCallBegin("dtrl_variant_redraw_info", &variant_keys_, redraw_on_ ? nullptr : "the batch has no variant redraw (call dtrl_variant_redraw first)", {env_ids, n}, nullptr); rc != DTRL_OK) return rc;
 	if (lo) *lo = redraw_cfg_.lo;
 	if (hi) *hi = redraw_cfg_.hi;
 	for (int i = 0; i < n; ++i) {
@@ -2159,17 +2173,8 @@ int Engine::VariantRedrawInfo(const int32_t* env_ids, int n, int32_t* lo, int32_
 
 // ---- variant rescale (include/dtrl.h: dtrl_variant_rescale, dtrl_variant_rescale_info, dtrl_variant_scalars) ----
 // The rule is rescale_step (dtrl_terrain_dev.h), run by Backend::VariantRescale on the group's stream at every frame boundary, behind the redraw and in front of the
-// push schedule and the reset launch -- queued by DeviceFrameWork and by HostFrameWork alike -- and in its listed form by RescaleListed under dtrl_reset. dtrl_engine.h
+// push schedule and the reset launch -- queued by DeviceFrameWork and by HostFrameWork alike (RulesBeforeResets) -- and in its listed form by StartEpisodes under dtrl_reset. dtrl_engine.h
 // says where the private records live and who writes them when.
-int Engine::RescaleListed(const std::vector<int32_t>& ids)
-{
-	if (!rescale_on_ || ids.empty()) return DTRL_OK;
-	// (the list as ApplyResets is about to lay it out again, on the same stream 0)
-	std::memcpy(pin_ids_, ids.data(), sizeof(int32_t) * ids.size());
-	if (!zero_copy_ && !be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * ids.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DevOk(RescaleQueue(nullptr, EnvSpan{0, static_cast<int>(ids.size()), zero_copy_ ? pin_ids_ : d_env_list_}));
-}
-
 int Engine::VariantRescale(int base, const int32_t* env_ids, int n, uint64_t seed, const double* lo4, const double* hi4, uint32_t per_link, bool remove)
 {
 	const std::string w = "dtrl_variant_rescale: ";
@@ -2226,12 +2231,7 @@ int Engine::VariantRescale(int base, const int32_t* env_ids, int n, uint64_t see
 
 int Engine::VariantRescaleInfo(const int32_t* env_ids, int n, int32_t* base, uint64_t* seed, double* lo4, double* hi4, uint32_t* per_link, int32_t* key, int32_t* episodes, double* factors)
 {
-	const std::string w = "dtrl_variant_rescale_info: ";
-	if (int rc = KeysIdle(variant_keys_, "dtrl_variant_rescale_info", 0); rc != DTRL_OK) return rc;
-	if (!rescale_on_) return Fail(DTRL_ERR_ARG, w + "the batch has no variant rescale (call dtrl_variant_rescale first)");
-	if (int rc = KeysRefresh(variant_keys_); rc != DTRL_OK) return rc;
-	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
-	if (int rc = DevOk(rescale_.Pull(*be_)); rc != DTRL_OK) return rc;
+	if (int rc = RuleCallBegin("dtrl_variant_rescale_info", &variant_keys_, rescale_on_ ? nullptr : "the batch has no variant rescale (call dtrl_variant_rescale first)", {env_ids, n}, &rescale_); rc != DTRL_OK) return rc;
 	if (base) *base = rescale_base_;
 	if (seed) *seed = rescale_cfg_.seed;
 	for (int q = 0; q < kRescaleQuantities; ++q) { if (lo4) lo4[q] = rescale_cfg_.lo[q]; if (hi4) hi4[q] = rescale_cfg_.hi[q]; }
@@ -2273,21 +2273,12 @@ int Engine::VariantScalars(int env, double* out6L, double* total_mass)
 
 // ---- push schedule (include/dtrl.h: dtrl_push_schedule, dtrl_push_scale, dtrl_push_info) ----
 // The rule is push_step (dtrl_terrain_dev.h), run by Backend::PushSchedule on the group's stream at every frame boundary in front of the reset launch -- queued by
-// DeviceFrameWork (-terrain_gen= device) and by HostFrameWork (host terrain) alike -- and with `start` here, by PushStart under dtrl_reset and a terrain restart.
+// DeviceFrameWork (-terrain_gen= device) and by HostFrameWork (host terrain) alike (RulesBeforeResets) -- and with `start` by StartEpisodes under dtrl_reset and a terrain restart.
 // Records and scales live in device memory only.
 int Engine::PushAlloc()
 {
-	if (push_.dev && push_scale_.dev) return DTRL_OK;
-	if (int rc = RecsAlloc(push_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
-	if (int rc = RecsAlloc(push_scale_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
-	push_.host.assign(static_cast<size_t>(n_), PushRec{0, 0u, 0, -1, {0.0, 0.0}, 0.0});   // (last_link -1: no push yet)
-	push_scale_.host.assign(static_cast<size_t>(n_), 1.0);
-	return DevOk(push_.Push(*be_) && push_scale_.Push(*be_));
-}
-int Engine::PushStart(int n_listed)
-{
-	if (!push_on_ || n_listed <= 0) return DTRL_OK;
-	return DevOk(be_->PushSchedule(nullptr, EnvSpan{0, n_listed, zero_copy_ ? pin_ids_ : d_env_list_}, buf_.st, push_.dev, push_scale_.dev, push_cfg_));
+	if (int rc = RecsAlloc(push_, static_cast<size_t>(n_), PushRec{0, 0u, 0, -1, {0.0, 0.0}, 0.0}); rc != DTRL_OK) return rc;   // (last_link -1: no push yet)
+	return RecsAlloc(push_scale_, static_cast<size_t>(n_), 1.0);
 }
 int Engine::PushSchedule(int min_wait, int max_wait, uint64_t seed, double min_force, double max_force, double min_dur, double max_dur)
 {
@@ -2309,13 +2300,12 @@ int Engine::PushSchedule(int min_wait, int max_wait, uint64_t seed, double min_f
 	push_cfg_ = PushCfg{min_wait, max_wait, min_force, max_force, min_dur, max_dur, seed, static_cast<int64_t>(cfg_.run.env_id_base), cfg_.model.L, 0};
 	push_on_ = true;
 	// every env of the schedule draws its first wait under the new settings (the counters go on where they were)
-	return DevOk(be_->PushSchedule(nullptr, EnvSpan{0, n_, nullptr}, buf_.st, push_.dev, push_scale_.dev, push_cfg_) && be_->Sync());
+	return DevOk(PushQueue(nullptr, EnvSpan{0, n_, nullptr}) && be_->Sync());
 }
 int Engine::PushScale(const int32_t* env_ids, int n, const double* scales)
 {
 	const std::string w = "dtrl_push_scale: ";
-	if (int rc = RequireIdle("dtrl_push_scale" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
-	if (int rc = CheckEnvList(w, env_ids, n, "; nothing changed", "scales", scales); rc != DTRL_OK) return rc;
+	if (int rc = RuleCallBegin("dtrl_push_scale", nullptr, nullptr, {env_ids, n, "; nothing changed", "scales", scales}, nullptr); rc != DTRL_OK) return rc;
 	for (int i = 0; i < n; ++i) {   // all or nothing
 		const int e = EnvIndex(env_ids, i);
 		if (!(scales[i] >= 0) || !std::isfinite(scales[i])) return Fail(DTRL_ERR_ARG, w + "scale " + std::to_string(scales[i]) + " of env " + std::to_string(e) + " must be a non-negative finite number; nothing changed");
@@ -2327,11 +2317,7 @@ int Engine::PushScale(const int32_t* env_ids, int n, const double* scales)
 }
 int Engine::PushInfo(const int32_t* env_ids, int n, int32_t* wait, int32_t* pushes, int32_t* last_link, double* last_force, double* last_dur)
 {
-	const std::string w = "dtrl_push_info: ";
-	if (int rc = RequireIdle("dtrl_push_info" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
-	if (!push_.dev) return Fail(DTRL_ERR_ARG, w + "the batch has no push schedule (call dtrl_push_schedule first)");
-	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
-	if (int rc = DevOk(push_.Pull(*be_)); rc != DTRL_OK) return rc;
+	if (int rc = RuleCallBegin("dtrl_push_info", nullptr, push_.dev ? nullptr : "the batch has no push schedule (call dtrl_push_schedule first)", {env_ids, n}, &push_); rc != DTRL_OK) return rc;
 	for (int i = 0; i < n; ++i) {
 		const PushRec& r = push_.host[EnvIndex(env_ids, i)];
 		if (wait) wait[i] = r.wait;
@@ -2345,24 +2331,12 @@ int Engine::PushInfo(const int32_t* env_ids, int n, int32_t* wait, int32_t* push
 
 // ---- episode limit (include/dtrl.h: dtrl_episode_limit, dtrl_episode_limit_envs, dtrl_episode_info) ----
 // The rule is episode_limit_step (dtrl_terrain_dev.h), run by Backend::EpisodeLimit on the group's stream at every frame boundary in front of every other rule --
-// queued first by DeviceFrameWork (-terrain_gen= device), behind the frame launch by LaunchGroup (host terrain) -- and in its listed form here, by EpisodeStart
-// under dtrl_reset, a terrain restart and an env coming in. Records and flags live in device memory only.
+// queued first by DeviceFrameWork (-terrain_gen= device), behind the frame launch by LaunchGroup (host terrain) (RulesBehindFrame) -- and in its listed form by
+// StartEpisodes under dtrl_reset and a terrain restart, and by dtrl_episode_limit_envs for an env coming in. Records and flags live in device memory only.
 int Engine::EpisodeAlloc()
 {
-	if (episode_.dev && episode_flag_.dev) return DTRL_OK;
 	if (int rc = RecsAlloc(episode_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;   // (zero-filled: no episode yet)
-	if (int rc = RecsAlloc(episode_flag_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
-	episode_flag_.host.assign(static_cast<size_t>(n_), uint8_t(1));
-	return DevOk(episode_flag_.Push(*be_));
-}
-int Engine::EpisodeStart(const std::vector<int32_t>& ids, bool staged)
-{
-	if (!episode_on_ || ids.empty()) return DTRL_OK;
-	if (!staged) {
-		std::memcpy(pin_ids_, ids.data(), sizeof(int32_t) * ids.size());
-		if (!zero_copy_ && !be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * ids.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
-	}
-	return DevOk(EpisodeQueue(nullptr, EnvSpan{0, static_cast<int>(ids.size()), zero_copy_ ? pin_ids_ : d_env_list_}));
+	return RecsAlloc(episode_flag_, static_cast<size_t>(n_), uint8_t(1));
 }
 int Engine::EpisodeLimit(int min_frames, int max_frames, double max_dist, uint64_t seed)
 {
@@ -2383,9 +2357,7 @@ int Engine::EpisodeLimit(int min_frames, int max_frames, double max_dist, uint64
 }
 int Engine::EpisodeLimitEnvs(const int32_t* env_ids, int n, const uint8_t* on)
 {
-	const std::string w = "dtrl_episode_limit_envs: ";
-	if (int rc = RequireIdle("dtrl_episode_limit_envs" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
-	if (int rc = CheckEnvList(w, env_ids, n, "; nothing changed", "on", on); rc != DTRL_OK) return rc;
+	if (int rc = RuleCallBegin("dtrl_episode_limit_envs", nullptr, nullptr, {env_ids, n, "; nothing changed", "on", on}, nullptr); rc != DTRL_OK) return rc;
 	if (int rc = EpisodeAlloc(); rc != DTRL_OK) return rc;
 	if (int rc = DevOk(episode_flag_.Pull(*be_)); rc != DTRL_OK) return rc;
 	const std::vector<uint8_t> before = episode_flag_.host;
@@ -2393,16 +2365,16 @@ int Engine::EpisodeLimitEnvs(const int32_t* env_ids, int n, const uint8_t* on)
 	std::vector<int32_t> came_in;
 	for (int e = 0; e < n_; ++e) if (episode_flag_.host[e] && !before[e]) came_in.push_back(e);
 	if (int rc = DevOk(episode_flag_.Push(*be_)); rc != DTRL_OK) return rc;
-	if (int rc = EpisodeStart(came_in, false); rc != DTRL_OK) return rc;   // an env that comes in while a limit runs starts an episode record now
+	if (episode_on_ && !came_in.empty()) {   // an env that comes in while a limit runs starts an episode record now
+		const int32_t* list = StageIds(came_in);
+		if (!list) return DTRL_ERR_DEVICE;
+		if (!EpisodeQueue(nullptr, EnvSpan{0, static_cast<int>(came_in.size()), list})) return Fail(DTRL_ERR_DEVICE, be_->error());
+	}
 	return DevOk(be_->Sync());
 }
 int Engine::EpisodeInfo(const int32_t* env_ids, int n, int32_t* frames, int32_t* limit, int64_t* by_fall, int64_t* by_limit, int32_t* last_frames, double* last_dist, int32_t* last_cause)
 {
-	const std::string w = "dtrl_episode_info: ";
-	if (int rc = RequireIdle("dtrl_episode_info" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
-	if (!episode_.dev) return Fail(DTRL_ERR_ARG, w + "the batch has no episode limit (call dtrl_episode_limit or dtrl_episode_limit_envs first)");
-	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
-	if (int rc = DevOk(episode_.Pull(*be_)); rc != DTRL_OK) return rc;
+	if (int rc = RuleCallBegin("dtrl_episode_info", nullptr, episode_.dev ? nullptr : "the batch has no episode limit (call dtrl_episode_limit or dtrl_episode_limit_envs first)", {env_ids, n}, &episode_); rc != DTRL_OK) return rc;
 	for (int i = 0; i < n; ++i) {
 		const EpisodeRec& r = episode_.host[EnvIndex(env_ids, i)];
 		if (frames) frames[i] = r.frames;
@@ -2529,15 +2501,9 @@ int Engine::AssignTerrains(const int32_t* env_ids, int n, const int32_t* terrain
 		std::vector<GroundGen> gen(static_cast<size_t>(n_));
 		if (!be_->D2H(gen.data(), buf_.gen, sizeof(GroundGen) * gen.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
 		for (int32_t e : reset_ids_) gen[e].key = terrain_stream_key(cfg_.terrain_seed, cfg_.run.env_id_base + e);
-		std::memcpy(pin_ids_, reset_ids_.data(), sizeof(int32_t) * reset_ids_.size());
-		if (!be_->H2D(buf_.gen, gen.data(), sizeof(GroundGen) * gen.size()) || !be_->H2DAsync(d_env_list_, pin_ids_, sizeof(int32_t) * reset_ids_.size())
-			|| !Boundary(EnvSpan{0, static_cast<int>(reset_ids_.size()), d_env_list_}, 2)) return Fail(DTRL_ERR_DEVICE, be_->error());
+		if (!be_->H2D(buf_.gen, gen.data(), sizeof(GroundGen) * gen.size())) return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
-	if (int rc = ApplyResets(reset_ids_, -1); rc != DTRL_OK) return rc;
-	if (int rc = PushStart(static_cast<int>(reset_ids_.size())); rc != DTRL_OK) return rc;   // push schedule: the listed envs start over, a new wait each
-	if (int rc = EpisodeStart(reset_ids_, true); rc != DTRL_OK) return rc;                   // episode limit: and a new episode record each
-	if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
-	return DTRL_OK;
+	return StartEpisodes(reset_ids_, false, 2);   // the listed envs start over: a new push wait and a new episode record each; a restart draws no model
 }
 
 int Engine::GetTerrains(const int32_t* env_ids, int n, int32_t* terrains_out)
@@ -2588,8 +2554,7 @@ int Engine::LadderInfo(const int32_t* env_ids, int n, double* mark_x_out, int32_
 	const std::string w = "dtrl_ladder_info: ";
 	if (terrain_keys_.filled.empty()) return Fail(DTRL_ERR_ARG, w + terrain_keys_.none_text);
 	if (!ladder_on_) return Fail(DTRL_ERR_ARG, w + "the batch has no terrain ladder (call dtrl_terrain_ladder first)");
-	if (int rc = KeysCurrent(terrain_keys_, "dtrl_ladder_info", true); rc != DTRL_OK) return rc;
-	if (int rc = CheckEnvList(w, env_ids, n); rc != DTRL_OK) return rc;
+	if (int rc = RuleCallBegin("dtrl_ladder_info", &terrain_keys_, nullptr, {env_ids, n}, nullptr); rc != DTRL_OK) return rc;   // (this call refuses a missing rule in front of a frame in flight)
 	for (int i = 0; i < n; ++i) {
 		const LadderRec& r = ladder_.host[EnvIndex(env_ids, i)];
 		if (mark_x_out) mark_x_out[i] = r.mark_x;

@@ -215,7 +215,6 @@ struct Snapshot {
 class Engine {
 public:
 	Engine() {}
-	// env snapshots (include/dtrl.h)
 	// external policy mode (include/dtrl.h)
 	bool external() const { return cfg_.external_policy; }
 	int PendingActions(int32_t* env_ids, void* states, int cap, int* out_n, bool device);
@@ -223,6 +222,7 @@ public:
 	int ExtStats(int64_t* awaiting, int64_t* ready, int64_t* env_steps_total, int64_t* env_frames_total);
 	int ExtEnvInfo(const int32_t* env_ids, int n, int32_t* park, int32_t* steps_left);
 	double ExtLaunchMs(int which) { return be_ ? be_->ExtLaunchMs(which) : -1.0; }
+	// env snapshots (include/dtrl.h)
 	int SnapshotSave(const int32_t* env_ids, int n, Snapshot** out);
 	int SnapshotRestore(const Snapshot* s, const int32_t* env_ids, int n);
 	int CloneEnvs(const int32_t* src_ids, const int32_t* dst_ids, int n);
@@ -343,7 +343,27 @@ private:
 		if (ladder_on_) { r.ladder = ladder_.dev; r.lc = ladder_cfg_; terrain_keys_.stale = true; }
 		return be_->TerrainBoundary(buf_, span, mode, r);
 	}
-	int ApplyResets(const std::vector<int32_t>& ids, int group);
+	// The one place an env list is laid out for the device: `ids` into the id staging at `off`, uploaded on the selected stream unless the device reads the staging
+	// itself (zero_copy_). Returns the list as the device reads it -- what every listed launch and rule of the call is handed -- or nullptr with the error set
+	const int32_t* StageIds(const std::vector<int32_t>& ids, int off = 0);
+	int ApplyResets(const std::vector<int32_t>& ids, int group, const int32_t* staged = nullptr);   // the reset launch; staged: StageIds(ids) of a user reset (group < 0)
+	// The per-env rules of the frame boundary, each queued where it is in force (else nothing) on the selected stream; false: the backend's error. status: the
+	// span's envs whose episode ended act (a frame boundary), or nullptr: every env of the span starts an episode (the listed form and the rule's creation).
+	bool EpisodeQueue(EnvStatus* status, const EnvSpan& span) { return !episode_on_ || be_->EpisodeLimit(status, span, buf_.st, episode_.dev, episode_flag_.dev, episode_cfg_); }
+	bool RedrawQueue(const EnvSpan& span) { if (!redraw_on_) return true; variant_keys_.stale = true; return be_->VariantRedraw(buf_.status, span, variant_keys_.d_env_key, redraw_.dev, redraw_cfg_); }   // (device terrain)
+	bool RescaleQueue(const EnvStatus* status, const EnvSpan& span) { return !rescale_on_ || be_->VariantRescale(status, span, variant_keys_.d_env_key, d_var_models_, static_cast<int>(var_models_.size()), rescale_.dev, d_rescale_base_, rescale_cfg_); }
+	bool PushQueue(const EnvStatus* status, const EnvSpan& span) { return !push_on_ || be_->PushSchedule(status, span, buf_.st, push_.dev, push_scale_.dev, push_cfg_); }
+	// THE ORDER OF THE RULES, at a frame boundary and at a listed episode start alike:
+	//   episode limit | terrain work (with the ladder) | redraw, rescale, push | reset launch             a frame boundary of a group's span
+	//                   terrain work (with the ladder) | redraw, rescale | reset launch | push, episode   the listed envs start an episode
+	// The limit comes first: for every other rule an env it ended is an env whose episode ended. Redraw and rescale come in front of the reset launch, which runs
+	// reset_env under the new model, the rescale behind the redraw (which acts on keys below V only). At a boundary the push comes in front of the reset launch (an
+	// env that fell draws a new wait and is not pushed; the launch clears nothing the rule wrote); the listed starts of push and limit come behind it.
+	bool RulesBehindFrame(const EnvSpan& span) { return EpisodeQueue(buf_.status, span); }   // behind a group's frame launch, in front of everything that reads its status
+	bool RulesBeforeResets(const EnvSpan& span) { return (!cfg_.device_terrain || RedrawQueue(span)) && RescaleQueue(buf_.status, span) && PushQueue(buf_.status, span); }   // (host terrain: the host status loop has run the redraw)
+	// "These envs start an episode now" (dtrl_reset: draw_models; a terrain restart: not), synchronised: the list staged once, with -terrain_gen= device the listed envs'
+	// terrain work under terrain_mode (Boundary: 1 = initialise, 2 = re-seed + initialise), then the second line above
+	int StartEpisodes(const std::vector<int32_t>& ids, bool draw_models, int terrain_mode);
 	int LaunchGroup(int group, int n_steps, double dt_step, bool frame_end);
 	// env groups: contiguous env ranges, each with its own stream, launch order and staging slices. Envs are independent, so a group
 	// starts its next frame as soon as ITS host work is done instead of waiting for the slowest wavefront of the whole batch
@@ -457,7 +477,13 @@ private:
 		bool Pull(Backend& be) override { if (!dev) return true; host.resize(count); return be.D2H(host.data(), dev, sizeof(Rec) * count); }   // host <- device, all of it
 		bool Push(Backend& be) { return !dev || be.H2D(dev, host.data(), sizeof(Rec) * host.size()); }                                         // device <- host, as far as the host form goes
 	};
-	template <class Rec> int RecsAlloc(RuleRecs<Rec>& r, size_t n);   // (dtrl_engine.cpp)
+	template <class Rec> int RecsAlloc(RuleRecs<Rec>& r, size_t n);   // (dtrl_engine.cpp) the device array, once
+	template <class Rec> int RecsAlloc(RuleRecs<Rec>& r, size_t n, const Rec& fill);   // the same, and on that first call the host form filled with `fill` and pushed
+	// The opening of a rule's info and per-env settings calls, in this order: refuse a frame in flight and wait for every stream (RequireIdle; with `keys` the
+	// family's KeysIdle), refuse with `no_rule` (nullptr: the rule is there), bring the keys and records a device rule moves up to date (KeysRefresh, with `keys`),
+	// check the env list, and pull `recs` (nullptr: nothing)
+	struct EnvListArg { const int32_t* ids; int n; const char* tail = ""; const char* name = nullptr; const void* required = nullptr; };   // (CheckEnvList's arguments)
+	int RuleCallBegin(const char* what, EnvAssignment* keys, const char* no_rule, const EnvListArg& list, RecsBase* recs);
 	int KeysRefresh(EnvAssignment& a);       // on_device and stale: host keys and the rule's records <- device (call with the streams idle); else nothing
 	// KeysIdle + KeysRefresh for an assignment whose keys move on the device; else nothing (`always`: KeysIdle even so -- the ladder's calls, in either terrain mode)
 	int KeysCurrent(EnvAssignment& a, const char* what, bool always = false);
@@ -513,8 +539,6 @@ private:
 	std::vector<ModelScalarsD> var_scalars_; // per variant: the character file's doubles (empty: no variants)
 	ModelScalarsD* d_rescale_base_ = nullptr;   // device: the base's copy
 	int32_t PublicKey(int32_t k) const { return k >= static_cast<int32_t>(var_models_.size()) ? rescale_base_ : k; }
-	bool RescaleQueue(const EnvStatus* status, const EnvSpan& span) { return be_->VariantRescale(status, span, variant_keys_.d_env_key, d_var_models_, static_cast<int>(var_models_.size()), rescale_.dev, d_rescale_base_, rescale_cfg_); }
-	int RescaleListed(const std::vector<int32_t>& ids);  // dtrl_reset: the rule for the listed envs, in front of the reset launch (stream 0)   // dtrl_reset: the rule for the listed envs on the host, keys and counters uploaded (streams idle)
 	// push schedule: settings, per-env records and per-env scales are batch state. The DEVICE records and scales are the truth in both terrain modes (the host form
 	// is staging): the rule runs in Backend::PushSchedule on the group's stream at every frame boundary, and the calls that read the records wait for queued work
 	bool push_on_ = false;
@@ -522,16 +546,13 @@ private:
 	RuleRecs<PushRec> push_; RuleRecs<double> push_scale_;   // device [n] each (allocated by the first dtrl_push_schedule / dtrl_push_scale; scales 1.0)
 	RuleRecs<PerturbRow> pert_rows_;                         // device [n]: the rows of one dtrl_add_perturb (allocated by the first call)
 	int PushAlloc();                                               // the two push arrays, once
-	int PushStart(int n_listed);   // dtrl_reset / terrain restart: the rule with `start` for the n_listed envs ApplyResets(ids, -1) has just launched (same list, stream 0)
 	// episode limit: settings, per-env records and per-env flags are batch state. The DEVICE records and flags are the only copy in both terrain modes (the host
-	// form is staging): the rule runs in Backend::EpisodeLimit on the group's stream in front of every other boundary rule -- first in DeviceFrameWork (-terrain_gen=
-	// device), behind the group's frame launch in LaunchGroup (host terrain: the wait HostFrameWork makes anyway covers it, and its loop reads the amended status)
+	// form is staging): the rule runs in Backend::EpisodeLimit on the group's stream in front of every other boundary rule (RulesBehindFrame) -- first in DeviceFrameWork
+	// (-terrain_gen= device), behind the group's frame launch in LaunchGroup (host terrain: the wait HostFrameWork makes anyway covers it, and its loop reads the amended status)
 	bool episode_on_ = false;
 	EpisodeCfg episode_cfg_{};
 	RuleRecs<EpisodeRec> episode_; RuleRecs<uint8_t> episode_flag_;   // device [n] each (allocated by the first dtrl_episode_limit / dtrl_episode_limit_envs; flags 1)
 	int EpisodeAlloc();                                              // the two arrays, once
-	bool EpisodeQueue(EnvStatus* status, const EnvSpan& span) { return be_->EpisodeLimit(status, span, buf_.st, episode_.dev, episode_flag_.dev, episode_cfg_); }
-	int EpisodeStart(const std::vector<int32_t>& ids, bool staged);  // the rule's listed form for `ids` on stream 0 (staged: ApplyResets(ids, -1) has put this list into the id staging)
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

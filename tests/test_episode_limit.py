@@ -386,6 +386,81 @@ def test_every_rule_at_once(da, om, tmp_path, mode):
     run_all_rules(om, tmp_path, mode)
 
 
+# ---- 6b. the listed episode starts under every rule at once ----
+HELD_OUT = 33
+
+
+def env_records(rec, e, n=N):
+    """env e's part of all_rules_records: a key list, or n equal runs of bytes"""
+    return {k: (v[e] if isinstance(v, list) else v[len(v) // n * e:len(v) // n * (e + 1)]) for k, v in rec.items()}
+
+
+def run_listed_starts(om, tmp_path, mode, n=N):
+    """dtrl_reset, dtrl_assign_terrains(restart) and an env coming into the limit, each between frames of a batch under all five rules (8 frames in all):
+    every call moves, once, exactly the records of the listed envs that its episode start names; all other records keep their bytes."""
+    b = all_rules_batch(om, tmp_path, mode, n)
+    spawn = float(root_x(b)[0])
+    b.EpisodeLimitEnvs(0, env_ids=[HELD_OUT])                            # (its record stays: one draw, at the limit's creation)
+    push, rule = R.PyPush(n, wait=PUSH_WAIT), PyEpisode(n, spawn_x=spawn)
+    rule.on[HELD_OUT] = 0
+
+    def frames(k):
+        for _ in range(k):
+            r0, e0 = resets(b), b.EpisodeInfo()
+            b.Update()
+            rose, fell = resets(b) - r0, (b.EpisodeInfo()["by_fall"] - e0["by_fall"]) > 0
+            for e in range(n):
+                push.boundary(e, bool(rose[e]))
+                rule.boundary(e, bool(fell[e]))
+                rule.last_dist[e] = None
+            R.check_equals_rule(b, push, "push schedule, in a frame")
+            check_equals_rule(b, rule, "episode limit, in a frame")
+
+    def started(call, listed, moved, draws):
+        """One call: `moved` names the record families an episode start of this kind may move; draws: the listed envs draw a variant or their scales"""
+        before = all_rules_records(b)
+        call()
+        after = all_rules_records(b)
+        for e in range(n):
+            x, y = env_records(before, e), env_records(after, e)
+            for k in x:
+                if e not in listed or k.split()[0] not in moved:
+                    assert x[k] == y[k], ("env %d: %s moved" % (e, k), listed)
+        info = {name: get() for name, get in (("redraw", b.VariantRedrawInfo), ("rescale", b.VariantRescaleInfo), ("ladder", b.LadderInfo))}
+        was = {name: np.frombuffer(before[name], np.int32) for name in ("redraw draws", "rescale episodes")}
+        for e in listed:
+            rescaled = e in RESCALED
+            assert info["redraw"]["draws"][e] - was["redraw draws"][e] == (1 if draws and not rescaled else 0), e
+            assert info["rescale"]["episodes"][e] - was["rescale episodes"][e] == (1 if draws and rescaled else 0), e
+            if "ladder" in moved:
+                assert info["ladder"]["mark_x"][e] == spawn, (e, info["ladder"]["mark_x"][e])
+            if "push" in moved:
+                push.start(e)
+            rule.start(e)
+        R.check_equals_rule(b, push, "push schedule, after the call")     # (once per listed env, however often it is listed; nothing of any other env)
+        check_equals_rule(b, rule, "episode limit, after the call")
+
+    frames(3)
+    draws = ("variant", "redraw", "rescale", "ladder", "push", "episode")
+    started(lambda: b.Reset([2, 2, 65, 2]), (2, 65), draws, True)
+    started(lambda: b.Reset([66]), (66,), draws, True)                   # (an env under a private record of the rescale, in the second block)
+    frames(2)
+    started(lambda: b.AssignTerrains([0, 1, 68, 1], [2, 0, 1, 2], restart=True), (0, 1, 68), ("terrain", "ladder", "push", "episode"), False)
+    assert [int(t) for t in b.GetTerrains([0, 1, 68])] == [2, 2, 1]
+    frames(2)
+    rule.on[HELD_OUT] = 1
+    started(lambda: b.EpisodeLimitEnvs([1, 1], env_ids=[HELD_OUT, 8]), (HELD_OUT,), ("episode",), False)   # (env 8 was in: nothing starts)
+    frames(1)
+    return X.env_states(b), b.RecordPoliState(), [X.ground_key(b, e) for e in range(n)], all_rules_records(b)
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_listed_starts_under_every_rule(da, om, tmp_path, mode):
+    """Each listed episode start moves every rule's records of the listed envs once, in the rule's own way -- a reset draws the variant or the scales, a terrain
+    restart does not, an env coming into the limit starts its episode record alone -- and leaves every other env's records byte for byte where they were."""
+    run_listed_starts(om, tmp_path, mode)
+
+
 # ---- 7. batch state and lifecycle ----
 @pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
 def test_batch_state_and_lifecycle(da, om, mode, n=N, frames=8):

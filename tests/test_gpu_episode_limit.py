@@ -2,7 +2,8 @@
 Backend::EpisodeLimit, here ONE launch of dtrl_episode_limit per env group and frame in both terrain modes -- and what only exists on HIP: the kernel against its
 host fallback (DTRL_EPISODE_FALLBACK=1) at 70 envs (two 64-thread blocks, the second partial) with one and two env groups in both libraries and both terrain
 modes, with falls among the endings; frames queued without a host wait (RunFrames) against frame-by-frame Update; run-to-run determinism; the fast kernel against
-the reference kernel under limits; every frame-boundary rule in ONE batch against all the host fallbacks at once; and the new symbols in both libraries."""
+the reference kernel under limits; every frame-boundary rule in ONE batch against all the host fallbacks at once, per frame and in the listed episode starts (dtrl_reset, a terrain restart, an
+env coming into the limit); and the new symbols in both libraries."""
 import ctypes
 import os
 
@@ -75,6 +76,11 @@ def test_shard_invariance(da, om, mode):
 @pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
 def test_every_rule_at_once(da, om, tmp_path, mode):
     E.test_every_rule_at_once(da, om, tmp_path, mode)
+
+
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_listed_starts_under_every_rule(da, om, tmp_path, mode):
+    E.test_listed_starts_under_every_rule(da, om, tmp_path, mode)
 
 
 @pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
@@ -162,6 +168,18 @@ def test_every_rule_at_once_equals_the_host_fallbacks(da, om, tmp_path, monkeypa
     for k in ("DTRL_TERRAINS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_EPISODE_FALLBACK"):
         monkeypatch.setenv(k, "1")
     E.assert_same_run(base, E.run_all_rules(om, tmp_path, mode), "host fallbacks")
+
+
+@pytest.mark.parametrize("groups", ["1", "2"], ids=["one_group", "two_groups"])
+@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
+def test_listed_starts_equal_the_host_fallbacks(da, om, tmp_path, monkeypatch, mode, groups):
+    """dtrl_reset, a terrain restart and an env coming into the limit between frames under all five rules: the listed launches against every DTRL_*_FALLBACK
+    knob at once, in states, windows and every rule's records."""
+    monkeypatch.setenv("DTRL_GROUPS", groups)
+    base = E.run_listed_starts(om, tmp_path, mode)
+    for k in ("DTRL_TERRAINS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_EPISODE_FALLBACK"):
+        monkeypatch.setenv(k, "1")
+    E.assert_same_run(base, E.run_listed_starts(om, tmp_path, mode), "host fallbacks")
 
 
 SYMBOLS = ("dtrl_episode_limit", "dtrl_episode_limit_envs", "dtrl_episode_info")
