@@ -948,31 +948,43 @@ struct FastPath {
 			const uint32_t mysub = hinge ? ws.M.sub_mask[lane - 2] : 0u;
 			real rhs0 = (lane < D) ? (ws.st.tau[lane] - ws.b[lane]) : 0.0;
 			if (__builtin_expect(ws.st.pert_on != 0, 0)) { if (lane < D) rhs0 += perturb_gen_force(ws, lane); }
-			// J_r^T for row r (r < R), the free right-hand side for r == R
-			auto rhs_of = [&](int r) -> real {
-				if (r >= R) return rhs0;
-				const int kind = ws.row_kind[r], link = ws.row_link[r];
-				const real dx = ws.row_dx[r];
-				if (kind == 0) return (lane == link + 2) ? dx : 0.0;
-				const real dy = ws.row_dy[r], x = ws.row_x[r], y = ws.row_y[r];
-				const int link2 = ws.row_link2[r];
-				if (lane == 0) return link2 < 0 ? dx : 0.0;
-				if (lane == 1) return link2 < 0 ? dy : 0.0;
-				const int on = static_cast<int>((mysub >> link) & 1u) - (link2 < 0 ? 0 : static_cast<int>((mysub >> link2) & 1u));
-				if (on == 0) return 0.0;
-				const real jr = dx * (-(y - mypy)) + dy * (x - mypx);
-				return on > 0 ? jr : -jr;
-			};
 			if (R < 1) {
 				// airborne, one right-hand side: the lane = DoF broadcast chain in registers is cheaper than the row form
-				// (spelled through rhs_of() under a second test of R: with `R == 0` and rhs0 used directly the compiler allocates the substep loop differently and spills in it)
+				// (under a second test of R: with `R == 0` alone the compiler allocates the substep loop differently and spills in it)
 				if (0 <= R) {
-					const real z = usolve_regs<D>(hrow, rhs_of(0));
+					const real z = usolve_regs<D>(hrow, rhs0);
 					if (lane < D) ws.Z[0][lane] = z;
 				}
 			} else {
-				// the R + 1 right-hand sides into Z unsolved (lane = DoF), then solved in place with lane = row
-				for (int r = 0; r <= R; ++r) { const real v = rhs_of(r); if (lane < D) ws.Z[r][lane] = v; }
+				// the R + 1 right-hand sides into Z unsolved (lane = DoF), then solved in place with lane = row.
+				// The row descriptors do not come through LDS one row at a time (kind and link, wait, link2, wait, dx / dy / x / y, wait -- three to four
+				// dependent trips per row in a loop that is neither unrolled nor pipelined): lane r loads ITS row's descriptor -- one batch, one wait; lane-indexed,
+				// unconditional and clamped like the batched PD set-up of controller_update() -- and row r's is broadcast from lane r (v_readlane with a wave-uniform
+				// lane index: the values arrive in SGPRs), so the kind of the row is wave-uniform as before and the operations are row_jac()'s, DoF = lane, on the same values.
+				// (Building row r's entries on lane r inside usolve_rows() instead was measured and lost: docs/EXPERIMENTS.md 33.)
+				{
+					const int ol = opaque_lane();   // (the seven lane-indexed addresses are formed here, not kept across the substep loop as loop invariants)
+					const int rc = ol < R ? ol : 0; // (lanes >= R: row 0 exists, the values are not used)
+					const int kind_l = ws.row_kind[rc], link_l = ws.row_link[rc], link2_l = ws.row_link2[rc];
+					const real dx_l = ws.row_dx[rc], dy_l = ws.row_dy[rc], x_l = ws.row_x[rc], y_l = ws.row_y[rc];
+					for (int r = 0; r < R; ++r) {
+						const int kind = __builtin_amdgcn_readlane(kind_l, r), link = __builtin_amdgcn_readlane(link_l, r);
+						const real dx = bcast(dx_l, r);
+						real v;
+						if (kind == 0) v = (lane == link + 2) ? dx : 0.0;
+						else {
+							const real dy = bcast(dy_l, r), x = bcast(x_l, r), y = bcast(y_l, r);
+							const int link2 = __builtin_amdgcn_readlane(link2_l, r);
+							const int on = static_cast<int>((mysub >> link) & 1u) - (link2 < 0 ? 0 : static_cast<int>((mysub >> link2) & 1u));
+							const real jr = dx * (-(y - mypy)) + dy * (x - mypx);
+							v = on == 0 ? 0.0 : (on > 0 ? jr : -jr);
+							v = (lane == 0) ? (link2 < 0 ? dx : 0.0) : v;
+							v = (lane == 1) ? (link2 < 0 ? dy : 0.0) : v;
+						}
+						if (lane < D) ws.Z[r][lane] = v;
+					}
+					if (lane < D) ws.Z[R][lane] = rhs0;
+				}
 				env_sync();
 				usolve_rows<Topo>(ws, R);
 			}
