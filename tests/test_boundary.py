@@ -314,34 +314,39 @@ def test_policy_hand_over_during_a_frame(da, om):
     run_policy_hand_over_during_a_frame(Scenario, om)
 
 
-def run_packed_drain_equals_plain_drain(scn, om, to_ptr=None, read=None):
+def run_packed_drain_equals_plain_drain(scn, om, to_ptr=None, read=None, n_envs=10, cap=32, small=2, frames=120, every=3, ring_cap=None, extra_b=None,
+                                        min_drain=0, min_multi_envs=0, min_carry=0):
     """dtrl_drain_tuples_packed: the rows of dtrl_drain_tuples sorted by env id (stable), flag word and GLOBAL env id appended, a header row with the
     count. Rows that do not fit the caller's block are CARRIED, not dropped: they stay in the ring, in order, in front of the newer rows, and a later
-    drain hands them out -- a consumer with a small block (two rows here) receives every row of the big-block stream, each env's rows in time order."""
+    drain hands them out -- a consumer with a small block (two rows here) receives every row of the big-block stream, each env's rows in time order.
+    The width parameters (tests/test_gpu_handover_width.py): n_envs envs drained every `every` frames into blocks of `cap` (always fits) and `small` rows,
+    rings of ring_cap rows, extra_b for the two packed batches; min_drain / min_multi_envs / min_carry are floors on the largest drain of `b`, on the envs with
+    two or more rows in one drain of `b` and on the largest carry in a header of `c`. Returns what was reached."""
     pol = dog_policy(om)
     args = dict(terrain_seed=31, rand_seed=2, global_env_offset=100)
-    a = scn("args/opt_args_train_mace.txt", 10, data_root=REFDATA, extra_args=args)
-    b = scn("args/opt_args_train_mace.txt", 10, data_root=REFDATA, extra_args=args)
-    c = scn("args/opt_args_train_mace.txt", 10, data_root=REFDATA, extra_args=args)
+    if ring_cap is not None:
+        args["tuple_ring_capacity"] = ring_cap
+    a = scn("args/opt_args_train_mace.txt", n_envs, data_root=REFDATA, extra_args=args)
+    b = scn("args/opt_args_train_mace.txt", n_envs, data_root=REFDATA, extra_args=dict(args, **(extra_b or {})))
+    c = scn("args/opt_args_train_mace.txt", n_envs, data_root=REFDATA, extra_args=dict(args, **(extra_b or {})))
     for x in (a, b, c):
         x.SetPolicy(pol[1], *pol[2:])
     W = a.W
-    cap = 32
     if to_ptr is None:
-        blk = np.zeros((cap + 1, W + 2), np.float32); blk_c = np.zeros((2 + 1, W + 2), np.float32)
+        blk = np.zeros((cap + 1, W + 2), np.float32); blk_c = np.zeros((small + 1, W + 2), np.float32)
         to_ptr = lambda t: t.ctypes.data; read = lambda t: t
     else:
         import torch
-        blk = torch.zeros((cap + 1, W + 2), dtype=torch.float32, device="cuda"); blk_c = torch.zeros((2 + 1, W + 2), dtype=torch.float32, device="cuda")
-    n_tot = n_multi = carried_max = 0
-    big, small = [], []
+        blk = torch.zeros((cap + 1, W + 2), dtype=torch.float32, device="cuda"); blk_c = torch.zeros((small + 1, W + 2), dtype=torch.float32, device="cuda")
+    n_tot = n_multi = carried_max = drain_max = multi_envs_max = 0
+    big, small_rows = [], []
     pending_c = 0
-    for f in range(120):
+    for f in range(frames):
         for x in (a, b, c):
             x.Update()
-        if f % 3 != 2:
-            continue                                                   # drain every third frame: several tuples per drain, some envs twice over time
-        ra, fa, ia = a.DrainTuples()
+        if f % every != every - 1:
+            continue                                                   # drain every third frame (by default): several tuples per drain, some envs twice over time
+        ra, fa, ia = a.DrainTuples(ring_cap)
         n = b.DrainTuplesPacked(to_ptr(blk), cap, want_count=True)
         h = read(blk)
         assert n == len(ra) and h[0, :3].view(np.int32).tolist() == [n, 0, 0]
@@ -350,33 +355,122 @@ def run_packed_drain_equals_plain_drain(scn, om, to_ptr=None, read=None):
         meta = h[1:n + 1, W:].view(np.int32)
         assert np.array_equal(meta[:, 0], fa[order].astype(np.int32)) and np.array_equal(meta[:, 1], ia[order] + 100)
         n_tot += n; n_multi += n >= 2
+        drain_max = max(drain_max, n)
+        multi_envs_max = max(multi_envs_max, int((np.bincount(meta[:, 1] - 100, minlength=n_envs) >= 2).sum()))   # (from b's own id column)
         big.append(h[1:n + 1].copy())
-        # a block with room for two rows only: the first two rows in (env id, time) order of what is pending, the rest carried and counted in the header
+        # a block with room for `small` rows only: the first rows in (env id, time) order of what is pending, the rest carried and counted in the header
         pending_c += n
-        m = c.DrainTuplesPacked(to_ptr(blk_c), 2, want_count=True)
+        m = c.DrainTuplesPacked(to_ptr(blk_c), small, want_count=True)
         hc = read(blk_c)
-        assert m == min(pending_c, 2) and hc[0, :3].view(np.int32).tolist() == [m, 0, pending_c - m]
-        pending_c -= m; carried_max = max(carried_max, pending_c)
-        small.append(hc[1:m + 1].copy())
+        assert m == min(pending_c, small) and hc[0, :3].view(np.int32).tolist() == [m, 0, pending_c - m]
+        pending_c -= m; carried_max = max(carried_max, int(hc[0, 2:3].view(np.int32)[0]))
+        small_rows.append(hc[1:m + 1].copy())
         assert c.TupleStats()["pending"] == pending_c
     assert n_tot >= 12 and n_multi >= 3 and carried_max >= 2
+    reached = dict(drain_max=drain_max, multi_envs_max=multi_envs_max, carried_max=carried_max, rows=n_tot)
+    print("packed drain at %d envs: %s" % (n_envs, reached))
+    assert drain_max > min_drain and multi_envs_max >= min_multi_envs and carried_max > min_carry, reached
     while pending_c > 0:                                                  # flush what the small block left behind
-        m = c.DrainTuplesPacked(to_ptr(blk_c), 2, want_count=True)
-        assert m == min(pending_c, 2)
+        m = c.DrainTuplesPacked(to_ptr(blk_c), small, want_count=True)
+        assert m == min(pending_c, small)
         pending_c -= m
-        small.append(read(blk_c)[1:m + 1].copy())
-    big, small = np.concatenate(big), np.concatenate(small)
-    assert len(big) == len(small) == n_tot
-    ids_b, ids_s = big[:, W + 1].view(np.int32), small[:, W + 1].view(np.int32)
-    for e in np.unique(ids_b):                                            # every env: the same rows in the same (time) order
-        assert np.array_equal(big[ids_b == e], small[ids_s == e]), e
+        small_rows.append(read(blk_c)[1:m + 1].copy())
+    big, small_rows = np.concatenate(big), np.concatenate(small_rows)
+    assert len(big) == len(small_rows) == n_tot
+    ids_b, ids_s = big[:, W + 1].view(np.int32), small_rows[:, W + 1].view(np.int32)
+    ob, os_ = np.argsort(ids_b, kind="stable"), np.argsort(ids_s, kind="stable")
+    assert np.array_equal(ids_b[ob], ids_s[os_])
+    assert np.array_equal(big[ob].view(np.int32), small_rows[os_].view(np.int32))   # every env: the same rows in the same (time) order (as bit patterns: a NaN equals itself)
     sb, sc = b.TupleStats(), c.TupleStats()
     assert sb["drained"] == n_tot and sb["dropped"] == 0 and sb["pending"] == 0
     assert sc["drained"] == n_tot and sc["dropped"] == 0 and sc["pending"] == 0
+    return reached
 
 
 def test_packed_drain_equals_plain_drain(da, om):
     run_packed_drain_equals_plain_drain(Scenario, om)
+
+
+def run_packed_drain_of_a_full_ring(scn, om, to_ptr=None, read=None, n_envs=1100, ring=1500, block=1200, frames=40, more_frames=6, min_lost=256):
+    """A packed drain of a ring that overflowed: header [block, lost, ring - block]. `a` is the twin with a ring that holds everything. Which rows of the frame
+    that filled the ring got in is decided by the cursor atomics, so `b`'s rows are held to properties: sorted by env id across both drains, every row (with its
+    flag word) a row of `a` of that env, none twice, each env's rows a subsequence of `a`'s in `a`'s order, and every row of the frames that ended before the ring
+    was full present. Afterwards both batches run on and their streams agree again: cursor and counters were reset. Returns the rows lost."""
+    pol = dog_policy(om)
+    args = dict(terrain_seed=31, rand_seed=2, global_env_offset=100)
+    big_ring = 8 * n_envs
+    a = scn("args/opt_args_train_mace.txt", n_envs, data_root=REFDATA, extra_args=dict(args, tuple_ring_capacity=big_ring))
+    b = scn("args/opt_args_train_mace.txt", n_envs, data_root=REFDATA, extra_args=dict(args, tuple_ring_capacity=ring))
+    for x in (a, b):
+        x.SetPolicy(pol[1], *pol[2:])
+    W = a.W
+    if to_ptr is None:
+        blk = np.zeros((max(block, ring) + 1, W + 2), np.float32)
+        to_ptr = lambda t: t.ctypes.data; read = lambda t: t
+    else:
+        import torch
+        blk = torch.zeros((max(block, ring) + 1, W + 2), dtype=torch.float32, device="cuda")
+    whole = 0                                                            # rows of `a` written by the frames that ended with the ring not yet full
+    for f in range(frames):
+        a.Update(); b.Update()
+        pa = a.TupleStats()["pending"]
+        if pa <= ring:
+            whole = pa
+    sa = a.TupleStats()
+    total_a = sa["pending"]
+    lost = total_a - ring
+    print("full ring at %d envs: %d rows in the twin, ring of %d, %d lost, %d from whole frames" % (n_envs, total_a, ring, lost, whole))
+    assert sa["dropped"] == 0 and sa["capacity"] == big_ring and lost >= min_lost and 0 < whole <= ring
+    sb = b.TupleStats()
+    assert (sb["capacity"], sb["pending"], sb["dropped"], sb["drained"]) == (ring, ring, lost, 0)
+    ra, fa, ia = a.DrainTuples(big_ring)                                 # ring order: frame by frame
+    assert len(ra) == total_a
+    n1 = b.DrainTuplesPacked(to_ptr(blk), block, want_count=True)
+    h1 = read(blk)[:block + 1].copy()
+    assert n1 == block and h1[0, :3].view(np.int32).tolist() == [block, lost, ring - block]
+    sb = b.TupleStats()
+    assert (sb["pending"], sb["dropped"], sb["drained"]) == (ring - block, lost, block)
+    n2 = b.DrainTuplesPacked(to_ptr(blk), block, want_count=True)
+    h2 = read(blk)[:ring - block + 1].copy()
+    assert n2 == ring - block and h2[0, :3].view(np.int32).tolist() == [ring - block, 0, 0]
+    sb = b.TupleStats()
+    assert (sb["pending"], sb["dropped"], sb["drained"]) == (0, lost, ring)
+    out = np.concatenate([h1[1:], h2[1:]]).view(np.int32)                # bit patterns: rows, flag word, global env id
+    ids_b = out[:, W + 1] - 100
+    assert len(out) == ring and np.all(np.diff(ids_b) >= 0) and ids_b[0] >= 0 and ids_b[-1] < n_envs
+    key = lambda row, flag: row.tobytes() + int(flag).to_bytes(4, "little", signed=True)
+    rows_a = {}
+    ra_i, fa_i = ra.view(np.int32), fa.astype(np.int32)
+    for k in range(total_a):
+        rows_a.setdefault(int(ia[k]), []).append(key(ra_i[k], fa_i[k]))
+    got = set()
+    at = {}
+    for k in range(ring):
+        e = int(ids_b[k]); kb = key(out[k, :W], out[k, W])
+        mine = rows_a.get(e, [])
+        j = at.get(e, 0)
+        while j < len(mine) and mine[j] != kb:
+            j += 1
+        assert j < len(mine), "row %d of the drain (env %d) is no row of the twin behind that env's earlier rows" % (k, e)
+        at[e] = j + 1                                                    # a subsequence in the twin's order; a row handed out twice would need a second match
+        got.add((e, kb))
+    assert len(got) == ring and len({(e, k) for e, v in rows_a.items() for k in v}) == total_a   # the twin's rows are distinct, so are the rows handed out
+    for k in range(whole):
+        assert (int(ia[k]), key(ra_i[k], fa_i[k])) in got, "row %d of the twin (env %d), written before the ring was full, is missing" % (k, ia[k])
+    # both run on: the same stream again
+    for f in range(more_frames):
+        a.Update(); b.Update()
+    ra, fa, ia = a.DrainTuples(big_ring)
+    n = b.DrainTuplesPacked(to_ptr(blk), ring, want_count=True)
+    h = read(blk)
+    o = np.argsort(ia, kind="stable")
+    assert n == len(ra) > 0 and h[0, :3].view(np.int32).tolist() == [n, 0, 0]
+    assert np.array_equal(h[1:n + 1, :W].view(np.int32), ra[o].view(np.int32))
+    meta = h[1:n + 1, W:].view(np.int32)
+    assert np.array_equal(meta[:, 0], fa[o].astype(np.int32)) and np.array_equal(meta[:, 1], ia[o] + 100)
+    sa, sb = a.TupleStats(), b.TupleStats()
+    assert (sb["pending"], sb["dropped"], sb["drained"]) == (0, lost, ring + n) and sa["drained"] == total_a + n
+    return lost
 
 
 def run_pipelined_drain_equals_sequential(scn, om, to_ptr=None, read=None, n_envs=12, cap=48, frames=90, extra=None, extra_b=None):

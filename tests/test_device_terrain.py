@@ -111,6 +111,59 @@ def test_device_terrain_determinism_and_shard_invariance(om):
     run_determinism_and_shard_invariance(EmulScenario, om)
 
 
+def run_wide_group_equals_its_shards(scn, om, n=2304, shards=3, frames=40, queued=20, sample=32, min_resets=20):
+    """One env group of n envs (DTRL_GROUPS=1: its launch list is ordered by one workgroup whose loops run more than once above 1024 envs) against the same
+    global env ids in `shards` batches of n / shards: poses, velocities, every env's cycle and reset counters, the distance log and the ground windows of a
+    sample of envs, bit for bit. A launch list that is no permutation steps one env twice and another not at all -- which the counters show even where a pose
+    happens to survive. `queued` of the frames are one RunFrames call: no host wait between them. Returns the resets of the wide batch."""
+    import test_external_policy as X
+    assert n % shards == 0
+    m = n // shards
+    prev = os.environ.get("DTRL_GROUPS")
+    os.environ["DTRL_GROUPS"] = "1"
+    try:
+        wide = make(scn, n, terrain_seed=9, rand_seed=3)
+        parts = [make(scn, m, terrain_seed=9, rand_seed=3, global_env_offset=k * m) for k in range(shards)]
+    finally:
+        if prev is None:
+            del os.environ["DTRL_GROUPS"]
+        else:
+            os.environ["DTRL_GROUPS"] = prev
+    head = (frames - queued) // 2
+    for b in [wide] + parts:
+        set_policy(b, om)
+        for _ in range(head):
+            b.Update()
+        b.RunFrames(queued)
+        for _ in range(frames - queued - head):
+            b.Update()
+    qw, qdw = wide.PoseVel()
+    qp, qdp = zip(*[b.PoseVel() for b in parts])
+    assert np.array_equal(qw, np.concatenate(qp)) and np.array_equal(qdw, np.concatenate(qdp))
+    sw = X.env_states(wide); sp = np.concatenate([X.env_states(b) for b in parts])
+    for name in ("num_cycles", "num_resets", "num_episodes"):
+        assert np.array_equal(sw[name], sp[name]), (name, np.flatnonzero(sw[name] != sp[name])[:10])
+    assert X.same_record(sw, sp) is None, X.same_record(sw, sp)
+    ew, ep = wide.EvalStats(), [b.EvalStats() for b in parts]
+    for name in ("episodes", "cycles", "resets"):
+        assert ew[name] == sum(x[name] for x in ep), (name, ew, ep)
+    assert ew["cycles"] == int(sw["num_cycles"].sum()) and ew["resets"] == int(sw["num_resets"].sum())
+    dw, iw = wide.GetDistLog()
+    dp, ip = zip(*[b.GetDistLog() for b in parts])
+    assert np.array_equal(dw, np.concatenate(dp)) and np.array_equal(iw, np.concatenate([i + k * m for k, i in enumerate(ip)]))
+    picks = sorted(set([0, m - 1, m, 1023, 1024, n - 1]) | set(np.random.RandomState(5).choice(n, sample, replace=False).tolist()))
+    picks = [e for e in picks if e < n]                               # (both sides of a shard seam and of the 1024-env stride, and a random sample)
+    assert len(picks) >= sample
+    for e in picks:
+        (w0, nb0), (w1, nb1) = wide.GroundWindow(e), parts[e // m].GroundWindow(e % m)
+        assert nb0 == nb1, e
+        for s in range(2):
+            assert w0[s][0] == w1[s][0] and w0[s][1] == w1[s][1] and np.array_equal(w0[s][2], w1[s][2]), e
+    print("wide group of %d envs vs %d shards: %s" % (n, shards, ew))
+    assert ew["resets"] >= min_resets, ew
+    return ew["resets"]
+
+
 def strip_features(h):
     """(number of vertical jumps > 5 cm, mean |slope| between jumps, fraction of vertices lower than 1 m below the running level = inside gaps)."""
     d = np.diff(h.astype(np.float64))

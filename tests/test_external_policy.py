@@ -410,3 +410,96 @@ def test_run_external_host_callable(da, om, n=16):
     c = batch(da, DOG, n, terrain_seed=5, rand_seed=3)
     with pytest.raises(ValueError):
         run_external(c, scripted(c), 1)
+
+
+class HostArrays:
+    """The arrays of the device calls on the lane-loop build, where "device" memory is host memory; the GPU twin passes the same four operations on torch tensors."""
+    @staticmethod
+    def full(shape, value, dtype):
+        return np.full(shape, value, dtype)
+
+    @staticmethod
+    def ptr(t):
+        return t.ctypes.data
+
+    @staticmethod
+    def read(t):
+        return t
+
+    @staticmethod
+    def write(t, values):
+        t[:len(values)] = values
+
+
+def run_hand_over_at_width(da, om, n=2304, ticks=20, arrays=HostArrays):
+    """dtrl_pending_actions / dtrl_pending_actions_device above 1024 envs (a chunk of three envs per thread of the collection at 2304), tick by tick against
+    ExtEnvInfo and RecordPoliState: the ids are the awaiting envs in ascending order, the states their policy states (float32 of them in the device call); a `cap`
+    below the number awaiting -- 1, 1000, awaiting - 1: it cuts the list inside one thread's chunk -- hands out exactly the first `cap` of them and leaves the
+    arrays behind `cap` as they were. One batch is driven through the host calls, one through the device calls, with the same float-rounded rows: equal at the end.
+    Returns (smallest, largest) number of awaiting envs seen."""
+    import ctypes
+    mk = lambda: batch(da, DOG, n, policy_mode="external", terrain_seed=9, rand_seed=1)
+    bd, bh = mk(), mk()
+    table = bh.ActionTable()
+    S = bh.S
+    ID_SENT, ST_SENT = -7, -12345.0
+    ids_t = arrays.full(n, ID_SENT, np.int32); st_t = arrays.full((n, S), ST_SENT, np.float32)
+    lab_t = arrays.full(n, 0, np.int32); prm_t = arrays.full((n, bd.n_opt), 0.0, np.float32)
+    ids_h = np.empty(n, np.int32); st_h = np.empty((n, S), np.float64)
+    seen, cut = [], {"one": 0, "thousand": 0, "all_but_one": 0}
+
+    def device_call(cap, want_ids, want_st32):
+        arrays.write(ids_t, np.full(n, ID_SENT, np.int32)); arrays.write(st_t, np.full((n, S), ST_SENT, np.float32))
+        m = bd.PendingActionsDevice(arrays.ptr(ids_t), arrays.ptr(st_t), cap)
+        assert m == min(len(want_ids), cap)
+        gi, gs = arrays.read(ids_t), arrays.read(st_t)
+        assert np.array_equal(gi[:m], want_ids[:m]) and np.array_equal(gs[:m], want_st32[:m])
+        assert np.all(gi[m:] == ID_SENT) and np.all(gs[m:] == ST_SENT), "written behind cap"
+        return m
+
+    def host_call(cap, want_ids, want_st):
+        ids_h[:] = ID_SENT; st_h[:] = ST_SENT
+        m = ctypes.c_int(-1)
+        bh._chk(bh._lib.dtrl_pending_actions(bh._h, da._p(ids_h), da._p(st_h), int(cap), ctypes.byref(m)))
+        m = m.value
+        assert m == min(len(want_ids), cap)
+        assert np.array_equal(ids_h[:m], want_ids[:m]) and np.array_equal(st_h[:m], want_st[:m])
+        assert np.all(ids_h[m:] == ID_SENT) and np.all(st_h[m:] == ST_SENT), "written behind cap"
+
+    for t in range(ticks):
+        bd.Update(); bh.Update()
+        park, _ = bh.ExtEnvInfo()
+        assert np.array_equal(park, bd.ExtEnvInfo()[0]), t
+        want_ids = np.flatnonzero(park == 1).astype(np.int32)
+        awaiting = len(want_ids)
+        seen.append(awaiting)
+        if awaiting == 0:
+            continue
+        want_st = bh.RecordPoliState(want_ids)
+        assert np.array_equal(want_st, bd.RecordPoliState(want_ids)), t
+        want_st32 = want_st.astype(np.float32)
+        for name, cap in (("one", 1), ("thousand", 1000), ("all_but_one", awaiting - 1)):
+            if 0 < cap < awaiting:
+                device_call(cap, want_ids, want_st32)
+                host_call(cap, want_ids, want_st)
+                cut[name] += 1
+        host_call(n, want_ids, want_st)
+        m = device_call(n, want_ids, want_st32)
+        # the same float-rounded rows to both: a function of the handed-out float32 state alone
+        lab = ((np.abs(want_st32[:, 200:].astype(np.float64)).sum(axis=1) * 1000).astype(np.int64) % len(table)).astype(np.int32)
+        prm = (table[lab] * (1.0 + 0.01 * np.sin(want_st32[:, 200:201].astype(np.float64)))).astype(np.float32)   # not a table row: exercises the float -> real conversion
+        arrays.write(lab_t, lab); arrays.write(prm_t, prm)
+        assert bd.SupplyActionsDevice(arrays.ptr(ids_t), m, arrays.ptr(lab_t), arrays.ptr(prm_t), 0) == 0
+        bh.SupplyActions(want_ids, lab, prm.astype(np.float64))
+    print("hand-over at %d envs: awaiting per tick %s, cutting caps used %s" % (n, seen, cut))
+    assert any(0 < k < 1024 for k in seen) and any(k > 1024 for k in seen), seen      # a sparse subset, and more than one env per thread of the collection
+    assert cut["one"] >= 2 and cut["thousand"] >= 1 and cut["all_but_one"] >= 2, cut
+    assert_same_full(full_state(bd), full_state(bh))
+    assert bd.ExtStats() == bh.ExtStats()
+    return min(k for k in seen if k > 0), max(seen)
+
+
+def test_hand_over_at_width(da, om):
+    """The reference logic and floors of run_hand_over_at_width on the lane-loop build, at the width of the GPU twin (tests/test_gpu_handover_width.py): about 25 s."""
+    lo, hi = run_hand_over_at_width(da, om)
+    assert 0 < lo < 1024 < hi
