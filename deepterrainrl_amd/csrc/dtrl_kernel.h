@@ -439,7 +439,7 @@ DTRL_HD inline void kin_dyn_terms(W& ws)
 		for (int k = 0; k < kMaxDepth; ++k) {
 			const int a = (k <= dep) ? static_cast<int>((pw[k / 4] >> (8 * (k % 4))) & 0xffu) : 0;
 			const real qa = ws.st.q[a + 2], wa = ws.st.qd[a + 2];
-			const real on = (k <= dep) ? 1.0 : 0.0;   // predicated accumulation as fma(x, 1|0, acc): same sum (x*1 is exact), but branch-free, so the LDS loads of the whole loop pipeline
+			const real on = (k <= dep) ? 1.0 : 0.0;   // predicated accumulation as fma(x, 1|0, acc): same sum (x*1 is exact), but branch-free. (The device compiler still waits for each element's loads before it issues the next: kin_dyn_terms_fast() of dtrl_kernel_fast.h batches them)
 			phi = fmadd(qa, on, phi); w = fmadd(wa, on, w);
 		}
 		ws.phi[j] = phi; ws.w[j] = w;
@@ -1699,6 +1699,7 @@ struct RefPath {
 	template <class W> static DTRL_HD void substep(W& ws, const DevModel& gm, const GroundRec& g, real h, bool kin_valid) { substep_ref(ws, gm, g, h, kin_valid); }
 	template <class W> static DTRL_HD void pd_solve(W& ws, real dt) { pd_solve_ref(ws, dt); }
 	template <class W> static DTRL_HD void contacts(W& ws, const DevModel& gm, const GroundRec& g, real) { detect_contacts(ws, gm, g); }
+	template <class W> static DTRL_HD void kinematics(W& ws) { kin_dyn_terms(ws); }
 };
 
 // 4x4 ridge solve of the contact-basis least squares (partial-pivot elimination), shared by both characters
@@ -2054,7 +2055,7 @@ DTRL_HD inline void env_step(W& ws, const DevModel& gm, const RunParams& rp, con
 	// or the post-step evaluation of the previous env-step), so the first substep does not recompute them
 	for (int s = 0; s < gm.num_sim_substeps; ++s) Path::substep(ws, gm, g, h, s == 0);
 	}
-	kin_dyn_terms(ws);                                                      // post-step kinematics: controller's RBD terms AND the next substep's
+	Path::kinematics(ws);                                                   // post-step kinematics: controller's RBD terms AND the next substep's
 	Path::contacts(ws, gm, g, h);                                               // cContactManager::Update
 	// UpdateGround is host-side at frame boundaries (the 1 m look-ahead margin makes that equivalent; DESIGN.md "Ground")
 	{ PROF_T0(); controller_update<Path, Ext>(ws, gm, rp, buf, g, env, dt, resume); PROF_ADD(ws, kProfCtrl); }   // UpdateCharacter

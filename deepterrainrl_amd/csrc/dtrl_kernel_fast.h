@@ -905,6 +905,177 @@ __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 	env_sync();
 }
 
+// kin_dyn_terms() of dtrl_kernel.h for a compiled-in skeleton: what substeps 2..n and the post-step evaluation of an env-step run (the cold evaluations -- frame start,
+// reset, resume -- keep the generic function). Every term that is "on" goes through the same operations on the same values in the same order, and every workspace
+// array the generic function writes is written; what changes is how the operands arrive. The generic function reads one path element, waits, adds, 12 and 11 times
+// over, re-reads from LDS what the lane itself produced a phase earlier, and opens every phase with a load of M.L and a branch: about 45 dependent LDS round trips per
+// evaluation. Here
+//   - the lane's path words, depth, parent, subtree-mask words and model constants arrive in ONE batch at the head, q / qd of the whole path in a second one;
+//   - the lane's own cs, sn, w (P1 -> P3), px, py (P3 -> bias) and the mask words (head -> P4) stay in registers;
+//   - P3's bone gather is issued in counted batches of kKinBatch path elements, the sums of one batch running under the loads of the next;
+//   - P4's six operand reads stand in front of the MFMAs;
+//   - the link count and the loop lengths are Topo's (topo_depth()), not M.L and kMaxDepth.
+// What still goes through LDS: the parent's cs / sn / w (P2), the bone gather (P3), the operands and the result layout of the subtree product (P4).
+// The dropped iterations topo_depth() .. kMaxDepth - 1 are exact: on every lane the generic function adds x * 0.0 there with x = q[2] / qd[2] (P1: finite) or link 0's
+// bone terms (P3: +0, the root has no parent), i.e. +-0 or +0 to the accumulator. An accumulator that started at +0 (phi, w, px, py, ax, ay) is never -0 under
+// round-to-nearest, so adding a zero of either sign leaves it as it is. vx, vy start at qd[0], qd[1] and can be -0 when every live term is -0; the generic function's
+// first dropped iteration turns that into -0 + +0 = +0 and the later ones keep it, which is what ONE `+ 0.0` does here (it is the identity on everything else, and on the
+// lanes whose path is shorter, where a masked iteration has already done it). Lanes >= Topo::L evaluate link 0 and store nothing.
+// Force-inlined at its two call sites (FastPath::substep, FastPath::kinematics). One __noinline__ instance per skeleton was measured too: the dog's uses 248 VGPRs and
+// saves twelve callee registers to scratch per call, and it gains half of what this form gains (docs/EXPERIMENTS.md 34).
+constexpr int kKinBatch = 3;   // path elements per batch of P3: 18 values in flight next to the 18 being summed (dog: 3 + 3 + 3, raptor: 3 + 2)
+template <class Topo>
+__device__ __forceinline__ void kin_dyn_terms_fast(WSFast& ws)
+{
+	constexpr int L = Topo::L, kDepth = topo_depth<Topo>();
+	static_assert(kDepth >= 2 && kDepth <= kMaxDepth, "path length of the skeleton against the model's path table");
+	constexpr int kWords = (kDepth + 3) / 4;
+	PROF_T0();
+	const int lane = opaque_lane();
+	const bool mine = lane < L;
+	const int j = mine ? lane : 0;
+	// ---- head: everything that is addressed by the lane id alone, one batch
+	const int dep = ws.M.depth[j], pa = ws.M.parent[j];
+	uint32_t pw[kWords];
+#pragma unroll
+	for (int t = 0; t < kWords; ++t) pw[t] = path_word(ws, j, t);
+	const int mc = lane & 15;
+	const uint32_t m0_l = ws.M.sub_mask[mc < L ? mc : 0], m1_l = ws.M.sub_mask[16 + mc < L ? 16 + mc : 0];   // rows mc and 16 + mc of the mask matrix (P4)
+	const real at0 = ws.M.attach[j][0], at1 = ws.M.attach[j][1], ba0 = ws.M.body_attach[j][0], ba1 = ws.M.body_attach[j][1];
+	const real m = ws.M.mass[j], inr = ws.M.inertia[j], subm = ws.M.sub_mass[j];
+	int a[kDepth];
+#pragma unroll
+	for (int k = 0; k < kDepth; ++k) a[k] = (k <= dep) ? static_cast<int>((pw[k / 4] >> (8 * (k % 4))) & 0xffu) : 0;
+	// ---- P1: q, qd of the path in one batch
+	real qa[kDepth], wa[kDepth];
+#pragma unroll
+	for (int k = 0; k < kDepth; ++k) { qa[k] = ws.st.q[a[k] + 2]; wa[k] = ws.st.qd[a[k] + 2]; }
+	const real vx0 = ws.st.qd[0], vy0 = ws.st.qd[1];
+#pragma unroll
+	for (int k = 0; k < kDepth; ++k) { pin_loaded(qa[k]); pin_loaded(wa[k]); }
+	real phi = 0, w = 0;
+#pragma unroll
+	for (int k = 0; k < kDepth; ++k) {
+		const real on = (k <= dep) ? 1.0 : 0.0;
+		phi = fmadd(qa[k], on, phi); w = fmadd(wa[k], on, w);
+	}
+	real sn, cs; sincos_r(phi, &sn, &cs);
+	if (mine) { ws.phi[j] = phi; ws.w[j] = w; ws.cs[j] = cs; ws.sn[j] = sn; }
+	env_sync();
+	PROF_ADD(ws, kProfP1);
+	// ---- P2: the bone vector of the link from the parent's angle and rate
+	{
+		const int pc = pa >= 0 ? pa : 0;
+		const real c = ws.cs[pc], s = ws.sn[pc], wp = ws.w[pc];
+		const real rx = c * at0 - s * at1;
+		const real ry = s * at0 + c * at1;
+		const real ux = -(wp * ry), uy = wp * rx;
+		const real w2 = wp * wp;
+		const real gx = -(w2 * rx), gy = -(w2 * ry);
+		const bool has = pa >= 0;
+		if (mine) {
+			ws.bx[j] = has ? rx : 0.0; ws.by[j] = has ? ry : 0.0; ws.ux[j] = has ? ux : 0.0; ws.uy[j] = has ? uy : 0.0; ws.gx[j] = has ? gx : 0.0; ws.gy[j] = has ? gy : 0.0;
+		}
+	}
+	env_sync();
+	PROF_ADD(ws, kProfP2);
+	// ---- P3: sums of the bone terms along the path, in counted batches (the loads of batch i + 1 are in flight while batch i is summed)
+	real px = 0, py = 0, vx = vx0, vy = vy0, ax = 0, ay = 0;
+	{
+		constexpr int kN = kDepth - 1;                      // path elements 1 .. kDepth - 1
+		real v[kN][6];
+		auto load = [&](int k) {                            // element k sits in v[k - 1]
+			const int e = a[k];
+			v[k - 1][0] = ws.bx[e]; v[k - 1][1] = ws.by[e]; v[k - 1][2] = ws.ux[e]; v[k - 1][3] = ws.uy[e]; v[k - 1][4] = ws.gx[e]; v[k - 1][5] = ws.gy[e];
+		};
+#pragma unroll
+		for (int k = 1; k <= (kKinBatch < kN ? kKinBatch : kN); ++k) load(k);
+		__builtin_amdgcn_sched_barrier(0);                  // (the scheduler otherwise interleaves the batches' loads, and the first wait drains them all)
+#pragma unroll
+		for (int b0 = 1; b0 <= kN; b0 += kKinBatch) {
+#pragma unroll
+			for (int k = b0 + kKinBatch; k < b0 + 2 * kKinBatch && k <= kN; ++k) load(k);
+			__builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+			for (int k = b0; k < b0 + kKinBatch && k <= kN; ++k) {
+#pragma unroll
+				for (int t = 0; t < 6; ++t) pin_loaded(v[k - 1][t]);
+			}
+#pragma unroll
+			for (int k = b0; k < b0 + kKinBatch && k <= kN; ++k) {
+				const real on = (k <= dep) ? 1.0 : 0.0;
+				px = fmadd(v[k - 1][0], on, px); py = fmadd(v[k - 1][1], on, py); vx = fmadd(v[k - 1][2], on, vx); vy = fmadd(v[k - 1][3], on, vy);
+				ax = fmadd(v[k - 1][4], on, ax); ay = fmadd(v[k - 1][5], on, ay);
+			}
+		}
+		if constexpr (kDepth < kMaxDepth) { vx = vx + 0.0; vy = vy + 0.0; }   // the generic function's dropped iterations (above)
+	}
+	{
+		const real ax0 = 0, ay0 = -kGravityY;
+		const real rx = cs * ba0 - sn * ba1;
+		const real ry = sn * ba0 + cs * ba1;
+		const real cx = px + rx, cy = py + ry;
+		const real w2 = w * w;
+		const real fx = m * ((ax0 + ax) - w2 * rx), fy = m * ((ay0 + ay) - w2 * ry);
+		if (mine) {
+			ws.px[j] = px; ws.py[j] = py; ws.vpx[j] = vx; ws.vpy[j] = vy;
+			ws.cx[j] = cx; ws.cy[j] = cy;
+			ws.vcx[j] = vx - w * ry; ws.vcy[j] = vy + w * rx;
+			ws.fx[j] = fx; ws.fy[j] = fy; ws.fn[j] = cx * fy - cy * fx;
+			ws.mcx[j] = m * cx; ws.mcy[j] = m * cy; ws.Io[j] = inr + m * (cx * cx + cy * cy);
+		}
+	}
+	env_sync();
+	PROF_ADD(ws, kProfP3);
+	// ---- P4: the subtree sums on the matrix pipe (kin_dyn_terms(): same operands, same k order), the six operand reads in front of the MFMAs
+	{
+		const int g = lane >> 4, c = lane & 15;
+		const real* V = &ws.fx[0];
+		const uint32_t m0 = (c < L) ? m0_l : 0u, m1 = (16 + c < L) ? m1_l : 0u;
+		real bv[kMaxL / 4];
+#pragma unroll
+		for (int s4 = 0; s4 < kMaxL / 4; ++s4) {
+			const int k = 4 * s4 + g;
+			const bool live = (c < 6) & (k < L);                                  // never multiply an unwritten LDS slot, not even by zero
+			bv[s4] = V[live ? c * kMaxL + k : 0];
+		}
+#pragma unroll
+		for (int s4 = 0; s4 < kMaxL / 4; ++s4) pin_loaded(bv[s4]);
+		v4r_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+#pragma unroll
+		for (int s4 = 0; s4 < kMaxL / 4; ++s4) {
+			const int k = 4 * s4 + g;
+			const bool live = (c < 6) & (k < L);
+			const real b = live ? bv[s4] : 0.0;
+			const real a0 = ((m0 >> k) & 1u) ? 1.0 : 0.0, a1 = ((m1 >> k) & 1u) ? 1.0 : 0.0;
+			acc0 = mfma_16x16x4(a0, b, acc0);
+			acc1 = mfma_16x16x4(a1, b, acc1);
+		}
+		if (c < 6) {
+			real* out = (c < 3) ? &ws.sfs[c][0] : (&ws.smx[0] + (c - 3) * kMaxL);   // smx, smy, sI are contiguous
+#pragma unroll
+			for (int r = 0; r < 4; ++r) {
+				const int j0 = mfma_row(r, g), j1 = 16 + mfma_row(r, g);
+				if (j0 < L) out[j0] = acc0[r];
+				if (j1 < L) out[j1] = acc1[r];
+			}
+		}
+	}
+	env_sync();
+	// ---- generalised bias
+	{
+		const real sfx = ws.sfs[0][j], sfy = ws.sfs[1][j], sfn = ws.sfs[2][j];
+		const real bl = sfn - px * sfy + py * sfx;
+		if (mine) {
+			ws.sm[j] = subm;
+			ws.b[j + 2] = bl;
+			if (j == 0) { ws.b[0] = sfx; ws.b[1] = sfy; }
+		}
+	}
+	env_sync();
+	PROF_ADD(ws, kProfP4);
+}
+
 #if defined(DTRL_PROFILE)
 // constraint-row bucket of the per-bucket counters (kProfFsubR0, kProfR0, kProfT0): 0 rows, 1-6, 7-12, 13-18, 19+
 __device__ __forceinline__ int prof_row_bucket(int R) { return R == 0 ? 0 : (R <= 6 ? 1 : (R <= 12 ? 2 : (R <= 18 ? 3 : 4))); }
@@ -919,7 +1090,7 @@ struct FastPath {
 #if defined(DTRL_PROFILE)
 		const unsigned long long prof_sub_t0 = __builtin_readcyclecounter();
 #endif
-		if (!kin_valid) { PROF_T0(); kin_dyn_terms(ws); PROF_ADD(ws, kProfFK); }
+		if (!kin_valid) { PROF_T0(); kin_dyn_terms_fast<Topo>(ws); PROF_ADD(ws, kProfFK); }
 		// constraint rows first, factorisation second: the two are independent (both read the kinematics only), and in this order neither the
 		// 23 doubles of the lane's matrix row are live across the contact pass (and its out-of-line calls) nor the sample points across the elimination.
 		// The post-step contact pass of the previous env-step (contacts() below) ran at this very configuration and left its constraint
@@ -1016,6 +1187,7 @@ struct FastPath {
 		if (threadIdx.x == 0) { ws.prof[kProfRowsSum] += R; ws.prof[kProfSubsteps] += 1; const int bk = prof_row_bucket(R); ws.prof[kProfR0 + bk] += 1; ws.prof[kProfT0 + bk] += __builtin_readcyclecounter() - prof_sub_t0; }
 #endif
 	}
+	static __device__ void kinematics(WSFast& ws) { kin_dyn_terms_fast<Topo>(ws); }   // env_step()'s post-step evaluation
 	static __device__ void pd_solve(WSFast& ws, real dt)
 	{
 		const int lane = static_cast<int>(threadIdx.x);

@@ -38,6 +38,14 @@ constexpr bool link_on_path(int a, int l)
 	while (l >= 0) { if (l == a) return true; l = T::parent(l); }
 	return false;
 }
+// entries of the longest root->link path (the link itself included): what the path loops of kin_dyn_terms_fast() run to (dog: 10, raptor: 6)
+template <class T>
+constexpr int topo_depth()
+{
+	int d = 0;
+	for (int l = 0; l < T::L; ++l) { int n = 0; for (int a = l; a >= 0; a = T::parent(a)) ++n; d = n > d ? n : d; }
+	return d;
+}
 // entry (j, k), j < k, of the joint-space inertia matrix is structurally non-zero during the leaf-first elimination. DoFs 0, 1 are the
 // root translations: every hinge hangs below them (H(0,1) itself starts at zero but fills in as the hinges are eliminated);
 // DoF d >= 2 is the hinge of link d - 2
