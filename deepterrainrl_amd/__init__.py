@@ -67,6 +67,7 @@ ABI_SYMBOLS = [
     "dtrl_variant_rescale", "dtrl_variant_rescale_info", "dtrl_variant_scalars",
     "dtrl_push_schedule", "dtrl_push_scale", "dtrl_push_info",
     "dtrl_episode_limit", "dtrl_episode_limit_envs", "dtrl_episode_info",
+    "dtrl_trace", "dtrl_trace_info", "dtrl_trace_read", "dtrl_trace_read_device",
     "dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats", "dtrl_terrain_ladder", "dtrl_ladder_info",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
@@ -183,6 +184,10 @@ def _bind(path):
     L.dtrl_episode_limit.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint64]
     L.dtrl_episode_limit_envs.argtypes = [vp, vp, C.c_int, vp]
     L.dtrl_episode_info.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.dtrl_trace.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.dtrl_trace_info.argtypes = [vp, i32p, i32p, i32p, vp, vp]
+    L.dtrl_trace_read.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.dtrl_trace_read_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.dtrl_terrains_create.argtypes = [vp, C.c_int]
     L.dtrl_terrain_set_file.argtypes = [vp, C.c_int, C.c_char_p, C.c_double]
     L.dtrl_terrain_set_params.argtypes = [vp, C.c_int, C.c_char_p, vp]
@@ -321,6 +326,7 @@ class BatchScenario:
         if arg_file is not None:
             argv += ["-arg_file=", str(arg_file)]
         self._argv = list(argv)
+        self._device_id = int(device_id)
         arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
         h = C.c_void_p()
         rc = self._lib.dtrl_create(arr, len(argv), int(num_envs), int(device_id), C.byref(h))
@@ -643,6 +649,63 @@ class BatchScenario:
                                               ("last_dist", np.float64), ("last_cause", np.int32))}
         self._chk(self._lib.dtrl_episode_info(self._h, _p(ids), n, *[_p(v) for v in out.values()]))
         return out
+
+    # ---- frame trace: per-frame state rows of chosen envs, recorded on the device (the reference writes cCharacter::WriteState per frame, or shows the GUI) ----
+    def Trace(self, env_ids=None, frames=300):
+        """dtrl_trace: from now on every listed env (distinct local ids in any order; None: every env) writes one compact row per frame boundary into its own ring
+        of `frames` rows in device memory -- behind the frame and the episode limit, in front of everything that resets an env, so a row holds the pose the frame
+        ended in (a fallen one included), the need_reset the later rules see and the keys the frame ran under. One small launch per env group and frame, no host
+        wait. A second call replaces the trace (counters from 0); Trace(None, 0) or TraceOff() removes it."""
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, np.int32)
+        n = 0 if int(frames) == 0 and ids is None else (self.num_envs if ids is None else len(ids))
+        self._chk(self._lib.dtrl_trace(self._h, _p(ids), n, int(frames)))
+
+    def TraceOff(self):
+        self._chk(self._lib.dtrl_trace(self._h, None, 0, 0))
+
+    def TraceInfo(self):
+        """dtrl_trace_info: {"n_traced", "frames", "width" (3 D + 2), "env_ids" (int32, Trace's order), "rows_written" (int64 per traced env)}."""
+        n, f, w = C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(self._lib.dtrl_trace_info(self._h, C.byref(n), C.byref(f), C.byref(w), None, None))
+        ids, rows = np.zeros(n.value, np.int32), np.zeros(n.value, np.int64)
+        if n.value:
+            self._chk(self._lib.dtrl_trace_info(self._h, None, None, None, _p(ids), _p(rows)))
+        return {"n_traced": n.value, "frames": f.value, "width": w.value, "env_ids": ids, "rows_written": rows}
+
+    TRACE_INTS = ("row", "need_reset", "action_id", "state", "stance", "contact_bits", "num_cycles", "num_resets", "slot", "variant", "terrain", "reserved")
+
+    def _trace_shape(self, env_ids, max_rows):
+        info = self.TraceInfo()
+        ids = info["env_ids"] if env_ids is None else np.ascontiguousarray(env_ids, np.int32)
+        rows = min(info["frames"], int(info["rows_written"].max()) if info["n_traced"] else 0) if max_rows is None else int(max_rows)
+        return ids, rows, info["width"]
+
+    def TraceRead(self, env_ids=None, max_rows=None):
+        """dtrl_trace_read: the last count[i] = min(rows written, frames, max_rows) rows of each listed traced env (None: all, in Trace's order), oldest first, as a
+        dict of arrays [n, max_rows, ...]: "time", "phase", "q", "qd", "tau" (float64), "row", "need_reset", "action_id", "state", "stance", "contact_bits",
+        "num_cycles", "num_resets", "slot", "variant", "terrain" (int32), plus "count" [n], "env_ids" [n] and the raw blocks "vals" / "ints". Rows beyond count[i]
+        are zero. max_rows None: as many rows as the fullest ring holds."""
+        ids, rows, W = self._trace_shape(env_ids, max_rows)
+        n, D = len(ids), self.D
+        vals, ints, count = np.zeros((n, rows, W), np.float64), np.zeros((n, rows, 12), np.int32), np.zeros(n, np.int32)
+        self._chk(self._lib.dtrl_trace_read(self._h, _p(ids), n, rows, _p(vals), _p(ints), _p(count)))
+        out = {"time": vals[:, :, 0], "phase": vals[:, :, 1], "q": vals[:, :, 2:2 + D], "qd": vals[:, :, 2 + D:2 + 2 * D], "tau": vals[:, :, 2 + 2 * D:2 + 3 * D]}
+        out.update({k: ints[:, :, i] for i, k in enumerate(self.TRACE_INTS) if k != "reserved"})
+        out.update({"count": count, "env_ids": ids, "vals": vals, "ints": ints})
+        return out
+
+    def TraceReadDevice(self, env_ids=None, max_rows=None):
+        """dtrl_trace_read_device: the same rows into two torch tensors on the batch's device -- (vals [n, max_rows, W] float64, ints [n, max_rows, 12] int32) -- and
+        count [n] as a numpy array; one launch, nothing but the counts crosses to the host."""
+        import torch
+        ids, rows, W = self._trace_shape(env_ids, max_rows)
+        n = len(ids)
+        dev = torch.device("cuda", self._device_id if self._device_id >= 0 else torch.cuda.current_device())
+        vals = torch.zeros((n, rows, W), dtype=torch.float64, device=dev); ints = torch.zeros((n, rows, 12), dtype=torch.int32, device=dev)
+        count = np.zeros(n, np.int32)
+        torch.cuda.synchronize(dev)   # (the zero fills run on torch's stream, the gather on the batch's)
+        self._chk(self._lib.dtrl_trace_read_device(self._h, _p(ids), n, rows, C.c_void_p(vals.data_ptr()), C.c_void_p(ints.data_ptr()), _p(count)))
+        return vals, ints, count
 
     def SetPoseVel(self, q, qd, env_ids=None):
         ids, n = self._ids(env_ids)

@@ -1,8 +1,8 @@
 // dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, launches over
 // envs of several slots or variants and the per-slot sums, and the per-env rules of the frame boundary (terrain work under the batch's terrain, a terrain set
-// or a ladder; variant redraw; variant rescale; push schedule; perturbation rows; episode limit), each built from the interface's own copies and Launch. The rules all run over an EnvSpan that
+// or a ladder; variant redraw; variant rescale; push schedule; perturbation rows; episode limit; frame trace), each built from the interface's own copies and Launch. The rules all run over an EnvSpan that
 // SpanList turns into a host vector. What the lane-loop check build runs; the HIP backend overrides every one of them with kernels and keeps these as its
-// cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1, DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1, DTRL_EPISODE_FALLBACK=1).
+// cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1, DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1, DTRL_EPISODE_FALLBACK=1, DTRL_TRACE_FALLBACK=1).
 // Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
 // lane-loop check build of any tests/ tree, the sanitizer scripts -- has the defaults, and no source list can lack them.
 #include "dtrl_engine.h"
@@ -246,6 +246,51 @@ bool Backend::EpisodeLimit(EnvStatus* status, const EnvSpan& span, EnvState* st,
 				|| !H2D(&status[e].need_reset, &es.need_reset, sizeof(es.need_reset)) || !H2D(&status[e].episode_dist, &es.episode_dist, sizeof(es.episode_dist))) return false;
 		}
 		if (!H2D(recs + e, &r, sizeof(r))) return false;   // (an env under the limit moves its record at every boundary: the frame count)
+	}
+	return true;
+}
+// Frame trace: the rule (trace_due / trace_value / trace_int) on the host, traced index by traced index, behind a wait for the selected stream: the env's state and
+// status record, its counter and its keys come down, the row goes up into its ring slot, then the counter.
+bool Backend::TraceRecord(const EnvState* st, const EnvStatus* status, const TraceView& tv, const int32_t* list, int n)
+{
+	if (n <= 0) return true;
+	std::vector<int32_t> ts(static_cast<size_t>(n));
+	if (!D2H(ts.data(), list, sizeof(int32_t) * ts.size()) || !SyncSelected()) return false;
+	EnvState s; EnvStatus es;
+	std::vector<double> vals(static_cast<size_t>(tv.W)); int32_t ints[kTraceInts];
+	for (int32_t t : ts) {
+		int32_t e = 0; int64_t w = 0; int32_t key[3] = {0, 0, 0};
+		if (!D2H(&e, tv.env_of + t, sizeof(e)) || !D2H(&s, st + e, sizeof(s))) return false;
+		if (!trace_due(s)) continue;
+		const int32_t* const key_dev[3] = {tv.env_slot, tv.env_variant, tv.env_terrain};
+		for (int k = 0; k < 3; ++k) if (key_dev[k] && !D2H(&key[k], key_dev[k] + e, sizeof(int32_t))) return false;
+		if (!D2H(&es, status + e, sizeof(es)) || !D2H(&w, tv.written + t, sizeof(w))) return false;
+		for (int k = 0; k < tv.W; ++k) vals[k] = trace_value(s, tv.D, k);
+		for (int k = 0; k < kTraceInts; ++k) ints[k] = trace_int(s, es, w, key[0], key[1], key[2], k);
+		const size_t row = static_cast<size_t>(t) * tv.frames + trace_slot(w, tv.frames);
+		w += 1;
+		if (!H2D(tv.vals + row * tv.W, vals.data(), sizeof(double) * vals.size()) || !H2D(tv.ints + row * kTraceInts, ints, sizeof(ints)) || !H2D(tv.written + t, &w, sizeof(w))) return false;
+	}
+	return true;
+}
+// The rings unrolled on the host, row by row: down from the ring, then into the destination -- with plain stores where it is page-locked memory, else up again.
+bool Backend::TraceGather(const TraceView& tv, const int32_t* list, int n, int max_rows, int row_stride, double* vals_out, int32_t* ints_out, int32_t* counts, bool dst_host)
+{
+	if (n <= 0) return true;
+	if (!SyncSelected()) return false;
+	std::vector<double> vals(static_cast<size_t>(tv.W)); int32_t ints[kTraceInts];
+	for (int i = 0; i < n; ++i) {
+		const int32_t t = list[i];
+		int64_t w = 0;
+		if (!D2H(&w, tv.written + t, sizeof(w))) return false;
+		const int32_t c = trace_count(w, tv.frames, max_rows);
+		counts[i] = c;
+		for (int32_t r = 0; r < c; ++r) {
+			const size_t src = static_cast<size_t>(t) * tv.frames + trace_read_slot(w, c, r, tv.frames), dst = static_cast<size_t>(i) * row_stride + r;
+			if (!D2H(vals.data(), tv.vals + src * tv.W, sizeof(double) * vals.size()) || !D2H(ints, tv.ints + src * kTraceInts, sizeof(ints))) return false;
+			if (dst_host) { std::copy(vals.begin(), vals.end(), vals_out + dst * tv.W); std::copy(ints, ints + kTraceInts, ints_out + dst * kTraceInts); }
+			else if (!H2D(vals_out + dst * tv.W, vals.data(), sizeof(double) * vals.size()) || !H2D(ints_out + dst * kTraceInts, ints, sizeof(ints))) return false;
+		}
 	}
 	return true;
 }

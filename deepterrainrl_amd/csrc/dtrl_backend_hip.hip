@@ -256,6 +256,52 @@ __global__ void __launch_bounds__(64) dtrl_episode_limit(EnvStatus* __restrict__
 	if (cause != kEpisodeRuns) episode_end(st[e], status[e], ec);
 	if (r.frames != 0) recs[e].frames = r.frames; else recs[e] = r;   // (frames == 0: an episode started or ended in this call)
 }
+// Frame trace (include/dtrl.h dtrl_trace): the traced envs of a group write the row of the frame that has just ended, behind the group's frame and the episode limit
+// and IN FRONT OF everything that moves a key or resets an env (trace_due / trace_value / trace_int, dtrl_terrain_dev.h). One wavefront per entry of the group's own
+// list of traced indices (built on the host when the trace is set; a group without a traced env launches nothing). An env that did not complete a frame (external
+// policy mode: parked) is left after two loads (wave-uniform). Lanes take consecutive words of the row: W = 3 D + 2 doubles (71 for the dog, 65 for the raptor:
+// more than a wavefront, so a lane-strided loop) read from consecutive elements of q, qd and tau, and lanes 0 .. 11 the integer part. The counter is read by every
+// lane in front of the stores and written by lane 0 behind them; nothing else touches the env's ring or counter while launches run: no atomics, no scratch. A
+// kernel of its own, all of it arguments: the frame, boundary and rule kernels stay as they are.
+__global__ void __launch_bounds__(kGroup) dtrl_trace_record(const EnvState* __restrict__ st, const EnvStatus* __restrict__ status, TraceView tv, const int32_t* __restrict__ list, int n)
+{
+	const int i = static_cast<int>(blockIdx.x);
+	if (i >= n) return;
+	const int t = list[i];            // wave-uniform, as everything down to the lane loops
+	const int e = tv.env_of[t];
+	const EnvState& s = st[e];
+	if (!trace_due(s)) return;
+	const int lane = static_cast<int>(threadIdx.x);
+	const int64_t w = tv.written[t];
+	const size_t row = static_cast<size_t>(t) * tv.frames + trace_slot(w, tv.frames);
+	double* vals = tv.vals + row * tv.W;
+	for (int k = lane; k < tv.W; k += kGroup) vals[k] = trace_value(s, tv.D, k);
+	if (lane < kTraceInts) {
+		const int32_t slot = tv.env_slot ? tv.env_slot[e] : 0, variant = tv.env_variant ? tv.env_variant[e] : 0, terrain = tv.env_terrain ? tv.env_terrain[e] : 0;
+		tv.ints[row * kTraceInts + lane] = trace_int(s, status[e], w, slot, variant, terrain, lane);
+	}
+	if (lane == 0) tv.written[t] = w + 1;
+}
+// dtrl_trace_read / dtrl_trace_read_device: the rings unrolled into chronological order. One wavefront per (listed env i, row r) of a grid of n x max(cap, 1), cap =
+// min(frames, max_rows): row r < c = min(written, frames, max_rows) of slice i comes from ring slot (written - c + r) % frames, lanes taking consecutive words; rows
+// beyond c are not touched; the wavefront of row 0 stores c. The destination is memory the device addresses: the caller's device buffers, or page-locked staging.
+__global__ void __launch_bounds__(kGroup) dtrl_trace_gather(TraceView tv, const int32_t* __restrict__ list, int n, int cap, int max_rows, int row_stride, double* __restrict__ vals_out, int32_t* __restrict__ ints_out,
+	int32_t* __restrict__ counts)
+{
+	const int per = cap > 0 ? cap : 1;
+	const int i = static_cast<int>(blockIdx.x) / per, r = static_cast<int>(blockIdx.x) % per;
+	if (i >= n) return;
+	const int lane = static_cast<int>(threadIdx.x);
+	const int t = list[i];            // wave-uniform
+	const int64_t w = tv.written[t];
+	const int32_t c = trace_count(w, tv.frames, max_rows);
+	if (r == 0 && lane == 0) counts[i] = c;
+	if (r >= c) return;
+	const size_t src = static_cast<size_t>(t) * tv.frames + trace_read_slot(w, c, r, tv.frames), dst = static_cast<size_t>(i) * row_stride + r;
+	const double* vs = tv.vals + src * tv.W; double* vd = vals_out + dst * tv.W;
+	for (int k = lane; k < tv.W; k += kGroup) vd[k] = vs[k];
+	if (lane < kTraceInts) ints_out[dst * kTraceInts + lane] = tv.ints[src * kTraceInts + lane];
+}
 // dtrl_add_perturb in one launch: a thread per row (the engine has reduced the rows to one per env), the seven slot fields each
 __global__ void __launch_bounds__(64) dtrl_perturb_scatter(EnvState* __restrict__ st, const PerturbRow* __restrict__ rows, int n)
 {
@@ -697,6 +743,22 @@ public:
 	{
 		if (EnvFlag("DTRL_EPISODE_FALLBACK")) return Backend::EpisodeLimit(status, s, st, recs, on, cfg);
 		return LaunchPerEnv(dtrl_episode_limit, s.n, "episode limit launch", status, s.e0, s.n, s.list, st, recs, on, cfg);
+	}
+	// frame trace: ONE launch per group and frame over the group's list of traced indices, ONE per read. DTRL_TRACE_FALLBACK=1 takes the host defaults
+	bool TraceRecord(const EnvState* st, const EnvStatus* status, const TraceView& tv, const int32_t* list, int n) override
+	{
+		if (EnvFlag("DTRL_TRACE_FALLBACK")) return Backend::TraceRecord(st, status, tv, list, n);
+		if (n <= 0) return true;
+		hipLaunchKernelGGL(dtrl_trace_record, dim3(n), dim3(kGroup), 0, stream_, st, status, tv, list, n);
+		return Check(hipGetLastError(), "trace record launch");
+	}
+	bool TraceGather(const TraceView& tv, const int32_t* list, int n, int max_rows, int row_stride, double* vals_out, int32_t* ints_out, int32_t* counts, bool dst_host) override
+	{
+		if (EnvFlag("DTRL_TRACE_FALLBACK")) return Backend::TraceGather(tv, list, n, max_rows, row_stride, vals_out, ints_out, counts, dst_host);
+		if (n <= 0) return true;
+		const int cap = std::min(max_rows, tv.frames);   // (the engine has checked that n x max(cap, 1) is a grid size)
+		hipLaunchKernelGGL(dtrl_trace_gather, dim3(static_cast<unsigned>(n) * static_cast<unsigned>(std::max(cap, 1))), dim3(kGroup), 0, stream_, tv, list, n, cap, max_rows, row_stride, vals_out, ints_out, counts);
+		return Check(hipGetLastError(), "trace gather launch") && Check(hipStreamSynchronize(stream_), "trace gather");
 	}
 	bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n) override
 	{

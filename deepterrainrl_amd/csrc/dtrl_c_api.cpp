@@ -283,6 +283,11 @@ dtrl_status dtrl_push_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t
 dtrl_status dtrl_episode_limit(dtrl_batch* b, int min_frames, int max_frames, double max_dist, uint64_t seed) { return guarded(b, [&](Engine& eng) { return eng.EpisodeLimit(min_frames, max_frames, max_dist, seed); }); }
 dtrl_status dtrl_episode_limit_envs(dtrl_batch* b, const int32_t* env_ids, int n, const uint8_t* on) { return guarded(b, [&](Engine& eng) { return eng.EpisodeLimitEnvs(env_ids, n, on); }); }
 dtrl_status dtrl_episode_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* frames, int32_t* limit, int64_t* by_fall, int64_t* by_limit, int32_t* last_frames, double* last_dist, int32_t* last_cause) { return guarded(b, [&](Engine& eng) { return eng.EpisodeInfo(env_ids, n, frames, limit, by_fall, by_limit, last_frames, last_dist, last_cause); }); }
+// frame trace
+dtrl_status dtrl_trace(dtrl_batch* b, const int32_t* env_ids, int n, int frames) { return guarded(b, [&](Engine& eng) { return eng.Trace(env_ids, n, frames); }); }
+dtrl_status dtrl_trace_info(dtrl_batch* b, int32_t* n_traced, int32_t* frames, int32_t* width, int32_t* env_ids_out, int64_t* rows_written_out) { return guarded(b, [&](Engine& eng) { return eng.TraceInfo(n_traced, frames, width, env_ids_out, rows_written_out); }); }
+dtrl_status dtrl_trace_read(dtrl_batch* b, const int32_t* env_ids, int n, int max_rows, double* vals, int32_t* ints, int32_t* counts) { return guarded(b, [&](Engine& eng) { return eng.TraceRead(env_ids, n, max_rows, vals, ints, counts, false); }); }
+dtrl_status dtrl_trace_read_device(dtrl_batch* b, const int32_t* env_ids, int n, int max_rows, double* vals_dev, int32_t* ints_dev, int32_t* counts) { return guarded(b, [&](Engine& eng) { return eng.TraceRead(env_ids, n, max_rows, vals_dev, ints_dev, counts, true); }); }
 // terrain sets
 dtrl_status dtrl_terrains_create(dtrl_batch* b, int n_terrains) { return guarded(b, [&](Engine& eng) { return eng.TerrainsCreate(n_terrains); }); }
 dtrl_status dtrl_terrain_set_file(dtrl_batch* b, int t, const char* terrain_file, double lerp) { return guarded(b, [&](Engine& eng) { return eng.TerrainSetFile(t, terrain_file, lerp); }); }

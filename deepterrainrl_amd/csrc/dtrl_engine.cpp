@@ -119,6 +119,7 @@ Engine::~Engine()
 	if (be_) {
 		be_->Sync();
 		for (Snapshot* s : snapshots_) { be_->Free(s->payload); s->payload = nullptr; s->owner = nullptr; }   // (the handles stay valid for dtrl_snapshot_info / _free)
+		TraceFree(); be_->FreeHostStaging(trace_stage_);
 		be_->FreeHostStaging(snap_ids_);
 		be_->FreeHostStaging(slot_keys_.part); be_->FreeHostStaging(variant_keys_.part); be_->FreeHostStaging(terrain_keys_.part);
 		if (ext_meta_) be_->FreeHostStaging(ext_meta_);
@@ -365,9 +366,9 @@ int Engine::LaunchGroup(int group, int n_steps, double dt_step, bool frame_end)
 	if (ok && tuple_pipelining_ && n_steps > 0) ok = be_->MarkFrame(group, wr_ring_);
 	// the policy hand-over is double-buffered: remember which weight buffer this launch reads, so that a later gather INTO it can wait for the launch on the device
 	if (ok && weights_alt_ && n_steps > 0) ok = be_->MarkWeightReader(group, b.weights == weights_buf0_ ? 0 : 1);
-	// episode limit, host terrain: the rule is queued behind the group's frame so that it has amended the status records when HostFrameWork's wait for this stream
-	// returns and its loop reads them (device terrain: DeviceFrameWork queues it in front of the boundary launch)
-	if (ok && !cfg_.device_terrain && n_steps > 0) ok = RulesBehindFrame(EnvSpan{g.e0, g.n, nullptr});
+	// episode limit and trace, host terrain: the rules are queued behind the group's frame so that the limit has amended the status records when HostFrameWork's wait
+	// for this stream returns and its loop reads them, and the trace has read the keys before that loop moves them (device terrain: DeviceFrameWork queues it in front of the boundary launch)
+	if (ok && !cfg_.device_terrain && n_steps > 0) ok = RulesBehindFrame(group);
 	if (g_ht.on) g_ht.t_launch += now_s() - lt0;
 	be_->SelectStream(0);
 	return ok ? DTRL_OK : Fail(DTRL_ERR_DEVICE, be_->error());
@@ -406,6 +407,7 @@ int Engine::UploadTerrainCfg(const double* params)
 // -terrain_gen= device: the frame boundary of one env group as three launches on the group's stream, behind its frame kernel and in front of its next
 // one -- the host neither waits nor loops over envs:
 //   dtrl_episode_limit     (with an episode limit) the envs whose episode reached its frame limit or the distance get need_reset, as if they had fallen
+//   dtrl_trace_record      (with a trace) the group's traced envs write the row of the frame that has just ended
 //   dtrl_terrain_boundary  fresh windows for the envs that fell, slid windows where the character got close to an edge, episode distances logged
 //   dtrl_order_by_cost     launch order of the next frame (costliest wavefronts first)
 //   dtrl_variant_redraw    (with a variant redraw) the envs that fell draw the model variant of their next episode
@@ -421,7 +423,7 @@ int Engine::DeviceFrameWork(int group)
 	b.env_list = nullptr; b.reset_listed = 2;
 	const EnvSpan span{grp.e0, grp.n, nullptr};
 	// (the order of the rules: dtrl_engine.h)
-	if (!RulesBehindFrame(span) || !Boundary(span, 0) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_) || !RulesBeforeResets(span)) return Fail(DTRL_ERR_DEVICE, be_->error());
+	if (!RulesBehindFrame(group) || !Boundary(span, 0) || !be_->OrderByCost(buf_.status, grp.e0, grp.n, d_order_) || !RulesBeforeResets(span)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	b.env_list = d_order_ + grp.e0;
 	if (!LaunchEnvs(b, grp.n, 0, 0.0, false, nullptr, grp.e0)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	return DTRL_OK;
@@ -2384,6 +2386,119 @@ int Engine::EpisodeInfo(const int32_t* env_ids, int n, int32_t* frames, int32_t*
 		if (last_frames) last_frames[i] = r.last_frames;
 		if (last_dist) last_dist[i] = r.last_dist;
 		if (last_cause) last_cause[i] = r.last_cause;
+	}
+	return DTRL_OK;
+}
+
+// ---- frame trace (include/dtrl.h: dtrl_trace, dtrl_trace_info, dtrl_trace_read, dtrl_trace_read_device) ----
+// The rule is trace_due / trace_value / trace_int (dtrl_terrain_dev.h), run by Backend::TraceRecord on the group's stream at every frame boundary right behind the
+// episode limit (RulesBehindFrame: queued by DeviceFrameWork with -terrain_gen= device, behind the frame launch by LaunchGroup with host terrain) over the group's
+// own list of traced indices. No listed episode start queues it. Rings, counters and lists live in device memory only.
+void Engine::TraceFree()
+{
+	void* const owned[] = {trace_.v.vals, trace_.v.ints, trace_.v.written, trace_.d_env_of, trace_.d_list};
+	for (void* p : owned) if (p) be_->Free(p);
+	trace_ = TraceState();
+}
+bool Engine::TraceQueue(int group)
+{
+	if (trace_.v.n_traced == 0 || trace_.group_n[group] == 0) return true;
+	TraceView v = trace_.v;
+	v.env_slot = slot_keys_.d_env_key; v.env_variant = variant_keys_.d_env_key; v.env_terrain = terrain_keys_.d_env_key;
+	return be_->TraceRecord(buf_.st, buf_.status, v, trace_.d_list + trace_.group_off[group], trace_.group_n[group]);
+}
+int Engine::Trace(const int32_t* env_ids, int n, int frames)
+{
+	const std::string w = "dtrl_trace: ";
+	if (int rc = RequireIdle("dtrl_trace" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (n == 0) { TraceFree(); return DTRL_OK; }   // removed
+	if (!env_ids) n = n_;   // every env
+	if (n < 0 || n > n_) return Fail(DTRL_ERR_ARG, w + "the env count must be 0 .. num_envs (" + std::to_string(n_) + "), not " + std::to_string(n) + "; nothing changed");
+	if (frames < 1) return Fail(DTRL_ERR_ARG, w + "frames must be >= 1, not " + std::to_string(frames) + "; nothing changed");
+	std::vector<int32_t> ids(static_cast<size_t>(n));
+	for (int i = 0; i < n; ++i) ids[i] = EnvIndex(env_ids, i);
+	if (int rc = CheckSlots(ids.data(), n, "dtrl_trace"); rc != DTRL_OK) { err_ += "; nothing changed"; return rc; }
+	// the old trace goes first: a second call replaces it, and a ring that does not fit leaves the batch without one
+	TraceFree();
+	const int D = cfg_.model.D, W = 3 * D + 2;
+	const size_t rows = static_cast<size_t>(n) * static_cast<size_t>(frames);
+	if (rows > (static_cast<size_t>(1) << 40) / (sizeof(double) * W))   // (n and frames are ints: the product fits; beyond 2^40 bytes the byte counts below are not formed at all)
+		return Fail(DTRL_ERR_CAPACITY, w + std::to_string(n) + " envs x " + std::to_string(frames) + " rows do not fit; the batch has no trace");
+	TraceState& t = trace_;
+	t.v.vals = static_cast<double*>(be_->Alloc(rows * W * sizeof(double)));
+	t.v.ints = t.v.vals ? static_cast<int32_t*>(be_->Alloc(rows * kTraceInts * sizeof(int32_t))) : nullptr;
+	t.v.written = t.v.ints ? static_cast<int64_t*>(be_->Alloc(sizeof(int64_t) * ids.size())) : nullptr;
+	t.d_env_of = t.v.written ? static_cast<int32_t*>(be_->Alloc(sizeof(int32_t) * ids.size())) : nullptr;
+	t.d_list = t.d_env_of ? static_cast<int32_t*>(be_->Alloc(sizeof(int32_t) * ids.size())) : nullptr;
+	if (!t.d_list) { const std::string why = be_->error(); TraceFree(); return Fail(DTRL_ERR_CAPACITY, w + "the ring of " + std::to_string(n) + " envs x " + std::to_string(frames) + " rows does not fit (" + why + "); the batch has no trace"); }
+	// the per-group lists: the traced indices regrouped by env group, the caller's order kept inside a group
+	const int G = static_cast<int>(groups_.size());
+	t.group_off.assign(static_cast<size_t>(G), 0); t.group_n.assign(static_cast<size_t>(G), 0);
+	t.index_of.assign(static_cast<size_t>(n_), -1);
+	std::vector<int32_t> list;
+	for (int g = 0; g < G; ++g) {
+		t.group_off[g] = static_cast<int32_t>(list.size());
+		for (int i = 0; i < n; ++i) if (ids[i] >= groups_[g].e0 && ids[i] < groups_[g].e0 + groups_[g].n) list.push_back(i);
+		t.group_n[g] = static_cast<int32_t>(list.size()) - t.group_off[g];
+	}
+	for (int i = 0; i < n; ++i) t.index_of[ids[i]] = i;
+	if (!be_->H2D(t.d_env_of, ids.data(), sizeof(int32_t) * ids.size()) || !be_->H2D(t.d_list, list.data(), sizeof(int32_t) * list.size()) || !be_->Sync()) {   // (Alloc's zero fill is queued: the rings and counters are 0 behind the wait)
+		const std::string why = be_->error(); TraceFree(); return Fail(DTRL_ERR_DEVICE, why);
+	}
+	t.ids.swap(ids);
+	t.v.env_of = t.d_env_of; t.v.frames = frames; t.v.D = D; t.v.W = W; t.v.n_traced = n;
+	return DTRL_OK;
+}
+int Engine::TraceInfo(int32_t* n_traced, int32_t* frames, int32_t* width, int32_t* env_ids_out, int64_t* rows_written_out)
+{
+	if (int rc = RequireIdle("dtrl_trace_info" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	const TraceView& v = trace_.v;
+	if (n_traced) *n_traced = v.n_traced;
+	if (frames) *frames = v.frames;
+	if (width) *width = 3 * cfg_.model.D + 2;
+	if (env_ids_out) std::copy(trace_.ids.begin(), trace_.ids.end(), env_ids_out);
+	if (rows_written_out && v.n_traced > 0) return DevOk(be_->D2H(rows_written_out, v.written, sizeof(int64_t) * static_cast<size_t>(v.n_traced)));
+	return DTRL_OK;
+}
+int Engine::TraceRead(const int32_t* env_ids, int n, int max_rows, double* vals, int32_t* ints, int32_t* counts, bool device)
+{
+	const char* what = device ? "dtrl_trace_read_device" : "dtrl_trace_read";
+	const std::string w = std::string(what) + ": ";
+	if (int rc = RequireIdle(what + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	const TraceView& v = trace_.v;
+	if (v.n_traced == 0) return Fail(DTRL_ERR_ARG, w + "the batch has no trace (call dtrl_trace first)");
+	if (!env_ids) n = v.n_traced;   // every traced env, in the order dtrl_trace listed them
+	if (n < 0 || n > v.n_traced) return Fail(DTRL_ERR_ARG, w + "the env count must be 0 .. " + std::to_string(v.n_traced) + " (the traced envs), not " + std::to_string(n));
+	if (max_rows < 0 || (n > 0 && (!counts || (max_rows > 0 && (!vals || !ints))))) return Fail(DTRL_ERR_ARG, w + "vals, ints and counts are required and max_rows must not be negative");
+	if (n == 0) return DTRL_OK;
+	const int cap = std::min(max_rows, v.frames);   // rows a slice can hold at most
+	if (static_cast<int64_t>(n) * std::max(cap, 1) > INT32_MAX) return Fail(DTRL_ERR_CAPACITY, w + std::to_string(n) + " envs x " + std::to_string(cap) + " rows are more than one call moves: read fewer envs or rows per call");
+	// staging: [vals n x cap x W, host read only][ints n x cap x 12, host read only][list n][counts n]
+	const size_t rows = device ? 0 : static_cast<size_t>(n) * cap;
+	const size_t off_ints = rows * v.W * sizeof(double), off_list = off_ints + rows * kTraceInts * sizeof(int32_t), bytes = off_list + 2 * sizeof(int32_t) * static_cast<size_t>(n);
+	if (trace_stage_bytes_ < bytes) {
+		be_->FreeHostStaging(trace_stage_);
+		trace_stage_bytes_ = 0;
+		trace_stage_ = static_cast<char*>(be_->HostStaging(bytes));
+		if (!trace_stage_) return Fail(DTRL_ERR_CAPACITY, w + "page-locked staging for " + std::to_string(n) + " envs x " + std::to_string(cap) + " rows does not fit: read fewer envs or rows per call");
+		trace_stage_bytes_ = bytes;
+	}
+	double* s_vals = reinterpret_cast<double*>(trace_stage_); int32_t* s_ints = reinterpret_cast<int32_t*>(trace_stage_ + off_ints);
+	int32_t* s_list = reinterpret_cast<int32_t*>(trace_stage_ + off_list); int32_t* s_counts = s_list + n;
+	for (int i = 0; i < n; ++i) {
+		const int e = env_ids ? env_ids[i] : trace_.ids[i];
+		if (e < 0 || e >= n_) return Fail(DTRL_ERR_ARG, w + "env id " + std::to_string(e) + " out of range");
+		if (trace_.index_of[e] < 0) return Fail(DTRL_ERR_ARG, w + "env " + std::to_string(e) + " is not traced");
+		s_list[i] = trace_.index_of[e]; s_counts[i] = 0;
+	}
+	const bool ok = device ? be_->TraceGather(v, s_list, n, max_rows, max_rows, vals, ints, s_counts, false) : be_->TraceGather(v, s_list, n, max_rows, cap, s_vals, s_ints, s_counts, true);
+	if (!ok || !be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	for (int i = 0; i < n; ++i) {
+		counts[i] = s_counts[i];
+		if (device) continue;
+		const size_t c = static_cast<size_t>(s_counts[i]), src = static_cast<size_t>(i) * cap, dst = static_cast<size_t>(i) * max_rows;
+		std::copy(s_vals + src * v.W, s_vals + (src + c) * v.W, vals + dst * v.W);
+		std::copy(s_ints + src * kTraceInts, s_ints + (src + c) * kTraceInts, ints + dst * kTraceInts);
 	}
 	return DTRL_OK;
 }

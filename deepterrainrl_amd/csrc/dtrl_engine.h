@@ -117,7 +117,7 @@ public:
 	virtual bool GatherF32On(void* stream, float* dst, const float* src, const int32_t* idx, size_t n) { (void)stream; return GatherF32(dst, src, idx, n); }
 	// ---- the per-env rules of the frame boundary (dtrl_terrain_dev.h), each over an EnvSpan and queued on the selected stream ----
 	// Every default is a host loop over the span's envs with per-env D2H / H2D of what the rule reads and writes, synchronised -- what the lane-loop check build
-	// runs, and DTRL_TERRAINS_FALLBACK=1 / DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 / DTRL_PERTURB_FALLBACK=1 / DTRL_EPISODE_FALLBACK=1 on HIP; the HIP backend overrides each with ONE
+	// runs, and DTRL_TERRAINS_FALLBACK=1 / DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 / DTRL_PERTURB_FALLBACK=1 / DTRL_EPISODE_FALLBACK=1 / DTRL_TRACE_FALLBACK=1 on HIP; the HIP backend overrides each with ONE
 	// launch of its kernel. All per-env arrays are device memory under the local env id, and are written back only where the rule changed them.
 	// the span as a host vector (a list is read back: the copy waits for the selected stream)
 	bool SpanList(const EnvSpan& span, std::vector<int32_t>& list);
@@ -147,6 +147,16 @@ public:
 	// the span starts an episode (the limit is set, dtrl_reset, a terrain restart). recs[e] moves; an env with on[e] == 0 is not touched. The default waits for the
 	// selected stream first (the lane-loop check build, DTRL_EPISODE_FALLBACK=1 on HIP); the HIP backend overrides it with one launch of dtrl_episode_limit.
 	virtual bool EpisodeLimit(EnvStatus* status, const EnvSpan& span, EnvState* st, EpisodeRec* recs, const uint8_t* on, const EpisodeCfg& cfg);
+	// Frame trace (include/dtrl.h dtrl_trace; trace_due / trace_value / trace_int). list[0 .. n) (device memory) are the traced indices t of one env group: each
+	// of them whose env completed a frame writes one row -- the env's state and status record and its three keys as they stand -- into slot written[t] % frames of
+	// its ring, then written[t] += 1. Reads state only; the ring and the counters are all it writes. The default waits for the selected stream first (the lane-loop
+	// check build, DTRL_TRACE_FALLBACK=1 on HIP); the HIP backend overrides it with one launch of dtrl_trace_record, one wavefront per listed index.
+	virtual bool TraceRecord(const EnvState* st, const EnvStatus* status, const TraceView& tv, const int32_t* list, int n);
+	// The rings in chronological order: for i < n, with t = list[i] (memory host and device address: HostStaging()) and c = min(written[t], frames, max_rows),
+	// counts[i] = c (HostStaging() memory) and rows r < c of slice i of vals_out [n][row_stride][W] / ints_out [n][row_stride][kTraceInts] = the env's last c rows,
+	// oldest first; rows beyond c are not touched. The destination is memory the device addresses: device memory, or with dst_host HostStaging() memory (which the
+	// default writes with plain stores). Queued on the selected stream and synchronised. Same default / override split, behind the same knob (dtrl_trace_gather).
+	virtual bool TraceGather(const TraceView& tv, const int32_t* list, int n, int max_rows, int row_stride, double* vals_out, int32_t* ints_out, int32_t* counts, bool dst_host);
 	// dtrl_add_perturb: rows[0 .. n) (device memory, at most one row per env: the row names its env, so there is no span) into the perturbation slots of
 	// st[rows[i].env] (perturb_write_slot). The default copies each env's whole EnvState down, edits the seven fields and copies it back.
 	virtual bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n);
@@ -305,6 +315,10 @@ public:
 	int EpisodeLimit(int min_frames, int max_frames, double max_dist, uint64_t seed);
 	int EpisodeLimitEnvs(const int32_t* env_ids, int n, const uint8_t* on);
 	int EpisodeInfo(const int32_t* env_ids, int n, int32_t* frames, int32_t* limit, int64_t* by_fall, int64_t* by_limit, int32_t* last_frames, double* last_dist, int32_t* last_cause);
+	// frame trace (include/dtrl.h)
+	int Trace(const int32_t* env_ids, int n, int frames);
+	int TraceInfo(int32_t* n_traced, int32_t* frames, int32_t* width, int32_t* env_ids_out, int64_t* rows_written_out);
+	int TraceRead(const int32_t* env_ids, int n, int max_rows, double* vals, int32_t* ints, int32_t* counts, bool device);
 	int ApplyRandForce(const int32_t* env_ids, int n, uint64_t seed);
 	int GetPoliState(const int32_t* env_ids, int n, double* s);
 	int GetPolicyOutput(const int32_t* env_ids, int n, double* y);
@@ -354,12 +368,15 @@ private:
 	bool RescaleQueue(const EnvStatus* status, const EnvSpan& span) { return !rescale_on_ || be_->VariantRescale(status, span, variant_keys_.d_env_key, d_var_models_, static_cast<int>(var_models_.size()), rescale_.dev, d_rescale_base_, rescale_cfg_); }
 	bool PushQueue(const EnvStatus* status, const EnvSpan& span) { return !push_on_ || be_->PushSchedule(status, span, buf_.st, push_.dev, push_scale_.dev, push_cfg_); }
 	// THE ORDER OF THE RULES, at a frame boundary and at a listed episode start alike:
-	//   episode limit | terrain work (with the ladder) | redraw, rescale, push | reset launch             a frame boundary of a group's span
-	//                   terrain work (with the ladder) | redraw, rescale | reset launch | push, episode   the listed envs start an episode
-	// The limit comes first: for every other rule an env it ended is an env whose episode ended. Redraw and rescale come in front of the reset launch, which runs
+	//   episode limit, trace | terrain work (with the ladder) | redraw, rescale, push | reset launch             a frame boundary of a group's span
+	//                          terrain work (with the ladder) | redraw, rescale | reset launch | push, episode   the listed envs start an episode
+	// The limit comes first: for every other rule an env it ended is an env whose episode ended. The trace comes right behind it and in front of everything that moves
+	// a key or resets an env: a row holds the state its frame ended in, the need_reset every later rule sees and the keys the frame ran under; a listed episode start
+	// writes no row. Redraw and rescale come in front of the reset launch, which runs
 	// reset_env under the new model, the rescale behind the redraw (which acts on keys below V only). At a boundary the push comes in front of the reset launch (an
 	// env that fell draws a new wait and is not pushed; the launch clears nothing the rule wrote); the listed starts of push and limit come behind it.
-	bool RulesBehindFrame(const EnvSpan& span) { return EpisodeQueue(buf_.status, span); }   // behind a group's frame launch, in front of everything that reads its status
+	bool TraceQueue(int group);   // (dtrl_engine.cpp) the group's traced envs write their rows; a group without one queues nothing
+	bool RulesBehindFrame(int group) { const Group& g = groups_[group]; return EpisodeQueue(buf_.status, EnvSpan{g.e0, g.n, nullptr}) && TraceQueue(group); }   // behind a group's frame launch, in front of everything that reads its status
 	bool RulesBeforeResets(const EnvSpan& span) { return (!cfg_.device_terrain || RedrawQueue(span)) && RescaleQueue(buf_.status, span) && PushQueue(buf_.status, span); }   // (host terrain: the host status loop has run the redraw)
 	// "These envs start an episode now" (dtrl_reset: draw_models; a terrain restart: not), synchronised: the list staged once, with -terrain_gen= device the listed envs'
 	// terrain work under terrain_mode (Boundary: 1 = initialise, 2 = re-seed + initialise), then the second line above
@@ -553,6 +570,17 @@ private:
 	EpisodeCfg episode_cfg_{};
 	RuleRecs<EpisodeRec> episode_; RuleRecs<uint8_t> episode_flag_;   // device [n] each (allocated by the first dtrl_episode_limit / dtrl_episode_limit_envs; flags 1)
 	int EpisodeAlloc();                                              // the two arrays, once
+	// frame trace: the rings, the per-env counters and the per-group lists of traced indices are batch state and live in device memory only (snapshots, restores,
+	// clones, blobs and resets leave them alone). The rule runs in Backend::TraceRecord on the group's stream right behind the episode limit (RulesBehindFrame), in
+	// both terrain modes; dtrl_trace replaces all of it with the streams idle, so stream order is the whole timing rule.
+	struct TraceState {
+		TraceView v{};                           // (the three key arrays are filled in when a launch is queued: a family may be created after the trace)
+		std::vector<int32_t> ids, index_of;      // traced index -> env id (the caller's order); env id -> traced index or -1
+		std::vector<int32_t> group_off, group_n; // per env group: its slice of d_list
+		int32_t* d_env_of = nullptr; int32_t* d_list = nullptr;   // device [n_traced] each: env_of, and the traced indices regrouped by env group
+	} trace_;
+	char* trace_stage_ = nullptr; size_t trace_stage_bytes_ = 0;   // page-locked staging of the two reads (list, counts and -- dtrl_trace_read -- the rows), grown on demand
+	void TraceFree();
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

@@ -384,6 +384,52 @@ DTRL_TG_HD inline void episode_end(EnvState& st, EnvStatus& es, const EpisodeCfg
 	st.need_reset = need; es.need_reset = need;
 }
 
+// ---- frame trace (include/dtrl.h dtrl_trace): a ring of per-frame state rows of chosen envs, written behind the frame and in front of every rule that resets ----
+// A traced env has an index t (its place in the caller's list): env_of[t] is its local env id, its ring is rows [t * frames, (t + 1) * frames) of `vals`
+// (W = 3 D + 2 doubles a row) and `ints` (kTraceInts int32 a row), and written[t] counts the rows it has written since the trace was set -- one counter per env,
+// so the groups' streams need no common frame number. The three key arrays are the families' device arrays (nullptr: the family has no table, the key reads 0).
+// A kernel ARGUMENT: DevBuffers and RunParams keep their layout
+constexpr int kTraceInts = 12;
+enum TraceInt { kTraceRow = 0, kTraceNeedReset, kTraceActionId, kTraceState, kTraceStance, kTraceContactBits, kTraceNumCycles, kTraceNumResets, kTraceSlot, kTraceVariant, kTraceTerrain, kTraceReserved };
+struct TraceView {
+	double* vals; int32_t* ints; int64_t* written;
+	const int32_t* env_of;
+	const int32_t* env_slot; const int32_t* env_variant; const int32_t* env_terrain;
+	int32_t frames, D, W, n_traced;
+};
+// The rule, the one body of host and device. trace_due: the env completed a frame in the launch in front of the rule (external policy mode: a parked env has
+// env-steps of its frame left and writes nothing; internal mode: the counter is always 0)
+DTRL_TG_HD inline bool trace_due(const EnvState& s) { return s.ext_steps_left == 0; }
+// word k < W of the row's value part: time, phase, q[D], qd[D], tau[D], each `real` converted to double exactly as the getters convert it
+DTRL_TG_HD inline double trace_value(const EnvState& s, int D, int k)
+{
+	if (k < 2) return static_cast<double>(k == 0 ? s.time : s.phase);
+	const int j = k - 2;
+	return static_cast<double>(j < D ? s.q[j] : (j < 2 * D ? s.qd[j - D] : s.tau[j - 2 * D]));
+}
+// word k < kTraceInts of the row's integer part; `row` = the env's counter in front of the write
+DTRL_TG_HD inline int32_t trace_int(const EnvState& s, const EnvStatus& es, int64_t row, int32_t slot, int32_t variant, int32_t terrain, int k)
+{
+	switch (k) {
+	case kTraceRow: return static_cast<int32_t>(row);
+	case kTraceNeedReset: return es.need_reset;
+	case kTraceActionId: return s.action_id;
+	case kTraceState: return s.state;
+	case kTraceStance: return s.stance;
+	case kTraceContactBits: return static_cast<int32_t>(s.contact_bits);
+	case kTraceNumCycles: return static_cast<int32_t>(s.num_cycles);
+	case kTraceNumResets: return static_cast<int32_t>(s.num_resets);
+	case kTraceSlot: return slot;
+	case kTraceVariant: return variant;
+	case kTraceTerrain: return terrain;
+	default: return 0;
+	}
+}
+// ring slot of the row an env writes next, and where the r-th of the last `count` rows sits (chronological read-out: oldest first)
+DTRL_TG_HD inline int32_t trace_slot(int64_t written, int32_t frames) { return static_cast<int32_t>(written % frames); }
+DTRL_TG_HD inline int32_t trace_count(int64_t written, int32_t frames, int32_t max_rows) { const int64_t c = written < frames ? written : frames; return static_cast<int32_t>(c < max_rows ? c : max_rows); }
+DTRL_TG_HD inline int32_t trace_read_slot(int64_t written, int32_t count, int32_t r, int32_t frames) { return static_cast<int32_t>((written - count + r) % frames); }
+
 // one row of dtrl_add_perturb as the engine uploads it (Backend::PerturbScatter): the rotated offset is the host's, bit for bit
 struct PerturbRow { int32_t env, link; real f[2], lp[2], dur; };
 DTRL_TG_HD inline void perturb_write_slot(EnvState& st, const PerturbRow& r)

@@ -585,6 +585,39 @@ dtrl_status dtrl_episode_limit_envs(dtrl_batch* b, const int32_t* env_ids, int n
  * and by a limit, and the last ended episode's length, root_x - spawn_x and cause (1 fall, 2 frame limit, 3 distance; 0 none yet). Refused between dtrl_step_begin
  * and dtrl_step_end and before the first dtrl_episode_limit / dtrl_episode_limit_envs, otherwise waits for queued work. Any output may be NULL. */
 dtrl_status dtrl_episode_info(dtrl_batch* b, const int32_t* env_ids, int n, int32_t* frames, int32_t* limit, int64_t* by_fall, int64_t* by_limit, int32_t* last_frames, double* last_dist, int32_t* last_cause);
+/* ---- frame trace: per-frame state rows of chosen envs, recorded on the device ----
+ * The reference looks at a run through its GUI, or by cCharacter::WriteState once per frame (`anim/Character.cpp:217-262`); here hundreds of frames are queued
+ * without the host looking at the batch (dtrl_run_frames, dtrl_step_poll, -terrain_gen= device), and every getter is a blocking copy of a whole EnvState per listed
+ * env BETWEEN frames -- by which time an env that fell has been reset. The trace is a ring of `frames` compact rows per traced env in device memory. At every FRAME
+ * BOUNDARY of an env group (the boundaries the episode limit counts), behind the group's frame launch and the episode limit and in front of the terrain work, the
+ * ladder, redraw, rescale, push and the reset launch, each traced env of the group that completed a frame in that launch writes one row into slot rows_written %
+ * frames of its own ring, then rows_written += 1 (a counter per env: the groups' streams need no common frame number). In -policy_mode= external "completed a
+ * frame" is ext_steps_left == 0 behind the tick: a parked env writes nothing. So a row shows the state the frame ended in -- a fallen pose included --, its
+ * need_reset is what everything queued behind it sees (a limit's truncation included), and its keys are the ones the frame ran under. The listed episode starts
+ * (dtrl_reset, a terrain restart, the creation of a rule) write no row. A row is W = 3 D + 2 doubles -- time, phase, q[D], qd[D], tau[D] (the clamped torques held
+ * for the next world update); the fp32 library converts each value exactly, as its getters do -- and 12 int32: row (the env's rows_written before the write),
+ * need_reset (the status record's), action_id, state, stance, contact_bits, the low words of num_cycles and num_resets, slot, variant, terrain (the env's key in
+ * each family as the device holds it at that moment, 0 without a table; a private rescale key reads V + e, as in dtrl_get_variants), 0 (reserved). One small launch
+ * per env group and frame over the group's own list of traced envs, on the group's stream in both terrain modes; a group without a traced env, and a batch without
+ * a trace, queue what they always queued. Ring, counters and lists are batch state: snapshots, restores, clones, blobs and resets leave them alone. */
+/* Replaces: cCharacter::WriteState called once per frame (`anim/Character.cpp:217-262`), and the GUI as the only way to look at a run. Starts a trace of the n
+ * listed local envs (distinct, in any order; env_ids == NULL: every env) with `frames` >= 1 rows per env. A second call replaces the trace: the old ring is freed
+ * and every counter starts from 0. n == 0 removes it. Refused between dtrl_step_begin and dtrl_step_end (it never waits for a frame), then waits for every stream.
+ * DTRL_ERR_ARG, nothing changed: an id out of range or listed twice, frames < 1. DTRL_ERR_CAPACITY: the ring does not fit; the batch is left without a trace. */
+dtrl_status dtrl_trace(dtrl_batch* b, const int32_t* env_ids, int n, int frames);
+/* Replaces: nothing the reference has (see dtrl_trace; `anim/Character.cpp:217-262`). The trace in force: traced envs (0: none), rows per ring, W (3 D + 2, also
+ * without a trace), the traced env ids in dtrl_trace's order and each one's rows_written (int64 per traced env). Any output may be NULL. Refused while a frame is
+ * in flight, otherwise waits for queued work. */
+dtrl_status dtrl_trace_info(dtrl_batch* b, int32_t* n_traced, int32_t* frames, int32_t* width, int32_t* env_ids_out, int64_t* rows_written_out);
+/* Replaces: reading back what cCharacter::WriteState wrote frame by frame (`anim/Character.cpp:217-262`; cMotion reads such frames, `anim/Motion.cpp:109-171`). For
+ * each listed traced env (env_ids == NULL: all of them, in dtrl_trace's order) the last counts[i] = min(rows_written, frames, max_rows) rows, OLDEST FIRST, into
+ * vals [n][max_rows][W] (double) and ints [n][max_rows][12] (int32); rows beyond counts[i] are left untouched. Refused while a frame is in flight, waits for queued
+ * work and returns synchronised. DTRL_ERR_ARG: no trace, an env that is not traced. */
+dtrl_status dtrl_trace_read(dtrl_batch* b, const int32_t* env_ids, int n, int max_rows, double* vals, int32_t* ints, int32_t* counts);
+/* Replaces: the same read (`anim/Character.cpp:217-262`) for a consumer on the device -- an external policy's extra inputs, an asymmetric critic, a learned
+ * discriminator: vals_dev / ints_dev are DEVICE pointers of the same shapes, counts is host memory. One launch unrolls the rings; nothing crosses to the host but
+ * the counts. */
+dtrl_status dtrl_trace_read_device(dtrl_batch* b, const int32_t* env_ids, int n, int max_rows, double* vals_dev, int32_t* ints_dev, int32_t* counts);
 /* Replaces: cNNController::RecordPoliState (sim/TerrainRLCharController.cpp:120-123). */
 dtrl_status dtrl_get_poli_state(dtrl_batch* b, const int32_t* env_ids, int n, double* s);
 /* Replaces: cNeuralNet::GetLayerState("output", y) (learning/NeuralNet.cpp:814-834) after the controller's last cNeuralNet::Eval
