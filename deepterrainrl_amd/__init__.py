@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "dtrl_push_schedule", "dtrl_push_scale", "dtrl_push_info",
     "dtrl_episode_limit", "dtrl_episode_limit_envs", "dtrl_episode_info",
     "dtrl_trace", "dtrl_trace_info", "dtrl_trace_read", "dtrl_trace_read_device",
+    "dtrl_episode_log", "dtrl_episode_log_info", "dtrl_episode_log_drain", "dtrl_variant_rescale_factors",
     "dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats", "dtrl_terrain_ladder", "dtrl_ladder_info",
     "dtrl_pending_actions", "dtrl_pending_actions_device", "dtrl_supply_actions", "dtrl_supply_actions_device", "dtrl_ext_stats", "dtrl_ext_env_info", "dtrl_action_dims", "dtrl_ext_launch_ms",
 ]
@@ -188,6 +189,10 @@ def _bind(path):
     L.dtrl_trace_info.argtypes = [vp, i32p, i32p, i32p, vp, vp]
     L.dtrl_trace_read.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.dtrl_trace_read_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.dtrl_episode_log.argtypes = [vp, C.c_int32]
+    L.dtrl_episode_log_info.argtypes = [vp, i32p, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.dtrl_episode_log_drain.argtypes = [vp, vp, C.c_int32, i32p, C.POINTER(C.c_int64)]
+    L.dtrl_variant_rescale_factors.argtypes = [vp, vp, vp, C.c_int32, vp]
     L.dtrl_terrains_create.argtypes = [vp, C.c_int]
     L.dtrl_terrain_set_file.argtypes = [vp, C.c_int, C.c_char_p, C.c_double]
     L.dtrl_terrain_set_params.argtypes = [vp, C.c_int, C.c_char_p, vp]
@@ -205,6 +210,12 @@ def _bind(path):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# the layout of dtrl_episode_row (include/dtrl.h): what dtrl_episode_log_drain fills
+EPISODE_ROW_DTYPE = np.dtype([("env", np.int32), ("cause", np.int32), ("frames", np.int32), ("cycles", np.int32), ("boundary", np.int64), ("episode", np.int64),
+                              ("dist", np.float64), ("need_reset", np.int32), ("zero", np.int32), ("slot", np.int32), ("variant", np.int32), ("terrain", np.int32), ("rescale_draw", np.int32)])
+assert EPISODE_ROW_DTYPE.itemsize == 64
 
 
 # ---- env snapshots: the layout of dtrl_types.h EnvState and of dtrl_engine.h SnapHeader, for reading or editing an exported blob ----
@@ -706,6 +717,55 @@ class BatchScenario:
         torch.cuda.synchronize(dev)   # (the zero fills run on torch's stream, the gather on the batch's)
         self._chk(self._lib.dtrl_trace_read_device(self._h, _p(ids), n, rows, C.c_void_p(vals.data_ptr()), C.c_void_p(ints.data_ptr()), _p(count)))
         return vals, ints, count
+
+    # ---- episode log: one row per ended episode, recorded on the device (the reference logs one distance per episode: cScenarioPoliEval::RecordDistTraveled) ----
+    def EpisodeLog(self, capacity):
+        """dtrl_episode_log: from now on every ended episode appends one 64-byte row to a ring of `capacity` rows per env group in page-locked host memory, written
+        on the device at the frame boundary behind the episode limit and the trace and in front of every rule that moves a key or redraws a scale: how long the
+        episode lasted, how far it got, why it ended and under which slot, variant, terrain and rescale draw it ran. One launch of one workgroup per env group and
+        frame, no host wait. A second call replaces the log (everything from 0); EpisodeLog(0) or EpisodeLogOff() removes it."""
+        self._chk(self._lib.dtrl_episode_log(self._h, int(capacity)))
+
+    def EpisodeLogOff(self):
+        self._chk(self._lib.dtrl_episode_log(self._h, 0))
+
+    def EpisodeLogInfo(self):
+        """dtrl_episode_log_info: {"capacity" (rows per ring, 0: no log), "n_groups", "written" (rows ever appended), "lost" (rows overwritten before a drain took them)}."""
+        cap, g, w, lost = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._chk(self._lib.dtrl_episode_log_info(self._h, C.byref(cap), C.byref(g), C.byref(w), C.byref(lost)))
+        return {"capacity": cap.value, "n_groups": g.value, "written": w.value, "lost": lost.value}
+
+    def EpisodeLogDrain(self, max_rows=None):
+        """dtrl_episode_log_drain: the rows not drained yet, merged over the env groups in (boundary, env) order, as a dict of numpy arrays, one per field of
+        EPISODE_ROW_DTYPE ("env", "cause" 1 fall / 2 frame limit / 3 distance, "frames", "cycles", "boundary", "episode", "dist", "need_reset", "slot", "variant",
+        "terrain", "rescale_draw"), plus "lost": rows this call found overwritten before it could take them. max_rows None: all of them. Never queues GPU work;
+        between UpdateBegin and UpdateEnd it does not wait and returns what has been published so far, otherwise it waits for queued work first."""
+        parts, lost_total = [], 0
+        left = None if max_rows is None else int(max_rows)
+        while left is None or left > 0:
+            cap = 4096 if left is None else min(left, 4096)
+            rows, n, lost = np.zeros(cap, EPISODE_ROW_DTYPE), C.c_int32(), C.c_int64()
+            self._chk(self._lib.dtrl_episode_log_drain(self._h, _p(rows), cap, C.byref(n), C.byref(lost)))
+            lost_total += lost.value
+            parts.append(rows[:n.value])
+            if left is not None:
+                left -= n.value
+            if n.value < cap:
+                break
+        rows = np.concatenate(parts) if parts else np.zeros(0, EPISODE_ROW_DTYPE)
+        out = {k: np.ascontiguousarray(rows[k]) for k in EPISODE_ROW_DTYPE.names if k != "zero"}
+        out["lost"] = lost_total
+        return out
+
+    def VariantRescaleFactors(self, env_ids, draws):
+        """dtrl_variant_rescale_factors: factors [n, 4, L] in RESCALE_QUANTITIES order that env env_ids[i] drew for its draw number draws[i] -- a row's
+        "rescale_draw" --, by the library's rule on the host; draw -1 gives all 1. What VariantRescaleInfo()["factors"] shows for the current episode alone."""
+        ids, dr = np.ascontiguousarray(env_ids, np.int32), np.ascontiguousarray(draws, np.int32)
+        if ids.shape != dr.shape or ids.ndim != 1:
+            raise DtrlError("VariantRescaleFactors: env_ids and draws must be two lists of the same length")
+        out = np.zeros((len(ids), 4, self.L), np.float64)
+        self._chk(self._lib.dtrl_variant_rescale_factors(self._h, _p(ids), _p(dr), len(ids), _p(out)))
+        return out
 
     def SetPoseVel(self, q, qd, env_ids=None):
         ids, n = self._ids(env_ids)

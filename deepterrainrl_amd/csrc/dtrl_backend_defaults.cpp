@@ -1,8 +1,8 @@
 // dtrl_backend_defaults.cpp -- the Backend interface's default implementations (dtrl_engine.h): snapshot transport, external-policy hand-over, launches over
 // envs of several slots or variants and the per-slot sums, and the per-env rules of the frame boundary (terrain work under the batch's terrain, a terrain set
-// or a ladder; variant redraw; variant rescale; push schedule; perturbation rows; episode limit; frame trace), each built from the interface's own copies and Launch. The rules all run over an EnvSpan that
+// or a ladder; variant redraw; variant rescale; push schedule; perturbation rows; episode limit; frame trace; episode log), each built from the interface's own copies and Launch. The rules all run over an EnvSpan that
 // SpanList turns into a host vector. What the lane-loop check build runs; the HIP backend overrides every one of them with kernels and keeps these as its
-// cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1, DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1, DTRL_EPISODE_FALLBACK=1, DTRL_TRACE_FALLBACK=1).
+// cross-check (DTRL_SNAPSHOT_FALLBACK=1, DTRL_SLOTS_FALLBACK=1, DTRL_VARIANTS_FALLBACK=1, DTRL_TERRAINS_FALLBACK=1, DTRL_PUSH_FALLBACK=1, DTRL_PERTURB_FALLBACK=1, DTRL_EPISODE_FALLBACK=1, DTRL_TRACE_FALLBACK=1, DTRL_EPISODE_LOG_FALLBACK=1).
 // Compiled as the tail of dtrl_engine.cpp (included there, listed in no Makefile): whoever builds the engine's three host sources -- the libraries, the
 // lane-loop check build of any tests/ tree, the sanitizer scripts -- has the defaults, and no source list can lack them.
 #include "dtrl_engine.h"
@@ -292,6 +292,47 @@ bool Backend::TraceGather(const TraceView& tv, const int32_t* list, int n, int m
 			else if (!H2D(vals_out + dst * tv.W, vals.data(), sizeof(double) * vals.size()) || !H2D(ints_out + dst * kTraceInts, ints, sizeof(ints))) return false;
 		}
 	}
+	return true;
+}
+// Episode log: the rule (log_count / log_row / log_start) on the host, env by env in ascending env id, behind a wait for the selected stream: what the rule reads
+// comes down by per-env copies, the record goes back where it moved; ring and cursor words are page-locked host memory and are written with plain stores, in the
+// kernel's order (reservation, rows, boundary counter, cursor). The rows of a boundary are collected first: of more than `capacity` only the last are stored.
+bool Backend::EpisodeLog(const EnvState* st, const EnvStatus* status, const EnvSpan& span, const LogView& v)
+{
+	std::vector<int32_t> list; bool done;
+	if (!SpanOpen(*this, span, true, list, &done)) return done;
+	LogRec r; int64_t num_cycles = 0;
+	if (!status) {
+		for (int32_t e : list) {
+			if (!D2H(&r, v.recs + e, sizeof(r)) || !D2H(&num_cycles, &st[e].num_cycles, sizeof(num_cycles))) return false;
+			log_start(r, num_cycles);
+			if (!H2D(v.recs + e, &r, sizeof(r))) return false;
+		}
+		return true;
+	}
+	const int64_t written = v.cursor[0], boundary = v.cursor[1];
+	std::vector<LogRow> rows;
+	EnvStatus es; int32_t left = 0;
+	for (int32_t e : list) {
+		if (v.external) { if (!D2H(&left, &st[e].ext_steps_left, sizeof(left))) return false; if (left != 0) continue; }
+		if (!D2H(&r, v.recs + e, sizeof(r)) || !D2H(&es, status + e, sizeof(es))) return false;
+		if (!log_count(r, es, true)) { if (!H2D(&v.recs[e].frames, &r.frames, sizeof(r.frames))) return false; continue; }
+		LogEnv le{0, 0, 0, 0, 0};
+		uint8_t on = 0;
+		if (v.episode) { if (!D2H(&on, v.episode_on + e, sizeof(on))) return false; if (on && !D2H(&le.limit_cause, &v.episode[e].last_cause, sizeof(int32_t))) return false; }
+		if (v.env_slot && !D2H(&le.slot, v.env_slot + e, sizeof(int32_t))) return false;
+		if (v.env_variant && !D2H(&le.variant, v.env_variant + e, sizeof(int32_t))) return false;
+		if (v.env_terrain && !D2H(&le.terrain, v.env_terrain + e, sizeof(int32_t))) return false;
+		if (v.rescale && !D2H(&le.rescale_episodes, &v.rescale[e].episodes, sizeof(int32_t))) return false;
+		if (!D2H(&num_cycles, &st[e].num_cycles, sizeof(num_cycles))) return false;
+		rows.push_back(log_row(r, es, num_cycles, boundary, le, v, e));
+		if (!H2D(v.recs + e, &r, sizeof(r))) return false;
+	}
+	const int64_t total = static_cast<int64_t>(rows.size());
+	if (total > 0) { v.cursor[2] = written + total; __atomic_thread_fence(__ATOMIC_SEQ_CST); }
+	for (int64_t k = 0; k < total; ++k) if (log_row_kept(total, k, v.capacity)) v.ring[log_slot(written, k, v.capacity)] = rows[static_cast<size_t>(k)];
+	__atomic_thread_fence(__ATOMIC_SEQ_CST);
+	v.cursor[1] = boundary + 1; v.cursor[0] = written + total;
 	return true;
 }
 // dtrl_add_perturb's rows, env by env: the whole EnvState down, the seven fields, the whole EnvState up (what Engine::AddPerturb did before there was a launch for it)

@@ -302,6 +302,84 @@ __global__ void __launch_bounds__(kGroup) dtrl_trace_gather(TraceView tv, const 
 	for (int k = lane; k < tv.W; k += kGroup) vd[k] = vs[k];
 	if (lane < kTraceInts) ints_out[dst * kTraceInts + lane] = tv.ints[src * kTraceInts + lane];
 }
+// Episode log (include/dtrl.h dtrl_episode_log): the envs of a group count the boundaries of their episodes behind the group's frame, the episode limit and the
+// trace and IN FRONT OF everything that moves a key or redraws a scale, and every env whose episode ended appends one 64-byte row to the group's ring in
+// page-locked host memory (log_count / log_row, dtrl_terrain_dev.h). Shaped like dtrl_ext_collect: ONE workgroup per env group and frame; thread t owns the
+// contiguous range [t c, (t + 1) c) of the group's span, counts its ended episodes, the counts are scanned across the workgroup (wave shuffles + one LDS level),
+// and the thread writes its rows behind the ranges in front of it, in ascending env id, each as four 16-byte stores at slot (written + k) % capacity. More than
+// `capacity` rows in one boundary: only the last `capacity` are stored (no two rows of a launch share a slot), the cursor advances by all of them. Publication:
+// thread 0 first stores the reservation written + rows (cursor word 2) behind a system-scope fence and a barrier, so that a host reader whose copy this launch
+// overwrites can tell; every thread that stored a row fences at system scope, the workgroup meets at a barrier, then thread 0 stores boundary + 1 and the new
+// cursor -- the host never sees a cursor ahead of its rows. Thread 0 reads the pair once and hands it on through LDS. No atomics, no scratch; a kernel of its own, all of it arguments.
+constexpr int kLogThreads = 1024;
+// a record of whole 16-byte words moved as such (the compiler otherwise splits the struct along its fields)
+typedef int32_t log_word __attribute__((ext_vector_type(4)));
+template <class T> __device__ __forceinline__ T load_words(const T* src)
+{
+	static_assert(sizeof(T) % 16 == 0 && alignof(T) >= 16, "whole 16-byte words");
+	log_word w[sizeof(T) / 16];
+	for (size_t i = 0; i < sizeof(T) / 16; ++i) w[i] = reinterpret_cast<const log_word*>(src)[i];
+	T v; __builtin_memcpy(&v, w, sizeof(T));
+	return v;
+}
+template <class T> __device__ __forceinline__ void store_words(T* dst, const T& v)
+{
+	static_assert(sizeof(T) % 16 == 0 && alignof(T) >= 16, "whole 16-byte words");
+	log_word w[sizeof(T) / 16];
+	__builtin_memcpy(w, &v, sizeof(T));
+	for (size_t i = 0; i < sizeof(T) / 16; ++i) reinterpret_cast<log_word*>(dst)[i] = w[i];
+}
+__device__ __forceinline__ bool log_due(const EnvState* __restrict__ st, const LogView& v, int e) { return !v.external || st[e].ext_steps_left == 0; }
+__global__ void __launch_bounds__(kLogThreads) dtrl_episode_log(const EnvState* __restrict__ st, const EnvStatus* __restrict__ status, int e0, int n, LogView v)
+{
+	__shared__ int part[kLogThreads / 64];
+	__shared__ int64_t cur[2];
+	const int t = static_cast<int>(threadIdx.x);
+	const int chunk = (n + kLogThreads - 1) / kLogThreads;
+	const int c0 = t * chunk < n ? t * chunk : n, c1 = c0 + chunk < n ? c0 + chunk : n;
+	if (t == 0) { cur[0] = v.cursor[0]; cur[1] = v.cursor[1]; }
+	int mine = 0;
+	for (int k = c0; k < c1; ++k) mine += log_due(st, v, e0 + k) && status[e0 + k].need_reset != 0;
+	int incl = mine;
+	for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d, 64); if ((t & 63) >= d) incl += o; }
+	if ((t & 63) == 63) part[t >> 6] = incl;
+	__syncthreads();
+	int base = 0, total = 0;
+	for (int w = 0; w < kLogThreads / 64; ++w) { const int c = part[w]; if (w < (t >> 6)) base += c; total += c; }
+	const int64_t written = cur[0], boundary = cur[1];
+	if (total > 0) {   // (uniform) the reservation goes out in front of the first row: a reader that copied a slot this launch overwrites finds out
+		if (t == 0) { v.cursor[2] = written + total; __threadfence_system(); }
+		__syncthreads();
+	}
+	int64_t row_k = base + incl - mine;
+	for (int k = c0; k < c1; ++k) {
+		const int e = e0 + k;
+		if (!log_due(st, v, e)) continue;
+		LogRec r = load_words(v.recs + e);
+		const EnvStatus es = status[e];
+		if (!log_count(r, es, true)) { v.recs[e].frames = r.frames; continue; }
+		LogEnv le;
+		le.limit_cause = (v.episode && v.episode_on[e]) ? v.episode[e].last_cause : 0;
+		le.slot = v.env_slot ? v.env_slot[e] : 0; le.variant = v.env_variant ? v.env_variant[e] : 0; le.terrain = v.env_terrain ? v.env_terrain[e] : 0;
+		le.rescale_episodes = v.rescale ? v.rescale[e].episodes : 0;
+		const LogRow row = log_row(r, es, st[e].num_cycles, boundary, le, v, e);
+		if (log_row_kept(total, row_k, v.capacity)) store_words(v.ring + log_slot(written, row_k, v.capacity), row);
+		row_k += 1;
+		store_words(v.recs + e, r);
+	}
+	if (mine) __threadfence_system();
+	__syncthreads();
+	if (t == 0) { v.cursor[1] = boundary + 1; v.cursor[0] = written + total; }
+}
+// the listed form (dtrl_reset, a terrain restart, the log is set): thread per listed env, the running episode is abandoned without a row (log_start)
+__global__ void __launch_bounds__(64) dtrl_episode_log_start(int e0, int n, const int32_t* __restrict__ env_list, const EnvState* __restrict__ st, LogRec* __restrict__ recs)
+{
+	int e;
+	if (!span_env(static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x), e0, n, env_list, e)) return;
+	LogRec r = recs[e];
+	log_start(r, st[e].num_cycles);
+	recs[e] = r;
+}
 // dtrl_add_perturb in one launch: a thread per row (the engine has reduced the rows to one per env), the seven slot fields each
 __global__ void __launch_bounds__(64) dtrl_perturb_scatter(EnvState* __restrict__ st, const PerturbRow* __restrict__ rows, int n)
 {
@@ -759,6 +837,15 @@ public:
 		const int cap = std::min(max_rows, tv.frames);   // (the engine has checked that n x max(cap, 1) is a grid size)
 		hipLaunchKernelGGL(dtrl_trace_gather, dim3(static_cast<unsigned>(n) * static_cast<unsigned>(std::max(cap, 1))), dim3(kGroup), 0, stream_, tv, list, n, cap, max_rows, row_stride, vals_out, ints_out, counts);
 		return Check(hipGetLastError(), "trace gather launch") && Check(hipStreamSynchronize(stream_), "trace gather");
+	}
+	// episode log: ONE launch of one workgroup per group and frame; the listed form is a per-env launch. DTRL_EPISODE_LOG_FALLBACK=1 takes the host default
+	bool EpisodeLog(const EnvState* st, const EnvStatus* status, const EnvSpan& s, const LogView& v) override
+	{
+		if (EnvFlag("DTRL_EPISODE_LOG_FALLBACK")) return Backend::EpisodeLog(st, status, s, v);
+		if (!status) return LaunchPerEnv(dtrl_episode_log_start, s.n, "episode log start launch", s.e0, s.n, s.list, st, v.recs);
+		if (s.n <= 0) return true;
+		hipLaunchKernelGGL(dtrl_episode_log, dim3(1), dim3(kLogThreads), 0, stream_, st, status, s.e0, s.n, v);
+		return Check(hipGetLastError(), "episode log launch");
 	}
 	bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n) override
 	{

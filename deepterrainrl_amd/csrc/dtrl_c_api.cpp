@@ -10,6 +10,7 @@
 
 using dtrl::Engine;
 using dtrl::EnvState;
+using dtrl::LogRow;
 
 struct dtrl_batch { Engine eng; };
 
@@ -288,6 +289,14 @@ dtrl_status dtrl_trace(dtrl_batch* b, const int32_t* env_ids, int n, int frames)
 dtrl_status dtrl_trace_info(dtrl_batch* b, int32_t* n_traced, int32_t* frames, int32_t* width, int32_t* env_ids_out, int64_t* rows_written_out) { return guarded(b, [&](Engine& eng) { return eng.TraceInfo(n_traced, frames, width, env_ids_out, rows_written_out); }); }
 dtrl_status dtrl_trace_read(dtrl_batch* b, const int32_t* env_ids, int n, int max_rows, double* vals, int32_t* ints, int32_t* counts) { return guarded(b, [&](Engine& eng) { return eng.TraceRead(env_ids, n, max_rows, vals, ints, counts, false); }); }
 dtrl_status dtrl_trace_read_device(dtrl_batch* b, const int32_t* env_ids, int n, int max_rows, double* vals_dev, int32_t* ints_dev, int32_t* counts) { return guarded(b, [&](Engine& eng) { return eng.TraceRead(env_ids, n, max_rows, vals_dev, ints_dev, counts, true); }); }
+// episode log (the row of the header is the rule's LogRow, field for field)
+static_assert(sizeof(dtrl_episode_row) == sizeof(LogRow) && offsetof(dtrl_episode_row, boundary) == offsetof(LogRow, boundary) && offsetof(dtrl_episode_row, dist) == offsetof(LogRow, dist)
+	&& offsetof(dtrl_episode_row, need_reset) == offsetof(LogRow, need_reset) && offsetof(dtrl_episode_row, slot) == offsetof(LogRow, slot) && offsetof(dtrl_episode_row, rescale_draw) == offsetof(LogRow, rescale_draw),
+	"dtrl_episode_row is LogRow");
+dtrl_status dtrl_episode_log(dtrl_batch* b, int32_t capacity) { return guarded(b, [&](Engine& eng) { return eng.EpisodeLog(capacity); }); }
+dtrl_status dtrl_episode_log_info(dtrl_batch* b, int32_t* capacity, int32_t* n_groups, int64_t* written, int64_t* lost) { return guarded(b, [&](Engine& eng) { return eng.EpisodeLogInfo(capacity, n_groups, written, lost); }); }
+dtrl_status dtrl_episode_log_drain(dtrl_batch* b, dtrl_episode_row* out, int32_t max_rows, int32_t* n, int64_t* lost) { return guarded(b, [&](Engine& eng) { return eng.EpisodeLogDrain(out, max_rows, n, lost); }); }
+dtrl_status dtrl_variant_rescale_factors(dtrl_batch* b, const int32_t* env_ids, const int32_t* draws, int32_t n, double* factors) { return guarded(b, [&](Engine& eng) { return eng.VariantRescaleFactors(env_ids, draws, n, factors); }); }
 // terrain sets
 dtrl_status dtrl_terrains_create(dtrl_batch* b, int n_terrains) { return guarded(b, [&](Engine& eng) { return eng.TerrainsCreate(n_terrains); }); }
 dtrl_status dtrl_terrain_set_file(dtrl_batch* b, int t, const char* terrain_file, double lerp) { return guarded(b, [&](Engine& eng) { return eng.TerrainSetFile(t, terrain_file, lerp); }); }

@@ -120,6 +120,7 @@ Engine::~Engine()
 		be_->Sync();
 		for (Snapshot* s : snapshots_) { be_->Free(s->payload); s->payload = nullptr; s->owner = nullptr; }   // (the handles stay valid for dtrl_snapshot_info / _free)
 		TraceFree(); be_->FreeHostStaging(trace_stage_);
+		LogFree();
 		be_->FreeHostStaging(snap_ids_);
 		be_->FreeHostStaging(slot_keys_.part); be_->FreeHostStaging(variant_keys_.part); be_->FreeHostStaging(terrain_keys_.part);
 		if (ext_meta_) be_->FreeHostStaging(ext_meta_);
@@ -366,8 +367,8 @@ int Engine::LaunchGroup(int group, int n_steps, double dt_step, bool frame_end)
 	if (ok && tuple_pipelining_ && n_steps > 0) ok = be_->MarkFrame(group, wr_ring_);
 	// the policy hand-over is double-buffered: remember which weight buffer this launch reads, so that a later gather INTO it can wait for the launch on the device
 	if (ok && weights_alt_ && n_steps > 0) ok = be_->MarkWeightReader(group, b.weights == weights_buf0_ ? 0 : 1);
-	// episode limit and trace, host terrain: the rules are queued behind the group's frame so that the limit has amended the status records when HostFrameWork's wait
-	// for this stream returns and its loop reads them, and the trace has read the keys before that loop moves them (device terrain: DeviceFrameWork queues it in front of the boundary launch)
+	// episode limit, trace and episode log, host terrain: the rules are queued behind the group's frame so that the limit has amended the status records when HostFrameWork's wait
+	// for this stream returns and its loop reads them, and trace and log have read the keys before that loop moves them (device terrain: DeviceFrameWork queues it in front of the boundary launch)
 	if (ok && !cfg_.device_terrain && n_steps > 0) ok = RulesBehindFrame(group);
 	if (g_ht.on) g_ht.t_launch += now_s() - lt0;
 	be_->SelectStream(0);
@@ -408,6 +409,7 @@ int Engine::UploadTerrainCfg(const double* params)
 // one -- the host neither waits nor loops over envs:
 //   dtrl_episode_limit     (with an episode limit) the envs whose episode reached its frame limit or the distance get need_reset, as if they had fallen
 //   dtrl_trace_record      (with a trace) the group's traced envs write the row of the frame that has just ended
+//   dtrl_episode_log       (with an episode log) the group's envs whose episode ended append one row each to the group's ring in page-locked host memory
 //   dtrl_terrain_boundary  fresh windows for the envs that fell, slid windows where the character got close to an edge, episode distances logged
 //   dtrl_order_by_cost     launch order of the next frame (costliest wavefronts first)
 //   dtrl_variant_redraw    (with a variant redraw) the envs that fell draw the model variant of their next episode
@@ -728,7 +730,7 @@ int Engine::StartEpisodes(const std::vector<int32_t>& ids, bool draw_models, int
 			if (!RescaleQueue(nullptr, span)) return Fail(DTRL_ERR_DEVICE, be_->error());
 		}
 		if (int rc = ApplyResets(ids, -1, list); rc != DTRL_OK) return rc;
-		if (!PushQueue(nullptr, span) || !EpisodeQueue(nullptr, span)) return Fail(DTRL_ERR_DEVICE, be_->error());
+		if (!PushQueue(nullptr, span) || !EpisodeQueue(nullptr, span) || !LogQueue(nullptr, span, -1)) return Fail(DTRL_ERR_DEVICE, be_->error());
 	}
 	return DevOk(be_->Sync());
 }
@@ -2499,6 +2501,133 @@ int Engine::TraceRead(const int32_t* env_ids, int n, int max_rows, double* vals,
 		const size_t c = static_cast<size_t>(s_counts[i]), src = static_cast<size_t>(i) * cap, dst = static_cast<size_t>(i) * max_rows;
 		std::copy(s_vals + src * v.W, s_vals + (src + c) * v.W, vals + dst * v.W);
 		std::copy(s_ints + src * kTraceInts, s_ints + (src + c) * kTraceInts, ints + dst * kTraceInts);
+	}
+	return DTRL_OK;
+}
+
+// ---- episode log (include/dtrl.h: dtrl_episode_log, dtrl_episode_log_info, dtrl_episode_log_drain, dtrl_variant_rescale_factors) ----
+// The rule is log_count / log_row / log_start (dtrl_terrain_dev.h), run by Backend::EpisodeLog on the group's stream at every frame boundary behind the episode
+// limit and the trace (RulesBehindFrame: queued by DeviceFrameWork with -terrain_gen= device, behind the frame launch by LaunchGroup with host terrain) over the
+// group's span into the group's own ring, and in its listed form by StartEpisodes. Rings and cursor words are page-locked host memory: a drain reads them with
+// plain loads and queues nothing, also while a frame is in flight.
+constexpr int kLogCursorWords = 4;   // per group: written, boundary, reserved, 0
+void Engine::LogFree()
+{
+	be_->FreeHostStaging(log_.rings); be_->FreeHostStaging(log_.cursors);
+	log_ = LogState();
+}
+bool Engine::LogQueue(const EnvStatus* status, const EnvSpan& span, int group)
+{
+	if (log_.capacity == 0) return true;
+	LogView v{};
+	v.recs = log_recs_.dev;
+	if (status) { v.ring = log_.rings + static_cast<size_t>(group) * static_cast<size_t>(log_.capacity); v.cursor = log_.cursors + static_cast<size_t>(group) * kLogCursorWords; }
+	if (episode_on_) { v.episode = episode_.dev; v.episode_on = episode_flag_.dev; }
+	v.env_slot = slot_keys_.d_env_key; v.env_variant = variant_keys_.d_env_key; v.env_terrain = terrain_keys_.d_env_key;   // (a family may be created after the log)
+	if (rescale_table_ && rescale_.dev) { v.rescale = rescale_.dev; v.private_base = static_cast<int32_t>(var_models_.size()); }
+	v.spawn_x = SpawnX(cfg_.model); v.capacity = log_.capacity; v.external = cfg_.external_policy ? 1 : 0;
+	return be_->EpisodeLog(buf_.st, status, span, v);
+}
+int Engine::EpisodeLog(int capacity)
+{
+	const std::string w = "dtrl_episode_log: ";
+	if (int rc = RequireIdle("dtrl_episode_log" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	if (capacity < 0) return Fail(DTRL_ERR_ARG, w + "capacity (" + std::to_string(capacity) + ") must not be negative (0 removes the log); nothing changed");
+	// the old log goes first: a second call replaces it, and a ring that does not fit leaves the batch without one
+	LogFree();
+	if (capacity == 0) return DTRL_OK;   // removed (the records stay allocated; the next log zeroes them)
+	if (int rc = RecsAlloc(log_recs_, static_cast<size_t>(n_)); rc != DTRL_OK) return rc;
+	const size_t G = groups_.size(), rows = G * static_cast<size_t>(capacity);
+	const std::string no_fit = w + std::to_string(G) + " rings of " + std::to_string(capacity) + " rows do not fit";
+	if (rows > (static_cast<size_t>(1) << 40) / sizeof(LogRow)) return Fail(DTRL_ERR_CAPACITY, no_fit + "; the batch has no episode log");
+	log_.rings = static_cast<LogRow*>(be_->HostStaging(rows * sizeof(LogRow)));
+	log_.cursors = log_.rings ? static_cast<int64_t*>(be_->HostStaging(G * kLogCursorWords * sizeof(int64_t))) : nullptr;
+	if (!log_.cursors) { const std::string why = be_->error(); LogFree(); return Fail(DTRL_ERR_CAPACITY, no_fit + " into page-locked host memory (" + why + "); the batch has no episode log"); }
+	std::memset(static_cast<void*>(log_.rings), 0, rows * sizeof(LogRow)); std::memset(log_.cursors, 0, G * kLogCursorWords * sizeof(int64_t));
+	log_.drained.assign(G, 0); log_.lost.assign(G, 0);
+	log_recs_.host.assign(static_cast<size_t>(n_), LogRec{0, 0, 0, 0, 0});
+	if (!log_recs_.Push(*be_)) { const std::string why = be_->error(); LogFree(); return Fail(DTRL_ERR_DEVICE, why); }
+	log_.capacity = capacity;
+	// every env's logged episode starts here: frames 0, cycles counted from the env's cycle counter as it stands
+	if (!LogQueue(nullptr, EnvSpan{0, n_, nullptr}, -1) || !be_->Sync()) { const std::string why = be_->error(); LogFree(); return Fail(DTRL_ERR_DEVICE, why); }
+	return DTRL_OK;
+}
+int Engine::EpisodeLogInfo(int32_t* capacity, int32_t* n_groups, int64_t* written, int64_t* lost)
+{
+	if (int rc = RequireIdle("dtrl_episode_log_info" + std::string(kFrameInFlight)); rc != DTRL_OK) return rc;
+	int64_t w = 0, l = 0;
+	for (size_t g = 0; g < log_.drained.size(); ++g) {
+		const int64_t wg = log_.cursors[g * kLogCursorWords];
+		w += wg;
+		l += log_.lost[g] + std::max<int64_t>(0, wg - log_.drained[g] - log_.capacity);   // found by a drain, or overwritten since the last one
+	}
+	if (capacity) *capacity = log_.capacity;
+	if (n_groups) *n_groups = log_.capacity ? static_cast<int32_t>(groups_.size()) : 0;
+	if (written) *written = w;
+	if (lost) *lost = l;
+	return DTRL_OK;
+}
+// Per group: read the cursor w0, copy rows [drained, w0) (at most the last `capacity`), then read the reservation and the cursor again and drop every copied row
+// whose slot a boundary written meanwhile has taken, or was taking. The groups' rows are then merged in (boundary, env) order; what max_rows leaves stays.
+int Engine::EpisodeLogDrain(void* out, int max_rows, int32_t* n_out, int64_t* lost)
+{
+	const std::string w = "dtrl_episode_log_drain: ";
+	if (n_out) *n_out = 0;
+	if (lost) *lost = 0;
+	if (log_.capacity == 0) return Fail(DTRL_ERR_ARG, w + "the batch has no episode log (call dtrl_episode_log first)");
+	if (max_rows < 0 || (max_rows > 0 && !out) || !n_out) return Fail(DTRL_ERR_ARG, w + "out and n are required and max_rows must not be negative");
+	if (!step_pending_ && !early_any_) {   // no frame in flight: every boundary queued so far is visible behind the wait. In flight: what has been published, no wait
+		be_->SelectStream(0);
+		if (!be_->Sync()) return Fail(DTRL_ERR_DEVICE, be_->error());
+	}
+	const size_t G = log_.drained.size();
+	const int64_t cap = log_.capacity;
+	std::vector<size_t> begin(G + 1, 0);
+	log_stage_.clear();
+	int64_t lost_now = 0;
+	for (size_t g = 0; g < G; ++g) {
+		const int64_t* cur = log_.cursors + g * kLogCursorWords;
+		const LogRow* ring = log_.rings + g * static_cast<size_t>(cap);
+		const int64_t w0 = __atomic_load_n(cur, __ATOMIC_ACQUIRE);
+		int64_t from = std::max(log_.drained[g], w0 - cap);
+		begin[g] = log_stage_.size();
+		for (int64_t i = from; i < w0; ++i) log_stage_.push_back(ring[i % cap]);
+		__atomic_thread_fence(__ATOMIC_SEQ_CST);
+		const int64_t r1 = __atomic_load_n(cur + 2, __ATOMIC_ACQUIRE), w1 = __atomic_load_n(cur, __ATOMIC_ACQUIRE);
+		const int64_t valid = std::max(from, std::max(r1, w1) - cap);
+		if (valid > from) { const size_t drop = static_cast<size_t>(std::min(valid, w0) - from); log_stage_.erase(log_stage_.begin() + begin[g], log_stage_.begin() + begin[g] + drop); from = std::min(valid, w0); }
+		lost_now += from - log_.drained[g]; log_.lost[g] += from - log_.drained[g];
+		log_.drained[g] = from;
+	}
+	begin[G] = log_stage_.size();
+	std::vector<size_t> at(begin.begin(), begin.begin() + G);
+	int32_t n = 0;
+	while (n < max_rows) {
+		int best = -1;
+		for (size_t g = 0; g < G; ++g) {
+			if (at[g] == begin[g + 1]) continue;
+			const LogRow& c = log_stage_[at[g]];
+			if (best < 0 || c.boundary < log_stage_[at[best]].boundary || (c.boundary == log_stage_[at[best]].boundary && c.env < log_stage_[at[best]].env)) best = static_cast<int>(g);
+		}
+		if (best < 0) break;
+		std::memcpy(static_cast<char*>(out) + static_cast<size_t>(n++) * sizeof(LogRow), &log_stage_[at[best]++], sizeof(LogRow));   // (the caller's buffer need not be 16-byte aligned)
+		log_.drained[best] += 1;
+	}
+	*n_out = n;
+	if (lost) *lost = lost_now;
+	return DTRL_OK;
+}
+int Engine::VariantRescaleFactors(const int32_t* env_ids, const int32_t* draws, int n, double* factors)
+{
+	const std::string w = "dtrl_variant_rescale_factors: ";
+	if (!rescale_on_) return Fail(DTRL_ERR_ARG, w + "the batch has no variant rescale (call dtrl_variant_rescale first)");
+	if (n < 0 || (n > 0 && (!env_ids || !draws || !factors))) return Fail(DTRL_ERR_ARG, w + "env_ids, draws and factors are required and n must not be negative");
+	const int L = cfg_.model.L;
+	for (int i = 0; i < n; ++i) if (env_ids[i] < 0 || env_ids[i] >= n_ || draws[i] < -1) return Fail(DTRL_ERR_ARG, w + "pair " + std::to_string(i) + ": env id " + std::to_string(env_ids[i]) + " out of range, or a draw below -1");
+	for (int i = 0; i < n; ++i) {
+		const uint64_t sk = rescale_stream_key(rescale_cfg_.seed, rescale_cfg_.env_id_base + env_ids[i]);
+		for (int q = 0; q < kRescaleQuantities; ++q) for (int j = 0; j < L; ++j)
+			factors[(static_cast<size_t>(i) * kRescaleQuantities + q) * L + j] = draws[i] >= 0 ? rescale_factor(rescale_cfg_, sk, draws[i], q, j) : 1.0;
 	}
 	return DTRL_OK;
 }

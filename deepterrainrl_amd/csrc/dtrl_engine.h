@@ -117,7 +117,7 @@ public:
 	virtual bool GatherF32On(void* stream, float* dst, const float* src, const int32_t* idx, size_t n) { (void)stream; return GatherF32(dst, src, idx, n); }
 	// ---- the per-env rules of the frame boundary (dtrl_terrain_dev.h), each over an EnvSpan and queued on the selected stream ----
 	// Every default is a host loop over the span's envs with per-env D2H / H2D of what the rule reads and writes, synchronised -- what the lane-loop check build
-	// runs, and DTRL_TERRAINS_FALLBACK=1 / DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 / DTRL_PERTURB_FALLBACK=1 / DTRL_EPISODE_FALLBACK=1 / DTRL_TRACE_FALLBACK=1 on HIP; the HIP backend overrides each with ONE
+	// runs, and DTRL_TERRAINS_FALLBACK=1 / DTRL_VARIANTS_FALLBACK=1 / DTRL_PUSH_FALLBACK=1 / DTRL_PERTURB_FALLBACK=1 / DTRL_EPISODE_FALLBACK=1 / DTRL_TRACE_FALLBACK=1 / DTRL_EPISODE_LOG_FALLBACK=1 on HIP; the HIP backend overrides each with ONE
 	// launch of its kernel. All per-env arrays are device memory under the local env id, and are written back only where the rule changed them.
 	// the span as a host vector (a list is read back: the copy waits for the selected stream)
 	bool SpanList(const EnvSpan& span, std::vector<int32_t>& list);
@@ -157,6 +157,14 @@ public:
 	// oldest first; rows beyond c are not touched. The destination is memory the device addresses: device memory, or with dst_host HostStaging() memory (which the
 	// default writes with plain stores). Queued on the selected stream and synchronised. Same default / override split, behind the same knob (dtrl_trace_gather).
 	virtual bool TraceGather(const TraceView& tv, const int32_t* list, int n, int max_rows, int row_stride, double* vals_out, int32_t* ints_out, int32_t* counts, bool dst_host);
+	// Episode log (include/dtrl.h dtrl_episode_log; log_count / log_row / log_start). status != nullptr: a frame boundary of the contiguous span [e0, e0 + n) of one
+	// env group (no list) -- every env that completed a frame counts it in v.recs[e], and every one whose status record has need_reset != 0 appends a row to the
+	// group's ring v.ring (page-locked host memory, `capacity` rows) in ascending env id behind v.cursor[0] rows written so far, at most the last `capacity` rows of
+	// the boundary being stored; then the cursor words move: cursor[2] (the reservation) = cursor[0] + the boundary's rows in FRONT of the first row, and behind the
+	// rows cursor[1] (the group's boundary counter) += 1, then cursor[0] += the boundary's rows. status == nullptr: the listed envs start an episode without a row. Reads state, status, the limit's records, the keys and the rescale's counters;
+	// writes v.recs, the ring and the cursor pair alone. The default waits for the selected stream first (the lane-loop check build,
+	// DTRL_EPISODE_LOG_FALLBACK=1 on HIP) and leaves the same bytes; the HIP backend overrides it with one launch of dtrl_episode_log (one workgroup) / dtrl_episode_log_start.
+	virtual bool EpisodeLog(const EnvState* st, const EnvStatus* status, const EnvSpan& span, const LogView& v);
 	// dtrl_add_perturb: rows[0 .. n) (device memory, at most one row per env: the row names its env, so there is no span) into the perturbation slots of
 	// st[rows[i].env] (perturb_write_slot). The default copies each env's whole EnvState down, edits the seven fields and copies it back.
 	virtual bool PerturbScatter(EnvState* st, const PerturbRow* rows, int n);
@@ -319,6 +327,11 @@ public:
 	int Trace(const int32_t* env_ids, int n, int frames);
 	int TraceInfo(int32_t* n_traced, int32_t* frames, int32_t* width, int32_t* env_ids_out, int64_t* rows_written_out);
 	int TraceRead(const int32_t* env_ids, int n, int max_rows, double* vals, int32_t* ints, int32_t* counts, bool device);
+	// episode log (include/dtrl.h)
+	int EpisodeLog(int capacity);
+	int EpisodeLogInfo(int32_t* capacity, int32_t* n_groups, int64_t* written, int64_t* lost);
+	int EpisodeLogDrain(void* out /* [max_rows] LogRow */, int max_rows, int32_t* n_out, int64_t* lost);
+	int VariantRescaleFactors(const int32_t* env_ids, const int32_t* draws, int n, double* factors);
 	int ApplyRandForce(const int32_t* env_ids, int n, uint64_t seed);
 	int GetPoliState(const int32_t* env_ids, int n, double* s);
 	int GetPolicyOutput(const int32_t* env_ids, int n, double* y);
@@ -368,15 +381,17 @@ private:
 	bool RescaleQueue(const EnvStatus* status, const EnvSpan& span) { return !rescale_on_ || be_->VariantRescale(status, span, variant_keys_.d_env_key, d_var_models_, static_cast<int>(var_models_.size()), rescale_.dev, d_rescale_base_, rescale_cfg_); }
 	bool PushQueue(const EnvStatus* status, const EnvSpan& span) { return !push_on_ || be_->PushSchedule(status, span, buf_.st, push_.dev, push_scale_.dev, push_cfg_); }
 	// THE ORDER OF THE RULES, at a frame boundary and at a listed episode start alike:
-	//   episode limit, trace | terrain work (with the ladder) | redraw, rescale, push | reset launch             a frame boundary of a group's span
-	//                          terrain work (with the ladder) | redraw, rescale | reset launch | push, episode   the listed envs start an episode
+	//   episode limit, trace, log | terrain work (with the ladder) | redraw, rescale, push | reset launch                  a frame boundary of a group's span
+	//                               terrain work (with the ladder) | redraw, rescale | reset launch | push, episode, log   the listed envs start an episode
 	// The limit comes first: for every other rule an env it ended is an env whose episode ended. The trace comes right behind it and in front of everything that moves
 	// a key or resets an env: a row holds the state its frame ended in, the need_reset every later rule sees and the keys the frame ran under; a listed episode start
-	// writes no row. Redraw and rescale come in front of the reset launch, which runs
+	// writes no row. The episode log comes behind the trace and, like it, in front of everything that moves a key or redraws a scale: a row shows the cause the limit
+	// recorded, the keys and the draw the episode ran under; its listed form (the running episode is abandoned without a row) comes behind the reset launch. Redraw and rescale come in front of the reset launch, which runs
 	// reset_env under the new model, the rescale behind the redraw (which acts on keys below V only). At a boundary the push comes in front of the reset launch (an
 	// env that fell draws a new wait and is not pushed; the launch clears nothing the rule wrote); the listed starts of push and limit come behind it.
 	bool TraceQueue(int group);   // (dtrl_engine.cpp) the group's traced envs write their rows; a group without one queues nothing
-	bool RulesBehindFrame(int group) { const Group& g = groups_[group]; return EpisodeQueue(buf_.status, EnvSpan{g.e0, g.n, nullptr}) && TraceQueue(group); }   // behind a group's frame launch, in front of everything that reads its status
+	bool LogQueue(const EnvStatus* status, const EnvSpan& span, int group);   // (dtrl_engine.cpp) the group's ended episodes append their rows (status == nullptr: the listed form; group: whose ring)
+	bool RulesBehindFrame(int group) { const Group& g = groups_[group]; const EnvSpan span{g.e0, g.n, nullptr}; return EpisodeQueue(buf_.status, span) && TraceQueue(group) && LogQueue(buf_.status, span, group); }   // behind a group's frame launch, in front of everything that reads its status
 	bool RulesBeforeResets(const EnvSpan& span) { return (!cfg_.device_terrain || RedrawQueue(span)) && RescaleQueue(buf_.status, span) && PushQueue(buf_.status, span); }   // (host terrain: the host status loop has run the redraw)
 	// "These envs start an episode now" (dtrl_reset: draw_models; a terrain restart: not), synchronised: the list staged once, with -terrain_gen= device the listed envs'
 	// terrain work under terrain_mode (Boundary: 1 = initialise, 2 = re-seed + initialise), then the second line above
@@ -581,6 +596,14 @@ private:
 	} trace_;
 	char* trace_stage_ = nullptr; size_t trace_stage_bytes_ = 0;   // page-locked staging of the two reads (list, counts and -- dtrl_trace_read -- the rows), grown on demand
 	void TraceFree();
+	// episode log: one ring of `capacity` rows per env group with its four cursor words {written, boundary, reserved, 0}, all in page-locked host memory the device writes (a drain
+	// queues nothing), and the per-env records in device memory (the only copy). Batch state: snapshots, restores, clones, blobs and resets leave it alone. The rule
+	// runs in Backend::EpisodeLog on the group's stream behind the limit and the trace (RulesBehindFrame), in both terrain modes; dtrl_episode_log sets, replaces and
+	// removes all of it with the streams idle, so stream order is the whole timing rule. drained / lost: per group, rows handed to the caller or found overwritten.
+	struct LogState { int32_t capacity = 0; LogRow* rings = nullptr; int64_t* cursors = nullptr; std::vector<int64_t> drained, lost; } log_;
+	RuleRecs<LogRec> log_recs_;              // device [n] (allocated by the first dtrl_episode_log)
+	std::vector<LogRow> log_stage_;          // the rows a drain has copied out of the rings, before the merge
+	void LogFree();
 	int32_t* d_relayout_ = nullptr;   // device weight index -> index into the caller's Caffe-order blob (-1 = padding), built at Create
 	std::string err_;
 };

@@ -430,6 +430,66 @@ DTRL_TG_HD inline int32_t trace_slot(int64_t written, int32_t frames) { return s
 DTRL_TG_HD inline int32_t trace_count(int64_t written, int32_t frames, int32_t max_rows) { const int64_t c = written < frames ? written : frames; return static_cast<int32_t>(c < max_rows ? c : max_rows); }
 DTRL_TG_HD inline int32_t trace_read_slot(int64_t written, int32_t count, int32_t r, int32_t frames) { return static_cast<int32_t>((written - count + r) % frames); }
 
+// ---- episode log (include/dtrl.h dtrl_episode_log): one compact row per ended episode, written at the frame boundary in front of every rule that moves a key ----
+// per-env record (device memory, the only copy): boundaries the running episode has seen, the episodes of this env logged since the log was set, and
+// EnvState::num_cycles at the episode's start. 32 bytes on a 16-byte boundary: word 0 {frames, episodes}, word 1 {cycles0}; a boundary that ends nothing stores
+// the frame count alone
+struct alignas(16) LogRec { int32_t frames, pad_; int64_t episodes; int64_t cycles0, pad2_; };
+static_assert(sizeof(LogRec) == 32, "LogRec is two 16-byte words");
+// a row: 64 bytes as four 16-byte words (the layout of dtrl_episode_row, include/dtrl.h; dtrl_c_api.cpp holds the two to each other)
+struct alignas(16) LogRow {
+	int32_t env, cause, frames, cycles;                 // local env id; 1 fall, 2 frame limit, 3 distance; boundaries the episode saw; num_cycles - cycles0
+	int64_t boundary, episode;                          // the group's boundary counter at which the episode ended (0-based since the log was set); the env's ordinal
+	double dist; int32_t need_reset, zero_;             // status.root_x - spawn_x; the status record's need_reset as every later rule sees it
+	int32_t slot, variant, terrain, rescale_draw;       // the keys as the device holds them (0 without a table; a private rescale key reads V + e); the draw n of the episode's factors, or -1
+};
+static_assert(sizeof(LogRow) == 64, "LogRow is four 16-byte words");
+// one env group's ring and cursor words {written, boundary, reserved, 0} (page-locked host memory the device writes; reserved = written + the rows of the
+// boundary being written, stored in FRONT of its first row: written <= reserved, and a slot of index i is being overwritten only once reserved > i + capacity), and what the rule reads beside state and status: the
+// limit's records and flags (nullptr: no limit in force, every cause is a fall), the three key arrays (nullptr: the family has no table, the key reads 0), the
+// rescale's counters with the first private key V (nullptr: no rescale, the draw reads -1). A kernel ARGUMENT: DevBuffers and RunParams keep their layout
+struct LogView {
+	LogRec* recs; LogRow* ring; int64_t* cursor;
+	const EpisodeRec* episode; const uint8_t* episode_on;
+	const int32_t* env_slot; const int32_t* env_variant; const int32_t* env_terrain;
+	const RescaleRec* rescale;
+	double spawn_x;
+	int32_t capacity, private_base, external, pad_;   // private_base: V, the key of env 0's private rescale record (with `rescale`); external: -policy_mode= external
+};
+// what a row takes from the arrays above, loaded by whoever runs the rule (the kernel from device memory, the host default by copies): EpisodeRec::last_cause of an
+// env under a limit (else 0), the three keys, RescaleRec::episodes (0 without a rescale)
+struct LogEnv { int32_t limit_cause, slot, variant, terrain, rescale_episodes; };
+// The rule, the one body of host and device. log_count: env at a frame boundary -- `due`: it completed a frame in the launch in front of the rule (trace_due; read
+// in external policy mode only) -- counts the boundary; true: its episode ended and the caller appends log_row. Doubles and integers only.
+DTRL_TG_HD inline bool log_count(LogRec& r, const EnvStatus& es, bool due)
+{
+	if (!due) return false;
+	r.frames += 1;
+	return es.need_reset != 0;
+}
+// the row of the episode that ended at `boundary`, from the env's status record, its cycle counter and `k` as they stand IN FRONT OF every rule that moves a key
+// or redraws a scale; the record then starts the next episode. The cause of an env under a limit is the one the limit rule recorded just in front of this rule on
+// the same stream; without a limit every episode ends by a fall
+DTRL_TG_HD inline LogRow log_row(LogRec& r, const EnvStatus& es, int64_t num_cycles, int64_t boundary, const LogEnv& k, const LogView& v, int env)
+{
+	LogRow o;
+	o.env = env;
+	o.cause = k.limit_cause != 0 ? k.limit_cause : static_cast<int32_t>(kEpisodeFall);
+	o.frames = r.frames; o.cycles = static_cast<int32_t>(num_cycles - r.cycles0);
+	o.boundary = boundary; o.episode = r.episodes;
+	o.dist = es.root_x - v.spawn_x; o.need_reset = es.need_reset; o.zero_ = 0;
+	o.slot = k.slot; o.variant = k.variant; o.terrain = k.terrain;
+	o.rescale_draw = (v.rescale && k.variant == v.private_base + env) ? k.rescale_episodes - 1 : -1;
+	r.frames = 0; r.episodes += 1; r.cycles0 = num_cycles;
+	return o;
+}
+// a listed episode start (dtrl_reset, a terrain restart; the log is set): the running episode is abandoned without a row
+DTRL_TG_HD inline void log_start(LogRec& r, int64_t num_cycles) { r.frames = 0; r.cycles0 = num_cycles; }
+// of `total` rows appended in one boundary behind `written` earlier ones, the k-th is stored only if it is among the last `capacity` (no two rows of one launch
+// share a slot), at slot (written + k) % capacity
+DTRL_TG_HD inline bool log_row_kept(int64_t total, int64_t k, int32_t capacity) { return k >= total - capacity; }
+DTRL_TG_HD inline int32_t log_slot(int64_t written, int64_t k, int32_t capacity) { return static_cast<int32_t>((written + k) % capacity); }
+
 // one row of dtrl_add_perturb as the engine uploads it (Backend::PerturbScatter): the rotated offset is the host's, bit for bit
 struct PerturbRow { int32_t env, link; real f[2], lp[2], dur; };
 DTRL_TG_HD inline void perturb_write_slot(EnvState& st, const PerturbRow& r)

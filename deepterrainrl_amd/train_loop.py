@@ -172,7 +172,7 @@ def setup_episode_limit(b, spec, greedy_envs=0):
 
 def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, device_id=-1, extra_args=None, seed=0, log_every=0, out_scale_file=None,
           trainer_device=None, overlap=False, frames_per_drain=1, scenario_cls=BatchScenario, trainer="torch", trainer_lib=None, poll=False,
-          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None, pushes=None, solver=None, rescale=None, episode_limit=None):
+          eval_every=None, eval_fn=None, out_model_file=None, greedy_envs=0, variants=None, pushes=None, solver=None, rescale=None, episode_limit=None, episode_log=None):
     """extra_args override / extend the arg file (both for the engine and for the -trainer_* keys read here).
     overlap=True trains on frame f's tuples while the GPU already rolls out frame f+1 (dtrl_step_begin / dtrl_step_end): the policy
     each frame runs with is one frame staler, as with the reference's concurrent env threads; overlap=False is the strictly
@@ -200,6 +200,10 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     (setup_episode_limit: on the device, no host work per frame), so that the per-episode draws of variants, rescale and pushes and the terrain ladder's mark keep
     moving under a policy that no longer falls; the greedy evaluation envs are held out as setup_pushes holds them out. stats["episode_limit"] then holds the
     held-out ids and EpisodeInfo() at the end. Combines with all of the above. None (default) runs exactly as before.
+    episode_log=capacity records every ended episode on the device (BatchScenario.EpisodeLog: a ring of `capacity` rows per env group) and drains the ring at every
+    log() call and at the end -- in the overlapped schedule beside the running frame, the drain queues no GPU work. With log_every, each entry of stats["log"]
+    gets a sixth element {"episodes", "mean_frames", "mean_dist", "fall_share"} over the episodes drained since the previous entry; stats["episode_log"] holds the
+    totals {"episodes", "frames", "dist", "falls", "lost"}. Combines with all of the above. None (default) runs exactly as before.
     solver=dict(type="adam", base_lr=1e-4, clip_gradients=10, ...): overrides laid over the parsed solver prototxt (trainer.parse_solver's keys), for both trainers
     (CACLA: over both nets' files). None (default) runs exactly as before."""
     if variants is not None and greedy_envs:
@@ -270,6 +274,16 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
     rescale_info = setup_rescale(b, rescale) if rescale is not None else None
     push_info = setup_pushes(b, pushes, greedy_envs) if pushes is not None else None
     limit_info = setup_episode_limit(b, episode_limit, greedy_envs) if episode_limit is not None else None
+    if episode_log is not None:
+        b.EpisodeLog(int(episode_log))                      # (behind every rule's set-up: their resets start no logged episode)
+    ep_total = {"episodes": 0, "frames": 0, "dist": 0.0, "falls": 0, "lost": 0}
+    ep_since = dict(ep_total)                               # ... since the last entry of stats["log"]
+
+    def drain_episodes():
+        d = b.EpisodeLogDrain()
+        for acc in (ep_total, ep_since):
+            acc["episodes"] += len(d["env"]); acc["frames"] += int(d["frames"].sum()); acc["dist"] += float(d["dist"].sum())
+            acc["falls"] += int((d["cause"] == 1).sum()); acc["lost"] += int(d["lost"])
     frames = tuples = 0
     next_eval = [0 if eval_fn else None]
     if eval_fn:
@@ -294,8 +308,15 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
         if next_eval[0] is not None and t.GetIter() >= next_eval[0]:
             eval_fn(t.GetIter(), t, b)
             next_eval[0] = (t.GetIter() // eval_every + 1) * eval_every if eval_every else None
+        if episode_log is not None:
+            drain_episodes()
         if log_every and frames % log_every == 0:
-            stats["log"].append((frames, t.GetIter(), t.GetNumTuples(), t.last_loss, b.EvalStats()))
+            entry = (frames, t.GetIter(), t.GetNumTuples(), t.last_loss, b.EvalStats())
+            if episode_log is not None:
+                k = max(ep_since["episodes"], 1)
+                entry += ({"episodes": ep_since["episodes"], "mean_frames": ep_since["frames"] / k, "mean_dist": ep_since["dist"] / k, "fall_share": ep_since["falls"] / k},)
+                ep_since.update(episodes=0, frames=0, dist=0.0, falls=0, lost=0)
+            stats["log"].append(entry)
             print("frame %d iter %d tuples %d critic-loss %s actor-iters %d" % (frames, t.GetIter(), t.GetNumTuples(), t.last_loss, t.actor_iter), flush=True)
             if greedy_envs:
                 print("frame %d greedy envs: %.3f falls / 1000 env-steps" % (frames, greedy_falls()), flush=True)
@@ -363,6 +384,9 @@ def train(arg_file, data_root, num_envs=4096, max_iters=None, max_frames=None, d
         stats["pushes"] = dict(push_info, **b.PushInfo())
     if limit_info is not None:
         stats["episode_limit"] = dict(limit_info, **b.EpisodeInfo())
+    if episode_log is not None:
+        drain_episodes()
+        stats["episode_log"] = dict(ep_total)
     return stats
 
 

@@ -618,6 +618,46 @@ dtrl_status dtrl_trace_read(dtrl_batch* b, const int32_t* env_ids, int n, int ma
  * discriminator: vals_dev / ints_dev are DEVICE pointers of the same shapes, counts is host memory. One launch unrolls the rings; nothing crosses to the host but
  * the counts. */
 dtrl_status dtrl_trace_read_device(dtrl_batch* b, const int32_t* env_ids, int n, int max_rows, double* vals_dev, int32_t* ints_dev, int32_t* counts);
+/* ---- episode log: one row per ended episode, recorded on the device ----
+ * The nearest thing the reference has is cScenarioPoliEval's distance log (`scenarios/ScenarioPoliEval.cpp:202-217` RecordDistTraveled into mDistLog, read by
+ * GetDistLog `:147-150`): one distance per episode and nothing else. Here every per-episode rule of the frame boundary (variant redraw, rescale, push schedule,
+ * terrain ladder, episode limit) acts on the device with no host wait, and dtrl_episode_info / dtrl_get_variants / dtrl_variant_rescale_info refuse a frame in
+ * flight, wait for every stream, hold the last episode alone and are read after the boundary has redrawn keys and scales. The episode log is a ring of 64-byte rows
+ * per ENV GROUP (one stream each: no atomics, no order between streams) in page-locked host memory the device writes. At every FRAME BOUNDARY of a group (the
+ * boundaries the episode limit and the trace count; dtrl_step_updates counts), behind the group's frame launch, the episode limit and the trace and in front of
+ * the terrain work, the ladder, redraw, rescale, push and the reset launch, every env of the group that completed a frame (-policy_mode= external: ext_steps_left
+ * == 0 behind the tick; a parked env counts nothing) counts the boundary, and one whose status record has need_reset != 0 appends a row, in ascending env id, at
+ * slot (written + k) % capacity; then its ordinal rises and its frame and cycle counts start over. Of more than `capacity` rows in one boundary the last
+ * `capacity` are stored; the group's cursor counts every row. The listed episode starts (dtrl_reset, a terrain restart) abandon the running episode without a row.
+ * One launch of one workgroup per env group and frame; a batch without a log queues what it always queued. Rings, cursors and the per-env records are batch
+ * state: snapshots, restores, clones, blobs and resets leave them alone. Also available with -policy_mode= external, where no episode limit exists. */
+typedef struct dtrl_episode_row {
+	int32_t env, cause, frames, cycles;       /* local env id; 1 fall, 2 frame limit, 3 distance; frame boundaries the episode saw; num_cycles at its end minus at its start */
+	int64_t boundary, episode;                /* the group's boundary counter at which the episode ended (0-based since the log was set); the env's ordinal 0, 1, 2 ... */
+	double dist; int32_t need_reset, zero;    /* root_x - spawn_x at the end (dtrl_episode_info's last_dist); the status record's need_reset as every later rule sees it; 0 */
+	int32_t slot, variant, terrain, rescale_draw;   /* the env's keys as the device holds them while the episode ran (0 without a table; a private rescale key reads V + e); the
+	                                                   draw number n of the episode's rescale factors (dtrl_variant_rescale_factors), -1 for an env not under its private key */
+} dtrl_episode_row;
+/* Replaces: cScenarioPoliEval::RecordDistTraveled's mDistLog (`scenarios/ScenarioPoliEval.cpp:202-217`) as the only per-episode record. Sets or replaces the log:
+ * `capacity` >= 1 rows per env group; cursors, boundary counters and per-env records start from 0, and every env's first logged episode starts at this call (its
+ * cycles count from the env's cycle counter as it stands). capacity == 0 removes the log. Refused between dtrl_step_begin and dtrl_step_end (it never waits for a
+ * frame), then waits for every stream. DTRL_ERR_ARG, nothing changed: capacity < 0. DTRL_ERR_CAPACITY: a ring cannot be allocated; the batch is left without a log. */
+dtrl_status dtrl_episode_log(dtrl_batch* b, int32_t capacity);
+/* Replaces: nothing the reference has (see dtrl_episode_log; `scenarios/ScenarioPoliEval.cpp:147-150`). Totals over the env groups: rows per ring (0: no log), the
+ * number of rings, rows ever appended, and rows overwritten before a drain took them. Any output may be NULL. Refused while a frame is in flight, otherwise
+ * waits for queued work. */
+dtrl_status dtrl_episode_log_info(dtrl_batch* b, int32_t* capacity, int32_t* n_groups, int64_t* written, int64_t* lost);
+/* Replaces: cScenarioPoliEval::GetDistLog (`scenarios/ScenarioPoliEval.cpp:147-150`). The rows not drained yet, merged over the groups in (boundary, env) order,
+ * at most max_rows of them into out; the rest stay for the next call. *n: rows returned; *lost (may be NULL): rows this call found overwritten before it could
+ * take them. NEVER queues GPU work. With no frame in flight it first waits for queued work, as the info calls do (with -terrain_gen= device dtrl_step returns with
+ * the boundary still queued); between dtrl_step_begin and dtrl_step_end it does not wait and returns what has been published so far. Per group the host reads
+ * the cursor, copies the rows behind its own mark, then reads the cursor and the writer's reservation again and drops every copied row whose slot a later boundary
+ * has taken or is taking. DTRL_ERR_ARG: no log, max_rows < 0. */
+dtrl_status dtrl_episode_log_drain(dtrl_batch* b, dtrl_episode_row* out, int32_t max_rows, int32_t* n, int64_t* lost);
+/* Replaces: nothing the reference has (`scenarios/ScenarioPoliEval.cpp:202-217` logs a distance, no model). The rescale's rule on the host for arbitrary (env,
+ * draw) pairs: factors [n][4][L] in dtrl_variant_rescale_info's layout, the factors env env_ids[i] drew for its draw number draws[i] (a row's rescale_draw); draw
+ * -1 gives all 1. What dtrl_variant_rescale_info does for the current episode alone. Needs no wait. DTRL_ERR_ARG: no rescale, an id out of range, a draw < -1. */
+dtrl_status dtrl_variant_rescale_factors(dtrl_batch* b, const int32_t* env_ids, const int32_t* draws, int32_t n, double* factors);
 /* Replaces: cNNController::RecordPoliState (sim/TerrainRLCharController.cpp:120-123). */
 dtrl_status dtrl_get_poli_state(dtrl_batch* b, const int32_t* env_ids, int n, double* s);
 /* Replaces: cNeuralNet::GetLayerState("output", y) (learning/NeuralNet.cpp:814-834) after the controller's last cNeuralNet::Eval

@@ -36,6 +36,7 @@ ap.add_argument("--rescale-per-link", nargs="*", default=[], choices=["mass", "k
 ap.add_argument("--rescale-seed", type=int, default=0, help="with --rescale: seed of the draws")
 ap.add_argument("--episode-limit", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="episode limits while training (train_loop.train(episode_limit=...)): every episode ends after LO .. HI frames at the latest, drawn per episode on the device, so that per-episode draws keep moving under a policy that no longer falls (not with --distributed)")
 ap.add_argument("--episode-limit-seed", type=int, default=0, help="with --episode-limit: seed of the draws")
+ap.add_argument("--episode-log", type=int, default=None, metavar="N", help="record every ended episode on the device (train_loop.train(episode_log=N): a ring of N rows per env group, drained with every log line): episodes, mean frames, mean distance and fall share per log interval (not with --distributed)")
 ap.add_argument("--pushes", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="random pushes while training (train_loop.train(pushes=...)): every env is pushed on the device every LO .. HI frames (not with --distributed)")
 ap.add_argument("--push-force", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --pushes: range of the force magnitude in N (default: the arg file's -min_perturb= / -max_perturb=)")
 ap.add_argument("--push-duration", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --pushes: range of the duration in s (default: the arg file's)")
@@ -65,6 +66,8 @@ if a.rescale and a.distributed:
 if a.episode_limit and a.distributed:
     ap.error("--episode-limit is not available with --distributed")
 episode_limit = dict(frames=tuple(a.episode_limit), seed=a.episode_limit_seed) if a.episode_limit else None
+if a.episode_log is not None and a.distributed:
+    ap.error("--episode-log is not available with --distributed")
 rescale = None
 if a.rescale:
     rescale = dict(seed=a.rescale_seed, per_link=tuple(a.rescale_per_link))
@@ -98,7 +101,9 @@ if a.distributed:
     sys.exit(0)
 st = train_loop.train(a.arg_file, a.data_root, a.envs, max_iters=a.iters, max_frames=a.frames, log_every=50, overlap=a.overlap, frames_per_drain=a.frames_per_drain,
                       extra_args=dict(({"reserve_cus": reserve} if reserve else {}), **({"trainer_num_init_samples": a.init_samples} if a.init_samples is not None else {})) or None,
-                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll, variants=variants, pushes=pushes, solver=solver, rescale=rescale, episode_limit=episode_limit)
+                      out_scale_file=(a.out + "_scale.txt") if a.out else None, trainer=a.trainer, poll=a.poll, variants=variants, pushes=pushes, solver=solver, rescale=rescale, episode_limit=episode_limit, episode_log=a.episode_log)
+if a.episode_log is not None:
+    print("[episode log] %(episodes)d episodes, %(frames)d frames, %(falls)d ended by a fall, %(lost)d rows lost" % st["episode_log"])
 if episode_limit:
     print("[episode limit] %d .. %d frames; %d episodes ended by the limit, %d by a fall" % (a.episode_limit[0], a.episode_limit[1], int(st["episode_limit"]["by_limit"].sum()), int(st["episode_limit"]["by_fall"].sum())))
 if a.out:
