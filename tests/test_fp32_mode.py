@@ -68,27 +68,70 @@ def test_fp32_distribution_level_parity_check_builds(da, om, arg, which):
 
 
 # ---- GPU ----
+CHECK_BUILD_CASES = [("args/dog_slopes_mixed_args.txt", "dog"), ("args/raptor_narrow_gaps_args.txt", "raptor"), ("args/goat_cliffs_args.txt", "goat")]
+
+
 @pytest.mark.gpu
-def test_gpu_fp32_library_vs_its_check_build(da, om):
-    """libdtrl_f32.so (HIP, gfx950) against the lane-loop build of the same fp32 source: 64 dogs on slopes_mixed with the policy forward in float (fp32 matrix pipe:
-    v_mfma_f32_16x16x4_f32, result rows 4 g + r instead of 4 r + g), 4 outer frames = 400 substeps; agreement at float rounding amplified by the contact rows."""
-    pol = dog_policy(om)
-    kw = dict(data_root=REFDATA, extra_args={"terrain_seed": 77, "physics_precision": "f32"})
-    b = da.BatchScenario("args/dog_slopes_mixed_args.txt", 64, **kw); c = emul_f32_scenario("args/dog_slopes_mixed_args.txt", 64, **kw)
-    assert "fp32" in b._lib.dtrl_version().decode()
-    maps = open("/proc/self/maps").read(); assert "libdtrl_f32.so" in maps
-    for s in (b, c):
-        s.SetPolicy(pol[1], *pol[2:])
-    worst = 0.0
-    for f in range(4):
-        b.Update(); c.Update()
-        qb, qdb = b.PoseVel(); qc, qdc = c.PoseVel()
-        worst = max(worst, np.abs(qb - qc).max())
-        assert np.array_equal(b.Contacts(), c.Contacts()) or f > 1
-    print("HIP fp32 vs lane-loop fp32, 64 envs x 400 substeps: max |dq| %.2e, median %.2e" % (worst, np.median(np.abs(qb - qc).max(1))))
-    assert np.median(np.abs(qb - qc).max(1)) < 1e-3 and np.isfinite(qb).all()
-    ps_b, ps_c = b.RecordPoliState(), c.RecordPoliState()
-    assert np.median(np.abs(ps_b - ps_c).max(1)) < 1e-2
+def test_gpu_fp32_library_vs_its_check_build(da, om, monkeypatch):
+    """libdtrl_f32.so (HIP, gfx950) against the lane-loop build of the same fp32 source: 64 envs of each skeleton instance (dog on slopes_mixed, raptor on narrow_gaps
+    with its own net and tile count, goat on cliffs_rugged) with the policy forward in float (fp32 matrix pipe: v_mfma_f32_16x16x4_f32, result rows 4 g + r instead of
+    4 r + g), 4 outer frames = 400 substeps, under the fast kernel AND under the reference kernel (DTRL_KERNEL=ref): both go through the same mfma_16x16x4() / mfma_row()
+    on the device, so a fault they share is invisible to the fast = reference tests and shows here alone. Agreement at float rounding amplified by the contact rows:
+    median over envs of max |dq| < 1e-3, policy states' median < 1e-2, everything finite, contact flags equal after frames 0 and 1; and the integer side, on which
+    hipcc and g++ agree: after the first frame the contact cache holds the same number of rows with the same row ids in every env (the check build against itself from
+    a start moved by 2e-7 and by 1e-6 keeps counts, ids and flags of all 64 envs of every skeleton through two frames while |dq| grows to 1e-5 .. 1e-3: one frame is
+    not too long for that). Observed max / median |dq| after 400 substeps (the dog's fast kernel before the other five were added: median 3.6e-5):
+      dog     fast 1.73e-4 / 3.58e-5, reference 1.73e-4 / 3.58e-5 (policy states' median 1.7e-6)
+      raptor  fast 2.09e-2 / 3.62e-4, reference 2.09e-2 / 3.62e-4 (3.7e-4)
+      goat    fast 7.35e-5 / 1.25e-5, reference 7.35e-5 / 1.25e-5 (1.4e-6)"""
+    figures, bad = [], []
+    for arg, skel in CHECK_BUILD_CASES:
+        pol = T.raptor_policy(om) if skel == "raptor" else dog_policy(om)
+        kw = dict(data_root=REFDATA, extra_args={"terrain_seed": 77, "physics_precision": "f32"})
+        c = emul_f32_scenario(arg, 64, **kw)
+        c.SetPolicy(pol[1], *pol[2:])
+        check = []
+        for f in range(4):
+            c.Update()
+            check.append((c.PoseVel()[0], c.Contacts(), c.ContactCache()[:2]))
+        ps_c = c.RecordPoliState()
+        for kernel in (None, "ref"):
+            if kernel:
+                monkeypatch.setenv("DTRL_KERNEL", kernel)
+            else:
+                monkeypatch.delenv("DTRL_KERNEL", raising=False)
+            what = "%s, %s kernel" % (skel, kernel or "fast")
+            b = da.BatchScenario(arg, 64, **kw)
+            assert "fp32" in b._lib.dtrl_version().decode()
+            maps = open("/proc/self/maps").read(); assert "libdtrl_f32.so" in maps
+            b.SetPolicy(pol[1], *pol[2:])
+            worst = 0.0
+            for f in range(4):
+                b.Update()
+                qb, qdb = b.PoseVel(); qc, flags_c, (cnt_c, rid_c) = check[f]
+                worst = max(worst, np.abs(qb - qc).max())
+                if f <= 1 and not np.array_equal(b.Contacts(), flags_c):
+                    bad.append("%s: contact flags differ after frame %d" % (what, f))
+                if f == 0:
+                    cnt_b, rid_b = b.ContactCache()[:2]
+                    live = np.arange(rid_c.shape[1])[None, :] < cnt_c[:, None]
+                    if not np.array_equal(cnt_b, cnt_c):
+                        bad.append("%s: contact cache counts differ after the first frame in envs %s" % (what, np.nonzero(cnt_b != cnt_c)[0].tolist()))
+                    elif not np.array_equal(rid_b[live], rid_c[live]):
+                        bad.append("%s: contact cache row ids differ after the first frame in envs %s" % (what, np.nonzero(((rid_b != rid_c) & live).any(axis=1))[0].tolist()))
+            med = np.median(np.abs(qb - qc).max(1))
+            ps_med = np.median(np.abs(b.RecordPoliState() - ps_c).max(1))
+            figures.append("%s: max |dq| %.2e, median %.2e, policy-state median %.2e" % (what, worst, med, ps_med))
+            if not (med < 1e-3):
+                bad.append("%s: median |dq| %.3e" % (what, med))
+            if not (np.isfinite(qb).all() and np.isfinite(qdb).all()):
+                bad.append("%s: not finite" % what)
+            if not (ps_med < 1e-2):
+                bad.append("%s: policy-state median %.3e" % (what, ps_med))
+            b.close()
+        c.close()
+    print("HIP fp32 vs lane-loop fp32, 64 envs x 400 substeps:\n  " + "\n  ".join(figures))
+    assert not bad, bad
 
 
 @pytest.mark.gpu

@@ -10,12 +10,19 @@ with the lane-loop CPU build, which satisfies them through the same calls -- rol
   (b) every third env (env % 3 == 0) is turned on its back and dropped, as in test_fsub_rows.py: the row-count histogram is non-empty at 0, 1-6, 7-12 and
       13+ (link cap and row cap paths, which consume the sample points).
   (c) by construction: the dog / goat (126 points) and the raptor (114) leave lanes 62 / 50 ... 63 without a second point (they evaluate a clamped index and
-      are deselected), and every skeleton has links that do not collide with the ground (col = 0: evaluated like the others, deselected)."""
+      are deselected), and every skeleton has links that do not collide with the ground (col = 0: evaluated like the others, deselected).
+
+Both libraries: the fp32 cases (-physics_precision= f32: libdtrl_f32.so) run the same rollout and compare the same fields. Env-frames with links in both segments and
+row counts 0 / 1-6 / 7-12 / 13+ in fp32, lane-loop check build | reference kernel on the device:
+  dog 187, 1699 / 3169 / 673 / 219 | 188, 1696 / 3198 / 647 / 219, raptor 490, 1152 / 2383 / 2173 / 52 | 485, 1169 / 2368 / 2170 / 53,
+  goat 71, 772 / 2792 / 1586 / 610 | 71, 775 / 2782 / 1599 / 604."""
 import numpy as np
 import pytest
 
 import test_host_and_emul as T
 from conftest import REFDATA, dog_policy
+from precision import both_precisions, check_build, extra_for
+from test_gpu_fsub_rhs import product
 
 CASES = [("args/dog_slopes_mixed_args.txt", "dog"), ("args/raptor_narrow_gaps_args.txt", "raptor"), ("args/goat_cliffs_args.txt", "goat")]
 N_ENVS, FRAMES, TERRAIN_SEED = 192, 30, 77
@@ -68,8 +75,8 @@ def policy_of(om, skel):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("arg,skel", CASES)
-def test_contact_points_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel):
+@pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
+def test_contact_points_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel, prec):
     pol = policy_of(om, skel)
 
     def run(kernel):
@@ -77,7 +84,7 @@ def test_contact_points_fast_equals_reference_bitwise(da, om, monkeypatch, arg, 
             monkeypatch.setenv("DTRL_KERNEL", kernel)
         else:
             monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        return rollout(lambda: da.BatchScenario(arg, N_ENVS, data_root=REFDATA, extra_args={"terrain_seed": TERRAIN_SEED}), pol)   # product path: libdtrl.so
+        return rollout(product(da, arg, N_ENVS, prec, terrain_seed=TERRAIN_SEED), pol)
 
     ff, cf, bf = run(None)
     fr, cr, br = run("ref")
@@ -87,3 +94,11 @@ def test_contact_points_fast_equals_reference_bitwise(da, om, monkeypatch, arg, 
         for name, x, y in zip(names, a, b_):
             assert np.array_equal(x, y), "frame %d: %s differ" % (f, name)
     assert bf == br and np.array_equal(cf, cr)
+
+
+@pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
+def test_contact_points_rollout_reaches_every_case_on_the_lane_loop_build(om, arg, skel, prec):
+    """The CPU twin: the same rollout through the lane-loop build of dtrl_kernel.h (of either precision) reaches (a) and (b)."""
+    pol = policy_of(om, skel)
+    _, counts, both = rollout(lambda: check_build(prec)(arg, N_ENVS, data_root=REFDATA, extra_args=extra_for(prec, terrain_seed=TERRAIN_SEED)), pol)
+    check_reached(counts, both)

@@ -13,12 +13,19 @@ below were chosen with the lane-loop CPU build, which goes through the same roll
   (c) a root angle several turns out (env % 6 == 2: + TURNS x 2 pi -- the argument reduction of sincos): |q[2]| > 4 pi in a compared frame, the env not reset since
   (d) an env spinning at >= 20 rad/s at the end of a compared frame (env % 6 == 4: lifted by a metre, the whole body turning at SPIN rad/s: the centripetal terms)
   (e) the hinge velocity of every link at the end of a longest path (the last iteration of the path loops) non-zero in a compared frame
-  (f) a reset in a frame that is not the last one (the cold generic evaluation of the reset, then fast ones on top of it)."""
+  (f) a reset in a frame that is not the last one (the cold generic evaluation of the reset, then fast ones on top of it).
+
+Both libraries: the fp32 cases (-physics_precision= f32: libdtrl_f32.so; the raptor instance at three waves per SIMD with scratch reloads in its substep loop) run the
+same rollout and compare the same fields. Env-frames that reached airborne / rows / turned_on_rows / turns_out / spinning / reset_before_last in fp32 (deepest_moving
+holds in all), lane-loop check build | reference kernel on the device:
+  dog 1694 / 4066 / 175 / 958 / 170 / 98 | 1701 / 4059 / 175 / 960 / 176 / 96, raptor 1312 / 4448 / 128 / 789 / 33 / 207 | 1317 / 4443 / 128 / 754 / 33 / 212,
+  goat 768 / 4992 / 255 / 903 / 3 / 142 | 791 / 4969 / 255 / 893 / 4 / 146 (the thinnest bin: the goat's spinning env-frames, 3 | 4; fp64: 3 | 3)."""
 import numpy as np
 import pytest
 
-from conftest import REFDATA, EmulScenario
-from test_gpu_fsub_rhs import CASES, policy_of
+from conftest import REFDATA
+from precision import both_precisions, check_build, extra_for
+from test_gpu_fsub_rhs import CASES, policy_of, product
 
 N_ENVS, FRAMES, TERRAIN_SEED = 192, 30, 77
 TURNS, SPIN, LIFT = 7, 25.0, 1.0
@@ -93,8 +100,8 @@ def check_reached(reached):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("arg,skel", CASES)
-def test_fast_kinematics_equals_reference_bitwise(da, om, monkeypatch, arg, skel):
+@pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
+def test_fast_kinematics_equals_reference_bitwise(da, om, monkeypatch, arg, skel, prec):
     pol = policy_of(om, skel)
 
     def run(kernel):
@@ -102,7 +109,7 @@ def test_fast_kinematics_equals_reference_bitwise(da, om, monkeypatch, arg, skel
             monkeypatch.setenv("DTRL_KERNEL", kernel)
         else:
             monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        return rollout(lambda: da.BatchScenario(arg, N_ENVS, data_root=REFDATA, extra_args={"terrain_seed": TERRAIN_SEED}), pol, skel)   # product path: libdtrl.so
+        return rollout(product(da, arg, N_ENVS, prec, terrain_seed=TERRAIN_SEED), pol, skel)
 
     ff, rf = run(None)
     fr, rr = run("ref")
@@ -115,9 +122,9 @@ def test_fast_kinematics_equals_reference_bitwise(da, om, monkeypatch, arg, skel
     assert rf == rr
 
 
-@pytest.mark.parametrize("arg,skel", CASES)
-def test_fast_kinematics_rollout_reaches_every_case_on_the_lane_loop_build(om, arg, skel):
-    """The CPU twin: the same rollout through the lane-loop build of dtrl_kernel.h reaches (a) .. (f)."""
+@pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
+def test_fast_kinematics_rollout_reaches_every_case_on_the_lane_loop_build(om, arg, skel, prec):
+    """The CPU twin: the same rollout through the lane-loop build of dtrl_kernel.h (of either precision) reaches (a) .. (f)."""
     pol = policy_of(om, skel)
-    _, reached = rollout(lambda: EmulScenario(arg, N_ENVS, data_root=REFDATA, extra_args={"terrain_seed": TERRAIN_SEED}), pol, skel)
+    _, reached = rollout(lambda: check_build(prec)(arg, N_ENVS, data_root=REFDATA, extra_args=extra_for(prec, terrain_seed=TERRAIN_SEED)), pol, skel)
     check_reached(reached)

@@ -12,12 +12,18 @@ poses below were chosen with the lane-loop CPU build, which goes through the sam
       every sixth (env % 6 == 2) is stood on its nose with the root SINK metres lower, a dozen and more sample points in the ground
   (d) a perturbation active while the env has rows (the free right-hand side carries perturb_gen_force): every fourth env (env % 4 == 1) is pushed for longer than
       the run lasts; an env-frame counts when the env has not been reset since the push (a reset clears the slot) and its last substep had rows
-  (e) airborne substeps (R = 0: the register chain, untouched)."""
+  (e) airborne substeps (R = 0: the register chain, untouched).
+
+Both libraries: the fp32 cases (-physics_precision= f32: libdtrl_f32.so, whose bcast() moves one register where the fp64 one moves a lo/hi pair) run the same rollout
+and compare the same fields. Env-frames that reached (a) / (b) / (c) / (e) / (d) in fp32, lane-loop check build | reference kernel on the device:
+  dog 2703 / 2408 / 129 / 1348 / 748 | 2711 / 2413 / 132 / 1337 / 754, raptor 2632 / 2678 / 25 / 1379 / 747 | 2659 / 2676 / 25 / 1369 / 740,
+  goat 4075 / 2793 / 178 / 649 / 755 | 4076 / 2792 / 177 / 645 / 762."""
 import numpy as np
 import pytest
 
 import test_host_and_emul as T
-from conftest import REFDATA, EmulScenario, dog_policy
+from conftest import REFDATA, dog_policy
+from precision import assert_library, both_precisions, check_build, extra_for
 
 CASES = [("args/dog_slopes_mixed_args.txt", "dog"), ("args/raptor_narrow_gaps_args.txt", "raptor"), ("args/goat_cliffs_args.txt", "goat")]
 N_ENVS, FRAMES, TERRAIN_SEED = 192, 30, 77
@@ -83,9 +89,18 @@ def policy_of(om, skel):
     return T.raptor_policy(om) if skel == "raptor" else dog_policy(om)
 
 
+def product(da, arg, n, prec, **extra):
+    """make() of the product path: libdtrl.so, libdtrl_f32.so for prec = "f32" (asserted: a case cannot silently run the other library)"""
+    def make():
+        b = da.BatchScenario(arg, n, data_root=REFDATA, extra_args=extra_for(prec, **extra))
+        assert_library(b, prec)
+        return b
+    return make
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("arg,skel", CASES)
-def test_fsub_rhs_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel):
+@pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
+def test_fsub_rhs_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel, prec):
     pol = policy_of(om, skel)
 
     def run(kernel):
@@ -93,7 +108,7 @@ def test_fsub_rhs_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel):
             monkeypatch.setenv("DTRL_KERNEL", kernel)
         else:
             monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        return rollout(lambda: da.BatchScenario(arg, N_ENVS, data_root=REFDATA, extra_args={"terrain_seed": TERRAIN_SEED}), pol, skel)   # product path: libdtrl.so
+        return rollout(product(da, arg, N_ENVS, prec, terrain_seed=TERRAIN_SEED), pol, skel)
 
     ff, rf = run(None)
     fr, rr = run("ref")
@@ -105,9 +120,9 @@ def test_fsub_rhs_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel):
     assert rf == rr
 
 
-@pytest.mark.parametrize("arg,skel", CASES)
-def test_fsub_rhs_rollout_reaches_every_case_on_the_lane_loop_build(om, arg, skel):
-    """The CPU twin: the same rollout through the lane-loop build of dtrl_kernel.h reaches (a) .. (e)."""
+@pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
+def test_fsub_rhs_rollout_reaches_every_case_on_the_lane_loop_build(om, arg, skel, prec):
+    """The CPU twin: the same rollout through the lane-loop build of dtrl_kernel.h (of either precision) reaches (a) .. (e)."""
     pol = policy_of(om, skel)
-    _, reached = rollout(lambda: EmulScenario(arg, N_ENVS, data_root=REFDATA, extra_args={"terrain_seed": TERRAIN_SEED}), pol, skel)
+    _, reached = rollout(lambda: check_build(prec)(arg, N_ENVS, data_root=REFDATA, extra_args=extra_for(prec, terrain_seed=TERRAIN_SEED)), pol, skel)
     check_reached(reached)

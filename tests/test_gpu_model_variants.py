@@ -7,6 +7,7 @@ import pytest
 import test_external_policy as X
 import test_model_variants as T
 from conftest import REFDATA
+from precision import assert_library, both_precisions, extra_for
 
 pytestmark = pytest.mark.gpu
 
@@ -78,6 +79,7 @@ def variant_run(om, monkeypatch, tmp_path, arg, env, extra, n=192, frames=90):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     b = T.with_variants(om, arg, n, T.write_variants(tmp_path, arg), [e % 3 for e in range(n)], dict(terrain_seed=77, rand_seed=4, **extra))
+    assert_library(b, extra.get("physics_precision", "f64"))
     for _ in range(frames):
         b.Update()
     out = end_state(b)
@@ -85,13 +87,14 @@ def variant_run(om, monkeypatch, tmp_path, arg, env, extra, n=192, frames=90):
     return out
 
 
-@pytest.mark.parametrize("arg", [T.DOG, T.RAPTOR], ids=["dog", "raptor"])
-def test_variant_fast_kernel_equals_variant_reference_kernel_and_per_variant_fallback(da, om, monkeypatch, tmp_path, arg):
+@pytest.mark.parametrize("arg,prec", both_precisions([T.DOG, T.RAPTOR], ids=["dog", "raptor"]))
+def test_variant_fast_kernel_equals_variant_reference_kernel_and_per_variant_fallback(da, om, monkeypatch, tmp_path, arg, prec):
     """One launch of the register-resident variant kernel against one launch of the LDS-phase variant kernel (DTRL_KERNEL=ref) and against the per-variant launches
-    of the SHIPPED single-model kernels (DTRL_VARIANTS_FALLBACK=1)."""
-    base = variant_run(om, monkeypatch, tmp_path, arg, {}, {})
-    assert_same_end(base, variant_run(om, monkeypatch, tmp_path, arg, {"DTRL_KERNEL": "ref"}, {}), "variant reference kernel")
-    assert_same_end(base, variant_run(om, monkeypatch, tmp_path, arg, {"DTRL_VARIANTS_FALLBACK": "1"}, {}), "per-variant fallback")
+    of the SHIPPED single-model kernels (DTRL_VARIANTS_FALLBACK=1). In libdtrl.so and in libdtrl_f32.so."""
+    extra = extra_for(prec)
+    base = variant_run(om, monkeypatch, tmp_path, arg, {}, extra)
+    assert_same_end(base, variant_run(om, monkeypatch, tmp_path, arg, {"DTRL_KERNEL": "ref"}, extra), "variant reference kernel")
+    assert_same_end(base, variant_run(om, monkeypatch, tmp_path, arg, {"DTRL_VARIANTS_FALLBACK": "1"}, extra), "per-variant fallback")
 
 
 def test_two_env_groups(da, om, monkeypatch, tmp_path):

@@ -8,6 +8,7 @@ import pytest
 
 import test_host_and_emul as T
 from conftest import REFDATA, GOLDEN, HIP_LIB, dog_policy, pin_to_oracle
+from precision import assert_library, both_precisions, extra_for
 
 pytestmark = pytest.mark.gpu
 
@@ -220,12 +221,12 @@ def test_full_size_4096_properties(da, om):
     assert n >= frames and ms > 0
 
 
-@pytest.mark.parametrize("arg,n,frames", [("args/dog_slopes_mixed_args.txt", 256, 30), ("args/raptor_narrow_gaps_args.txt", 192, 40),
-                                          ("args/opt_args_train_mace.txt", 128, 40), ("args/goat_cliffs_args.txt", 128, 40)])
-def test_fast_kernel_equals_reference_kernel_bitwise(da, om, monkeypatch, arg, n, frames):
+@pytest.mark.parametrize("arg,n,frames,prec", both_precisions([("args/dog_slopes_mixed_args.txt", 256, 30), ("args/raptor_narrow_gaps_args.txt", 192, 40),
+                                                               ("args/opt_args_train_mace.txt", 128, 40), ("args/goat_cliffs_args.txt", 128, 40)]))
+def test_fast_kernel_equals_reference_kernel_bitwise(da, om, monkeypatch, arg, n, frames, prec):
     """The register-resident gfx950 kernels (fast<23> dog/goat, fast<21> raptor) and the LDS-phase reference kernel (DTRL_KERNEL=ref)
     perform the same arithmetic in the same order: falls, resets, policy forwards, exploration and tuples included, everything must
-    agree bit for bit."""
+    agree bit for bit -- in libdtrl.so and in libdtrl_f32.so (-physics_precision= f32), which holds its own pair of kernels."""
     raptor = "raptor" in arg
     pol = T.raptor_policy(om) if raptor else dog_policy(om)
     def run(kernel):
@@ -233,7 +234,8 @@ def test_fast_kernel_equals_reference_kernel_bitwise(da, om, monkeypatch, arg, n
             monkeypatch.setenv("DTRL_KERNEL", kernel)
         else:
             monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        b = T.batch(da, arg, n, terrain_seed=77)
+        b = T.batch(da, arg, n, **extra_for(prec, terrain_seed=77))
+        assert_library(b, prec)
         b.SetPolicy(pol[1], *pol[2:])
         b.RunFrames(frames)
         rows, flags, ids = b.DrainTuples()

@@ -6,6 +6,7 @@ import pytest
 
 import test_external_policy as X
 import test_policy_slots as T
+from precision import assert_library, both_precisions, extra_for
 
 pytestmark = pytest.mark.gpu
 
@@ -79,6 +80,7 @@ def slot_run(om, monkeypatch, arg, env, extra, n=192, frames=90):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     b = T.slotted(arg, n, T.policies(om, arg), T.EXPLORE, [e % 3 for e in range(n)], dict(terrain_seed=77, rand_seed=4, **extra))
+    assert_library(b, extra.get("physics_precision", "f64"))
     for _ in range(frames):
         b.Update()
     out = end_state(b)
@@ -86,13 +88,14 @@ def slot_run(om, monkeypatch, arg, env, extra, n=192, frames=90):
     return out
 
 
-@pytest.mark.parametrize("arg", [T.DOG, T.RAPTOR], ids=["dog", "raptor"])
-def test_slot_fast_kernel_equals_slot_reference_kernel_and_per_slot_fallback(da, om, monkeypatch, arg):
+@pytest.mark.parametrize("arg,prec", both_precisions([T.DOG, T.RAPTOR], ids=["dog", "raptor"]))
+def test_slot_fast_kernel_equals_slot_reference_kernel_and_per_slot_fallback(da, om, monkeypatch, arg, prec):
     """One launch of the register-resident slot kernel against one launch of the LDS-phase slot kernel (DTRL_KERNEL=ref) and against the per-slot launches of the
-    SHIPPED single-policy kernels (DTRL_SLOTS_FALLBACK=1)."""
-    base = slot_run(om, monkeypatch, arg, {}, {})
-    assert_same_end(base, slot_run(om, monkeypatch, arg, {"DTRL_KERNEL": "ref"}, {}), "slot reference kernel")
-    assert_same_end(base, slot_run(om, monkeypatch, arg, {"DTRL_SLOTS_FALLBACK": "1"}, {}), "per-slot fallback")
+    SHIPPED single-policy kernels (DTRL_SLOTS_FALLBACK=1). In libdtrl.so and in libdtrl_f32.so."""
+    extra = extra_for(prec)
+    base = slot_run(om, monkeypatch, arg, {}, extra)
+    assert_same_end(base, slot_run(om, monkeypatch, arg, {"DTRL_KERNEL": "ref"}, extra), "slot reference kernel")
+    assert_same_end(base, slot_run(om, monkeypatch, arg, {"DTRL_SLOTS_FALLBACK": "1"}, extra), "per-slot fallback")
 
 
 def test_two_env_groups(da, om, monkeypatch):
