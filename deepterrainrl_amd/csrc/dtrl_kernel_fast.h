@@ -37,6 +37,9 @@ __device__ __forceinline__ int opaque_lane()
 // a loaded value the optimiser must have in a register HERE: the load behind it can neither be sunk into a later branch nor be moved behind this point. No instruction
 template <class T>
 __device__ __forceinline__ void pin_loaded(T& v) { asm volatile("" : "+v"(v)); }
+// every LDS read issued so far has arrived HERE: one s_waitcnt lgkmcnt(0) (gfx9 encoding: vmcnt and expcnt left at their maxima, i.e. not waited for). For loads that
+// leave a nest of branches at different depths in front of a loop: still counted as pending at the loop's head, each of their uses in the loop gets a wait of its own
+__device__ __forceinline__ void lds_loads_arrived() { __builtin_amdgcn_s_waitcnt(0xc07f); }
 // the EXEC-window helpers below are spelled per arithmetic type (dtrl_types.h: fp64 shipped, fp32 opt-in build)
 #if defined(DTRL_REAL_F32)
 #define DTRL_VFMA "v_fma_f32"
@@ -603,11 +606,12 @@ __device__ __forceinline__ void build_rows_fast(WSFast& ws, const DevModel& gm, 
 // lanes (entry e = packed index), so a 16-row system is 3 passes of 23-long dot products instead of 16; the rows of Z are
 // read from LDS (odd row stride: lanes on different rows hit different banks, lanes on the same row broadcast).
 // Per-entry operation order is the one of build_delassus(), so the bits are the same.
+// R: the row count, wave-uniform (FastPath::substep reads it once). Returns the lane's row residual w (lanes >= R: 0), which pgs_solve_fast() takes in a
+// register; wv is written all the same (the reference layout).
 template <int D>
-__device__ __forceinline__ void build_delassus_fast(WSFast& ws, real h, real dinv_mine)
+__device__ __forceinline__ real build_delassus_fast(WSFast& ws, real h, real dinv_mine, int R)
 {
 	const int lane = static_cast<int>(threadIdx.x);
-	const int R = ws.R;
 	const int n_ent = R * (R + 1) / 2;
 	if (R < 16) {
 		// up to 15 rows (all but 0.2 % of the substeps): [A | zz] = (Z D^-1) Z^T for the R constraint rows plus the free right-hand side as
@@ -616,22 +620,43 @@ __device__ __forceinline__ void build_delassus_fast(WSFast& ws, real h, real din
 		// Operand layout: A[i = lane % 16][k = lane / 16], B[k = lane / 16][n = lane % 16], D register r = D[4 r + lane / 16][lane % 16].
 		typedef v4r_t v4d_t;
 		const int g = lane >> 4, c = lane & 15;
-		// row residual's velocity term, on the lanes that finish wv below (independent of the product: overlaps it)
-		real jv = 0;
-		if (lane < R) {
-			const int sw = lane;
-			if (ws.row_kind[sw] == 0) jv = ws.row_dx[sw] * ws.st.qd[ws.row_link[sw] + 2];
-			else jv = row_point_jv(ws, sw);
+		// row residual's velocity term, on the lanes that finish wv below (independent of the product: overlaps it). Lane r loads ITS row's descriptor as the first
+		// substitution does (FastPath::substep) -- kind, links, direction, point, target: one batch, unconditional, clamped -- then the velocity terms of `link` and of
+		// max(link2, 0) in a second one, where row_point_jv() makes a trip for the kind, one for the link, one for the point and the link's terms and up to two for
+		// link2. link_point_vel() runs for both links; which value counts is selected on the kind and on link2 < 0, and its operations and their order are
+		// row_point_jv()'s. (A limit row's point and second direction component hold what an earlier substep left: in bounds, selected away.)
+		real jv, tgt;
+		{
+			const int ol = opaque_lane();
+			const int rc = ol < R ? ol : 0;                        // (lanes >= R: row 0 exists, the values are not used)
+			const int kind_l = ws.row_kind[rc], link_l = ws.row_link[rc], link2_l = ws.row_link2[rc];
+			const real dx_l = ws.row_dx[rc], dy_l = ws.row_dy[rc], x_l = ws.row_x[rc], y_l = ws.row_y[rc];
+			tgt = ws.row_tgt[rc];
+			const int l2c = link2_l < 0 ? 0 : link2_l;
+			const real qd_l = ws.st.qd[link_l + 2];
+			const real jv1 = link_point_vel(ws, link_l, x_l, y_l, dx_l, dy_l), jv2 = link_point_vel(ws, l2c, x_l, y_l, dx_l, dy_l);
+			const real jp = link2_l < 0 ? jv1 : jv1 - jv2;
+			jv = kind_l == 0 ? dx_l * qd_l : jp;
 		}
 		const int zrow = c <= R ? c : 0;                        // rows above R are never stored; any finite-or-not value will do
-		v4d_t acc = {0, 0, 0, 0};
+		// the twelve operand reads stand in front of the six MFMAs (kin_dyn_terms_fast() P4): counted waits instead of load, wait, MFMA six times over
+		constexpr int kSteps = (D + 3) / 4;
+		real zv[kSteps], dv[kSteps];
 #pragma unroll
-		for (int s4 = 0; s4 < (D + 3) / 4; ++s4) {
+		for (int s4 = 0; s4 < kSteps; ++s4) {
 			const int k = 4 * s4 + g;
 			const bool live = k < D;
-			const real z = ws.Z[zrow][live ? k : 0], dk = ws.dinv[live ? k : 0];
-			const real b = live ? z : 0.0;
-			const real a = live ? z * dk : 0.0;
+			zv[s4] = ws.Z[zrow][live ? k : 0]; dv[s4] = ws.dinv[live ? k : 0];
+		}
+#pragma unroll
+		for (int s4 = 0; s4 < kSteps; ++s4) { pin_loaded(zv[s4]); pin_loaded(dv[s4]); }
+		v4d_t acc = {0, 0, 0, 0};
+#pragma unroll
+		for (int s4 = 0; s4 < kSteps; ++s4) {
+			const int k = 4 * s4 + g;
+			const bool live = k < D;
+			const real b = live ? zv[s4] : 0.0;
+			const real a = live ? zv[s4] * dv[s4] : 0.0;
 			acc = mfma_16x16x4(a, b, acc);
 		}
 #pragma unroll
@@ -641,9 +666,10 @@ __device__ __forceinline__ void build_delassus_fast(WSFast& ws, real h, real din
 			if (i < R && c == R) ws.wv[i] = acc[r];               // zz_i, finished below
 		}
 		env_sync();
-		if (lane < R) ws.wv[lane] = jv + h * ws.wv[lane] - ws.row_tgt[lane];
+		real w = 0.0;
+		if (lane < R) { w = jv + h * ws.wv[lane] - tgt; ws.wv[lane] = w; }
 		env_sync();
-		return;
+		return w;
 	}
 	const real* di = ws.dinv;   // general path (16+ rows, 0.2 % of the substeps): entry-parallel dot products
 	auto entry_rows = [](int e, int& s, int& r) {
@@ -654,6 +680,7 @@ __device__ __forceinline__ void build_delassus_fast(WSFast& ws, real h, real din
 	};
 	// first pass: the lane's matrix entry (all of them for R <= 10) and, on lanes < R, the row's initial residual w = J v_free - target.
 	// The two 23-term dot products are independent dependent chains; evaluated in one loop they cost the latency of one
+	real w = 0.0;
 	{
 		const bool has_e = lane < n_ent, has_w = lane < R;
 		int s = 0, r = 0;
@@ -672,7 +699,7 @@ __device__ __forceinline__ void build_delassus_fast(WSFast& ws, real h, real din
 #pragma unroll 4
 		for (int i = 0; i < D; ++i) { a = fmadd(zs[i] * di[i], zr[i], a); zz = fmadd(zw[i] * di[i], z0[i], zz); }
 		if (has_e) ws.Apk[lane] = a;
-		if (has_w) ws.wv[lane] = jv + h * zz - ws.row_tgt[lane];
+		if (has_w) { w = jv + h * zz - ws.row_tgt[lane]; ws.wv[lane] = w; }
 	}
 	for (int e = lane + kGroup; e < n_ent; e += kGroup) {
 		int s, r; entry_rows(e, s, r);
@@ -684,6 +711,7 @@ __device__ __forceinline__ void build_delassus_fast(WSFast& ws, real h, real din
 		ws.Apk[e] = a;
 	}
 	env_sync();
+	return w;
 }
 
 // projected Gauss-Seidel in lambda space with the row state in registers: lane s owns row s (w_s, lambda_s, 1/A_ss, kind).
@@ -776,40 +804,104 @@ __device__ __forceinline__ void pgs_rows_warm(const real (&a)[K], real& w, real 
 		}
 	}
 }
+// ---- the two passes of a sweep under Bullet's contact persistence, each walking ITS OWN rows only ----
+// The list is limit rows followed by (normal, tangent) pairs, so in row order each pass steps over the other pass's slots: three scalar instructions for "is this slot
+// in this pass" and three for "was this the last", around nine to ten of a row step. Here the lane's Delassus entries sit in SLOT order: the rows of pass 0 (limit and
+// normal rows that are active) take slots 0, 1, ... in list order, the rows of pass 1 (active friction rows) take slots K - 1, K - 2, ... in list order. A pass enters
+// its nested sequence at a compile-time slot and leaves at its first absent one: one scalar compare and branch per executed step. Lane ownership does not change (lane s
+// owns row s: w, lambda, 1/A_ss, kind), so wave_shr1(lam) and the final store stay; the row of a slot is wave-uniform, read from lane `slot` of one VGPR (srow) that is
+// built once per solve, and a step broadcasts from that row and commits on `lane == row` against the scalar. Same operations on the same operands in the same order per
+// lane as in row order, i.e. as pgs_solve().
+__device__ __forceinline__ real pgs_slot_entry(const WSFast& ws, int lane, bool mine, int row)
+{
+	const int mx = lane > row ? lane : row, mn = lane < row ? lane : row;
+	return ws.Apk[mine ? mx * (mx + 1) / 2 + mn : 0];
+}
+// a[slot] = A(lane, row(slot)) for the n0 slots from 0 up and the n1 slots from K - 1 down
+template <int j, int K>
+__device__ __forceinline__ void pgs_slots_load_up(real (&a)[K], const WSFast& ws, int lane, bool mine, int srow, int n0)
+{
+	if constexpr (j < K) {
+		if (j < n0) {
+			a[j] = pgs_slot_entry(ws, lane, mine, __builtin_amdgcn_readlane(srow, j));
+			pgs_slots_load_up<j + 1, K>(a, ws, lane, mine, srow, n0);
+		}
+	}
+}
+template <int j, int K>
+__device__ __forceinline__ void pgs_slots_load_down(real (&a)[K], const WSFast& ws, int lane, bool mine, int srow, int n1)
+{
+	if constexpr (j < K) {
+		if (j < n1) {
+			a[K - 1 - j] = pgs_slot_entry(ws, lane, mine, __builtin_amdgcn_readlane(srow, K - 1 - j));
+			pgs_slots_load_down<j + 1, K>(a, ws, lane, mine, srow, n1);
+		}
+	}
+}
+// pass 0: slots 0 .. n0 - 1
+template <int j, int K>
+__device__ __forceinline__ void pgs_slots_pass0(const real (&a)[K], real& w, real& lam, real rinv, int lane, int srow, int n0)
+{
+	if constexpr (j < K) {
+		if (j < n0) {
+			pgs_row_step<kPgsRowNormal>(w, lam, rinv, a[j], __builtin_amdgcn_readlane(srow, j), lane, false, 0.0, 0.0);
+			pgs_slots_pass0<j + 1, K>(a, w, lam, rinv, lane, srow, n0);
+		}
+	}
+}
+// pass 1: slots K - 1 .. K - n1. A friction row that Bullet's rule holds in this sweep (its bit of `rows` clear) must not run: fma(a, +-0, w) can change the sign of a zero
+template <int j, int K>
+__device__ __forceinline__ void pgs_slots_pass1(const real (&a)[K], real& w, real& lam, real rinv, real lo, real hi, int lane, int srow, int n1, unsigned long long rows)
+{
+	if constexpr (j < K) {
+		if (j < n1) {
+			const int row = __builtin_amdgcn_readlane(srow, K - 1 - j);
+			if ((rows >> row) & 1ull) pgs_row_step<kPgsRowFriction>(w, lam, rinv, a[K - 1 - j], row, lane, false, lo, hi);
+			pgs_slots_pass1<j + 1, K>(a, w, lam, rinv, lo, hi, lane, srow, n1, rows);
+		}
+	}
+}
 // Bullet's persistent contact points on the wave (warm_match() of dtrl_kernel.h): lane r looks the identity of fresh row r up among the rows of the last solved
-// substep (<= 24 broadcast reads of 16-bit ids) and starts from kWarmFactor x that row's impulse; the fresh list then becomes the cache
-__device__ __forceinline__ void warm_match_fast(WSFast& ws)
+// substep and starts from kWarmFactor x that row's impulse; the fresh list then becomes the cache. Lane p loads cached id p in the same batch as its own row's id, and
+// the loop over the cache takes id p from lane p (v_readlane, wave-uniform p) instead of one broadcast LDS read, wait and compare per cached row; the select is the
+// same, so the same -- last -- match wins. The impulse of the hit is the one dependent trip left.
+// R, Rp (row count of the last solved substep), warm (DevModel::warm_start): wave-uniform, read once by FastPath::substep
+__device__ __forceinline__ void warm_match_fast(WSFast& ws, int R, int Rp, bool warm)
 {
 	const int lane = opaque_lane();
-	const int R = ws.R, Rp = ws.st.ws_R;   // wave-uniform
 	if (R == 0) { if (Rp != 0 && lane == 0) ws.st.ws_R = 0; return; }   // (a fifth of the substeps: airborne)
-	int id = kNoRowId;
-	if (lane < R) id = ws.row_id[lane];
+	const int own = ws.row_id[lane < R ? lane : 0];
+	const int cached = ws.st.ws_id[lane < Rp ? lane : 0];   // (Rp = 0: entry 0 is in bounds and not looked at)
+	const int id = lane < R ? own : kNoRowId;
 	real l0 = 0.0;
-	if (ws.M.warm_start != 0 && Rp > 0) {
+	if (warm && Rp > 0) {
 		int hit = -1;
-		for (int p = 0; p < Rp; ++p) hit = (ws.st.ws_id[p] == id) ? p : hit;
-		if (id < kFirstPairRowId && hit >= 0) l0 = kWarmFactor * ws.st.ws_lam[hit];   // ground contact rows only
+		for (int p = 0; p < Rp; ++p) hit = (__builtin_amdgcn_readlane(cached, p) == id) ? p : hit;
+		const real lh = ws.st.ws_lam[hit >= 0 ? hit : 0];
+		if (id < kFirstPairRowId && hit >= 0) l0 = kWarmFactor * lh;   // ground contact rows only
 	}
 	// (no barrier between the reads above and the writes below: one wavefront, and its LDS operations complete in issue order)
 	if (lane < R) { ws.st.ws_lam[lane] = l0; ws.st.ws_id[lane] = static_cast<uint16_t>(id); }
 	if (lane == 0) ws.st.ws_R = R;
 	// (no fence behind the writes either: their next reader is the Gauss-Seidel solve, several phase boundaries further on)
 }
-template <int kPgsRegRows>
-__device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
+// R, warm: wave-uniform (FastPath::substep); w: the lane's row residual from build_delassus_fast() (lanes >= R: 0)
+// kSlotOrder: the two passes of a sweep walk their own rows in slot order (pgs_slots_pass0() / pgs_slots_pass1() above); false: the row-order sequences
+template <int kPgsRegRows, bool kSlotOrder>
+__device__ __forceinline__ void pgs_solve_fast(WSFast& ws, int R, bool warm, real w)
 {
 	const int lane = opaque_lane();
-	const int R = ws.R;
 	const bool mine = lane < R;
-	real w = mine ? ws.wv[lane] : 0.0;
+	// the diagonal entry, the warm-start impulse and the row kind in one batch (unconditional, clamped: lanes >= R read row 0's)
+	const int rc = mine ? lane : 0;
+	const real ass = ws.Apk[rc * (rc + 3) / 2], lam_ws = ws.st.ws_lam[rc];
+	const int kind = ws.row_kind[rc];
 	real rinv = 0.0;
-	if (mine) { const real ass = ws.Apk[lane * (lane + 3) / 2]; rinv = (ass >= 1e-12) ? 1.0 / ass : 0.0; }
-	real lam = (mine && rinv != 0.0) ? ws.st.ws_lam[lane] : 0.0;   // warm_match_fast(): kWarmFactor x the row's previous impulse; rows with a vanishing effective mass stay at zero
-	const bool tang = mine && ws.row_kind[lane] == 2;
+	if (mine) rinv = (ass >= 1e-12) ? 1.0 / ass : 0.0;
+	real lam = (mine && rinv != 0.0) ? lam_ws : 0.0;   // warm_match_fast(): kWarmFactor x the row's previous impulse; rows with a vanishing effective mass stay at zero
+	const bool tang = mine && kind == 2;
 	const unsigned long long act = __ballot(rinv != 0.0);
 	// Bullet's contact persistence: a sweep resolves the limit and normal rows (list order), then the friction rows; a friction row only under a loaded normal row
-	const bool warm = ws.M.warm_start != 0;   // wave-uniform
 	const unsigned long long tmask = __ballot(tang);
 	const unsigned long long nz_l0 = __ballot(lam != 0.0);
 	const bool any_l0 = nz_l0 != 0ull;
@@ -820,30 +912,66 @@ __device__ __forceinline__ void pgs_solve_fast(WSFast& ws)
 	// (the first test is a compile-time constant: an instance whose register rows cover every row count does not contain the plain loop)
 	if (kPgsRegRows == kMaxRows || R <= kPgsRegRows) {
 		real a[kPgsRegRows];
-		pgs_rows_load<0, kPgsRegRows>(a, ws, lane, mine, R);
+		if (!kSlotOrder || !warm || any_l0) pgs_rows_load<0, kPgsRegRows>(a, ws, lane, mine, R);   // row order: the warm-start columns, the -warm_start= 0 sweep, the instances that keep the row-order passes
+		// every a[r] has arrived here, once per solve: the nested loads leave at R different depths, and without this wait the FMA of every row step of both passes
+		// gets an s_waitcnt lgkmcnt(0) of its own (docs/EXPERIMENTS.md 38)
+		lds_loads_arrived();
 		const unsigned long long actR = act & ((R < 64) ? ((1ull << R) - 1ull) : ~0ull);
 		if (any_l0) pgs_rows_warm<0, kPgsRegRows>(a, w, lam, nz_l0, R);
 		const unsigned long long pass0 = warm ? (actR & ~tmask) : actR, pass1 = actR & tmask;
 		if (warm) {
-			// a pass leaves the nested row sequence behind its LAST row (not at R): the rows of the other pass that follow it are not even looked at
-			const int end0 = (pass0 == 0ull) ? R : 64 - __builtin_clzll(pass0);
+			if constexpr (kSlotOrder) {
+				// (w += A lambda_0 above ran on the entries in ROW order, column by column in list order as pgs_solve() does; the same registers now take them in slot order.
+				// A solve with a warm impulse therefore reads the lane's Delassus row twice, two batches and two waits; reading the warm-start columns straight from Apk
+				// instead needs R more live registers next to a[] or a second nest of loads, and was not built: docs/EXPERIMENTS.md 38 "Not done")
+				const int n0 = __popcll(pass0), n1 = __popcll(pass1);
+				int srow;
+				{
+					// lane r knows the slot of row r (its rank in its pass); one cross-lane push turns that into slot -> row. Lanes without a slot push to lane 63, which no
+					// slot uses (K <= kMaxRows < 63)
+					const unsigned long long below = (1ull << lane) - 1ull;
+					const bool has = ((actR >> lane) & 1ull) != 0ull;
+					const int slot = tang ? kPgsRegRows - 1 - __popcll(pass1 & below) : __popcll(pass0 & below);
+					srow = __builtin_amdgcn_ds_permute((has ? slot : 63) << 2, lane);
+				}
+				pgs_slots_load_up<0, kPgsRegRows>(a, ws, lane, mine, srow, n0);
+				pgs_slots_load_down<0, kPgsRegRows>(a, ws, lane, mine, srow, n1);
+				lds_loads_arrived();   // (as above: every entry has arrived before the sweeps)
 #pragma unroll 1
-			for (int it = 0; it < kPgsIters; ++it) {
-				// pass0 / end0 do not change over the sweeps. Left visible as loop invariants, the nested per-row tests below are hoisted out of the loop as two
-				// 64-bit booleans per row, which have no SGPRs to live in: a block in front of every solve writes them to VGPR lanes and every row of every
-				// sweep reads them back. Through an opaque per-sweep copy they are tested where they are used, as the friction pass's per-sweep `rows` is:
-				// s_cmp / s_bitcmp + branch per row, nothing kept.
-				// (the mask travels as two 32-bit halves: with a 64-bit operand next to the 32-bit one the fp32 build does not compile)
-				unsigned rows0_lo = static_cast<unsigned>(pass0), rows0_hi = static_cast<unsigned>(pass0 >> 32); int last0 = end0;
-				asm volatile("" : "+s"(rows0_lo), "+s"(rows0_hi), "+s"(last0));
-				const unsigned long long rows0 = (static_cast<unsigned long long>(rows0_hi) << 32) | rows0_lo;
-				if (rows0 != 0ull) pgs_rows_pass<kPgsRowNormal, 0, kPgsRegRows>(a, w, lam, rinv, 0.0, 0.0, rows0, lane, last0);
-				// friction pass: every normal row is final for this sweep, so the bounds +-mu lambda_n are fixed for the pass, and which friction rows Bullet's rule HOLDS
-				// (normal row without impulse: their update is exactly zero) is known up front -- they leave the pass instead of walking through a row step each
-				const real ln = wave_shr1(lam);   // (all lanes: a DPP move under a narrowed EXEC does not see the lanes that are switched off)
-				const real lim = kMu * ln;
-				const unsigned long long rows = pass1 & __ballot(tang && ln > kHoldEps);
-				if (rows != 0ull) pgs_rows_pass<kPgsRowFriction, 0, kPgsRegRows>(a, w, lam, rinv, -lim, lim, rows, lane, 64 - __builtin_clzll(rows));
+				for (int it = 0; it < kPgsIters; ++it) {
+					// n0 / n1 / srow do not change over the sweeps. Left visible as loop invariants, the per-slot tests and row indices are hoisted out of the loop into SGPRs
+					// that do not exist (they spill to VGPR lanes and every row of every sweep reads them back): through an opaque per-sweep copy they are formed where they are used
+					int n0s = n0, n1s = n1, srows = srow;
+					asm volatile("" : "+s"(n0s), "+s"(n1s), "+v"(srows));
+					pgs_slots_pass0<0, kPgsRegRows>(a, w, lam, rinv, lane, srows, n0s);
+					// friction pass: every normal row is final for this sweep, so the bounds +-mu lambda_n are fixed for the pass, and which friction rows Bullet's rule HOLDS
+					// (normal row without impulse: their update is exactly zero) is known up front
+					const real ln = wave_shr1(lam);   // (all lanes: a DPP move under a narrowed EXEC does not see the lanes that are switched off)
+					const real lim = kMu * ln;
+					const unsigned long long rows = pass1 & __ballot(tang && ln > kHoldEps);
+					if (rows != 0ull) pgs_slots_pass1<0, kPgsRegRows>(a, w, lam, rinv, -lim, lim, lane, srows, n1s, rows);
+				}
+			} else {
+				// a pass leaves the nested row sequence behind its LAST row (not at R): the rows of the other pass that follow it are not even looked at
+				const int end0 = (pass0 == 0ull) ? R : 64 - __builtin_clzll(pass0);
+#pragma unroll 1
+				for (int it = 0; it < kPgsIters; ++it) {
+					// pass0 / end0 do not change over the sweeps. Left visible as loop invariants, the nested per-row tests below are hoisted out of the loop as two
+					// 64-bit booleans per row, which have no SGPRs to live in: a block in front of every solve writes them to VGPR lanes and every row of every
+					// sweep reads them back. Through an opaque per-sweep copy they are tested where they are used, as the friction pass's per-sweep `rows` is:
+					// s_cmp / s_bitcmp + branch per row, nothing kept.
+					// (the mask travels as two 32-bit halves: with a 64-bit operand next to the 32-bit one the fp32 build does not compile)
+					unsigned rows0_lo = static_cast<unsigned>(pass0), rows0_hi = static_cast<unsigned>(pass0 >> 32); int last0 = end0;
+					asm volatile("" : "+s"(rows0_lo), "+s"(rows0_hi), "+s"(last0));
+					const unsigned long long rows0 = (static_cast<unsigned long long>(rows0_hi) << 32) | rows0_lo;
+					if (rows0 != 0ull) pgs_rows_pass<kPgsRowNormal, 0, kPgsRegRows>(a, w, lam, rinv, 0.0, 0.0, rows0, lane, last0);
+					// friction pass: every normal row is final for this sweep, so the bounds +-mu lambda_n are fixed for the pass, and which friction rows Bullet's rule HOLDS
+					// (normal row without impulse: their update is exactly zero) is known up front -- they leave the pass instead of walking through a row step each
+					const real ln = wave_shr1(lam);   // (all lanes: a DPP move under a narrowed EXEC does not see the lanes that are switched off)
+					const real lim = kMu * ln;
+					const unsigned long long rows = pass1 & __ballot(tang && ln > kHoldEps);
+					if (rows != 0ull) pgs_rows_pass<kPgsRowFriction, 0, kPgsRegRows>(a, w, lam, rinv, -lim, lim, rows, lane, 64 - __builtin_clzll(rows));
+				}
 			}
 		} else {
 #pragma unroll 1
@@ -1080,6 +1208,13 @@ __device__ __forceinline__ void kin_dyn_terms_fast(WSFast& ws)
 // constraint-row bucket of the per-bucket counters (kProfFsubR0, kProfR0, kProfT0): 0 rows, 1-6, 7-12, 13-18, 19+
 __device__ __forceinline__ int prof_row_bucket(int R) { return R == 0 ? 0 : (R <= 6 ? 1 : (R <= 12 ? 2 : (R <= 18 ? 3 : 4))); }
 #endif
+// Which instances run the slot-order passes: those compiled for two waves per SIMD (256 VGPRs). An instance compiled for three (168 VGPRs: the fp32 library's raptor)
+// keeps the row-order sequences: in slot order its substep loop holds 135 scratch instructions against 8, and the fp32 leg of configs[2] loses 11 %
+// (docs/EXPERIMENTS.md 38, profiles/contact_solve.txt 2).
+// WavesPerEu<Topo> is the register budget the unit gives the instance (dtrl_frame_entry.h). It is only declared here and looked up when FastPath<Topo> is instantiated:
+// a unit that instantiates the fast path without defining it does not compile.
+template <class Topo> struct WavesPerEu;
+template <class Topo> struct PgsSlotOrder { static constexpr bool value = WavesPerEu<Topo>::value <= 2; };
 template <class Topo>
 struct FastPath {
 	static constexpr int D = Topo::L + 2;
@@ -1104,12 +1239,15 @@ struct FastPath {
 			{ PROF_T0(); cp = eval_points<Topo::L, false>(ws, gm, g); PROF_ADD(ws, kProfDetect); }   // the per-link contact flags are the post-step pass's business (contacts() below)
 			{ PROF_T0(); build_rows_fast<NP>(ws, gm, cp, h); PROF_ADD(ws, kProfRows); }
 		}
-		{ PROF_T0(); warm_match_fast(ws); PROF_ADD(ws, kProfRows); }
 		real hrow[D];
 		{ PROF_T0(); mass_row<D>(ws, hrow); PROF_ADD(ws, kProfMass); }
 		real dinv;
 		{ PROF_T0(); dinv = factorize_regs<Topo>(ws, hrow); PROF_ADD(ws, kProfFact); }
-		const int R = ws.R;
+		// the row count, the cache's and the warm-start switch: read ONCE, here, and handed down to warm_match_fast(), build_delassus_fast() and pgs_solve_fast() as
+		// wave-uniform values
+		const int R = __builtin_amdgcn_readfirstlane(ws.R), Rp = __builtin_amdgcn_readfirstlane(ws.st.ws_R);
+		const bool warm = __builtin_amdgcn_readfirstlane(ws.M.warm_start) != 0;
+		{ PROF_T0(); warm_match_fast(ws, R, Rp, warm); PROF_ADD(ws, kProfRows); }
 		if (lane == 0) ws.cost += 8 + R;
 		{
 			PROF_T0();
@@ -1167,8 +1305,9 @@ struct FastPath {
 #endif
 		}
 		if (R > 0) {
-			{ PROF_T0(); build_delassus_fast<D>(ws, h, dinv); PROF_ADD(ws, kProfDelassus); }
-			{ PROF_T0(); pgs_solve_fast<Topo::kPgsRegRows>(ws); PROF_ADD(ws, kProfPgs); }
+			real w;
+			{ PROF_T0(); w = build_delassus_fast<D>(ws, h, dinv, R); PROF_ADD(ws, kProfDelassus); }
+			{ PROF_T0(); pgs_solve_fast<Topo::kPgsRegRows, PgsSlotOrder<Topo>::value>(ws, R, warm, w); PROF_ADD(ws, kProfPgs); }
 		}
 		{
 			PROF_T0();

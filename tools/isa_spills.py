@@ -6,13 +6,14 @@ Two kinds of spill are counted:
             of the same function (the reload; a v_readlane of any other VGPR is a broadcast of lane data and is not counted)
 The VGPRs that v_writelane_b32 targets are the ones reserved for SGPR spills; they are listed with the totals.
 Memory round trips: gload = global_load_* instructions, vmwait = s_waitcnt instructions that wait on vmcnt (each one a point where the wave may stand still for a
-trip to memory: a chain of load, wait, load, wait shows as vmwait close to gload).
+trip to memory: a chain of load, wait, load, wait shows as vmwait close to gload). lgkmwait = s_waitcnt instructions that wait on lgkmcnt (LDS and scalar-memory
+round trips, counted the same way).
 A loop's "own" columns count the blocks whose innermost loop it is, the "nest" columns add every loop nested in it (the substep loop of the frame kernel is the
 depth-2 loop with the largest nest).
 Usage: tools/isa_spills.py file.s kernel_substring"""
 import re, sys, collections
 
-COLS = ("instr", "valu", "salu", "scratch", "wl", "rl", "gload", "vmwait")
+COLS = ("instr", "valu", "salu", "scratch", "wl", "rl", "gload", "vmwait", "lgkmwait")
 
 
 def parse(src, key):
@@ -59,6 +60,7 @@ def parse(src, key):
         if t.startswith("scratch_"): c["scratch"] += 1
         if t.startswith("global_load_"): c["gload"] += 1
         if t == "s_waitcnt" and "vmcnt" in s: c["vmwait"] += 1
+        if t == "s_waitcnt" and "lgkmcnt" in s: c["lgkmwait"] += 1
         if t == "v_writelane_b32": c["wl"] += 1
         if t == "v_readlane_b32":
             m = re.match(r"v_readlane_b32\s+\S+\s*,\s*(v\d+)\s*,", s)
@@ -74,16 +76,16 @@ def main():
         for a in [k] + parents.get(k, []): nest[a].update(c)
     tot = collections.Counter()
     for c in own.values(): tot.update(c)
-    print("kernel *%s*: %d instr, %d VALU, %d SALU, %d scratch, %d v_writelane (SGPR spill stores), %d v_readlane of spill VGPRs (SGPR spill reloads), %d global loads, %d vmcnt waits"
+    print("kernel *%s*: %d instr, %d VALU, %d SALU, %d scratch, %d v_writelane (SGPR spill stores), %d v_readlane of spill VGPRs (SGPR spill reloads), %d global loads, %d vmcnt waits, %d lgkmcnt waits"
           % ((key,) + tuple(tot[k] for k in COLS)))
     vs = sorted(spill_vgprs, key=lambda v: int(v[1:]))
     print("VGPRs reserved for SGPR spills: %d (%s)" % (len(vs), " ".join(vs)))
-    print("%-12s %5s | %s | %s" % ("loop", "depth", " ".join("%7s" % k for k in COLS), " ".join("%7s" % k for k in COLS)))
-    print("%-12s %5s | %-63s | %s" % ("", "", "own blocks", "nest (with the loops inside it)"))
+    print("%-12s %5s | %s | %s" % ("loop", "depth", " ".join("%8s" % k for k in COLS), " ".join("%8s" % k for k in COLS)))
+    print("%-12s %5s | %-72s | %s" % ("", "", "own blocks", "nest (with the loops inside it)"))
     for k, c in sorted(nest.items(), key=lambda kv: -kv[1]["instr"])[:25]:
         if k == "-": continue
-        print("%-12s %5d | %s | %s" % (k, depth.get(k, 0), " ".join("%7d" % own[k][x] for x in COLS), " ".join("%7d" % c[x] for x in COLS)))
-    print("%-12s %5d | %s |" % ("(no loop)", 0, " ".join("%7d" % own["-"][x] for x in COLS)))
+        print("%-12s %5d | %s | %s" % (k, depth.get(k, 0), " ".join("%8d" % own[k][x] for x in COLS), " ".join("%8d" % c[x] for x in COLS)))
+    print("%-12s %5d | %s |" % ("(no loop)", 0, " ".join("%8d" % own["-"][x] for x in COLS)))
 
 
 if __name__ == "__main__":
