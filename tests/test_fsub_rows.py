@@ -11,14 +11,15 @@ import pytest
 import test_host_and_emul as T
 from conftest import REFDATA, dog_policy
 from precision import both_precisions, check_build, extra_for
-from test_gpu_fsub_rhs import product
+from product import fast_and_reference
+from test_gpu_fsub_rhs import NAMES, product
 
 CASES = [("args/dog_slopes_mixed_args.txt", "dog"), ("args/raptor_narrow_gaps_args.txt", "raptor"), ("args/goat_cliffs_args.txt", "goat")]
 N_ENVS, FRAMES = 192, 30
 
 
 def rollout(make, pol, n=N_ENVS, frames=FRAMES):
-    """make() -> BatchScenario. Returns the row counts of all frames, the contact cache of every frame, the end state and EvalStats."""
+    """make() -> BatchScenario. Returns the contact cache of every frame, the row counts of all frames, the end state and EvalStats."""
     b = make()
     b.SetPolicy(pol[1], *pol[2:])
     b.RunFrames(2)
@@ -35,7 +36,7 @@ def rollout(make, pol, n=N_ENVS, frames=FRAMES):
         counts.append(cnt.copy())
         trace.append((cnt, rid, lam))
     qf, qdf = b.PoseVel()
-    return np.concatenate(counts), trace, qf, qdf, b.Torques(), b.EvalStats()
+    return trace, np.concatenate(counts), qf, qdf, b.Torques(), b.EvalStats()
 
 
 def check_reached(counts):
@@ -49,19 +50,10 @@ def check_reached(counts):
 @pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
 def test_fsub_rows_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel, prec):
     pol = T.raptor_policy(om) if skel == "raptor" else dog_policy(om)
-
-    def run(kernel):
-        if kernel:
-            monkeypatch.setenv("DTRL_KERNEL", kernel)
-        else:
-            monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        return rollout(product(da, arg, N_ENVS, prec, terrain_seed=77), pol)
-
-    cf, tf, qf, qdf, (tcf, taf), sf = run(None)
-    cr, tr, qr, qdr, (tcr, tar), sr = run("ref")
+    # (the per-frame records are the contact cache: the first three of NAMES)
+    (tf, cf, qf, qdf, (tcf, taf), sf), (tr, cr, qr, qdr, (tcr, tar), sr) = fast_and_reference(
+        monkeypatch, lambda: rollout(product(da, arg, N_ENVS, prec, terrain_seed=77), pol), NAMES[:3])
     check_reached(cr)                                          # on the reference kernel's run: the condition does not depend on the code under test
-    for (a, b_) in zip(tf, tr):
-        assert all(np.array_equal(x, y) for x, y in zip(a, b_))
     assert np.array_equal(qf, qr) and np.array_equal(qdf, qdr) and np.array_equal(tcf, tcr) and np.array_equal(taf, tar)
     assert sf == sr
     assert np.array_equal(cf, cr)
@@ -71,5 +63,5 @@ def test_fsub_rows_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel,
 def test_fsub_rows_rollout_fills_the_bins_on_the_lane_loop_build(om, arg, skel, prec):
     """The CPU twin: the same rollout through the lane-loop build of dtrl_kernel.h (of either precision) fills the bins."""
     pol = T.raptor_policy(om) if skel == "raptor" else dog_policy(om)
-    counts = rollout(lambda: check_build(prec)(arg, N_ENVS, data_root=REFDATA, extra_args=extra_for(prec, terrain_seed=77)), pol)[0]
+    counts = rollout(lambda: check_build(prec)(arg, N_ENVS, data_root=REFDATA, extra_args=extra_for(prec, terrain_seed=77)), pol)[1]
     check_reached(counts)

@@ -22,7 +22,8 @@ import pytest
 import test_host_and_emul as T
 from conftest import REFDATA, dog_policy
 from precision import both_precisions, check_build, extra_for
-from test_gpu_fsub_rhs import product
+from product import fast_and_reference
+from test_gpu_fsub_rhs import NAMES, product
 
 CASES = [("args/dog_slopes_mixed_args.txt", "dog"), ("args/raptor_narrow_gaps_args.txt", "raptor"), ("args/goat_cliffs_args.txt", "goat")]
 N_ENVS, FRAMES, TERRAIN_SEED = 192, 30, 77
@@ -78,21 +79,9 @@ def policy_of(om, skel):
 @pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
 def test_contact_points_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel, prec):
     pol = policy_of(om, skel)
-
-    def run(kernel):
-        if kernel:
-            monkeypatch.setenv("DTRL_KERNEL", kernel)
-        else:
-            monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        return rollout(product(da, arg, N_ENVS, prec, terrain_seed=TERRAIN_SEED), pol)
-
-    ff, cf, bf = run(None)
-    fr, cr, br = run("ref")
+    (_, cf, bf), (_, cr, br) = fast_and_reference(monkeypatch, lambda: rollout(product(da, arg, N_ENVS, prec, terrain_seed=TERRAIN_SEED), pol),
+                                                      NAMES[:8] + NAMES[-1:])    # (this rollout's records hold no cycle and reset counters)
     check_reached(cr, br)
-    names = ("cache count", "cache ids", "cache impulses", "contact flags", "pose", "velocity", "control torques", "applied torques", "eval stats")
-    for f, (a, b_) in enumerate(zip(ff, fr)):
-        for name, x, y in zip(names, a, b_):
-            assert np.array_equal(x, y), "frame %d: %s differ" % (f, name)
     assert bf == br and np.array_equal(cf, cr)
 
 

@@ -22,9 +22,9 @@ import pytest
 import test_gpu_fsub_rhs as F
 from conftest import REFDATA
 from precision import both_precisions, check_build, extra_for
+from product import fast_and_reference
 
 GROUND_IDS = F.FIRST_PAIR_ROW_ID      # ground contact rows: 2 x sample point + (0 normal, 1 tangent)
-NAMES = ("cache count", "cache ids", "cache impulses", "contact flags", "pose", "velocity", "control torques", "applied torques", "cycle counters", "reset counters", "eval stats")
 
 
 def solve_cases(frames):
@@ -59,22 +59,10 @@ def check_solve_cases(got):
 @pytest.mark.parametrize("arg,skel,prec", both_precisions(F.CASES))
 def test_contact_solve_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel, prec):
     pol = F.policy_of(om, skel)
-
-    def run(kernel):
-        if kernel:
-            monkeypatch.setenv("DTRL_KERNEL", kernel)
-        else:
-            monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        return F.rollout(F.product(da, arg, F.N_ENVS, prec, terrain_seed=F.TERRAIN_SEED), pol, skel)
-
-    ff, rf = run(None)
-    fr, rr = run("ref")
+    (ff, rf), (fr, rr) = fast_and_reference(monkeypatch, lambda: F.rollout(F.product(da, arg, F.N_ENVS, prec, terrain_seed=F.TERRAIN_SEED), pol, skel), F.NAMES)
     check_solve_cases(solve_cases(fr))
     F.check_reached(rr)
     assert len(ff) == len(fr) == F.FRAMES
-    for f, (a, b_) in enumerate(zip(ff, fr)):
-        for name, x, y in zip(NAMES, a, b_):
-            assert np.array_equal(x, y), "frame %d: %s differ" % (f, name)
     assert rf == rr
 
 

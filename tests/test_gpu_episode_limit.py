@@ -4,9 +4,6 @@ host fallback (DTRL_EPISODE_FALLBACK=1) at 70 envs (two 64-thread blocks, the se
 modes, with falls among the endings; frames queued without a host wait (RunFrames) against frame-by-frame Update; run-to-run determinism; the fast kernel against
 the reference kernel under limits; every frame-boundary rule in ONE batch against all the host fallbacks at once, per frame and in the listed episode starts (dtrl_reset, a terrain restart, an
 env coming into the limit); and the new symbols in both libraries."""
-import ctypes
-import os
-
 import pytest
 
 import test_episode_limit as E
@@ -17,100 +14,25 @@ import test_policy_slots as P
 import test_push_schedule as R
 import test_terrain_ladder as LD
 import test_terrain_sets as T
-from conftest import HIP_LIB
+from product import assert_same_end, end_state, product_batch, set_knobs, symbols_test
+# ---- twins: the CPU tests themselves, collected here under the module's gpu mark and fixture (both libraries: the rule is doubles and integers in either, so
+# the fp32 library's records equal the same Python rule, given its own falls) ----
+from test_episode_limit import (test_a_truncation_is_a_reset, test_batch_state_and_lifecycle, test_distance_limit_and_poli_eval, test_every_rule_at_once,  # noqa: F401
+                                test_fsm_dog_resets_at_exactly_its_drawn_limits, test_held_out_envs_equal_a_batch_without_limit, test_listed_starts_under_every_rule,
+                                test_records_equal_the_rule_under_the_net, test_records_equal_the_rule_with_falls, test_refusals,
+                                test_setup_episode_limit_holds_the_greedy_envs_out, test_shard_invariance)
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("DTRL_KERNEL", "DTRL_TERRAINS_FALLBACK", "DTRL_SLOTS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_EPISODE_FALLBACK", "DTRL_GROUPS")
-
-
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    for mod in (R, T, V, X, P, LD, H):
-        monkeypatch.setattr(mod, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-
-
-# ---- twins ----
-@pytest.mark.parametrize("prec", E.PRECISIONS, ids=E.PRECISION_IDS)
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_records_equal_the_rule_under_the_net(da, om, mode, prec):
-    """(both libraries: the rule is doubles and integers in either, so the fp32 library's records equal the same Python rule, given its own falls)"""
-    E.test_records_equal_the_rule_under_the_net(da, om, mode, prec)
-
-
-@pytest.mark.parametrize("prec", E.PRECISIONS, ids=E.PRECISION_IDS)
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_records_equal_the_rule_with_falls(da, om, mode, prec):
-    E.test_records_equal_the_rule_with_falls(da, om, mode, prec)
-
-
-@pytest.mark.parametrize("prec", E.PRECISIONS, ids=E.PRECISION_IDS)
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_fsm_dog_resets_at_exactly_its_drawn_limits(da, om, mode, prec):
-    E.test_fsm_dog_resets_at_exactly_its_drawn_limits(da, om, mode, prec)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_a_truncation_is_a_reset(da, om, mode):
-    E.test_a_truncation_is_a_reset(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_distance_limit_and_poli_eval(da, om, mode):
-    E.test_distance_limit_and_poli_eval(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_held_out_envs_equal_a_batch_without_limit(da, om, mode):
-    E.test_held_out_envs_equal_a_batch_without_limit(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_shard_invariance(da, om, mode):
-    E.test_shard_invariance(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_every_rule_at_once(da, om, tmp_path, mode):
-    E.test_every_rule_at_once(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_listed_starts_under_every_rule(da, om, tmp_path, mode):
-    E.test_listed_starts_under_every_rule(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_batch_state_and_lifecycle(da, om, mode):
-    E.test_batch_state_and_lifecycle(da, om, mode)
-
-
-def test_refusals(da, om):
-    E.test_refusals(da, om)
-
-
-def test_setup_episode_limit_holds_the_greedy_envs_out(da, om):
-    E.test_setup_episode_limit_holds_the_greedy_envs_out(da, om)
-
+hip_batch = product_batch(R, T, V, X, P, LD, H)
+NOT_TWINNED = {}
 
 # ---- GPU only: 70 envs (two blocks of 64 threads, the second partial), bit for bit ----
 N, FRAMES = E.N, 30
 HELD = [e for e in range(N) if e % 7 == 3]      # held-out envs in both blocks
 
 
-def end_state(b):
-    info = b.EpisodeInfo()
-    return X.env_states(b), b.RecordPoliState(), [X.ground_key(b, e) for e in range(b.num_envs)], {"episode " + k: v.tobytes() for k, v in info.items()}, info
-
-
 def limit_run(om, monkeypatch, env, mode, extra, run_frames=False, pushes=None):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_knobs(monkeypatch, env)
     if pushes is not None:
         extra = dict(extra, min_perturb=pushes[0], max_perturb=pushes[1], min_pertrub_duration=0.1, max_perturb_duration=0.25)
     b = E.limit_batch(om, N, mode, limit=False, **extra)
@@ -123,14 +45,13 @@ def limit_run(om, monkeypatch, env, mode, extra, run_frames=False, pushes=None):
             if pushes is not None and f % 2 == 0:
                 b.ApplyRandForce(f)
             b.Update()
-    out = end_state(b)
-    info = out[4]
+    info = b.EpisodeInfo()
     inn = [e for e in range(N) if e not in HELD]
     # (no episode outlasts the largest limit, whichever way it ends)
     assert (info["by_limit"] + info["by_fall"])[inn].min() >= FRAMES // E.LIMITS[1] and not any(v[HELD].any() for v in info.values()) and info["by_limit"][64:].sum() >= 1, info
     if pushes is not None:
         assert info["by_fall"].sum() >= 10, info["by_fall"]
-    return out
+    return end_state(b, info, **{"episode " + k: v.tobytes() for k, v in info.items()})
 
 
 @pytest.mark.parametrize("groups", ["1", "2"], ids=["one_group", "two_groups"])
@@ -140,7 +61,7 @@ def test_limit_kernel_equals_host_fallback(da, om, monkeypatch, mode, prec, grou
     """One launch of dtrl_episode_limit per group and frame against the rule run on the host, env by env (DTRL_EPISODE_FALLBACK=1), under hard pushes so that
     episodes end by falls too; two groups: the second starts at a non-zero e0."""
     base = limit_run(om, monkeypatch, {"DTRL_GROUPS": groups}, mode, prec, pushes=E.HARD)
-    E.assert_same_run(base, limit_run(om, monkeypatch, {"DTRL_GROUPS": groups, "DTRL_EPISODE_FALLBACK": "1"}, mode, prec, pushes=E.HARD), "host fallback")
+    assert_same_end(base, limit_run(om, monkeypatch, {"DTRL_GROUPS": groups, "DTRL_EPISODE_FALLBACK": "1"}, mode, prec, pushes=E.HARD), "host fallback")
 
 
 @pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
@@ -148,14 +69,17 @@ def test_queued_frames_equal_frame_by_frame_and_repeat(da, om, monkeypatch, mode
     """RunFrames -- with device terrain every frame, limit, boundary and reset launch queued, the host never waits between them: equal bits show that the rule
     needs no host wait -- equals frame-by-frame Update(); a second run gives the same bits."""
     base = limit_run(om, monkeypatch, {}, mode, {})
-    E.assert_same_run(base, limit_run(om, monkeypatch, {}, mode, {}, run_frames=True), "RunFrames")
-    E.assert_same_run(base, limit_run(om, monkeypatch, {}, mode, {}), "run after run")
+    assert_same_end(base, limit_run(om, monkeypatch, {}, mode, {}, run_frames=True), "RunFrames")
+    assert_same_end(base, limit_run(om, monkeypatch, {}, mode, {}), "run after run")
 
 
 def test_fast_kernel_equals_reference_kernel_under_limits(da, om, monkeypatch):
     mode = dict(terrain_gen="device")
     base = limit_run(om, monkeypatch, {}, mode, {})
-    E.assert_same_run(base, limit_run(om, monkeypatch, {"DTRL_KERNEL": "ref"}, mode, {}), "DTRL_KERNEL=ref")
+    assert_same_end(base, limit_run(om, monkeypatch, {"DTRL_KERNEL": "ref"}, mode, {}), "DTRL_KERNEL=ref")
+
+
+FALLBACKS = dict.fromkeys(("DTRL_TERRAINS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_EPISODE_FALLBACK"), "1")
 
 
 @pytest.mark.parametrize("groups", ["1", "2"], ids=["one_group", "two_groups"])
@@ -163,10 +87,9 @@ def test_fast_kernel_equals_reference_kernel_under_limits(da, om, monkeypatch):
 def test_every_rule_at_once_equals_the_host_fallbacks(da, om, tmp_path, monkeypatch, mode, groups):
     """Ladder, redraw, rescale, push schedule and episode limit in one batch: the one-launch paths against every DTRL_*_FALLBACK knob at once, in states, windows
     and every rule's records."""
-    monkeypatch.setenv("DTRL_GROUPS", groups)
+    set_knobs(monkeypatch, {"DTRL_GROUPS": groups})
     base = E.run_all_rules(om, tmp_path, mode)
-    for k in ("DTRL_TERRAINS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_EPISODE_FALLBACK"):
-        monkeypatch.setenv(k, "1")
+    set_knobs(monkeypatch, dict(FALLBACKS, DTRL_GROUPS=groups))
     E.assert_same_run(base, E.run_all_rules(om, tmp_path, mode), "host fallbacks")
 
 
@@ -175,18 +98,10 @@ def test_every_rule_at_once_equals_the_host_fallbacks(da, om, tmp_path, monkeypa
 def test_listed_starts_equal_the_host_fallbacks(da, om, tmp_path, monkeypatch, mode, groups):
     """dtrl_reset, a terrain restart and an env coming into the limit between frames under all five rules: the listed launches against every DTRL_*_FALLBACK
     knob at once, in states, windows and every rule's records."""
-    monkeypatch.setenv("DTRL_GROUPS", groups)
+    set_knobs(monkeypatch, {"DTRL_GROUPS": groups})
     base = E.run_listed_starts(om, tmp_path, mode)
-    for k in ("DTRL_TERRAINS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_EPISODE_FALLBACK"):
-        monkeypatch.setenv(k, "1")
+    set_knobs(monkeypatch, dict(FALLBACKS, DTRL_GROUPS=groups))
     E.assert_same_run(base, E.run_listed_starts(om, tmp_path, mode), "host fallbacks")
 
 
-SYMBOLS = ("dtrl_episode_limit", "dtrl_episode_limit_envs", "dtrl_episode_info")
-
-
-@pytest.mark.parametrize("lib", ["libdtrl.so", "libdtrl_f32.so"])
-def test_new_symbols_resolve(lib):
-    lib_ = ctypes.CDLL(os.path.join(os.path.dirname(HIP_LIB), lib))
-    for name in SYMBOLS:
-        assert getattr(lib_, name) is not None, name
+test_new_symbols_resolve = symbols_test(("dtrl_episode_limit", "dtrl_episode_limit_envs", "dtrl_episode_info"))

@@ -4,9 +4,6 @@ against its host fallback (DTRL_EPISODE_LOG_FALLBACK=1) byte for byte in the dra
 ranges, the second ragged) with one and two env groups, both terrain modes and both libraries, with rings of 4096 rows and of 4 (the slot-collision case: 70 rows in
 one boundary); at 1100 envs in one group (two envs per thread with a ragged tail, rows from every wave through the scan's second level); frames queued without a
 host wait (RunFrames) against frame-by-frame Update, run after run; and the new symbols in both libraries."""
-import ctypes
-import os
-
 import pytest
 
 import test_episode_limit as E
@@ -19,68 +16,16 @@ import test_push_schedule as R
 import test_terrain_ladder as LD
 import test_terrain_sets as T
 import test_variant_rescale as VR
-from conftest import HIP_LIB
+from product import product_batch, set_knobs, symbols_test
+# ---- twins: the CPU tests themselves, collected here under the module's gpu mark and fixture ----
+from test_episode_log import (test_a_parked_env_counts_no_frame, test_drain_while_a_frame_is_in_flight, test_episode_outcomes_tool, test_external_log_equals_internal,  # noqa: F401
+                              test_keys_and_draws_are_the_episodes_own, test_listed_starts_and_lifecycle, test_ring_keeps_the_last_rows_of_a_boundary,
+                              test_rows_carry_the_slot, test_rows_equal_frame_by_frame_polling, test_rows_equal_frame_by_frame_polling_fp32,
+                              test_two_env_groups_merge_in_boundary_env_order)
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("DTRL_KERNEL", "DTRL_TERRAINS_FALLBACK", "DTRL_SLOTS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_EPISODE_FALLBACK", "DTRL_TRACE_FALLBACK",
-         "DTRL_EPISODE_LOG_FALLBACK", "DTRL_GROUPS")
-
-
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    for mod in (R, T, V, X, P, LD, H, VR):
-        monkeypatch.setattr(mod, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-
-
-# ---- twins ----
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_rows_equal_frame_by_frame_polling(da, om, mode):
-    L.test_rows_equal_frame_by_frame_polling(da, om, mode)
-
-
-def test_rows_equal_frame_by_frame_polling_fp32(da, om):
-    L.test_rows_equal_frame_by_frame_polling_fp32(da, om)
-
-
-def test_two_env_groups_merge_in_boundary_env_order(da, om, monkeypatch):
-    L.test_two_env_groups_merge_in_boundary_env_order(da, om, monkeypatch)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_keys_and_draws_are_the_episodes_own(da, om, tmp_path, mode):
-    L.test_keys_and_draws_are_the_episodes_own(da, om, tmp_path, mode)
-
-
-def test_rows_carry_the_slot(da, om):
-    L.test_rows_carry_the_slot(da, om)
-
-
-@pytest.mark.parametrize("groups", ["1", "2"], ids=["one_group", "two_groups"])
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_ring_keeps_the_last_rows_of_a_boundary(da, om, monkeypatch, mode, groups):
-    L.test_ring_keeps_the_last_rows_of_a_boundary(da, om, monkeypatch, mode, groups)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_listed_starts_and_lifecycle(da, om, mode):
-    L.test_listed_starts_and_lifecycle(da, om, mode)
-
-
-def test_external_log_equals_internal(da, om, monkeypatch):
-    L.test_external_log_equals_internal(da, om, monkeypatch)
-
-
-def test_a_parked_env_counts_no_frame(da, om):
-    L.test_a_parked_env_counts_no_frame(da, om)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_drain_while_a_frame_is_in_flight(da, om, mode):
-    L.test_drain_while_a_frame_is_in_flight(da, om, mode)
+hip_batch = product_batch(R, T, V, X, P, LD, H, VR)
+NOT_TWINNED = {}
 
 
 @pytest.mark.parametrize("overlap", [False, True], ids=["sequential", "overlapped"])
@@ -89,19 +34,12 @@ def test_train_loop_logs_episodes(da, om, monkeypatch, overlap):
     L.test_train_loop_logs_episodes(da, om, overlap)
 
 
-def test_episode_outcomes_tool(da, om):
-    L.test_episode_outcomes_tool(da, om)
-
-
 # ---- GPU only: the kernel against its host fallback, byte for byte ----
 N, FRAMES = L.N, 30
 
 
 def logged_run(om, monkeypatch, env, mode, extra, capacity, run_frames=False, n=N, frames=FRAMES, limits=E.LIMITS, pushes=True):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_knobs(monkeypatch, env)
     if pushes:
         extra = dict(extra, min_perturb=E.HARD[0], max_perturb=E.HARD[1], min_pertrub_duration=0.1, max_perturb_duration=0.25)   # hard pushes: falls among the rows
     b = E.limit_batch(om, n, mode, frames=limits, **extra)
@@ -175,11 +113,4 @@ def test_queued_frames_equal_frame_by_frame_and_repeat(da, om, monkeypatch, mode
     assert_same_log(base, logged_run(om, monkeypatch, {}, mode, {}, 4096), "run after run")
 
 
-SYMBOLS = ("dtrl_episode_log", "dtrl_episode_log_info", "dtrl_episode_log_drain", "dtrl_variant_rescale_factors")
-
-
-@pytest.mark.parametrize("lib", ["libdtrl.so", "libdtrl_f32.so"])
-def test_new_symbols_resolve(lib):
-    lib_ = ctypes.CDLL(os.path.join(os.path.dirname(HIP_LIB), lib))
-    for name in SYMBOLS:
-        assert getattr(lib_, name) is not None, name
+test_new_symbols_resolve = symbols_test(("dtrl_episode_log", "dtrl_episode_log_info", "dtrl_episode_log_drain", "dtrl_variant_rescale_factors"))

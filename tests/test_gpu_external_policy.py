@@ -6,45 +6,14 @@ import pytest
 import test_external_policy as T
 from conftest import REFDATA, EmulScenario
 from precision import assert_library, both_precisions, extra_for
+from product import product_batch, set_knobs
+# ---- twins: the CPU tests themselves, collected here under the module's gpu mark and fixture ----
+from test_external_policy import (test_exp_scenario_tuples_equal, test_first_decision_against_oracle_forward, test_liveness_and_accounting, test_refusals,  # noqa: F401
+                                  test_replay_internal_run_bit_for_bit, test_run_external_host_callable, test_snapshots_carry_park_state_and_delivered_actions)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    monkeypatch.setattr(T, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: T.batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
-
-
-# ---- twins ----
-@pytest.mark.parametrize("arg,extra", T.REPLAY_CASES)
-def test_replay_internal_run_bit_for_bit(da, om, arg, extra):
-    T.test_replay_internal_run_bit_for_bit(da, om, arg, extra)
-
-
-def test_exp_scenario_tuples_equal(da, om):
-    T.test_exp_scenario_tuples_equal(da, om)
-
-
-def test_first_decision_against_oracle_forward(da, om):
-    T.test_first_decision_against_oracle_forward(da, om)
-
-
-def test_liveness_and_accounting(da, om):
-    T.test_liveness_and_accounting(da, om)
-
-
-@pytest.mark.parametrize("extra", [dict(), dict(terrain_gen="device")], ids=["host_terrain", "device_terrain"])
-def test_snapshots_carry_park_state_and_delivered_actions(da, om, extra):
-    T.test_snapshots_carry_park_state_and_delivered_actions(da, om, extra)
-
-
-def test_refusals(da, om):
-    T.test_refusals(da, om)
-
-
-def test_run_external_host_callable(da, om):
-    T.test_run_external_host_callable(da, om)
+hip_batch = product_batch(T)
+NOT_TWINNED = {"test_hand_over_at_width": "runs at the same width in tests/test_gpu_handover_width.py, on torch tensors, with the other hand-over kernels' second paths"}
 
 
 # ---- cross-checks ----
@@ -86,10 +55,7 @@ def test_external_fast_kernel_equals_external_reference_kernel_bitwise(da, om, m
     the first decision. Reached under by_env, lane-loop check build | reference kernel on the device: 101 ticks,
     1629 cycles, 76 resets, 108 distinct x | 101 ticks, 1626 cycles, 91 resets, 102 distinct x."""
     def run(kernel):
-        if kernel:
-            monkeypatch.setenv("DTRL_KERNEL", kernel)
-        else:
-            monkeypatch.delenv("DTRL_KERNEL", raising=False)
+        set_knobs(monkeypatch, {"DTRL_KERNEL": kernel} if kernel else {})
         b = T.batch(da, arg, n, **extra_for(prec, policy_mode="external", terrain_seed=77, rand_seed=4))
         assert_library(b, prec)
         out = drive(b, frames, tuples, by_env=(prec == "f32" and arg == T.RAPTOR))
@@ -114,10 +80,7 @@ def test_external_kernels_against_lane_loop_build(da, om, monkeypatch, arg, n=32
     def make(cls, **kw):
         return cls(arg, n, data_root=REFDATA, extra_args=dict(policy_mode="external", terrain_seed=77, rand_seed=4, **kw))
     for kernel in (None, "ref"):
-        if kernel:
-            monkeypatch.setenv("DTRL_KERNEL", kernel)
-        else:
-            monkeypatch.delenv("DTRL_KERNEL", raising=False)
+        set_knobs(monkeypatch, {"DTRL_KERNEL": kernel} if kernel else {})
         g = make(da.BatchScenario); c = make(EmulScenario)
         policy = T.scripted(c)
         for _ in range(3):                                     # first env-step (every env parks), then two whole frames

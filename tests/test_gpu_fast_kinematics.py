@@ -25,9 +25,13 @@ import pytest
 
 from conftest import REFDATA
 from precision import both_precisions, check_build, extra_for
+from product import fast_and_reference
 from test_gpu_fsub_rhs import CASES, policy_of, product
 
 N_ENVS, FRAMES, TERRAIN_SEED = 192, 30, 77
+# this rollout's records: the link states in front, no eval stats (not test_gpu_fsub_rhs.NAMES)
+NAMES = ("link COM", "link velocity", "link angle", "pose", "velocity", "control torques", "applied torques", "contact flags", "cache count", "cache ids", "cache impulses",
+         "cycle counters", "reset counters")
 TURNS, SPIN, LIFT = 7, 25.0, 1.0
 PARENT = {   # dtrl_topo.h
     "dog": (-1, 0, 1, 2, 3, 4, 5, 6, 7, 0, 9, 10, 11, 5, 13, 14, 15, 0, 17, 18, 19),
@@ -103,22 +107,8 @@ def check_reached(reached):
 @pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
 def test_fast_kinematics_equals_reference_bitwise(da, om, monkeypatch, arg, skel, prec):
     pol = policy_of(om, skel)
-
-    def run(kernel):
-        if kernel:
-            monkeypatch.setenv("DTRL_KERNEL", kernel)
-        else:
-            monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        return rollout(product(da, arg, N_ENVS, prec, terrain_seed=TERRAIN_SEED), pol, skel)
-
-    ff, rf = run(None)
-    fr, rr = run("ref")
+    (_, rf), (_, rr) = fast_and_reference(monkeypatch, lambda: rollout(product(da, arg, N_ENVS, prec, terrain_seed=TERRAIN_SEED), pol, skel), NAMES)
     check_reached(rr)
-    names = ("link COM", "link velocity", "link angle", "pose", "velocity", "control torques", "applied torques", "contact flags", "cache count", "cache ids", "cache impulses",
-             "cycle counters", "reset counters")
-    for f, (a, b_) in enumerate(zip(ff, fr)):
-        for name, x, y in zip(names, a, b_):
-            assert np.array_equal(x, y), "frame %d: %s differ" % (f, name)
     assert rf == rr
 
 

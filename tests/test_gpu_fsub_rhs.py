@@ -24,6 +24,7 @@ import pytest
 import test_host_and_emul as T
 from conftest import REFDATA, dog_policy
 from precision import assert_library, both_precisions, check_build, extra_for
+from product import fast_and_reference
 
 CASES = [("args/dog_slopes_mixed_args.txt", "dog"), ("args/raptor_narrow_gaps_args.txt", "raptor"), ("args/goat_cliffs_args.txt", "goat")]
 N_ENVS, FRAMES, TERRAIN_SEED = 192, 30, 77
@@ -31,6 +32,8 @@ NO_ROW_ID, FIRST_PAIR_ROW_ID, MAX_ROWS = 0xffff, 512, 24      # dtrl_kernel.h kN
 FOLD = {"dog": ((14, 2.95), (15, 0.3)), "goat": ((14, 2.95), (15, 0.3)), "raptor": ((12, 2.6), (13, -2.6))}   # (link, hinge angle): a leg folded until two of its boxes overlap
 PUSH_FRAME = 3
 SINK = 0.25
+# the fields of a frame's record, in rollout()'s order: the one tuple of names of the fast-against-reference tests
+NAMES = ("cache count", "cache ids", "cache impulses", "contact flags", "pose", "velocity", "control torques", "applied torques", "cycle counters", "reset counters", "eval stats")
 
 
 def rollout(make, pol, skel, n=N_ENVS, frames=FRAMES):
@@ -102,21 +105,8 @@ def product(da, arg, n, prec, **extra):
 @pytest.mark.parametrize("arg,skel,prec", both_precisions(CASES))
 def test_fsub_rhs_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel, prec):
     pol = policy_of(om, skel)
-
-    def run(kernel):
-        if kernel:
-            monkeypatch.setenv("DTRL_KERNEL", kernel)
-        else:
-            monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        return rollout(product(da, arg, N_ENVS, prec, terrain_seed=TERRAIN_SEED), pol, skel)
-
-    ff, rf = run(None)
-    fr, rr = run("ref")
+    (_, rf), (_, rr) = fast_and_reference(monkeypatch, lambda: rollout(product(da, arg, N_ENVS, prec, terrain_seed=TERRAIN_SEED), pol, skel), NAMES)
     check_reached(rr)
-    names = ("cache count", "cache ids", "cache impulses", "contact flags", "pose", "velocity", "control torques", "applied torques", "cycle counters", "reset counters", "eval stats")
-    for f, (a, b_) in enumerate(zip(ff, fr)):
-        for name, x, y in zip(names, a, b_):
-            assert np.array_equal(x, y), "frame %d: %s differ" % (f, name)
     assert rf == rr
 
 

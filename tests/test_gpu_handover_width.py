@@ -12,17 +12,10 @@ import test_boundary as B
 import test_device_terrain as D
 import test_external_policy as X
 import test_policy_slots as P
+from product import product_batch
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    for mod in (B, X, P):
-        monkeypatch.setattr(mod, "Scenario", deepterrainrl_amd.BatchScenario)
-    for k in ("DTRL_KERNEL", "DTRL_SLOTS_FALLBACK", "DTRL_GROUPS"):
-        monkeypatch.delenv(k, raising=False)
+hip_batch = product_batch(B, X, P)
 
 
 @pytest.fixture(autouse=True)

@@ -4,25 +4,20 @@ kernels against the variant reference kernel and the per-variant fallback, two e
 import numpy as np
 import pytest
 
-import test_external_policy as X
 import test_model_variants as T
 from conftest import REFDATA
 from precision import assert_library, both_precisions, extra_for
+from product import assert_same_end, end_state, product_batch, set_knobs
+# ---- twins: the CPU tests themselves, collected here under the module's gpu mark and fixture ----
+from test_model_variants import (test_batch_state_and_host_readers, test_batch_without_variants_launches_as_before, test_exp_scenario_tuples, test_refusals,  # noqa: F401
+                                 test_scaled_variant_equals_the_file, test_variant_stats, test_variant_stats_more_variants_than_one_window)
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("DTRL_KERNEL", "DTRL_VARIANTS_FALLBACK", "DTRL_GROUPS")
-
-
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    monkeypatch.setattr(T, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: T.batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+hip_batch = product_batch(T)
+NOT_TWINNED = {}
 
 
-# ---- twins ----
+# ---- the twin with cases of its own: both libraries ----
 F32_CASES = [(T.DOG, dict(terrain_seed=11, physics_precision="f32")), (T.RAPTOR, dict(terrain_seed=5, physics_precision="f32"))]
 
 
@@ -31,60 +26,16 @@ def test_equals_single_model_runs(da, om, tmp_path, arg, extra):
     T.run_equals_single_model(om, tmp_path, arg, extra)
 
 
-def test_exp_scenario_tuples(da, om, tmp_path):
-    T.test_exp_scenario_tuples(da, om, tmp_path)
-
-
-def test_variant_stats(da, om, tmp_path):
-    T.test_variant_stats(da, om, tmp_path)
-
-
-def test_variant_stats_more_variants_than_one_window(da, om):
-    T.test_variant_stats_more_variants_than_one_window(da, om)
-
-
-def test_batch_state_and_host_readers(da, om, tmp_path):
-    T.test_batch_state_and_host_readers(da, om, tmp_path)
-
-
-def test_scaled_variant_equals_the_file(da, om, tmp_path):
-    T.test_scaled_variant_equals_the_file(da, om, tmp_path)
-
-
-def test_refusals(da, om, tmp_path):
-    T.test_refusals(da, om, tmp_path)
-
-
-def test_batch_without_variants_launches_as_before(da, om, tmp_path):
-    T.test_batch_without_variants_launches_as_before(da, om, tmp_path)
-
-
 # ---- cross-checks: 192 envs, 3 variants, 90 frames, bit for bit ----
-def end_state(b):
-    n = b.num_envs
-    return X.env_states(b), b.RecordPoliState(), [X.ground_key(b, e) for e in range(n)], b.EvalStats(), [b.VariantStats(v) for v in range(b.num_variants)]
-
-
-def assert_same_end(x, y, what):
-    bad = X.same_record(x[0], y[0])
-    assert bad is None, "%s: EnvState.%s differs" % (what, bad)
-    assert x[1].tobytes() == y[1].tobytes(), "%s: policy states differ" % what
-    assert x[2] == y[2], "%s: ground windows / build counts differ" % what
-    assert x[3] == y[3] and x[4] == y[4], "%s: statistics differ" % what
-
-
 def variant_run(om, monkeypatch, tmp_path, arg, env, extra, n=192, frames=90):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_knobs(monkeypatch, env)
     b = T.with_variants(om, arg, n, T.write_variants(tmp_path, arg), [e % 3 for e in range(n)], dict(terrain_seed=77, rand_seed=4, **extra))
     assert_library(b, extra.get("physics_precision", "f64"))
     for _ in range(frames):
         b.Update()
-    out = end_state(b)
-    assert out[3]["cycles"] > n and out[3]["resets"] > 0 and all(s["cycles"] > 0 for s in out[4])
-    return out
+    ev, variants = b.EvalStats(), [b.VariantStats(v) for v in range(b.num_variants)]
+    assert ev["cycles"] > n and ev["resets"] > 0 and all(s["cycles"] > 0 for s in variants)
+    return end_state(b, statistics=(ev, variants))
 
 
 @pytest.mark.parametrize("arg,prec", both_precisions([T.DOG, T.RAPTOR], ids=["dog", "raptor"]))

@@ -9,6 +9,7 @@ import pytest
 import test_host_and_emul as T
 from conftest import REFDATA, GOLDEN, HIP_LIB, dog_policy, pin_to_oracle
 from precision import assert_library, both_precisions, extra_for
+from product import set_knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -20,6 +21,7 @@ def hip_batch(monkeypatch):
     monkeypatch.setattr(T, "batch", make)
     import deepterrainrl_amd
     monkeypatch.setattr(T, "Scenario", deepterrainrl_amd.BatchScenario)
+    set_knobs(monkeypatch, {})
 
 
 def test_native_library_is_loaded(da):
@@ -230,10 +232,7 @@ def test_fast_kernel_equals_reference_kernel_bitwise(da, om, monkeypatch, arg, n
     raptor = "raptor" in arg
     pol = T.raptor_policy(om) if raptor else dog_policy(om)
     def run(kernel):
-        if kernel:
-            monkeypatch.setenv("DTRL_KERNEL", kernel)
-        else:
-            monkeypatch.delenv("DTRL_KERNEL", raising=False)
+        set_knobs(monkeypatch, {"DTRL_KERNEL": kernel} if kernel else {})
         b = T.batch(da, arg, n, **extra_for(prec, terrain_seed=77))
         assert_library(b, prec)
         b.SetPolicy(pol[1], *pol[2:])

@@ -7,19 +7,17 @@ import pytest
 import test_external_policy as X
 import test_policy_slots as T
 from precision import assert_library, both_precisions, extra_for
+from product import assert_same_end, end_state, product_batch, set_knobs
+# ---- twins: the CPU tests themselves, collected here under the module's gpu mark and fixture ----
+from test_policy_slots import (test_alias_follows_slot0, test_batch_without_slots_launches_as_before, test_exp_scenario_tuples, test_reassignment_mid_run,  # noqa: F401
+                               test_refusals, test_slot_stats, test_slot_stats_waits_for_a_frame_in_flight, test_snapshots_and_clones_keep_the_assignment)
 
 pytestmark = pytest.mark.gpu
+hip_batch = product_batch(T)
+NOT_TWINNED = {"test_train_loop_greedy_envs": "the loop's host logic, on a recording subclass of the lane-loop scenario: lane-loop build only"}
 
 
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    monkeypatch.setattr(T, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: T.batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
-    for k in ("DTRL_KERNEL", "DTRL_SLOTS_FALLBACK", "DTRL_GROUPS"):
-        monkeypatch.delenv(k, raising=False)
-
-
-# ---- twins ----
+# ---- the twin with cases of its own: both libraries ----
 F32_CASES = [(T.DOG, dict(terrain_seed=11, physics_precision="f32")), (T.RAPTOR, dict(terrain_seed=5, physics_precision="f32"))]
 
 
@@ -28,64 +26,16 @@ def test_equals_single_policy_runs(da, om, arg, extra):
     T.run_equals_single_policy(om, arg, extra)
 
 
-def test_exp_scenario_tuples(da, om):
-    T.test_exp_scenario_tuples(da, om)
-
-
-def test_alias_follows_slot0(da, om):
-    T.test_alias_follows_slot0(da, om)
-
-
-def test_reassignment_mid_run(da, om):
-    T.test_reassignment_mid_run(da, om)
-
-
-def test_snapshots_and_clones_keep_the_assignment(da, om):
-    T.test_snapshots_and_clones_keep_the_assignment(da, om)
-
-
-def test_slot_stats(da, om):
-    T.test_slot_stats(da, om)
-
-
-def test_refusals(da, om):
-    T.test_refusals(da, om)
-
-
-def test_slot_stats_waits_for_a_frame_in_flight(da, om):
-    T.test_slot_stats_waits_for_a_frame_in_flight(da, om)
-
-
-def test_batch_without_slots_launches_as_before(da, om):
-    T.test_batch_without_slots_launches_as_before(da, om)
-
-
 # ---- cross-checks: 192 envs, 3 slots, 90 frames, bit for bit ----
-def end_state(b):
-    n = b.num_envs
-    return X.env_states(b), b.RecordPoliState(), [X.ground_key(b, e) for e in range(n)], b.EvalStats(), [b.SlotStats(s) for s in range(b.num_slots)]
-
-
-def assert_same_end(x, y, what):
-    bad = X.same_record(x[0], y[0])
-    assert bad is None, "%s: EnvState.%s differs" % (what, bad)
-    assert x[1].tobytes() == y[1].tobytes(), "%s: policy states differ" % what
-    assert x[2] == y[2], "%s: ground windows / build counts differ" % what
-    assert x[3] == y[3] and x[4] == y[4], "%s: statistics differ" % what
-
-
 def slot_run(om, monkeypatch, arg, env, extra, n=192, frames=90):
-    for k in ("DTRL_KERNEL", "DTRL_SLOTS_FALLBACK", "DTRL_GROUPS"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_knobs(monkeypatch, env)
     b = T.slotted(arg, n, T.policies(om, arg), T.EXPLORE, [e % 3 for e in range(n)], dict(terrain_seed=77, rand_seed=4, **extra))
     assert_library(b, extra.get("physics_precision", "f64"))
     for _ in range(frames):
         b.Update()
-    out = end_state(b)
-    assert out[3]["cycles"] > n and out[3]["resets"] > 0 and all(s["cycles"] > 0 for s in out[4])
-    return out
+    ev, slots = b.EvalStats(), [b.SlotStats(s) for s in range(b.num_slots)]
+    assert ev["cycles"] > n and ev["resets"] > 0 and all(s["cycles"] > 0 for s in slots)
+    return end_state(b, statistics=(ev, slots))
 
 
 @pytest.mark.parametrize("arg,prec", both_precisions([T.DOG, T.RAPTOR], ids=["dog", "raptor"]))

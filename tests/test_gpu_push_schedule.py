@@ -4,9 +4,6 @@ dtrl_perturb_scatter per dtrl_add_perturb -- and what only exists on HIP: the ke
 at 70 envs / rows (two 64-thread blocks, the second partial) with one and two env groups in both libraries, frames queued without a host wait (RunFrames) against
 frame-by-frame Update, run-to-run determinism, the fast kernel against the reference kernel under a schedule, every frame-boundary rule (ladder, redraw, schedule) in ONE batch
 against all the host fallbacks at once, and the new symbols in both libraries."""
-import ctypes
-import os
-
 import pytest
 
 import test_external_policy as X
@@ -16,87 +13,24 @@ import test_policy_slots as P
 import test_push_schedule as R
 import test_terrain_ladder as LD
 import test_terrain_sets as T
-from conftest import HIP_LIB
+from product import assert_same_end, end_state, product_batch, set_knobs, symbols_test
+# ---- twins: the CPU tests themselves, collected here under the module's gpu mark and fixture ----
+from test_push_schedule import (test_add_perturb_equals_row_by_row, test_apply_rand_force_goes_through_the_launch, test_batch_state_resets_and_removal,  # noqa: F401
+                                test_held_out_envs_equal_a_batch_without_schedule, test_push_robustness_tool, test_refusals, test_replay_through_add_perturb,
+                                test_scale_multiplies_the_force_and_nothing_else, test_scheduled_push_vs_oracle, test_shard_invariance,
+                                test_with_model_variants_and_redraw, test_with_policy_slots, test_with_terrain_ladder)
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("DTRL_KERNEL", "DTRL_TERRAINS_FALLBACK", "DTRL_SLOTS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_GROUPS")
-
-
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    for mod in (R, T, V, X, P, LD, H):
-        monkeypatch.setattr(mod, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+hip_batch = product_batch(R, T, V, X, P, LD, H)
+NOT_TWINNED = {}
 
 
-# ---- twins ----
+# ---- twins with cases or a body of their own ----
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 @pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
 def test_records_equal_the_rule(da, om, mode, precision):
     """(both libraries: the rule is doubles and integers in either, so the fp32 library's records equal the same Python rule, given its own falls)"""
     R.test_records_equal_the_rule(da, om, mode, **(dict(physics_precision="f32") if precision == "f32" else {}))
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_replay_through_add_perturb(da, om, mode):
-    R.test_replay_through_add_perturb(da, om, mode)
-
-
-def test_scheduled_push_vs_oracle(da, om):
-    R.test_scheduled_push_vs_oracle(da, om)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_held_out_envs_equal_a_batch_without_schedule(da, om, mode):
-    R.test_held_out_envs_equal_a_batch_without_schedule(da, om, mode)
-
-
-def test_scale_multiplies_the_force_and_nothing_else(da, om):
-    R.test_scale_multiplies_the_force_and_nothing_else(da, om)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_batch_state_resets_and_removal(da, om, mode):
-    R.test_batch_state_resets_and_removal(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_shard_invariance(da, om, mode):
-    R.test_shard_invariance(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_with_policy_slots(da, om, mode):
-    R.test_with_policy_slots(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_with_model_variants_and_redraw(da, om, tmp_path, mode):
-    R.test_with_model_variants_and_redraw(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_with_terrain_ladder(da, om, mode):
-    R.test_with_terrain_ladder(da, om, mode)
-
-
-def test_refusals(da, om):
-    R.test_refusals(da, om)
-
-
-def test_add_perturb_equals_row_by_row(da, om, tmp_path):
-    R.test_add_perturb_equals_row_by_row(da, om, tmp_path)
-
-
-def test_apply_rand_force_goes_through_the_launch(da, om):
-    R.test_apply_rand_force_goes_through_the_launch(da, om)
-
-
-def test_push_robustness_tool(da, om):
-    R.test_push_robustness_tool(da, om)
 
 
 def test_train_loop_with_pushes(da, om):
@@ -109,16 +43,13 @@ def test_train_loop_with_pushes(da, om):
 N, FRAMES = 70, 30
 
 
-def end_state(b):
+def push_end(b):
     info = b.PushInfo()
-    return X.env_states(b), b.RecordPoliState(), [X.ground_key(b, e) for e in range(b.num_envs)], {k: v.tobytes() for k, v in info.items()}, info
+    return end_state(b, info, push_records={k: v.tobytes() for k, v in info.items()})
 
 
 def push_run(om, monkeypatch, env, mode, extra, run_frames=False):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_knobs(monkeypatch, env)
     scale = [0.0 if e % 7 == 3 else 1.0 + 0.25 * (e % 3) for e in range(N)]     # held-out envs and a magnitude sweep in both blocks
     b = R.push_batch(om, N, mode, scale=scale, **extra)
     if run_frames:
@@ -126,9 +57,9 @@ def push_run(om, monkeypatch, env, mode, extra, run_frames=False):
     else:
         for _ in range(FRAMES):
             b.Update()
-    out = end_state(b)
-    pushes = out[4]["pushes"]
-    assert pushes[[e for e in range(N) if e % 7 != 3]].min() >= 3 and not pushes[3::7].any() and out[0]["num_resets"][64:].sum() >= 1, pushes
+    out = push_end(b)
+    pushes = out["info"]["pushes"]
+    assert pushes[[e for e in range(N) if e % 7 != 3]].min() >= 3 and not pushes[3::7].any() and out["env_states"]["num_resets"][64:].sum() >= 1, pushes
     return out
 
 
@@ -140,7 +71,7 @@ def test_push_kernel_equals_host_fallback(da, om, monkeypatch, mode, precision, 
     non-zero e0."""
     extra = dict(physics_precision="f32") if precision == "f32" else {}
     base = push_run(om, monkeypatch, {"DTRL_GROUPS": groups}, mode, extra)
-    R.assert_same_end(base, push_run(om, monkeypatch, {"DTRL_GROUPS": groups, "DTRL_PUSH_FALLBACK": "1"}, mode, extra), "host fallback")
+    assert_same_end(base, push_run(om, monkeypatch, {"DTRL_GROUPS": groups, "DTRL_PUSH_FALLBACK": "1"}, mode, extra), "host fallback")
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
@@ -152,9 +83,7 @@ def test_perturb_scatter_equals_host_fallback(da, om, tmp_path, monkeypatch, pre
     extra = dict(terrain_seed=11, **(dict(physics_precision="f32") if precision == "f32" else {}))
 
     def run(fallback):
-        monkeypatch.delenv("DTRL_PERTURB_FALLBACK", raising=False)
-        if fallback:
-            monkeypatch.setenv("DTRL_PERTURB_FALLBACK", "1")
+        set_knobs(monkeypatch, {"DTRL_PERTURB_FALLBACK": "1"} if fallback else {})
         b = V.with_variants(om, R.DOG, n, paths, [e % 4 for e in range(n)], extra)
         b.Update()
         b.AddPerturb(link, force, dur, local_pos=lp, env_ids=env)
@@ -177,14 +106,14 @@ def test_queued_frames_equal_frame_by_frame_and_repeat(da, om, monkeypatch, mode
     """RunFrames -- with device terrain every frame, boundary, push and reset launch queued, the host never waits between them -- equals frame-by-frame Update(); a
     second run gives the same bits."""
     base = push_run(om, monkeypatch, {}, mode, {})
-    R.assert_same_end(base, push_run(om, monkeypatch, {}, mode, {}, run_frames=True), "RunFrames")
-    R.assert_same_end(base, push_run(om, monkeypatch, {}, mode, {}), "run after run")
+    assert_same_end(base, push_run(om, monkeypatch, {}, mode, {}, run_frames=True), "RunFrames")
+    assert_same_end(base, push_run(om, monkeypatch, {}, mode, {}), "run after run")
 
 
 def test_fast_kernel_equals_reference_kernel_under_a_schedule(da, om, monkeypatch):
     mode = dict(terrain_gen="device")
     base = push_run(om, monkeypatch, {}, mode, {})
-    R.assert_same_end(base, push_run(om, monkeypatch, {"DTRL_KERNEL": "ref"}, mode, {}), "DTRL_KERNEL=ref")
+    assert_same_end(base, push_run(om, monkeypatch, {"DTRL_KERNEL": "ref"}, mode, {}), "DTRL_KERNEL=ref")
 
 
 # ---- GPU only: every frame-boundary rule in one batch ----
@@ -193,10 +122,7 @@ RESET_IDS = [69, 3, 64, 17, 66, 0, 40, 65]     # out of order, in both 64-thread
 
 def all_rules_run(om, tmp_path, monkeypatch, env, n=N, frames=FRAMES):
     """Terrain sets under a ladder, model variants under a redraw and a push schedule on device terrain; a reset of RESET_IDS halfway."""
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_knobs(monkeypatch, env)
     paths = V.write_variants(tmp_path, R.DOG)
     b = V.with_variants(om, R.DOG, n, paths, [e % 3 for e in range(n)], dict(terrain_seed=31, rand_seed=3, terrain_gen="device"))
     T.fill(b, T.four_walkable_files(T.DOG))
@@ -216,7 +142,7 @@ def all_rules_run(om, tmp_path, monkeypatch, env, n=N, frames=FRAMES):
     keys.update(("redraw " + k, v.tobytes() if hasattr(v, "tobytes") else v) for k, v in redraw.items())
     assert keys["variant"] == list(redraw["variant"])
     moved = int(ladder["ups"].sum() + ladder["downs"].sum())
-    return end_state(b), keys, (moved, int(redraw["draws"].sum()), int(redraw["draws"][64:].sum()))
+    return push_end(b), keys, (moved, int(redraw["draws"].sum()), int(redraw["draws"][64:].sum()))
 
 
 @pytest.mark.parametrize("groups", ["1", "2"], ids=["one_group", "two_groups"])
@@ -226,19 +152,12 @@ def test_all_rules_in_one_batch_equal_the_host_fallbacks(da, om, tmp_path, monke
     DTRL_PUSH_FALLBACK) -- env states, windows, terrain and variant keys, ladder records, redraw counters and push records bit for bit. Two calls of
     dtrl_get_terrains with no frame between return the same levels (the second refreshes nothing)."""
     base, keys, (moved, draws, draws_hi) = all_rules_run(om, tmp_path, monkeypatch, {"DTRL_GROUPS": groups})
-    assert moved >= 1 and draws >= len(RESET_IDS) + 1 and draws_hi >= 1 and base[4]["pushes"].min() >= 1, (moved, draws, draws_hi, base[4]["pushes"])
+    assert moved >= 1 and draws >= len(RESET_IDS) + 1 and draws_hi >= 1 and base["info"]["pushes"].min() >= 1, (moved, draws, draws_hi, base["info"]["pushes"])
     fb = {"DTRL_GROUPS": groups, "DTRL_TERRAINS_FALLBACK": "1", "DTRL_VARIANTS_FALLBACK": "1", "DTRL_PUSH_FALLBACK": "1"}
     other, other_keys, _ = all_rules_run(om, tmp_path, monkeypatch, fb)
-    R.assert_same_end(base, other, "host fallbacks")
+    assert_same_end(base, other, "host fallbacks")
     for k in keys:
         assert keys[k] == other_keys[k], "%s differs from the host fallbacks" % k
 
 
-SYMBOLS = ("dtrl_push_schedule", "dtrl_push_scale", "dtrl_push_info")
-
-
-@pytest.mark.parametrize("lib", ["libdtrl.so", "libdtrl_f32.so"])
-def test_new_symbols_resolve(lib):
-    lib_ = ctypes.CDLL(os.path.join(os.path.dirname(HIP_LIB), lib))
-    for name in SYMBOLS:
-        assert getattr(lib_, name) is not None, name
+test_new_symbols_resolve = symbols_test(("dtrl_push_schedule", "dtrl_push_scale", "dtrl_push_info"))

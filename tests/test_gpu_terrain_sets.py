@@ -2,124 +2,34 @@
 Backend::TerrainBoundary, here ONE launch of dtrl_terrain_boundary_keyed per env group and frame -- and what only exists on HIP: the keyed kernel against the
 host fallback (DTRL_TERRAINS_FALLBACK=1) with one and two env groups, in both libraries and under the reference frame kernel, determinism and shard invariance of
 mixed device terrain, and the new symbols in both libraries."""
-import ctypes
-import os
-
-import numpy as np
 import pytest
 
 import test_external_policy as X
 import test_model_variants as V
 import test_policy_slots as P
 import test_terrain_sets as T
-from conftest import HIP_LIB
+from product import assert_same_end, end_state, product_batch, set_knobs, symbols_test
+# ---- twins: the CPU tests themselves, collected here under the module's gpu mark and fixture ----
+from test_terrain_sets import (test_batch_state, test_batch_without_terrains_launches_as_before, test_envs_are_independent, test_no_restart_equals_curriculum_step,  # noqa: F401
+                               test_queued_behind_unfinished_frames, test_refusals, test_restart_after_frames_equals_creation, test_restart_equals_creation,
+                               test_terrain_zero_follows_the_curriculum, test_terrains_with_external_policy, test_terrains_with_model_variants,
+                               test_terrains_with_policy_slots, test_two_shards_equal_one_process)
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("DTRL_KERNEL", "DTRL_TERRAINS_FALLBACK", "DTRL_SLOTS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_GROUPS")
-
-
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    for mod in (T, V, P, X):
-        monkeypatch.setattr(mod, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-
-
-# ---- twins ----
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-@pytest.mark.parametrize("arg", [T.DOG, T.RAPTOR], ids=["dog", "raptor"])
-def test_restart_equals_creation(da, om, arg, mode):
-    T.test_restart_equals_creation(da, om, arg, mode)
-
-
-def test_restart_after_frames_equals_creation(da, om):
-    T.test_restart_after_frames_equals_creation(da, om)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_no_restart_equals_curriculum_step(da, om, tmp_path, mode):
-    T.test_no_restart_equals_curriculum_step(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-@pytest.mark.parametrize("arg", [T.DOG, T.RAPTOR], ids=["dog", "raptor"])
-def test_envs_are_independent(da, om, arg, mode):
-    T.run_envs_are_independent(om, arg, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_terrains_with_policy_slots(da, om, mode):
-    T.run_with_slots(om, T.DOG, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_terrains_with_model_variants(da, om, tmp_path, mode):
-    T.run_with_variants(om, tmp_path, T.DOG, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_terrains_with_external_policy(da, om, mode):
-    T.run_with_external_policy(da, om, T.DOG, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_batch_state(da, om, mode):
-    T.test_batch_state(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_two_shards_equal_one_process(da, om, mode):
-    T.test_two_shards_equal_one_process(da, om, mode)
-
-
-def test_refusals(da, om, tmp_path):
-    T.test_refusals(da, om, tmp_path)
-
-
-def test_terrain_zero_follows_the_curriculum(da, om, tmp_path):
-    T.test_terrain_zero_follows_the_curriculum(da, om, tmp_path)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_batch_without_terrains_launches_as_before(da, om, mode):
-    T.test_batch_without_terrains_launches_as_before(da, om, mode)
-
-
-def test_queued_behind_unfinished_frames(da, om):
-    T.test_queued_behind_unfinished_frames(da, om)
+hip_batch = product_batch(T, V, P, X)
+NOT_TWINNED = {"test_terrain_sweep_tool": "a tool test (tools/terrain_sweep.py); had no twin before this change"}
 
 
 # ---- 7a / 7b. the keyed kernel against the host fallback: 192 envs, 4 terrains (cliffs_rugged among them), 90 frames, bit for bit ----
-def end_state(b):
-    n = b.num_envs
-    dist, ids = b.GetDistLog()
-    return (X.env_states(b), b.RecordPoliState(), [X.ground_key(b, e) for e in range(n)], b.EvalStats(), [b.TerrainStats(t) for t in range(b.num_terrains)],
-            [dist[ids == e].tobytes() for e in range(n)])
-
-
-def assert_same_end(x, y, what):
-    bad = X.same_record(x[0], y[0])
-    assert bad is None, "%s: EnvState.%s differs" % (what, bad)
-    assert x[1].tobytes() == y[1].tobytes(), "%s: policy states differ" % what
-    assert x[2] == y[2], "%s: ground windows / build counts differ" % what
-    assert x[3] == y[3] and x[4] == y[4], "%s: statistics differ" % what
-    assert x[5] == y[5], "%s: distance logs differ" % what
-
-
 def mixed_run(om, monkeypatch, env, extra, n=192, frames=90):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_knobs(monkeypatch, env)
     b = T.mixed_batch(om, T.DOG, n, T.four_files(T.DOG), [e % 4 for e in range(n)], dict(terrain_seed=77, rand_seed=4, terrain_gen="device", **extra), trained=True)
     for _ in range(frames):
         b.Update()
-    out = end_state(b)
-    assert out[3]["resets"] > 0 and all(s["cycles"] > 0 for s in out[4])
-    assert sum(1 for e in range(n) if out[2][e][1] % 2 == 1) > 0, "no window slid"      # (a fall builds two segments, a slide one)
+    dist, ids = b.GetDistLog()
+    out = end_state(b, statistics=(b.EvalStats(), [b.TerrainStats(t) for t in range(b.num_terrains)]), distance_logs=[dist[ids == e].tobytes() for e in range(n)])
+    assert out["statistics"][0]["resets"] > 0 and all(s["cycles"] > 0 for s in out["statistics"][1])
+    assert sum(1 for e in range(n) if out["ground"][e][1] % 2 == 1) > 0, "no window slid"      # (a fall builds two segments, a slide one)
     return out
 
 
@@ -164,11 +74,5 @@ def test_mixed_device_terrain_determinism_and_shard_invariance(da, om, frames=60
 
 
 # ---- 7d. ABI ----
-SYMBOLS = ("dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains", "dtrl_terrain_stats")
-
-
-@pytest.mark.parametrize("lib", ["libdtrl.so", "libdtrl_f32.so"])
-def test_new_symbols_resolve(lib):
-    L = ctypes.CDLL(os.path.join(os.path.dirname(HIP_LIB), lib))
-    for name in SYMBOLS:
-        assert getattr(L, name) is not None, name
+test_new_symbols_resolve = symbols_test(("dtrl_terrains_create", "dtrl_terrain_set_file", "dtrl_terrain_set_params", "dtrl_terrain_info", "dtrl_assign_terrains", "dtrl_get_terrains",
+                                         "dtrl_terrain_stats"))

@@ -4,9 +4,6 @@ dtrl_trace_gather per read -- and what only exists on HIP: the kernels against t
 traced, the ids unsorted, with one and two env groups (with three envs traced all of them sit in the first group: the second queues nothing), both terrain modes
 and both libraries, with falls among the rows; frames queued without a host wait (RunFrames) against frame-by-frame Update; the read into device memory against the
 read into host memory; run-to-run determinism; and the new symbols in both libraries."""
-import ctypes
-import os
-
 import pytest
 
 import test_episode_limit as E
@@ -18,70 +15,16 @@ import test_push_schedule as R
 import test_terrain_ladder as LD
 import test_terrain_sets as T
 import test_trace as TR
-from conftest import HIP_LIB
+from product import product_batch, set_knobs, symbols_test
+# ---- twins: the CPU tests themselves, collected here under the module's gpu mark and fixture ----
+from test_trace import (test_a_fallen_envs_row_is_its_last_pose, test_a_parked_env_writes_no_row, test_export_motion_files, test_external_trace_equals_internal,  # noqa: F401
+                        test_lifecycle_and_refusals, test_ring_and_untouched_batch, test_row_carries_the_keys_the_frame_ran_under,
+                        test_row_carries_the_limits_need_reset, test_rows_equal_getters_dog_with_variants_and_terrains, test_rows_equal_getters_fp32,
+                        test_rows_equal_getters_raptor_with_slots)
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("DTRL_KERNEL", "DTRL_TERRAINS_FALLBACK", "DTRL_SLOTS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_PUSH_FALLBACK", "DTRL_PERTURB_FALLBACK", "DTRL_EPISODE_FALLBACK", "DTRL_TRACE_FALLBACK", "DTRL_GROUPS")
-
-
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    for mod in (R, T, V, X, P, LD, H):
-        monkeypatch.setattr(mod, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-
-
-# ---- twins ----
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_rows_equal_getters_dog_with_variants_and_terrains(da, om, tmp_path, mode):
-    TR.test_rows_equal_getters_dog_with_variants_and_terrains(da, om, tmp_path, mode)
-
-
-def test_rows_equal_getters_raptor_with_slots(da, om):
-    TR.test_rows_equal_getters_raptor_with_slots(da, om)
-
-
-def test_rows_equal_getters_fp32(da, om):
-    TR.test_rows_equal_getters_fp32(da, om)
-
-
-def test_a_fallen_envs_row_is_its_last_pose(da, om):
-    TR.test_a_fallen_envs_row_is_its_last_pose(da, om)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_ring_and_untouched_batch(da, om, mode):
-    TR.test_ring_and_untouched_batch(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_row_carries_the_limits_need_reset(da, om, mode):
-    TR.test_row_carries_the_limits_need_reset(da, om, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_row_carries_the_keys_the_frame_ran_under(da, om, tmp_path, mode):
-    TR.test_row_carries_the_keys_the_frame_ran_under(da, om, tmp_path, mode)
-
-
-def test_external_trace_equals_internal(da, om, monkeypatch):
-    TR.test_external_trace_equals_internal(da, om, monkeypatch)
-
-
-def test_a_parked_env_writes_no_row(da, om):
-    TR.test_a_parked_env_writes_no_row(da, om)
-
-
-def test_lifecycle_and_refusals(da, om):
-    TR.test_lifecycle_and_refusals(da, om)
-
-
-def test_export_motion_files(da, om, tmp_path):
-    TR.test_export_motion_files(da, om, tmp_path)
-
+hip_batch = product_batch(R, T, V, X, P, LD, H)
+NOT_TWINNED = {}
 
 # ---- GPU only: 70 envs, bit for bit ----
 N, FRAMES, RING = E.N, 30, 20         # (the ring is shorter than the run: the reads unroll a ring that has wrapped)
@@ -89,10 +32,7 @@ LISTS = {"one": [66], "three": [30, 2, 17], "all": None}    # "three": unsorted,
 
 
 def traced_run(om, monkeypatch, env, mode, extra, traced, run_frames=False, device_read=False):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_knobs(monkeypatch, env)
     extra = dict(extra, min_perturb=E.HARD[0], max_perturb=E.HARD[1], min_pertrub_duration=0.1, max_perturb_duration=0.25)   # hard pushes: falls among the rows
     b = E.limit_batch(om, N, mode, limit=False, **extra)
     b.PushSchedule((3, 6), seed=R.SEED)
@@ -157,11 +97,4 @@ def test_run_frames_12_equals_twelve_updates(da, om):
     assert list(ta["count"]) == [12, 12] and TR.same(ta["vals"], tb["vals"]) and TR.same(ta["ints"], tb["ints"])
 
 
-SYMBOLS = ("dtrl_trace", "dtrl_trace_info", "dtrl_trace_read", "dtrl_trace_read_device")
-
-
-@pytest.mark.parametrize("lib", ["libdtrl.so", "libdtrl_f32.so"])
-def test_new_symbols_resolve(lib):
-    lib_ = ctypes.CDLL(os.path.join(os.path.dirname(HIP_LIB), lib))
-    for name in SYMBOLS:
-        assert getattr(lib_, name) is not None, name
+test_new_symbols_resolve = symbols_test(("dtrl_trace", "dtrl_trace_info", "dtrl_trace_read", "dtrl_trace_read_device"))

@@ -3,80 +3,21 @@ Backend::VariantRedraw, here ONE launch of dtrl_variant_redraw per env group and
 the host fallback (DTRL_VARIANTS_FALLBACK=1) at 70 envs (two 64-thread blocks, the second partial) with one and two env groups in both libraries, frames queued
 without a host wait (RunFrames) against frame-by-frame Update, run-to-run determinism, the variant fast kernel against the reference kernel under redraw, and the
 new symbols in both libraries."""
-import ctypes
-import os
-
 import pytest
 
 import test_external_policy as X
 import test_model_variants as V
 import test_terrain_sets as T
 import test_variant_redraw as R
-from conftest import HIP_LIB
+from product import assert_same_end, end_state, product_batch, set_knobs, symbols_test
+# ---- twins: the CPU tests themselves, collected here under the module's gpu mark and fixture ----
+from test_variant_redraw import (test_batch_state_resets_and_restart, test_envs_outside_the_range_are_untouched, test_every_episode_equals_its_single_model_run,  # noqa: F401
+                                 test_key_ownership, test_keys_and_counters_equal_the_rule, test_overlapped_loop_equals_frame_by_frame, test_refusals, test_removal,
+                                 test_shard_invariance, test_the_reset_runs_under_the_new_model)
 
 pytestmark = pytest.mark.gpu
-
-KNOBS = ("DTRL_KERNEL", "DTRL_TERRAINS_FALLBACK", "DTRL_SLOTS_FALLBACK", "DTRL_VARIANTS_FALLBACK", "DTRL_GROUPS")
-
-
-@pytest.fixture(autouse=True)
-def hip_batch(monkeypatch):
-    import deepterrainrl_amd
-    for mod in (R, T, V, X):
-        monkeypatch.setattr(mod, "Scenario", deepterrainrl_amd.BatchScenario)   # product path: batch() now loads libdtrl.so (libdtrl_f32.so for physics_precision=f32)
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-
-
-# ---- twins ----
-@pytest.mark.parametrize("weights", R.WEIGHT_CASES, ids=R.WEIGHT_IDS)
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_keys_and_counters_equal_the_rule(da, om, tmp_path, mode, weights):
-    R.test_keys_and_counters_equal_the_rule(da, om, tmp_path, mode, weights)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_every_episode_equals_its_single_model_run(da, om, tmp_path, mode):
-    R.test_every_episode_equals_its_single_model_run(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_the_reset_runs_under_the_new_model(da, om, tmp_path, mode):
-    R.test_the_reset_runs_under_the_new_model(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_envs_outside_the_range_are_untouched(da, om, tmp_path, mode):
-    R.test_envs_outside_the_range_are_untouched(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_removal(da, om, tmp_path, mode):
-    R.test_removal(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_batch_state_resets_and_restart(da, om, tmp_path, mode):
-    R.test_batch_state_resets_and_restart(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_key_ownership(da, om, tmp_path, mode):
-    R.test_key_ownership(da, om, tmp_path, mode)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_shard_invariance(da, om, tmp_path, mode):
-    R.test_shard_invariance(da, om, tmp_path, mode)
-
-
-def test_refusals(da, om, tmp_path):
-    R.test_refusals(da, om, tmp_path)
-
-
-@pytest.mark.parametrize("mode", T.MODES, ids=T.MODE_IDS)
-def test_overlapped_loop_equals_frame_by_frame(da, om, tmp_path, mode):
-    R.test_overlapped_loop_equals_frame_by_frame(da, om, tmp_path, mode)
+hip_batch = product_batch(R, T, V, X)
+NOT_TWINNED = {}
 
 
 def test_train_loop_with_variants(da, om):
@@ -90,37 +31,18 @@ def test_train_loop_with_variants(da, om):
 N, FRAMES, TERRAIN_SEED = 70, 40, 41
 
 
-def end_state(b):
-    info = b.VariantRedrawInfo()
-    return (X.env_states(b), b.RecordPoliState(), [X.ground_key(b, e) for e in range(b.num_envs)], list(b.GetVariants()), info["draws"].tobytes(),
-            [b.VariantStats(v) for v in range(b.num_variants)], info)
-
-
-def assert_same_end(x, y, what):
-    bad = X.same_record(x[0], y[0])
-    assert bad is None, "%s: EnvState.%s differs" % (what, bad)
-    assert x[1].tobytes() == y[1].tobytes(), "%s: policy states differ" % what
-    assert x[2] == y[2], "%s: ground windows / build counts differ" % what
-    assert x[3] == y[3], "%s: variants differ" % what
-    assert x[4] == y[4], "%s: draw counters differ" % what
-    assert x[5] == y[5], "%s: variant statistics differ" % what
-
-
 def redraw_run(om, tmp_path, monkeypatch, env, extra, run_frames=False):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_knobs(monkeypatch, env)
     b = R.redraw_batch(om, tmp_path, N, dict(terrain_gen="device"), seed=9, weights=(1, 2, 1), terrain_seed=TERRAIN_SEED, **extra)
     if run_frames:
         b.RunFrames(FRAMES)
     else:
         for _ in range(FRAMES):
             b.Update()
-    out = end_state(b)
-    draws = out[6]["draws"]
+    info = b.VariantRedrawInfo()
+    draws = info["draws"]
     assert draws.sum() >= 5 and draws[64:].sum() >= 1, draws
-    return out
+    return end_state(b, info, variants=list(b.GetVariants()), draw_counters=draws.tobytes(), variant_statistics=[b.VariantStats(v) for v in range(b.num_variants)])
 
 
 @pytest.mark.parametrize("groups", ["1", "2"], ids=["one_group", "two_groups"])
@@ -146,11 +68,4 @@ def test_fast_kernel_equals_reference_kernel_under_redraw(da, om, tmp_path, monk
     assert_same_end(base, redraw_run(om, tmp_path, monkeypatch, {"DTRL_KERNEL": "ref"}, {}), "DTRL_KERNEL=ref")
 
 
-SYMBOLS = ("dtrl_variant_redraw", "dtrl_variant_redraw_info")
-
-
-@pytest.mark.parametrize("lib", ["libdtrl.so", "libdtrl_f32.so"])
-def test_new_symbols_resolve(lib):
-    lib_ = ctypes.CDLL(os.path.join(os.path.dirname(HIP_LIB), lib))
-    for name in SYMBOLS:
-        assert getattr(lib_, name) is not None, name
+test_new_symbols_resolve = symbols_test(("dtrl_variant_redraw", "dtrl_variant_redraw_info"))

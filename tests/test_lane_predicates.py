@@ -19,7 +19,8 @@ import pytest
 import test_host_and_emul as T
 from conftest import REFDATA, dog_policy
 from precision import both_precisions, check_build, extra_for
-from test_gpu_fsub_rhs import product
+from product import fast_and_reference
+from test_gpu_fsub_rhs import NAMES, product
 
 CELLS = [("args/dog_slopes_mixed_args.txt", "dog", 12), ("args/raptor_narrow_gaps_args.txt", "raptor", 30), ("args/goat_cliffs_args.txt", "goat", 12)]
 N_ENVS = 96
@@ -66,19 +67,10 @@ def extra_of(prec, warm_start):
 @pytest.mark.parametrize("arg,skel,frames,prec", both_precisions(CELLS, ids=[c[1] for c in CELLS]))
 def test_lane_predicates_fast_equals_reference_bitwise(da, om, monkeypatch, arg, skel, frames, prec, warm_start):
     pol = T.raptor_policy(om) if skel == "raptor" else dog_policy(om)
-
-    def run(kernel):
-        if kernel:
-            monkeypatch.setenv("DTRL_KERNEL", kernel)
-        else:
-            monkeypatch.delenv("DTRL_KERNEL", raising=False)
-        return rollout(product(da, arg, N_ENVS, prec, **extra_of(None, warm_start)), pol, frames)
-
-    tr, qr, qdr, (tcr, tar), sr = run("ref")
-    check_reached(tr, skel)                                    # the inputs first: the reference kernel alone fills the bins
-    tf, qf, qdf, (tcf, taf), sf = run(None)
-    for f, (a, b_) in enumerate(zip(tf, tr)):
-        assert all(np.array_equal(x, y) for x, y in zip(a, b_)), "contact cache differs in frame %d" % f
+    # (the per-frame records are the contact cache: the first three of NAMES)
+    (tf, qf, qdf, (tcf, taf), sf), (tr, qr, qdr, (tcr, tar), sr) = fast_and_reference(
+        monkeypatch, lambda: rollout(product(da, arg, N_ENVS, prec, **extra_of(None, warm_start)), pol, frames), NAMES[:3])
+    check_reached(tr, skel)                                    # the inputs: the reference kernel alone fills the bins
     assert np.array_equal(qf, qr) and np.array_equal(qdf, qdr)
     assert np.array_equal(tcf, tcr) and np.array_equal(taf, tar)
     assert sf == sr
